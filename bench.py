@@ -4,6 +4,7 @@ bench.py — rasterizer forward+backward views/sec on MI355X (BASELINE.json metr
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C4] [--opacity A|B] [--scaling weak|strong]
                     [--shard frames|views] [--allreduce-grads] [--frames-in-flight F] [--no-cpu-baseline] [--no-extras]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -28,8 +29,8 @@ next step.
 
 The JSON line carries `roofline` (dominant kernel by HIP-event time, algorithmic bytes per launch, HBM traffic and the
 vector-ALU counters of the committed rocprofv3 passes), `cpu_baseline` (oracle/raster_oracle.c, OpenMP, bounded sample,
-min of 5), `repeats` (every figure is the median of >= 5 timed regions of >= 100 ms each: a region is the --steps block
-repeated as often as that takes), `scenario_b` (unsaturated opacities), `single_view` (the reference's own call shape: one
+min of 5), `repeats` (`value`, `sequential` and `scenario_b` each time ONE region of exactly --steps steps; the other side figures
+are medians of several regions of their own), `scenario_b` (unsaturated opacities), `single_view` (the reference's own call shape: one
 camera per call, P = 8,280, 512x375), `small_v` (1 and 3 views of the config-2 scene per call: a view-sharded rank's launch),
 `forecast` (step time at 24 / 12 / 6 / 3 views => view-sharded strong scaling at 2 / 4 / 8 GPUs), `view_sharded` (the same
 split executed: rank r renders views r::N of every frame), `c4` (BASELINE config 4 with its own roofline), `dense_1m` (one view,
@@ -38,6 +39,7 @@ iteration of the texture loop, train.py:729-741, at that size), `loss` (the
 fused photometric loss at three shapes with its own roofline), `bake_8192` (BASELINE config 5 with its own roofline and the
 reference's own code timed beside it), `full_iteration` (render + fused loss + Adam/pins), `drop_in` and `sequential` — see
 DESIGN.md §6.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -45,6 +47,7 @@ import argparse
 import contextlib
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -233,6 +236,9 @@ class Workload:
         self.loss_bufs = [torch.zeros(V, device=dev) for _ in range(nb)]
         self.gath_bufs = [torch.zeros(V * world, device=dev) for _ in range(nb)]
         self.pending = [None] * nb
+        # --dump-outputs: step() keeps what it computed, and last_outputs holds the arrays of the latest step
+        self.keep_outputs = False
+        self.last_outputs = None
         # everything above was uploaded on the current stream: the side streams' first steps must not start before it
         for st in self.streams:
             if st is not None:
@@ -247,7 +253,7 @@ class Workload:
                 self.pending[k] = None
             losses = self.loss_bufs[k]
             b = self.batches[slot]
-            b.forward(rv["means3D"], rv["opacities"], rv["scales"], rv["rotations"], rv.get("colors_precomp"), rv.get("shs"))
+            fwd = b.forward(rv["means3D"], rv["opacities"], rv["scales"], rv["rotations"], rv.get("colors_precomp"), rv.get("shs"))
             # per-view scalar loss term <colour, dL/dcolour>: the backward's replay ends holding exactly this inner product per
             # pixel, so it comes out of t4d_rasterize_backward (cotangent_dot), not out of a second pass over both images
             g = b.backward(self.dc, self.dd, self.da, cotangent_dot=losses)
@@ -258,9 +264,11 @@ class Workload:
                 summed = [t.reshape(self.G, self.V, *t.shape[1:]).sum(1) for t in g.values() if t is not None]
                 self.t4d_dist.all_reduce_grads(summed)
             if self.gather:
-                out, work = self.t4d_dist.gather_losses_async(losses, self.gath_bufs[k])
+                losses, work = self.t4d_dist.gather_losses_async(losses, self.gath_bufs[k])
                 self.pending[k] = work
-                return out, [g]
+        if self.keep_outputs:
+            self.last_outputs = dict(zip(("color", "radii", "depth", "alpha"), fwd), loss=losses,
+                                     **{"grad_" + name: t for name, t in g.items() if t is not None})
         return losses, [g]
 
     def drain(self):
@@ -283,14 +291,14 @@ class Workload:
         return [b.fetch_status() for b in self.batches]
 
 
-MIN_REGION_S = 0.1      # a timed region lasts at least this long: the --steps block is repeated as often as that takes
-N_REGIONS = 5           # ... and there are this many regions; figures are the median, min and max ride along
+MIN_REGION_S = 0.1      # a side figure's timed region lasts at least this long: its block of steps is repeated as often as that takes
 
 
-def timed_run(wl, steps, warmup, prewarm_s, barrier, all_reduce_max, regions=N_REGIONS, min_region_s=MIN_REGION_S):
+def timed_run(wl, steps, warmup, prewarm_s, barrier, all_reduce_max, regions=1, min_region_s=0.0):
     """W untimed steps (after a clock-settling pre-warm), then `regions` timed regions, each EXACTLY `blocks * steps` steps
     between two barriers (barrier + torch.cuda.synchronize on both sides, MAX over ranks).  Returns (median seconds per
-    block of `steps` steps, host enqueue seconds per block, stats dict)."""
+    block of `steps` steps, host enqueue seconds per block, stats dict).  The defaults time ONE region of exactly `steps` steps
+    (what --steps asks for); side figures pass their own `regions` / `min_region_s`."""
     dev = wl.dev
     # A GPU that has just been idle (fresh box, or a profiler run before this one) needs tens of milliseconds of work
     # before its clocks settle: a cold 50-step run measured 1.23 ms/step against 0.62 warm.  Untimed, like the W steps.
@@ -325,8 +333,35 @@ def timed_run(wl, steps, warmup, prewarm_s, barrier, all_reduce_max, regions=N_R
     stats = {"regions": len(times), "blocks_per_region": blocks, "steps_per_region": blocks * steps,
              "region_ms": round(1e3 * med * blocks, 3),
              "ms_per_step": {"min": round(1e3 * srt[0] / steps, 4), "median": round(1e3 * med / steps, 4), "max": round(1e3 * srt[-1] / steps, 4)},
-             "note": "a region = the --steps block repeated until it lasts >= 100 ms, bracketed by barrier + synchronize; value is the MEDIAN region"}
+             "note": "a region = `blocks_per_region` blocks of the timed steps, bracketed by barrier + synchronize; the figure is the MEDIAN region"}
     return med, sorted(enq)[len(enq) // 2], stats
+
+
+DUMP_MAX_ELEMENTS = 1 << 20     # per array (4 MB of float32): at most 16 arrays stay within 64 MB
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: writes the arrays of `outputs` (a caller's view of one step: colour, radii, depth, alpha, the per-view
+    losses and gradients) as out_dir/<name>.npy in float32 (radii are small integers: exact).  An array of more than
+    DUMP_MAX_ELEMENTS elements is written as a fixed sample: its flattened elements at the sorted unique indices of
+    DUMP_MAX_ELEMENTS draws from default_rng(0), the same indices for the same shape in every run.  Returns what was written."""
+    if len(outputs) * DUMP_MAX_ELEMENTS * 4 > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {len(outputs)} arrays do not fit in {DUMP_MAX_BYTES >> 20} MB")
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in outputs.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        sampled = n > DUMP_MAX_ELEMENTS
+        if sampled:
+            idx = np.unique(np.random.default_rng(0).integers(0, n, DUMP_MAX_ELEMENTS))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if sampled else a.reshape(tuple(t.shape)))
+        written[name] = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""),
+                         "written": "sample of %d elements" % a.size if sampled else "all"}
+    return written
 
 
 def kernel_profile(wl, steps):
@@ -919,15 +954,18 @@ def main():
     ap.add_argument("--frames-in-flight", dest="in_flight", type=int, default=int(os.environ.get("T4D_BENCH_IN_FLIGHT", "0")),
                     help="independent frames in flight on as many HIP streams (1 = one frame after the other on one stream; "
                          "default: 3 for config 2, 2 for config 4)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (rank 0: colour, radii, depth, alpha, losses, "
+                         "gradients) as DIR/<name>.npy, float32, at most 64 MB (larger arrays as a fixed seeded sample)")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 64 if args.scaling == "strong" else 50
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # started by hand without a launcher: become `python -m torch.distributed.run ... bench.py <same flags>`
-        os.execvp(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                   "--master-addr", "127.0.0.1", "--master-port", str(29500 + os.getpid() % 1000),
-                                   os.path.abspath(__file__)] + sys.argv[1:])
+        # started by hand without a launcher: run `python -m torch.distributed.run ... bench.py <same flags>` as a child process
+        raise SystemExit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                                          "--master-addr", "127.0.0.1", "--master-port", str(29500 + os.getpid() % 1000),
+                                          os.path.abspath(__file__)] + sys.argv[1:]))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1003,7 +1041,14 @@ def main():
         return float(t.item())
 
     wl.learn_capacity()
+    wl.keep_outputs = bool(args.dump_outputs)
     dt, t_enqueue, repeats = timed_run(wl, my_steps, args.warmup, args.prewarm_s, barrier, all_reduce_max)
+    dumped = None
+    if args.dump_outputs:
+        wl.keep_outputs = False
+        if rank == 0:
+            dumped = {"dir": args.dump_outputs, "step": my_steps - 1, "arrays": dump_outputs(wl.last_outputs, args.dump_outputs)}
+        wl.last_outputs = None
     sequential = None
     if wl.F > 1:                     # the same steps, one frame after the other on one stream: what the overlap is worth
         wl.sequential = True
@@ -1195,6 +1240,8 @@ def main():
             ("weak" if (args.scaling == "strong" and not by_views) else "strong"): other,
             "dist_backend": (dist.get_backend() if dist is not None else None),
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if last_losses is not None:
             out["gathered_losses_first_steps"] = last_losses       # rank-major: out.view(world, -1).t() is view order in --shard views
             out["grad_checksums_first_steps_rank0"] = grad_sums

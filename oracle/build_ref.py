@@ -7,7 +7,8 @@ its own single source file: the CPU UV-space triangle rasterizer `_render_colors
 The source is compiled WHERE IT LIES (never copied into this repo), with the flags the reference's own
 setup.py/distutils would use for the arithmetic (-O2, no fast-math), into oracle/_ref/libmesh_core_ref.so
 (git-ignored; travels to the GPU box with the snapshot).  The C++ symbol is called through its mangled name, so no
-shim source is needed.  Also (re)writes tests/golden/g5_render_colors.npz from that library.
+shim source is needed.  `python oracle/build_ref.py` also (re)writes tests/golden/g5_render_colors.npz and
+g11_render_colors_uv_meshes.npz from that library.
 
 Run:  python oracle/build_ref.py          (only works where /root/reference exists)
 """
@@ -60,9 +61,27 @@ def write_golden():
                         hw=np.array([h, w]), image=img, verts_z=verts_z, tris_z=tris2, image_z=img_z)
 
 
+def write_golden_uv_meshes():
+    """tests/golden/g11_render_colors_uv_meshes.npz: sha256 digests of the reference's own outputs for the cases of
+    tests/test_texture_oracle.py (texture_oracle.uv_mesh_cases), so that the port is held bit-identical to the reference also
+    where oracle/_ref cannot be built.  Digests rather than the images: the check is bit identity, and the images of random
+    colours do not compress (0.9 MB)."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    from oracle import texture_oracle as TX
+    out = {}
+    for with_depth in (False, True):
+        for name, (args, kw) in TX.uv_mesh_cases(with_depth).items():
+            res = TX.render_colors_ref(*args, **kw)
+            for part, a in zip(("image", "depth"), res if isinstance(res, tuple) else (res,)):
+                out[f"{name}_{part}"] = np.array(TX.digest(a))
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "g11_render_colors_uv_meshes.npz"), **out)
+
+
 if __name__ == "__main__":
     p = build(force="--force" in sys.argv)
     print("reference mesh_core:", p)
     if p:
         write_golden()
-        print("wrote tests/golden/g5_render_colors.npz")
+        write_golden_uv_meshes()
+        print("wrote tests/golden/g5_render_colors.npz, tests/golden/g11_render_colors_uv_meshes.npz")

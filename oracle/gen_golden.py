@@ -17,7 +17,7 @@ G8  train.get_loss_dense(..., use_mask=True) (train.py:380-417: helpers.get_mask
 G9  train.get_loss(..., use_mask=True) (train.py:300-377) for is_initial_timestep True and False: the branch train.py:631 makes the
     live one - helpers.get_mask(["inner_mouth"]) (helpers.py:811-823), masked_gt = 0.1 x gt there, camera affine (:310)
 G10 train.get_loss_dense(..., use_mask=False) (train.py:380-417 as :632,:735 call it) incl. 0.02 x soft_color (helpers.py:119-120)
-G6  SELF-GENERATED (not reference-derived): forward outputs + all gradients of oracle/torch_oracle.py (float64)
+G6  SELF-GENERATED (not reference-derived): forward outputs + all gradients of oracle/torch_oracle.py (float64), with their float32 inputs,
     on a 64x64 / P=200 scene; pins the oracle against accidental edits.
 The rasterizer itself has no reference-derived golden vectors: its source is absent from /root/reference
  — parity unpinned.
@@ -290,6 +290,28 @@ def gen_g10(helpers):
                         dense_seen=variables["dense_seen"].numpy(), dense_max_2D_radius=variables["dense_max_2D_radius"].numpy())
 
 
+def gen_g6():
+    """G6 (self-generated): the float64 oracle on a seeded scene.  The fixture keeps its float32 inputs (in_*, cam_*, cotangents)
+    too: elementwise exp and the 4x4 camera maths round differently with the host's math library, and the oracle's outputs
+    must not depend on which host regenerates the scene."""
+    from oracle import torch_oracle as TO
+    from scaffold import reference_boundary as boundary, scene
+    p = scene.make_gaussians(10, 20, opacity="B", seed=6)
+    rvv = {k: v.detach() for k, v in boundary.params2rendervar(p).items()}
+    cam = scene.camera_rig(64, 64, n_views=3)[1]
+    dc, dd, da = scene.output_cotangents(1, 64, 64, seed=7, depth_alpha=True)
+    outs, grads = TO.rasterize_with_grads(TO.View(*cam), rvv["means3D"], rvv["opacities"], rvv["scales"], rvv["rotations"],
+                                          colors_precomp=rvv["colors_precomp"], dL_dcolor=dc[0], dL_ddepth=dd[0],
+                                          dL_dalpha=da[0])
+    g6 = {"color": outs["color"].numpy(), "depth": outs["depth"].numpy(), "alpha": outs["alpha"].numpy(),
+          "radii": outs["radii"].numpy(), "n_contrib": outs["n_contrib"].numpy()}
+    g6.update({f"grad_{k}": v.numpy() for k, v in grads.items()})
+    g6.update({f"in_{k}": rvv[k].numpy() for k in ("means3D", "opacities", "scales", "rotations", "colors_precomp")})
+    g6.update({f"cam_{k}": getattr(cam, k).numpy() for k in ("viewmatrix", "projmatrix", "campos")})
+    g6.update(dL_dcolor=dc[0].numpy(), dL_ddepth=dd[0].numpy(), dL_dalpha=da[0].numpy())
+    np.savez_compressed(os.path.join(OUT, "g6_self_oracle_f64.npz"), **g6)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     helpers, external = import_reference_helpers()
@@ -379,20 +401,7 @@ def main():
     gen_g9(helpers)
     gen_g10(helpers)
 
-    # ---- G6 (self-generated) --------------------------------------------------------------------------------
-    from oracle import torch_oracle as TO
-    from scaffold import reference_boundary as boundary, scene
-    p = scene.make_gaussians(10, 20, opacity="B", seed=6)
-    rvv = {k: v.detach() for k, v in boundary.params2rendervar(p).items()}
-    cam = scene.camera_rig(64, 64, n_views=3)[1]
-    dc, dd, da = scene.output_cotangents(1, 64, 64, seed=7, depth_alpha=True)
-    outs, grads = TO.rasterize_with_grads(TO.View(*cam), rvv["means3D"], rvv["opacities"], rvv["scales"], rvv["rotations"],
-                                          colors_precomp=rvv["colors_precomp"], dL_dcolor=dc[0], dL_ddepth=dd[0],
-                                          dL_dalpha=da[0])
-    g6 = {"color": outs["color"].numpy(), "depth": outs["depth"].numpy(), "alpha": outs["alpha"].numpy(),
-          "radii": outs["radii"].numpy(), "n_contrib": outs["n_contrib"].numpy()}
-    g6.update({f"grad_{k}": v.numpy() for k, v in grads.items()})
-    np.savez_compressed(os.path.join(OUT, "g6_self_oracle_f64.npz"), **g6)
+    gen_g6()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))
 

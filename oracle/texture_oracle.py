@@ -4,6 +4,7 @@ into oracle/_ref/ and (b) the plain-C restatement oracle/texture_oracle.c.  Used
 (as the CPU baseline, kind "reference") only.
 """
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -63,3 +64,22 @@ def render_colors_port(vertices, triangles, colors, h, w, c=3, BG=None, return_d
 def render_colors_cpu(*a, **k):
     """Best available CPU answer: the real reference when its .so is present, else the port."""
     return render_colors_ref(*a, **k) if have_ref() else render_colors_port(*a, **k)
+
+
+def uv_mesh_cases(with_depth):
+    """The seeded calls tests/test_texture_oracle.py makes of the reference and the port (golden G11 holds the digests of the
+    reference's outputs): {name: (args, kwargs)} - two shuffled uv meshes, then 50 triangles of the second over a background."""
+    from scaffold.scene import uv_mesh
+    cases = {}
+    for n, h, w, seed in ((24, 96, 80, 1), (40, 128, 128, 2)):
+        verts, tris, colors = uv_mesh(n, h, w, seed, with_depth)
+        cases[f"n{n}_s{seed}_z{int(with_depth)}"] = ((verts, tris, colors, h, w), {"return_depth": True})
+    bg = np.random.default_rng(3).uniform(size=(h, w, 3)).astype(np.float32)
+    cases[f"bg_z{int(with_depth)}"] = ((verts, tris[:50], colors, h, w), {"BG": bg})
+    return cases
+
+
+def digest(a) -> str:
+    """sha256 over an output's shape and float32 bytes: equal digests = bit-identical outputs."""
+    a = np.ascontiguousarray(a, np.float32)
+    return hashlib.sha256(repr(a.shape).encode() + a.tobytes()).hexdigest()

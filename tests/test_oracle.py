@@ -99,6 +99,17 @@ def test_g6_fixture_pins_both_oracles():
     rv = {k: v.detach() for k, v in boundary.params2rendervar(p).items()}
     cam = scene.camera_rig(64, 64, n_views=3)[1]
     dc, dd, da = scene.output_cotangents(1, 64, 64, seed=7, depth_alpha=True)
+    # the fixture's float32 inputs are this seeded scene's up to the host's rounding (elementwise exp, the 4x4 camera maths) ...
+    for k in ("means3D", "opacities", "scales", "rotations", "colors_precomp"):
+        np.testing.assert_allclose(rv[k].numpy(), g[f"in_{k}"], rtol=1e-6, atol=1e-7)
+        rv[k] = torch.from_numpy(g[f"in_{k}"])
+    for k in ("viewmatrix", "projmatrix", "campos"):
+        np.testing.assert_allclose(getattr(cam, k).numpy(), g[f"cam_{k}"], rtol=1e-6, atol=1e-7)
+    cam = cam._replace(**{k: torch.from_numpy(g[f"cam_{k}"]) for k in ("viewmatrix", "projmatrix", "campos")})
+    for name, t in (("dL_dcolor", dc[0]), ("dL_ddepth", dd[0]), ("dL_dalpha", da[0])):
+        np.testing.assert_allclose(t.numpy(), g[name], rtol=1e-6, atol=1e-9)
+    dc, dd, da = (torch.from_numpy(g[n])[None] for n in ("dL_dcolor", "dL_ddepth", "dL_dalpha"))
+    # ... and both oracles run on the fixture's own inputs
     outs, grads = util.torch_oracle_render(cam, rv, dc[0], dd[0], da[0])
     np.testing.assert_allclose(outs["color"].numpy(), g["color"], rtol=0, atol=1e-12)
     np.testing.assert_array_equal(outs["radii"].numpy(), g["radii"])

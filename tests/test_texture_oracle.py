@@ -1,15 +1,15 @@
-"""CPU: the texture-bake oracle (oracle/texture_oracle.c) against the REAL reference code (oracle/_ref, built from
-/root/reference/face3d/mesh/cython/mesh_core.cpp where that tree exists) and against golden G5 (outputs of that
-real code, committed)."""
+"""CPU: the texture-bake oracle (oracle/texture_oracle.c) against the REAL reference code: its outputs committed as golden G5, the
+digests of its outputs committed as golden G11 (both written by oracle/build_ref.py), and the reference itself (oracle/_ref) where
+build() could compile it."""
 import os
 
 import numpy as np
 import pytest
 
 from oracle import texture_oracle as TX
-from scaffold.scene import uv_mesh
 
 G = os.path.join(os.path.dirname(__file__), "golden", "g5_render_colors.npz")
+G11 = os.path.join(os.path.dirname(__file__), "golden", "g11_render_colors_uv_meshes.npz")
 
 
 def test_port_matches_golden_outputs_of_the_real_reference():
@@ -21,18 +21,20 @@ def test_port_matches_golden_outputs_of_the_real_reference():
     assert (g["image"][ring] < 0).any(), "fixture exercises the extrapolating border ring (mesh_core.cpp:211)"
 
 
-@pytest.mark.skipif(not TX.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("with_depth", [False, True])
 def test_port_is_bit_identical_to_the_real_reference(with_depth):
-    for n, h, w, seed in ((24, 96, 80, 1), (40, 128, 128, 2)):
-        verts, tris, colors = uv_mesh(n, h, w, seed, with_depth)
-        a, da = TX.render_colors_ref(verts, tris, colors, h, w, return_depth=True)
-        b, db = TX.render_colors_port(verts, tris, colors, h, w, return_depth=True)
-        np.testing.assert_array_equal(a, b)
-        np.testing.assert_array_equal(da, db)
-    bg = np.random.default_rng(3).uniform(size=(h, w, 3)).astype(np.float32)
-    np.testing.assert_array_equal(TX.render_colors_ref(verts, tris[:50], colors, h, w, BG=bg),
-                                  TX.render_colors_port(verts, tris[:50], colors, h, w, BG=bg))
+    """The port against the digests of the real reference's outputs (golden G11, written by oracle/build_ref.py) and, where
+    oracle/_ref is built, against the reference itself."""
+    g = np.load(G11)
+    for name, (args, kw) in TX.uv_mesh_cases(with_depth).items():
+        port = TX.render_colors_port(*args, **kw)
+        port = port if isinstance(port, tuple) else (port,)
+        for part, a in zip(("image", "depth"), port):
+            assert TX.digest(a) == str(g[f"{name}_{part}"]), f"{name}: the port's {part} differs from the reference's"
+        if TX.have_ref():
+            ref = TX.render_colors_ref(*args, **kw)
+            for a, b in zip(ref if isinstance(ref, tuple) else (ref,), port):
+                np.testing.assert_array_equal(a, b)
 
 
 def test_process_uv_mirror():
