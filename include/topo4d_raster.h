@@ -230,6 +230,55 @@ size_t t4d_soft_color_scratch_bytes(void);
 int t4d_soft_color_loss(int64_t rows, int32_t width, const float *x, const float *y, float weight, float *loss, float *grad,
                         int32_t accumulate, void *scratch, size_t scratch_bytes, void *hip_stream);
 
+/* Topology priors of the geometry loop: the regularisers of get_loss (train.py:328-368) on the RAW parameters, forward and
+ * backward in two launches, no host synchronisation, no floating-point atomics (bit-identical from run to run).
+ *   later frames (is_initial == 0): rigid, rot, iso (train.py:330-346); flat, flat_lip_bottom (FlattenLoss); flat_eye,
+ *     flat_face_bottom, flat_lip_socket (FlattenLoss_v2); flat_lid_top, flat_lid_bottom, flat_lip, flat_mouth (SoftFlattenLoss
+ *     against cos_init) (train.py:349-357)
+ *   frame 0 (is_initial != 0): scale, scale_max, and the four soft terms without cos_init, whose cos is written into cos_init
+ *     (train.py:359-368)
+ * means3D [P,3], unnorm_rotations [P,4], log_scales [P,3]: the optimiser's tensors (normalize / exp of helpers.py:91-100 are
+ * applied inside).  losses [T4D_PRIORS_TERMS + 1]: weights[t] * L_t in the T4D_PRIOR_* order (0 for the terms the frame does not
+ * evaluate), then their sum.  d_* (+)= upstream * dL/d(raw tensor) (upstream NULL: 1; flags & T4D_PRIORS_ACCUMULATE: added to what
+ * the buffers hold, e.g. t4d_rasterize_backward's gradients; otherwise overwritten).  Every index array is validated by the caller
+ * (0 <= index < P): the kernels do not check them. */
+#define T4D_PRIORS_TERMS 14
+enum { T4D_PRIOR_SCALE, T4D_PRIOR_SCALE_MAX, T4D_PRIOR_RIGID, T4D_PRIOR_ROT, T4D_PRIOR_ISO, T4D_PRIOR_FLAT,
+       T4D_PRIOR_FLAT_LIP_BOTTOM, T4D_PRIOR_FLAT_EYE, T4D_PRIOR_FLAT_FACE_BOTTOM, T4D_PRIOR_FLAT_LIP_SOCKET,
+       T4D_PRIOR_FLAT_LID_TOP, T4D_PRIOR_FLAT_LID_BOTTOM, T4D_PRIOR_FLAT_LIP, T4D_PRIOR_FLAT_MOUTH };
+#define T4D_PRIORS_EDGE_TERMS 6     /* flat, flat_lip_bottom, flat_lid_top, flat_lid_bottom, flat_lip, flat_mouth */
+#define T4D_PRIORS_REGION_TERMS 3   /* flat_eye, flat_face_bottom, flat_lip_socket */
+#define T4D_PRIORS_ACCUMULATE 1
+typedef struct T4DPriors {
+    int32_t P, K;                               /* Gaussians (= mesh vertices), padded one-ring width */
+    const int32_t *nbr;                         /* [P,K] neighbor_indices, padded with the vertex's own index */
+    const float *nbr_dist, *rig_w, *rot_w, *iso_w, *nbr_mask;   /* [P,K]; nbr_mask: FlattenLoss_v2's 0/1 padding mask */
+    const int32_t *nbr_num;                     /* [P] one-ring sizes (FlattenLoss_v2.neighbor_num) */
+    const float *init_scale;                    /* [P] */
+    int32_t n_edges[T4D_PRIORS_EDGE_TERMS];     /* interior edges of each flatten term, in the order above */
+    const int32_t *edges[T4D_PRIORS_EDGE_TERMS];/* [4, n]: v0s | v1s | v2s | v3s */
+    int32_t n_region[T4D_PRIORS_REGION_TERMS];
+    const int32_t *region[T4D_PRIORS_REGION_TERMS];
+    /* transposed incidence (CSR, built once by the caller): nbr_t_idx[nbr_t_off[v] .. nbr_t_off[v+1]) = every e = g*K+k with
+     * nbr[e] == v, ascending; rec_idx[f][rec_off[f][v] .. ) = the position records (t4d_priors_record_layout) that name vertex v
+     * among the terms frame kind f evaluates (f = 0: frame 0, 1: later frames), ascending */
+    const int32_t *nbr_t_off, *nbr_t_idx;
+    const int32_t *rec_off[2], *rec_idx[2];
+    float weights[T4D_PRIORS_TERMS];            /* losses_weights (train.py:535-540) */
+    /* per-frame state (initialize_per_timestep, train.py:420-438; cos_init: train.py:365-368) */
+    const float *prev_inv_rot;                  /* [P,4] */
+    const float *prev_offset;                   /* [P,K,3] */
+    float *cos_init[4];                         /* flat_lid_top, flat_lid_bottom, flat_lip, flat_mouth: [n_edges] */
+} T4DPriors;
+/* Position records: edge term t occupies 4 * n_edges[t] records (record base + 4 i + j names vertex edges[t][j * n + i]), region
+ * term r occupies (K + 1) * n_region[r] (slot k < K names nbr[v, k], slot K the region vertex v itself), in the order edge terms
+ * 0..5 then region terms 0..2.  Returns the total number of records and writes each term's first record into base[9]. */
+int64_t t4d_priors_record_layout(const T4DPriors *pr, int64_t *base);
+size_t t4d_priors_scratch_bytes(const T4DPriors *pr);
+int t4d_priors_eval(const T4DPriors *pr, int32_t is_initial, const float *means3D, const float *unnorm_rotations,
+                    const float *log_scales, float *d_means3D, float *d_unnorm_rotations, float *d_log_scales,
+                    const float *upstream, uint32_t flags, float *losses, void *scratch, size_t scratch_bytes, void *hip_stream);
+
 /* Fused optimiser step of Topo4D's loop: torch.optim.Adam (one group per tensor, train.py:272-297) for up to
  * T4D_ADAM_MAX_TENSORS tensors in ONE launch, followed by the per-iteration region freezes of train.py:676-700
  * (`params[name][mask] = values`) expressed as a per-row pin mask + pinned values.  grad == NULL: the tensor only gets its

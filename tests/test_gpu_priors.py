@@ -1,0 +1,297 @@
+"""GPU: the fused topology priors (t4d_priors_eval, topo4d_amd.priors) against G12 - the reference's own get_loss on the real
+facial-region topology - and against the plain-torch evaluation; determinism, accumulation, the cos_init cache, the autograd
+wrapper, and the geometry loop with priors= (eager, explicit, graphed)."""
+import numpy as np
+import pytest
+import torch
+
+from tests.test_priors_host import KEYS, _golden, check_grads, frame0_cos_init, make_priors
+
+pytestmark = pytest.mark.gpu
+
+
+def _params(z, frame):
+    return {k: torch.tensor(z[f"f{frame}_in_{k}"]).cuda().contiguous() for k in KEYS}
+
+
+def _check_against_golden(z, frame, detail, grads, grad_tol=1e-4):
+    names = [k[len(f"f{frame}_detail_"):] for k in z if k.startswith(f"f{frame}_detail_")]
+    assert sorted(names) == sorted(detail)
+    for k in names:
+        ref = float(z[f"f{frame}_detail_{k}"])
+        got = float(detail[k])
+        assert abs(got - ref) <= 1e-5 * abs(ref), (frame, k, got, ref)
+    check_grads(z, frame, {k: g.cpu().numpy() for k, g in zip(KEYS, grads)}, grad_tol)
+
+
+def _check_against_torch(pr, z, frame, grads):
+    """Every row of the fused gradients against the plain-torch evaluation (itself pinned to G12) on the same device."""
+    pt = {k: torch.nn.Parameter(v.clone()) for k, v in _params(z, frame).items()}
+    pr.evaluate_torch(pt, frame == 0)[0].backward()
+    for k, g in zip(KEYS, grads):
+        r = pt[k].grad if pt[k].grad is not None else torch.zeros_like(g)
+        scale = float(r.abs().max())
+        assert float((g - r).abs().max()) <= 1e-4 * max(scale, 1e-30), (frame, k, float((g - r).abs().max()), scale)
+
+
+def test_fused_priors_match_the_reference_both_frames():
+    """Every term and all three gradients, frame 0 and a later frame: losses within 1e-5 relative, gradients within 1e-4 of each
+    tensor's largest entry (no looser bound was needed for the soft terms' acos) - on G12's rows against the reference, on every row
+    against the plain-torch evaluation."""
+    z = _golden()
+    pr = make_priors(z, "cuda")
+    total, detail = pr.evaluate(_params(z, 0), True)
+    _check_against_golden(z, 0, detail, pr.grads)
+    assert abs(float(total) - float(z["f0_loss"])) <= 1e-5 * abs(float(z["f0_loss"]))
+    ref_cos = frame0_cos_init(z)
+    for k, c in pr.cos_init.items():
+        np.testing.assert_allclose(c.cpu().numpy(), ref_cos[k].numpy(), rtol=0, atol=2e-6)
+    grads0 = [g.clone() for g in pr.grads]
+    _check_against_torch(make_priors(z, "cuda"), z, 0, grads0)
+    pr.begin_frame(_params(z, 0))
+    for k, c in pr.cos_init.items():                     # the reference's own cos_init: the later frame's acos is pinned alone
+        c.copy_(ref_cos[k])
+    total, detail = pr.evaluate(_params(z, 1), False)
+    _check_against_golden(z, 1, detail, pr.grads)
+    _check_against_torch(pr, z, 1, [g.clone() for g in pr.grads])
+    assert abs(float(total) - float(z["f1_loss"])) <= 1e-5 * abs(float(z["f1_loss"]))
+
+
+def test_begin_frame_is_initialize_per_timestep_bit_for_bit():
+    z = _golden()
+    pr = make_priors(z, "cuda")
+    p = _params(z, 0)
+    pr.begin_frame(p)
+    rot = torch.nn.functional.normalize(p["unnorm_rotations"])
+    inv = rot.clone()
+    inv[:, 1:] = -1 * inv[:, 1:]
+    assert torch.equal(pr.prev_inv_rot_fg, inv)
+    x = p["means3D"]
+    assert torch.equal(pr.prev_offset, x[torch.tensor(z["neighbor_indices"]).cuda().long()] - x[:, None])
+    # and the offsets are the reference's: a gather and a subtraction are exact on any device
+    x_cpu = torch.tensor(z["f0_in_means3D"])
+    assert torch.equal(pr.prev_offset.cpu(), x_cpu[torch.tensor(z["neighbor_indices"]).long()] - x_cpu[:, None])
+
+
+def test_two_runs_are_bit_identical():
+    z = _golden()
+    pr = make_priors(z, "cuda")
+    pr.begin_frame(_params(z, 0))
+    for frame in (0, 1):
+        out = []
+        for _ in range(2):
+            pr.evaluate(_params(z, frame), frame == 0)
+            out.append([pr.losses.clone()] + [g.clone() for g in pr.grads])
+        for a, b in zip(*out):
+            assert torch.equal(a, b)
+
+
+def test_accumulate_adds_exactly_and_upstream_scales():
+    z = _golden()
+    pr = make_priors(z, "cuda")
+    pr.begin_frame(_params(z, 0))
+    g = torch.Generator(device="cuda").manual_seed(1)
+    for frame in (0, 1):
+        p = _params(z, frame)
+        pr.evaluate(p, frame == 0)
+        ref = [t.clone() for t in pr.grads]
+        pre = [torch.randn(t.shape, generator=g, device="cuda") for t in ref]
+        buf = [t.clone() for t in pre]
+        pr.evaluate(p, frame == 0, grads=buf, accumulate=True)
+        for a, b, r in zip(buf, pre, ref):
+            assert torch.equal(a, b + r)
+        two = torch.tensor(2.0, device="cuda")
+        buf = [torch.full_like(t, 7.0) for t in ref]
+        pr.evaluate(p, frame == 0, grads=buf, accumulate=False, upstream=two)
+        for a, r in zip(buf, ref):
+            assert torch.equal(a, r * 2.0)
+
+
+def test_cos_init_holds_the_last_frame0_call():
+    z = _golden()
+    pr = make_priors(z, "cuda")
+    p0 = _params(z, 0)
+    p1 = dict(p0)
+    p1["means3D"] = p0["means3D"] + 1e-3 * torch.randn(p0["means3D"].shape, generator=torch.Generator(device="cuda").manual_seed(2),
+                                                       device="cuda")
+    pr.evaluate(p0, True)
+    first = {k: v.clone() for k, v in pr.cos_init.items()}
+    pr.evaluate(p1, True)
+    fresh = make_priors(z, "cuda")
+    fresh.evaluate(p1, True)
+    for k in pr.cos_init:
+        assert torch.equal(pr.cos_init[k], fresh.cos_init[k])
+        assert not torch.equal(pr.cos_init[k], first[k])
+
+
+def test_autograd_function_equals_the_explicit_path():
+    z = _golden()
+    pr = make_priors(z, "cuda")
+    pr.begin_frame(_params(z, 0))
+    for frame in (0, 1):
+        p = {k: torch.nn.Parameter(v) for k, v in _params(z, frame).items()}
+        total, _ = pr.evaluate(p, frame == 0)
+        total = total.clone()
+        ref = [g.clone() for g in pr.grads]
+        l = pr.as_extra_loss(frame == 0)(p, None)
+        l.backward()
+        assert torch.equal(l.detach(), total)
+        for k, r in zip(KEYS, ref):
+            assert torch.equal(p[k].grad, r), k
+
+
+# ---- a triangulated lat-lon head (scaffold.scene.make_gaussians' vertex order) with its own topology ------------------------
+def grid_priors(n_lat, n_lon, means3D, seed=0, device="cuda"):
+    from topo4d_amd import priors as T
+    P = n_lat * n_lon
+    vid = lambda i, j: i * n_lon + (j % n_lon)
+    faces = []
+    for i in range(n_lat - 1):
+        for j in range(n_lon):
+            a, b, c, d = vid(i, j), vid(i, j + 1), vid(i + 1, j + 1), vid(i + 1, j)
+            faces += [(a, b, c), (a, c, d)]
+    faces = np.array(faces)
+    ring = [set() for _ in range(P)]
+    edge_faces = {}
+    for f in faces:
+        for u in range(3):
+            v0, v1, v2 = f[u], f[(u + 1) % 3], f[(u + 2) % 3]
+            ring[v0].update((v1, v2))
+            edge_faces.setdefault((min(v0, v1), max(v0, v1)), []).append(v2)
+    K = max(len(r) for r in ring)
+    nbr = np.array([sorted(r) + [i] * (K - len(r)) for i, r in enumerate(ring)])
+    nnum = np.array([len(r) for r in ring])
+    inter = [(e, o) for e, o in sorted(edge_faces.items()) if len(o) == 2]
+    rng = np.random.default_rng(seed)
+    edges = {}
+    for k in T.EDGE_TERMS:
+        pick = [inter[i] for i in sorted(rng.choice(len(inter), size=len(inter) // 2, replace=False))]
+        edges[k] = tuple(np.array(col) for col in zip(*[(e[0], e[1], o[0], o[1]) for e, o in pick]))
+    regions = {k: rng.choice(P, size=P // 5, replace=False) for k in T.REGION_TERMS}
+    x = means3D.detach().cpu().numpy().astype(np.float64)
+    dist = np.sqrt(((x[nbr] - x[:, None]) ** 2).sum(-1))
+    w = np.exp(-2000 * dist ** 2)
+    w[nbr == np.arange(P)[:, None]] = 0.0
+    init_scale = rng.uniform(0.002, 0.01, P)
+    return T.TopologyPriors(nbr, dist, w * rng.uniform(0, 1, w.shape), w * rng.uniform(0, 2, w.shape), w, init_scale, nnum, edges,
+                            regions, device=device)
+
+
+def _moved(p, scale, seed):
+    g = torch.Generator().manual_seed(seed)
+    out = {k: v.clone() for k, v in p.items()}
+    out["means3D"] = out["means3D"] + scale * torch.randn(out["means3D"].shape, generator=g)
+    out["unnorm_rotations"] = out["unnorm_rotations"] + 10 * scale * torch.randn(out["unnorm_rotations"].shape, generator=g)
+    return out
+
+
+def test_fused_vs_torch_at_ten_times_the_vertices():
+    """82,800 vertices (10x the facial mesh) on the scaffold head, both frame kinds: fused vs evaluate_torch on the same device."""
+    from scaffold import scene
+    n_lat, n_lon = 180, 460
+    p0 = scene.make_gaussians(n_lat, n_lon, seed=4)
+    p0["log_scales"] = p0["log_scales"] + 0.2 * torch.randn(p0["log_scales"].shape, generator=torch.Generator().manual_seed(1))
+    fused = grid_priors(n_lat, n_lon, p0["means3D"])
+    ref = grid_priors(n_lat, n_lon, p0["means3D"])
+    for frame, p in ((0, p0), (1, _moved(p0, 1e-3, 5))):
+        if frame == 1:
+            fused.begin_frame({k: v.cuda() for k, v in p0.items()})
+            ref.begin_frame({k: v.cuda() for k, v in p0.items()})
+        pc = {k: p[k].cuda().contiguous() for k in KEYS}
+        total, detail = fused.evaluate(pc, frame == 0)
+        pt = {k: torch.nn.Parameter(v.clone()) for k, v in pc.items()}
+        t_total, t_detail = ref.evaluate_torch(pt, frame == 0)
+        t_total.backward()
+        for k in t_detail:
+            r = float(t_detail[k])
+            assert abs(float(detail[k]) - r) <= 1e-4 * abs(r) + 1e-12, (frame, k, float(detail[k]), r)
+        for k, g in zip(KEYS, fused.grads):
+            r = pt[k].grad if pt[k].grad is not None else torch.zeros_like(g)
+            scale = float(r.abs().max())
+            assert float((g - r).abs().max()) <= 1e-4 * max(scale, 1e-30), (frame, k, float((g - r).abs().max()), scale)
+
+
+def _loop_scene():
+    from tests import util
+    from scaffold import scene
+    H, W = 64, 80
+    n_lat, n_lon = 12, 20
+    p0 = scene.make_gaussians(n_lat, n_lon, opacity="B", seed=3)
+    p0['log_scales'] = p0['log_scales'] + torch.randn(240, 3, generator=torch.Generator().manual_seed(9)) * 0.3
+    p0['cam_m'] = torch.zeros(3, 3); p0['cam_c'] = torch.zeros(3, 3)
+    cams = util.to_device(scene.camera_rig(H, W, n_views=3), "cuda")
+    g = torch.Generator().manual_seed(5)
+    dataset = [{'cam': cams[i], 'im': torch.rand(3, H, W, generator=g).cuda(), 'id': i} for i in range(3)]
+    lrs = {'means3D': 1.6e-4, 'rgb_colors': 0.0025, 'unnorm_rotations': 0.001, 'logit_opacities': 0.05, 'log_scales': 0.001,
+           'cam_m': 1e-3, 'cam_c': 1e-3}
+    return p0, dataset, lrs, (n_lat, n_lon)
+
+
+def _groups(params, lrs):
+    return [{'params': [v], 'name': k, 'lr': lrs[k]} for k, v in params.items()]
+
+
+@pytest.mark.parametrize("initial", [True, False])
+def test_optimise_views_with_priors_follows_the_torch_priors(initial):
+    """optimise_views(priors=...) - the fused evaluation added after the rasterizer's backward - against optimise_views with the
+    same terms as extra_loss=evaluate_torch (through autograd), 8 steps, the loop tests' tolerances."""
+    from topo4d_amd import loop
+    from topo4d_amd.optim import FusedAdamPins
+    p0, dataset, lrs, (n_lat, n_lon) = _loop_scene()
+    start = _moved(p0, 0.0 if initial else 1e-3, 6)
+    res = []
+    for mode in ("fused", "torch", "fused_autograd"):
+        pr = grid_priors(n_lat, n_lon, p0["means3D"])
+        if not initial:
+            pr.begin_frame({k: v.cuda() for k, v in p0.items()})
+        params = {k: torch.nn.Parameter(v.clone().cuda()) for k, v in start.items()}
+        opt = FusedAdamPins(_groups(params, lrs), eps=1e-15)
+        if mode == "fused":
+            losses = loop.optimise_views(params, dataset, opt, n_iters=8, seed=4, priors=pr, is_initial_timestep=initial)
+        elif mode == "fused_autograd":
+            losses = loop.optimise_views(params, dataset, opt, n_iters=8, seed=4, priors=pr, is_initial_timestep=initial, explicit=False)
+        else:
+            losses = loop.optimise_views(params, dataset, opt, n_iters=8, seed=4, is_initial_timestep=initial,
+                                         extra_loss=lambda p, rv: pr.evaluate_torch(p, initial)[0])
+        res.append(({k: v.detach().clone() for k, v in params.items()}, torch.stack(losses)))
+    (pf, lf), (pt, lt), (pa, la) = res
+    assert torch.allclose(lf, lt, rtol=2e-5, atol=1e-7), (lf, lt)
+    assert torch.allclose(lf, la, rtol=2e-5, atol=1e-7), (lf, la)
+    for k in pf:
+        moved = (pt[k] - start[k].cuda()).abs()
+        assert ((pf[k] - pt[k]).abs() <= 0.02 * moved + 3e-5).float().mean() > 0.97, k
+        assert ((pf[k] - pa[k]).abs() <= 0.02 * moved + 3e-5).float().mean() > 0.97, k
+
+
+def test_graphed_views_with_priors_replay_the_eager_steps():
+    import random
+    import topo4d_amd
+    from topo4d_amd import loop
+    from topo4d_amd.optim import FusedAdamPins
+    p0, dataset, lrs, (n_lat, n_lon) = _loop_scene()
+    start = _moved(p0, 1e-3, 6)
+    res = []
+    for graphed in (True, False):
+        pr = grid_priors(n_lat, n_lon, p0["means3D"])
+        pr.begin_frame({k: v.cuda() for k, v in p0.items()})
+        params = {k: torch.nn.Parameter(v.clone().cuda()) for k, v in start.items()}
+        opt = FusedAdamPins(_groups(params, lrs), eps=1e-15, capturable=graphed)
+        if graphed:
+            gv = loop.GraphedViews(params, dataset, opt, priors=pr, is_initial_timestep=False)
+            assert gv.explicit
+            topo4d_amd.set_sync_mode("lazy")
+            try:
+                rng, todo, losses = random.Random(4), [], []
+                for _ in range(8):
+                    curr, todo = loop.get_batch(todo, dataset, rng)
+                    losses.append(gv.step(curr['id']).clone())
+                gv.check()
+            finally:
+                topo4d_amd.set_sync_mode("checked")
+        else:
+            losses = loop.optimise_views(params, dataset, opt, n_iters=8, seed=4, priors=pr, is_initial_timestep=False, explicit=True)
+        res.append(({k: v.detach().clone() for k, v in params.items()}, torch.stack(losses)))
+    (pg, lg), (pe, le) = res
+    assert torch.allclose(lg, le, rtol=2e-6, atol=1e-8), (lg, le)
+    for k in pg:
+        assert torch.allclose(pg[k], pe[k], rtol=2e-6, atol=1e-7), (k, (pg[k] - pe[k]).abs().max())

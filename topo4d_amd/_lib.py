@@ -34,6 +34,7 @@ EXPORTS = (
     "t4d_masked_l1_loss", "t4d_masked_l1_scratch_bytes",
     "t4d_adam_pin_step", "t4d_adam_pin_step_graph", "t4d_adam_step_counters", "t4d_dense_interpolate", "t4d_activate_forward", "t4d_activate_backward",
     "t4d_sum_views", "t4d_label_mask_target", "t4d_soft_color_loss", "t4d_soft_color_scratch_bytes",
+    "t4d_priors_record_layout", "t4d_priors_scratch_bytes", "t4d_priors_eval",
 )
 
 
@@ -79,6 +80,22 @@ class T4DAdamTensor(C.Structure):
 
 
 T4D_ADAM_CLEAR_GRAD = 1
+
+
+T4D_PRIORS_TERMS = 14
+T4D_PRIORS_EDGE_TERMS = 6
+T4D_PRIORS_REGION_TERMS = 3
+T4D_PRIORS_ACCUMULATE = 1
+
+
+class T4DPriors(C.Structure):
+    _fields_ = [("P", C.c_int32), ("K", C.c_int32)] + [(n, C.c_void_p) for n in (
+        "nbr", "nbr_dist", "rig_w", "rot_w", "iso_w", "nbr_mask", "nbr_num", "init_scale")] + [
+        ("n_edges", C.c_int32 * T4D_PRIORS_EDGE_TERMS), ("edges", C.c_void_p * T4D_PRIORS_EDGE_TERMS),
+        ("n_region", C.c_int32 * T4D_PRIORS_REGION_TERMS), ("region", C.c_void_p * T4D_PRIORS_REGION_TERMS),
+        ("nbr_t_off", C.c_void_p), ("nbr_t_idx", C.c_void_p), ("rec_off", C.c_void_p * 2), ("rec_idx", C.c_void_p * 2),
+        ("weights", C.c_float * T4D_PRIORS_TERMS), ("prev_inv_rot", C.c_void_p), ("prev_offset", C.c_void_p),
+        ("cos_init", C.c_void_p * 4)]
 
 
 class ExtensionMissing(RuntimeError):
@@ -149,6 +166,13 @@ def load():
     lib.t4d_soft_color_loss.restype = C.c_int
     lib.t4d_soft_color_loss.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_size_t, C.c_void_p]
+    lib.t4d_priors_record_layout.restype = C.c_int64
+    lib.t4d_priors_record_layout.argtypes = [C.POINTER(T4DPriors), C.POINTER(C.c_int64)]
+    lib.t4d_priors_scratch_bytes.restype = C.c_size_t
+    lib.t4d_priors_scratch_bytes.argtypes = [C.POINTER(T4DPriors)]
+    lib.t4d_priors_eval.restype = C.c_int
+    lib.t4d_priors_eval.argtypes = [C.POINTER(T4DPriors), C.c_int32] + [C.c_void_p] * 7 + [C.c_uint32, C.c_void_p, C.c_void_p,
+                                                                                            C.c_size_t, C.c_void_p]
     lib.t4d_adam_pin_step.restype = C.c_int
     lib.t4d_adam_pin_step.argtypes = [C.POINTER(T4DAdamTensor), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]
     lib.t4d_adam_step_counters.restype = C.c_int64

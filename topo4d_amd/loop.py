@@ -20,8 +20,9 @@ loss branches train.py actually executes (train.py:631-632 hard-code use_mask = 
          + 0.02 * l1_loss_v2(dense_rgb_colors, dense_init_colors)                   t4d_soft_color_loss             (train.py:407,541-543)
     loss.backward(); optimizer.step()                                               t4d_rasterize_backward, t4d_adam_pin_step (train.py:738-741)
 
-Same schedule as the reference: one view per iteration, one Adam step per view.  The topology regularisers (train.py:330-368) are
-out of scope; `extra_loss` lets a caller add them as plain torch.  This package has no torch loss of its own:
+Same schedule as the reference: one view per iteration, one Adam step per view.  The topology regularisers (train.py:328-368) run
+fused when a `priors=` TopologyPriors (priors.py, t4d_priors_eval) is given: two launches after the rasterizer's backward that ADD
+their gradients into the buffers the Adam step consumes.  `extra_loss` still lets a caller add further terms as plain torch.  This package has no torch loss of its own:
 `loss_fn` takes the caller's (Topo4D's own l1_loss_v1 / calc_ssim, or the checker in oracle/loss_oracle.py) when the fused
 kernel is not wanted.
 """
@@ -148,7 +149,8 @@ def dense_iteration(params, variables, curr_data, loss_fn: Optional[Callable] = 
 # one iteration chained by hand (no autograd)
 # ------------------------------------------------------------------------------------------------------------
 def explicit_iteration(params, curr_data, cam_grads=None, status_sink=None, target: Optional[torch.Tensor] = None,
-                       dense: bool = False, soft_color=None, extra_loss: Optional[Callable] = None):
+                       dense: bool = False, soft_color=None, extra_loss: Optional[Callable] = None, priors=None,
+                       is_initial_timestep: bool = True):
     """photometric_iteration (or, with `dense`, dense_iteration) + loss.backward() WITHOUT autograd: t4d_rasterize_forward,
     t4d_photometric_loss, t4d_rasterize_backward chained by hand - the activations and their backward inside the rasterizer
     (T4D_FLAG_RAW_PARAMS: the arithmetic of t4d_activate_forward / t4d_activate_backward, no launch of their own) - and none of
@@ -164,11 +166,16 @@ def explicit_iteration(params, curr_data, cam_grads=None, status_sink=None, targ
     `rendervar`), their gradients ADDED to the render's hand-chained ones: the photometric part of the iteration still runs without
     autograd.  (The sum of two gradients is order-independent; a parameter with more extra terms than one is summed in autograd's
     order: equal to the all-autograd iteration to rounding, not bit for bit.)
+    `priors` (a priors.TopologyPriors): the topology regularisers of get_loss (train.py:328-368) for the frame kind
+    `is_initial_timestep` says, fused (t4d_priors_eval) on the iteration's stream after the rasterizer's backward, their gradients
+    ADDED to its gradient buffers and their total to the loss: no autograd and no allocation of its own per step.
     `cam_grads`: {'cam_m': [n_cams, 3], 'cam_c': ...} persistent ZERO buffers; the loss kernel writes row `id` of each.
     `status_sink`: data pointer of 16 bytes of pinned host memory for the forward's status block (ViewBatch.status_sink).
     Returns (loss: device scalar, radius, grads: {parameter name: gradient tensor} for the parameters that require a gradient,
     ViewBatch, dL/dmeans2D)."""
     from . import rasterizer as R
+    if priors is not None and dense:
+        raise ValueError("explicit_iteration: the topology priors belong to the geometry loop (dense=False)")
     cam = curr_data['cam']
     n = _names(dense)
     dev = params[n['means3D']].device
@@ -200,6 +207,9 @@ def explicit_iteration(params, curr_data, cam_grads=None, status_sink=None, targ
             dcm.zero_(); dcc.zero_()
         raise
     total = l[0]
+    if priors is not None:
+        l_pri, _ = priors.evaluate(params, is_initial_timestep, grads=(g['means3D'], g['rotations'], g['scales']), accumulate=True)
+        total = torch.add(total, l_pri)
     if soft_color is not None:
         init, weight = soft_color
         l_soft, _ = t4d_loss.soft_color_loss_raw(d('rgb_colors'), init, float(weight), grad=g['colors_precomp'], accumulate=True)
@@ -239,13 +249,14 @@ def explicit_iteration(params, curr_data, cam_grads=None, status_sink=None, targ
 
 
 def explicit_frame_iteration(params, frame: List[dict], gt: Optional[torch.Tensor] = None, cam_grads=None, use_mask: bool = False,
-                             is_initial_timestep: bool = True, label_colors=None):
+                             is_initial_timestep: bool = True, label_colors=None, priors=None):
     """explicit_iteration for ALL cameras of a frame in one launch set (24 views cost 0.45 ms where one costs 0.08): activations,
     one multi-view render, one batched loss, one multi-view backward, view-summed gradients (t4d_sum_views), activation backward -
     chained by hand, no autograd.  `frame`: the cameras' dataset entries; `gt`: their target images stacked [V,3,H,W] (stacked
     here from target_image(...) when None - pass it to keep that copy out of the loop).  The entries' ids must be one ascending
     range (rows of cam_m / cam_c are passed as a view).  Returns (per-view losses [V], radii [V,P], grads of the loss SUMMED
-    over the views, ViewBatch)."""
+    over the views, ViewBatch).  `priors`: the topology regularisers, evaluated ONCE for the frame kind `is_initial_timestep` says
+    and added to the summed gradients (as explicit_iteration); their weighted terms and total are in `priors.losses`."""
     from . import rasterizer as R
     cams = [e['cam'] for e in frame]
     V = len(cams)
@@ -271,6 +282,8 @@ def explicit_frame_iteration(params, frame: List[dict], gt: Optional[torch.Tenso
     l, d_im, dcm, dcc = t4d_loss.photometric_loss_raw(im, gt, cm, cc, dcm, dcc)
     g = R._sum_views(batch.backward(d_im), V, need_means2D=False)
     d_ur, d_lo, d_ls = activate_backward(ur, op, sc, g['rotations'], g['opacities'], g['scales'])
+    if priors is not None:
+        priors.evaluate(params, is_initial_timestep, grads=(g['means3D'], d_ur, d_ls), accumulate=True)
     grads = {'means3D': g['means3D'], 'rgb_colors': g['colors_precomp'], 'unnorm_rotations': d_ur, 'logit_opacities': d_lo,
              'log_scales': d_ls}
     grads = {k: v for k, v in grads.items() if params[k].requires_grad}
@@ -309,16 +322,29 @@ def _adopt_cam_grads(params, optimizer):
     return cam_grads
 
 
+def _with_priors(extra_loss: Optional[Callable], priors, is_initial_timestep: bool) -> Optional[Callable]:
+    """extra_loss plus the fused priors behind their autograd.Function (the iterations that go through autograd)."""
+    if priors is None:
+        return extra_loss
+    fused = priors.as_extra_loss(is_initial_timestep)
+    if extra_loss is None:
+        return fused
+    return lambda params, rendervar: extra_loss(params, rendervar) + fused(params, rendervar)
+
+
 def optimise_views(params, dataset: List[dict], optimizer, n_iters: int, seed: int = 0, loss_fn: Optional[Callable] = None,
                    extra_loss: Optional[Callable] = None, max_2D_radius: Optional[torch.Tensor] = None,
-                   explicit: Optional[bool] = None, use_mask: bool = False, is_initial_timestep: bool = True, label_colors=None):
+                   explicit: Optional[bool] = None, use_mask: bool = False, is_initial_timestep: bool = True, label_colors=None,
+                   priors=None):
     """train.py:661-673 for `n_iters` iterations.  Returns the list of per-iteration losses (device scalars, no sync).
     `use_mask`, `is_initial_timestep`: get_loss's branch (train.py:315-327; Topo4D runs use_mask=True, i.e. the masked target in
     every frame after the first - `label_colors` as in prepare_masked_targets, which is called here once).
     `explicit` (default: when possible - fused loss, a FusedAdamPins optimiser, the scale + rotation / RGB parametrisation): the
     render, its loss and its backward are chained by hand (explicit_iteration) instead of going through autograd - same
     arithmetic, a third of the host time; `extra_loss` terms (the regularisers of train.py:330-368) are differentiated on their
-    own and their gradients added."""
+    own and their gradients added.  `priors` (priors.TopologyPriors): the topology regularisers of get_loss (train.py:328-368)
+    for the frame kind `is_initial_timestep` says, fused into every iteration (explicit: added into the gradient buffers after the
+    rasterizer's backward; otherwise through their autograd.Function)."""
     rng = Random(seed)
     todo: list = []
     losses = []
@@ -335,7 +361,8 @@ def optimise_views(params, dataset: List[dict], optimizer, n_iters: int, seed: i
             for _ in range(n_iters):
                 curr, todo = get_batch(todo, dataset, rng)
                 l, radius, grads, _, _ = explicit_iteration(params, curr, cam_grads, target=curr['masked_im'] if masked else None,
-                                                            extra_loss=extra_loss)
+                                                            extra_loss=extra_loss, priors=priors,
+                                                            is_initial_timestep=is_initial_timestep)
                 for k, gr in grads.items():
                     params[k].grad = gr
                 optimizer.step()
@@ -345,6 +372,7 @@ def optimise_views(params, dataset: List[dict], optimizer, n_iters: int, seed: i
         finally:
             optimizer.clear_grad = before
         return losses
+    extra_loss = _with_priors(extra_loss, priors, is_initial_timestep)
     for _ in range(n_iters):
         curr, todo = get_batch(todo, dataset, rng)
         l, radius, _ = photometric_iteration(params, curr, loss_fn, extra_loss, use_mask=use_mask,
@@ -419,7 +447,9 @@ class GraphedViews:
         gv.load_frame(next_dataset)                        # next frame: new target images into the recorded buffers
                                                            # (dense=True: ALSO the re-bound dense_init_colors / dense_means3D, below)
 
-    `use_mask` / `is_initial_timestep` / `label_colors`: get_loss's branch, as optimise_views.  `dense=True` (with `variables`)
+    `use_mask` / `is_initial_timestep` / `label_colors`: get_loss's branch, as optimise_views.  `priors`: the fused topology
+    regularisers of that frame kind, recorded in every camera's graph (begin_frame writes the state they read in place, so the
+    graphs stay valid from frame to frame).  `dense=True` (with `variables`)
     records the texture loop's iteration instead (pins before the render, dense parameters, no affine, soft colour).
     The recorded kernels read `variables['dense_init_colors']` and `params['dense_means3D']` through the pointers they had at
     capture time, and the reference RE-BINDS both to new tensors in every later frame (update_dense_states, train.py:498-507).
@@ -433,7 +463,7 @@ class GraphedViews:
 
     def __init__(self, params, dataset: List[dict], optimizer, loss_fn: Optional[Callable] = None, extra_loss: Optional[Callable] = None,
                  explicit: Optional[bool] = None, use_mask: bool = False, is_initial_timestep: bool = True, label_colors=None,
-                 dense: bool = False, variables: Optional[dict] = None, soft_color_weight: float = SOFT_COLOR_WEIGHT):
+                 dense: bool = False, variables: Optional[dict] = None, soft_color_weight: float = SOFT_COLOR_WEIGHT, priors=None):
         from . import rasterizer as R
         if not getattr(optimizer, "capturable", False):
             raise ValueError("GraphedViews needs FusedAdamPins(..., capturable=True)")
@@ -456,7 +486,11 @@ class GraphedViews:
         self.explicit = can if explicit is None else bool(explicit)
         if dense and not self.explicit:
             raise ValueError("GraphedViews(dense=True) records the hand-chained iteration only (fused losses)")
+        if dense and priors is not None:
+            raise ValueError("GraphedViews: the topology priors belong to the geometry loop (dense=False)")
+        self._priors = priors
         self._loss_fn, self._extra_loss = loss_fn, extra_loss
+        self._extra_loss_autograd = _with_priors(extra_loss, priors, bool(is_initial_timestep))
         self._cam_grads = None
         self._clear_before = set(optimizer.clear_grad)
         self.graphs, self._status_host = [], None
@@ -534,7 +568,7 @@ class GraphedViews:
     def _autograd_forward(self, i, data):
         entry = dict(data)
         entry['im'] = self._targets[i]                 # (the branch is resolved already: the recorded buffer IS the target)
-        return photometric_iteration(self.params, entry, self._loss_fn, self._extra_loss)
+        return photometric_iteration(self.params, entry, self._loss_fn, self._extra_loss_autograd)
 
     def _explicit_step(self, i, data):
         """One iteration chained by hand: gradients handed to the optimiser as `.grad`, then the fused step."""
@@ -547,7 +581,8 @@ class GraphedViews:
                                                               soft_color=(self.variables['dense_init_colors'], self.soft_color_weight))
         else:
             l, radius, grads, batch, g2d = explicit_iteration(self.params, data, self._cam_grads, sink, target=self._targets[i],
-                                                              extra_loss=self._extra_loss)
+                                                              extra_loss=self._extra_loss, priors=self._priors,
+                                                              is_initial_timestep=self._branch[1])
         for k, gr in grads.items():
             self.params[k].grad = gr
         self.opt.step(pins=not self.dense)
