@@ -322,6 +322,51 @@ int t4d_dense_interpolate(const float *attribute, const int32_t *quad_faces /* [
                           const int32_t *vertex_father /* [n_dense] */, const double *weight /* [n_dense,4] */,
                           int64_t n_coarse, int64_t n_dense, int32_t width, float *out, void *hip_stream);
 
+/* UV-space densification of the texture pass: train.py:214-243 - helpers.build_dense_vertices_2 / bilinear_interpolate_2
+ * (helpers.py:421-654), the face lists of train.py:233-236 and triangulate_faces (helpers.py:657-667) - on the device, in the same
+ * order and with the same bits (the reference runs it once per run in Python: minutes at --density 30).  The sequential `edge_dict`
+ * of the reference is replaced by a host pre-pass (topo4d_amd/densify.py:plan_dense_mesh) that gives every frontal quad q:
+ *   plan[2q]   = flags: bit s set = edge slot s is borrowed (slot 0: row i = 0, face[0] -> face[3]; 1: column j = 0, face[0] ->
+ *                face[1]; 2: row i = d+1, face[1] -> face[2]; 3: column j = d+1, face[3] -> face[2])
+ *   plan[2q+1] = the exclusive prefix sum of the quads' generated-point counts (d+2)^2 - 4 - d * popcount(flags)
+ *   src[4q+s]  = owner quad * 4 + owner slot of a borrowed slot (the first frontal quad containing the edge), -1 otherwise.
+ * Outputs (device): dense_vertex [n_vert + n_points, 3] float64 (float32 values: coarse rows, then the generated points),
+ * vertex_father [n_points] int32, vertex_weight [n_points, 4] float64, dense_uvs [n_uv + n_points, 2] float64, and the
+ * triangulated faces / uv_faces [n_faces, 3] int32: triangles, then the densified quads, then the non-frontal quads, each quad as
+ * [0,1,2], [0,2,3].  Every index the kernels read is range-checked; a violation sets the int32 at the start of the scratch to a
+ * nonzero value (the caller reads it after the stream) and skips the read. */
+typedef struct T4DDenseMesh {
+    int32_t n_vert, n_uv;                       /* coarse vertices (params['means3D'] rows), len(uvs_ori) */
+    int32_t n_quads, density;                   /* frontal quads (densified), d >= 1 */
+    int32_t n_tri, n_rest;                      /* triangles, non-frontal quads */
+    int64_t n_points, n_faces;                  /* generated points (sum of the counts), n_tri + 2 (n_quads (d+1)^2 + n_rest) */
+    const float *vertices;                      /* [n_vert,3] */
+    const double *uvs;                          /* [n_uv,2] uvs_ori */
+    const int32_t *quads, *uv_quads;            /* [n_quads,4] frontal quads and their UV faces, in processing order */
+    const int32_t *plan, *src;                  /* [n_quads,2], [n_quads,4]: see above */
+    const int32_t *tri, *uv_tri;                /* [n_tri,3] */
+    const int32_t *rest, *uv_rest;              /* [n_rest,4] */
+    double *dense_vertex;
+    int32_t *vertex_father;
+    double *vertex_weight;
+    double *dense_uvs;
+    int32_t *faces, *uv_faces;
+} T4DDenseMesh;
+size_t t4d_dense_scratch_bytes(const T4DDenseMesh *mesh);
+int t4d_dense_build(const T4DDenseMesh *mesh, void *scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Exact k-nearest-neighbour mean squared distance: helpers.py:147-157 `o3d_knn(pts, k)` followed by `.mean(-1)` (train.py:131-132
+ * with k = 1, :245-246 with k = 4).  points [n,3] float64 (device); mean [n] float64: per point the k+1 smallest squared distances,
+ * its own zero included, summed in ascending order and divided by k, each distance ((dx*dx + dy*dy) + dz*dz) without contraction
+ * (nanoflann's L2 adaptor for dim 3) - equal to the reference's drop-the-first-hit mean whatever order ties and duplicates fall
+ * in, and bit-identical from run to run.  log_scales [n,3] float32 or NULL: float(log(sqrt(max(mean, 1e-7)))) tiled to three
+ * columns (dense_log_scales, train.py:262).  A hashed uniform grid over the occupied cells, searched in cube shells; no host
+ * synchronisation.  1 <= k <= T4D_KNN_MAX_K, k < n < 2^30. */
+#define T4D_KNN_MAX_K 15
+size_t t4d_knn_scratch_bytes(int64_t n, int32_t k);
+int t4d_knn_mean_sq_dist(const double *points, int64_t n, int32_t k, double *mean, float *log_scales, void *scratch,
+                         size_t scratch_bytes, void *hip_stream);
+
 /* Parameter activations of params2rendervar (helpers.py:91-100: rotations = F.normalize(unnorm_rotations), opacities =
  * sigmoid(logit_opacities), scales = exp(log_scales)) in one launch, and their vector-Jacobian products in one launch
  * (torch runs three kernels forward and about a dozen through autograd backward, every iteration: SURVEY.md row a2).

@@ -35,6 +35,7 @@ EXPORTS = (
     "t4d_adam_pin_step", "t4d_adam_pin_step_graph", "t4d_adam_step_counters", "t4d_dense_interpolate", "t4d_activate_forward", "t4d_activate_backward",
     "t4d_sum_views", "t4d_label_mask_target", "t4d_soft_color_loss", "t4d_soft_color_scratch_bytes",
     "t4d_priors_record_layout", "t4d_priors_scratch_bytes", "t4d_priors_eval",
+    "t4d_dense_scratch_bytes", "t4d_dense_build", "t4d_knn_scratch_bytes", "t4d_knn_mean_sq_dist",
 )
 
 
@@ -96,6 +97,16 @@ class T4DPriors(C.Structure):
         ("nbr_t_off", C.c_void_p), ("nbr_t_idx", C.c_void_p), ("rec_off", C.c_void_p * 2), ("rec_idx", C.c_void_p * 2),
         ("weights", C.c_float * T4D_PRIORS_TERMS), ("prev_inv_rot", C.c_void_p), ("prev_offset", C.c_void_p),
         ("cos_init", C.c_void_p * 4)]
+
+
+T4D_KNN_MAX_K = 15
+
+
+class T4DDenseMesh(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_vert", "n_uv", "n_quads", "density", "n_tri", "n_rest")] + [
+        ("n_points", C.c_int64), ("n_faces", C.c_int64)] + [(n, C.c_void_p) for n in (
+            "vertices", "uvs", "quads", "uv_quads", "plan", "src", "tri", "uv_tri", "rest", "uv_rest",
+            "dense_vertex", "vertex_father", "vertex_weight", "dense_uvs", "faces", "uv_faces")]
 
 
 class ExtensionMissing(RuntimeError):
@@ -173,6 +184,14 @@ def load():
     lib.t4d_priors_eval.restype = C.c_int
     lib.t4d_priors_eval.argtypes = [C.POINTER(T4DPriors), C.c_int32] + [C.c_void_p] * 7 + [C.c_uint32, C.c_void_p, C.c_void_p,
                                                                                             C.c_size_t, C.c_void_p]
+    lib.t4d_dense_scratch_bytes.restype = C.c_size_t
+    lib.t4d_dense_scratch_bytes.argtypes = [C.POINTER(T4DDenseMesh)]
+    lib.t4d_dense_build.restype = C.c_int
+    lib.t4d_dense_build.argtypes = [C.POINTER(T4DDenseMesh), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.t4d_knn_scratch_bytes.restype = C.c_size_t
+    lib.t4d_knn_scratch_bytes.argtypes = [C.c_int64, C.c_int32]
+    lib.t4d_knn_mean_sq_dist.restype = C.c_int
+    lib.t4d_knn_mean_sq_dist.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.t4d_adam_pin_step.restype = C.c_int
     lib.t4d_adam_pin_step.argtypes = [C.POINTER(T4DAdamTensor), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]
     lib.t4d_adam_step_counters.restype = C.c_int64

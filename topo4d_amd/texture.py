@@ -26,6 +26,8 @@ _CAP = {}
 def process_uv(uv_coords, uv_h: int = 256, uv_w: int = 256):
     """helpers.py:945-950: u*(w-1), flip v, append z = 0.  (The reference mutates its argument in place and then
     returns a new hstack'ed array; this mirror leaves the argument untouched.)"""
+    if isinstance(uv_coords, torch.Tensor):                    # e.g. variables['dense_uvs'] from densify.build_dense_mesh
+        uv_coords = uv_coords.detach().cpu().numpy()
     uv = np.array(uv_coords, dtype=np.float64, copy=True)
     uv[:, 0] = uv[:, 0] * (uv_w - 1)
     uv[:, 1] = uv[:, 1] * (uv_h - 1)
@@ -122,21 +124,23 @@ def compute_vertex_attribute_by_weight(variables, attribute: torch.Tensor) -> to
     """helpers.py:237-253 `compute_vertex_attribute_by_weight_2` on the device: `attribute` [n_coarse, d] (float32, GPU) ->
     [n_dense_total, d] float32, without the per-frame device->host->device round trip of train.py:504-506.
     `variables` holds the same keys the reference uses: 'dense_vertex_father' [n_dense(,1)], 'dense_vertex_weight'
-    [n_dense,4], 'dense_quad_faces' [n_quads,4], 'dense_vertex' (only its length is used).  The index/weight arrays are
-    uploaded once and cached on the dict."""
+    [n_dense,4], 'dense_quad_faces' [n_quads,4], 'dense_vertex' (only its length is used) - numpy arrays as the reference
+    builds them, or the device tensors of densify.build_dense_mesh.  The index/weight arrays are uploaded once and cached on
+    the dict."""
     if not attribute.is_cuda:
         raise RuntimeError("topo4d_amd has no CPU path: tensors must live on a HIP device")
     lib = _lib.load()
     dev = attribute.device
     cache = variables.setdefault("_t4d_dense_cache", {})
     if cache.get("device") != dev:
-        cache["father"] = torch.as_tensor(np.asarray(variables["dense_vertex_father"]).reshape(-1), dtype=torch.int32).to(dev)
-        cache["weight"] = torch.as_tensor(np.asarray(variables["dense_vertex_weight"], dtype=np.float64)).to(dev).contiguous()
-        cache["quads"] = torch.as_tensor(np.asarray(variables["dense_quad_faces"]), dtype=torch.int32).to(dev).contiguous()
+        up = lambda a, dt: (a.to(device=dev, dtype=dt) if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a), dtype=dt).to(dev))
+        cache["father"] = up(variables["dense_vertex_father"], torch.int32).reshape(-1).contiguous()
+        cache["weight"] = up(variables["dense_vertex_weight"], torch.float64).contiguous()
+        cache["quads"] = up(variables["dense_quad_faces"], torch.int32).contiguous()
         cache["device"] = dev
     attr = attribute.detach().float().contiguous()
     n_coarse, width = int(attr.shape[0]), int(attr.shape[1])
-    n_total = int(np.asarray(variables["dense_vertex"]).shape[0])
+    n_total = int(variables["dense_vertex"].shape[0]) if hasattr(variables["dense_vertex"], "shape") else len(variables["dense_vertex"])
     n_dense = n_total - n_coarse
     assert n_dense == cache["father"].numel() == cache["weight"].shape[0]
     out = torch.empty(n_total, width, dtype=torch.float32, device=dev)
