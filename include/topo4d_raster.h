@@ -403,6 +403,19 @@ int t4d_texture_render_colors(const float *vertices, const int32_t *triangles, c
                               float *image, float *depth_buffer, void *scratch, size_t scratch_bytes, int64_t pair_capacity,
                               int64_t *pairs_needed, void *hip_stream);
 
+/* Lossless PNG encoder for a device image (write_texture(..., encoder="gpu"): the last CPU step of save_mesh, helpers.py:953-960).
+ * image [h,w,c] on the device, uint8 (is_float32 = 0) or float32 (is_float32 = 1, quantised exactly like numpy's
+ * (x*255).astype(np.uint8) on x86-64: truncation toward zero to int32, low byte kept, NaN -> 0); c in {1, 3, 4} gives colour
+ * type 0 / 2 / 6, 8-bit, no interlace.  Writes the whole file (signature, IHDR, IDATs, IEND) to `out` (device,
+ * out_capacity >= t4d_png_max_bytes) and its length to *out_bytes (device).  The rows are filtered with the PNG filter of least
+ * sum |int8 residual|; the deflate stream is independent 16 KiB segments of literals and distance-1 runs under one dynamic
+ * Huffman block each (or stored).  The bytes are a pure function of the pixels and the shape.  t4d_png_max_bytes is a function
+ * of (h, w, c) alone, so the caller allocates once.  Does not synchronise the stream. */
+size_t t4d_png_max_bytes(int32_t h, int32_t w, int32_t c);
+size_t t4d_png_scratch_bytes(int32_t h, int32_t w, int32_t c);
+int t4d_png_encode(const void *image, int32_t is_float32, int32_t h, int32_t w, int32_t c, uint8_t *out, size_t out_capacity,
+                   int64_t *out_bytes /* device */, void *scratch, size_t scratch_bytes, void *hip_stream);
+
 /* Optional per-kernel timing with HIP events recorded on the stream the kernels are launched on.  Between
  * t4d_profile_begin() and t4d_profile_end() every kernel launch of this library is bracketed by two events;
  * t4d_profile_end() synchronises them and returns, per kernel, the summed elapsed time and the launch count.

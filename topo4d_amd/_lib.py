@@ -36,6 +36,7 @@ EXPORTS = (
     "t4d_sum_views", "t4d_label_mask_target", "t4d_soft_color_loss", "t4d_soft_color_scratch_bytes",
     "t4d_priors_record_layout", "t4d_priors_scratch_bytes", "t4d_priors_eval",
     "t4d_dense_scratch_bytes", "t4d_dense_build", "t4d_knn_scratch_bytes", "t4d_knn_mean_sq_dist",
+    "t4d_png_max_bytes", "t4d_png_scratch_bytes", "t4d_png_encode",
 )
 
 
@@ -192,6 +193,13 @@ def load():
     lib.t4d_knn_scratch_bytes.argtypes = [C.c_int64, C.c_int32]
     lib.t4d_knn_mean_sq_dist.restype = C.c_int
     lib.t4d_knn_mean_sq_dist.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.t4d_png_max_bytes.restype = C.c_size_t
+    lib.t4d_png_max_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.t4d_png_scratch_bytes.restype = C.c_size_t
+    lib.t4d_png_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.t4d_png_encode.restype = C.c_int
+    lib.t4d_png_encode.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]
     lib.t4d_adam_pin_step.restype = C.c_int
     lib.t4d_adam_pin_step.argtypes = [C.POINTER(T4DAdamTensor), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]
     lib.t4d_adam_step_counters.restype = C.c_int64

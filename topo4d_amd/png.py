@@ -1,0 +1,92 @@
+"""
+Lossless PNG encoding of a device image on the GPU, over `t4d_png_encode` (include/topo4d_raster.h, csrc/t4d_png.hip).
+
+    encode_png(image) -> bytes        uint8 or float32 [H,W] / [H,W,C], C in {1, 3, 4}, on a HIP device
+    write_png(path, image)
+    max_encoded_bytes(h, w, c)        the output bound the encoder allocates (a function of the shape alone)
+
+float32 is quantised exactly as numpy's `(x * 255).astype(np.uint8)` on x86-64, so `encode_png(render_colors(...))` decodes to
+the array `texture.bake_texture` returns.  Only the finished file crosses to the host.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from ._lib import T4D_OK
+
+_PINNED = {}
+
+
+def _shape(h: int, w: int, c: int) -> None:
+    if h < 1 or w < 1 or c not in (1, 3, 4):
+        raise ValueError(f"PNG image must be [H,W] or [H,W,C] with H, W >= 1 and C in (1, 3, 4); got {(h, w, c)}")
+
+
+def max_encoded_bytes(h: int, w: int, c: int) -> int:
+    """Upper bound on the file size for an [h,w,c] image: every segment stored uncompressed, plus the chunk framing."""
+    _shape(int(h), int(w), int(c))
+    n = _lib.load().t4d_png_max_bytes(int(h), int(w), int(c))
+    if n == 0:
+        raise ValueError(f"t4d_png_max_bytes: {_lib.last_error()}")
+    return int(n)
+
+
+def _check(image) -> tuple:
+    if not isinstance(image, torch.Tensor):
+        raise ValueError("encode_png expects a torch tensor")
+    if image.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"encode_png expects uint8 or float32, got {image.dtype}")
+    if image.dim() == 2:
+        h, w, c = int(image.shape[0]), int(image.shape[1]), 1
+    elif image.dim() == 3:
+        h, w, c = (int(d) for d in image.shape)
+    else:
+        raise ValueError(f"encode_png expects [H,W] or [H,W,C], got shape {tuple(image.shape)}")
+    _shape(h, w, c)
+    if not image.is_cuda:
+        raise RuntimeError("topo4d_amd has no CPU path: encode_png needs the image on a HIP device")
+    return h, w, c
+
+
+def _pinned(nbytes: int) -> torch.Tensor:
+    buf = _PINNED.get("host")
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        _PINNED["host"] = buf
+    return buf
+
+
+def encode_png(image: torch.Tensor) -> bytes:
+    """The PNG file of `image` (see the module docstring).  Runs on torch's current stream; synchronises once to read the length,
+    then copies exactly that many bytes through a reused pinned buffer."""
+    h, w, c = _check(image)
+    lib = _lib.load()
+    dev = image.device
+    img = image.contiguous()
+    cap = max_encoded_bytes(h, w, c)
+    nscratch = int(lib.t4d_png_scratch_bytes(h, w, c))
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+    length = torch.empty(1, dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    rc = lib.t4d_png_encode(C.c_void_p(img.data_ptr()), 1 if img.dtype == torch.float32 else 0, h, w, c, C.c_void_p(out.data_ptr()),
+                            cap, C.c_void_p(length.data_ptr()), C.c_void_p(scratch.data_ptr()), nscratch,
+                            C.c_void_p(stream.cuda_stream))
+    if rc != T4D_OK:
+        raise RuntimeError(f"t4d_png_encode failed (code {rc}): {_lib.last_error()}")
+    n = int(length.item())                                        # the one synchronisation
+    if n <= 0 or n > cap:
+        raise RuntimeError(f"t4d_png_encode: bad output length {n} (capacity {cap})")
+    host = _pinned(n)
+    host[:n].copy_(out[:n])
+    return host[:n].numpy().tobytes()
+
+
+def write_png(path, image: torch.Tensor) -> None:
+    """encode_png(image) written to `path`."""
+    data = encode_png(image)
+    with open(path, "wb") as f:
+        f.write(data)

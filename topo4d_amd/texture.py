@@ -4,7 +4,7 @@ Texture bake on the GPU — host-side mirror of the reference interface for BASE
 Mirrors, name for name:
   process_uv(uv_coords, uv_h, uv_w)                       helpers.py:945-950
   render_colors(vertices, triangles, colors, h, w, c, BG) face3d/mesh/render.py:52-86   (-> _render_colors_core)
-  write_texture(path, uvs, colors, faces, res)            helpers.py:953-960
+  write_texture(path, uvs, colors, faces, res)            helpers.py:953-960   (encoder="gpu": png.encode_png)
 over `t4d_texture_render_colors` (include/topo4d_raster.h).  Results are bit-identical to the reference's CPU code
 (tests/test_gpu_texture.py compares with the reference's own source compiled into oracle/_ref).
 There is no CPU path here either.
@@ -114,8 +114,15 @@ def bake_texture_sharded(uvs, colors, faces, res: int = 1024, device="cuda") -> 
     return (full.cpu().numpy() * 255).astype(np.uint8)
 
 
-def write_texture(path, uvs, colors, faces, res: int = 1024, device="cuda") -> None:
-    """helpers.py:953-960 (`io.imsave` replaced by PIL, which this image has)."""
+def write_texture(path, uvs, colors, faces, res: int = 1024, device="cuda", encoder: str = "pil") -> None:
+    """helpers.py:953-960 (`io.imsave` replaced by PIL, which this image has).  encoder="gpu" encodes the device image with
+    png.encode_png instead: no image copy to the host, no numpy pass, no zlib; the file decodes to the same pixels."""
+    if encoder not in ("pil", "gpu"):
+        raise ValueError(f"write_texture: encoder must be 'pil' or 'gpu', got {encoder!r}")
+    if encoder == "gpu":
+        from .png import write_png
+        write_png(path, render_colors(process_uv(uvs, res, res), faces, colors, res, res, c=3, device=device))
+        return
     from PIL import Image
     Image.fromarray(np.squeeze(bake_texture(uvs, colors, faces, res, device))).save(path)
 
