@@ -34,6 +34,38 @@ def test_library_exports_every_declared_symbol():
     assert lib.t4d_abi_version() == _lib.T4D_ABI_VERSION
 
 
+def header_prototypes():
+    """{name: (return type, [argument types])} of the header's functions; a pointer type is "*", a scalar its C name."""
+    txt = re.sub(r"/\*.*?\*/|//[^\n]*|^#[^\n]*", "", open(HEADER).read(), flags=re.S | re.M)
+    kind = lambda decl: "*" if "*" in decl else decl.replace("const", "").split()[0]
+    protos = {}
+    for ret, name, args in re.findall(r"([\w\s*]+?)\b(t4d_\w+)\s*\(([^)]*)\)\s*;", txt):
+        args = [] if args.strip() == "void" else [kind(a) for a in args.split(",")]
+        protos[name] = (kind(ret), args)
+    return protos
+
+
+def test_signature_table_matches_the_header_prototypes():
+    """Every ctypes binding has the arity, pointer-ness, width and float-ness of its prototype (a wrong table entry would pass
+    the arguments of a call wrongly without any error)."""
+    from topo4d_amd import _lib
+    scalars = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+               "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+
+    def shape(t):                                         # a ctypes type -> "*" or (bytes, floating point)
+        if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+            return "*"
+        return C.sizeof(t), issubclass(t, (C.c_float, C.c_double))
+
+    protos = header_prototypes()
+    assert list(protos) == list(_lib.SIGNATURES), "one table entry per prototype, in header order"
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        ret, args = protos[name]
+        want = lambda c: c if c == "*" else shape(scalars[c])
+        assert shape(restype) == want(ret), (name, "return type")
+        assert [shape(t) for t in argtypes] == [want(a) for a in args], (name, "arguments")
+
+
 def test_struct_layouts_match_ctypes():
     from topo4d_amd import _lib
     src = r'''

@@ -4,11 +4,16 @@ ctypes binding of the C-ABI shared library (include/topo4d_raster.h).
 The library is built in-tree by `__graft_entry__.build()` / `python -m topo4d_amd.build` with
 `hipcc --offload-arch=gfx950`.  There is NO fallback: if the shared object is missing or does not load, every
 entry point of the product raises — a rasterizer that silently ran on the CPU would void every parity claim.
+
+Every entry point is bound from one table, SIGNATURES (tests/test_abi.py pins it to the header); `ptr`, `stream`, `call` and
+`error` are what the wrappers of the other modules share.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+
+import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # T4D_LIB: load another build of the SAME library (an experiment build next to the shipped one, tools/ab_build.sh); there
@@ -24,21 +29,6 @@ T4D_FLAG_CHECKED, T4D_FLAG_DEBUG_SYNC, T4D_FLAG_PREFILTERED, T4D_FLAG_ASYNC_STAT
 T4D_FLAG_SHORT_BINS = 32
 T4D_FLAG_LONG_LISTS = 64
 T4D_FLAG_RAW_PARAMS = 128
-
-# every symbol include/topo4d_raster.h declares (tests/test_abi.py checks header <-> this list <-> the .so)
-EXPORTS = (
-    "t4d_abi_version", "t4d_last_error", "t4d_state_bytes", "t4d_backward_scratch_bytes",
-    "t4d_rasterize_forward", "t4d_rasterize_backward", "t4d_fetch_status", "t4d_mark_visible",
-    "t4d_debug_state_layout", "t4d_profile_begin", "t4d_profile_end", "t4d_view_dot", "t4d_view_dot_scratch_bytes",
-    "t4d_texture_bake", "t4d_texture_render_colors", "t4d_texture_bake_scratch_bytes", "t4d_photometric_loss", "t4d_photometric_scratch_bytes",
-    "t4d_masked_l1_loss", "t4d_masked_l1_scratch_bytes",
-    "t4d_adam_pin_step", "t4d_adam_pin_step_graph", "t4d_adam_step_counters", "t4d_dense_interpolate", "t4d_activate_forward", "t4d_activate_backward",
-    "t4d_sum_views", "t4d_label_mask_target", "t4d_soft_color_loss", "t4d_soft_color_scratch_bytes",
-    "t4d_priors_record_layout", "t4d_priors_scratch_bytes", "t4d_priors_eval",
-    "t4d_dense_scratch_bytes", "t4d_dense_build", "t4d_knn_scratch_bytes", "t4d_knn_mean_sq_dist",
-    "t4d_png_max_bytes", "t4d_png_scratch_bytes", "t4d_png_encode",
-)
-
 
 class T4DProblem(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("n_views", C.c_int32), ("P", C.c_int32), ("H", C.c_int32),
@@ -110,6 +100,56 @@ class T4DDenseMesh(C.Structure):
             "dense_vertex", "vertex_father", "vertex_weight", "dense_uvs", "faces", "uv_faces")]
 
 
+_VP, _I32, _I64, _F32, _SZ, _INT = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t, C.c_int
+_PROB = C.POINTER(T4DProblem)
+
+# name -> (restype, argtypes) of every function include/topo4d_raster.h declares, in header order (tests/test_abi.py checks the
+# names against the header and the .so, and every signature against its prototype); a data pointer or stream is a c_void_p
+SIGNATURES = {
+    "t4d_abi_version": (C.c_uint32, []),
+    "t4d_last_error": (C.c_char_p, []),
+    "t4d_state_bytes": (_SZ, [_PROB]),
+    "t4d_backward_scratch_bytes": (_SZ, [_PROB]),
+    "t4d_rasterize_forward": (_INT, [_PROB, C.POINTER(T4DForwardIO), C.POINTER(T4DStatus), _VP]),
+    "t4d_rasterize_backward": (_INT, [_PROB, C.POINTER(T4DBackwardIO), _VP]),
+    "t4d_fetch_status": (_INT, [_PROB, _VP, C.POINTER(T4DStatus), _VP]),
+    "t4d_mark_visible": (_INT, [_I32] + [_VP] * 4),
+    "t4d_view_dot_scratch_bytes": (_SZ, [_I32]),
+    "t4d_view_dot": (_INT, [_I32, _I64] + [_VP] * 5),
+    "t4d_sum_views": (_INT, [_I32, _I32, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(_I64), _VP]),
+    "t4d_photometric_scratch_bytes": (_SZ, [_I32] * 3),
+    "t4d_photometric_loss": (_INT, [_I32] * 3 + [_VP] * 10 + [_SZ, _VP]),
+    "t4d_masked_l1_scratch_bytes": (_SZ, [_I32]),
+    "t4d_masked_l1_loss": (_INT, [_I32] * 3 + [_VP] * 7 + [_SZ, _VP]),
+    "t4d_label_mask_target": (_INT, [_I32, _I32, _I32, _VP, C.POINTER(_F32), _I32, _VP, _F32, _VP, _VP, _VP]),
+    "t4d_soft_color_scratch_bytes": (_SZ, []),
+    "t4d_soft_color_loss": (_INT, [_I64, _I32, _VP, _VP, _F32, _VP, _VP, _I32, _VP, _SZ, _VP]),
+    "t4d_priors_record_layout": (_I64, [C.POINTER(T4DPriors), C.POINTER(_I64)]),
+    "t4d_priors_scratch_bytes": (_SZ, [C.POINTER(T4DPriors)]),
+    "t4d_priors_eval": (_INT, [C.POINTER(T4DPriors), _I32] + [_VP] * 7 + [C.c_uint32, _VP, _VP, _SZ, _VP]),
+    "t4d_adam_pin_step": (_INT, [C.POINTER(T4DAdamTensor), _I32, _F32, _F32, _F32, _VP]),
+    "t4d_adam_step_counters": (_I64, [C.POINTER(T4DAdamTensor), _I32]),
+    "t4d_adam_pin_step_graph": (_INT, [C.POINTER(T4DAdamTensor), _I32, _F32, _F32, _F32, _VP, _I64, _VP, _VP]),
+    "t4d_dense_interpolate": (_INT, [_VP] * 4 + [_I64, _I64, _I32, _VP, _VP]),
+    "t4d_dense_scratch_bytes": (_SZ, [C.POINTER(T4DDenseMesh)]),
+    "t4d_dense_build": (_INT, [C.POINTER(T4DDenseMesh), _VP, _SZ, _VP]),
+    "t4d_knn_scratch_bytes": (_SZ, [_I64, _I32]),
+    "t4d_knn_mean_sq_dist": (_INT, [_VP, _I64, _I32, _VP, _VP, _VP, _SZ, _VP]),
+    "t4d_activate_forward": (_INT, [_I64] + [_VP] * 7),
+    "t4d_activate_backward": (_INT, [_I64] + [_VP] * 10),
+    "t4d_texture_bake_scratch_bytes": (_SZ, [_I32, _I32, _I64]),
+    "t4d_texture_bake": (_INT, [_VP] * 3 + [_I32] * 7 + [_VP] * 3 + [_SZ, _I64, C.POINTER(_I64), _VP]),
+    "t4d_texture_render_colors": (_INT, [_VP] * 4 + [_I32] * 7 + [_VP] * 3 + [_SZ, _I64, C.POINTER(_I64), _VP]),
+    "t4d_png_max_bytes": (_SZ, [_I32] * 3),
+    "t4d_png_scratch_bytes": (_SZ, [_I32] * 3),
+    "t4d_png_encode": (_INT, [_VP] + [_I32] * 4 + [_VP, _SZ, _VP, _VP, _SZ, _VP]),
+    "t4d_profile_begin": (_INT, []),
+    "t4d_profile_end": (_INT, [C.POINTER(T4DKernelTime), _INT, C.POINTER(_INT)]),
+    "t4d_debug_state_layout": (_INT, [_PROB, _INT, C.POINTER(C.c_uint64), _INT]),
+}
+EXPORTS = tuple(SIGNATURES)
+
+
 class ExtensionMissing(RuntimeError):
     pass
 
@@ -130,93 +170,9 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise ExtensionMissing(f"could not load {LIB_PATH}: {e}") from e
-    lib.t4d_abi_version.restype = C.c_uint32
-    lib.t4d_last_error.restype = C.c_char_p
-    lib.t4d_state_bytes.restype = C.c_size_t
-    lib.t4d_state_bytes.argtypes = [C.POINTER(T4DProblem)]
-    lib.t4d_backward_scratch_bytes.restype = C.c_size_t
-    lib.t4d_backward_scratch_bytes.argtypes = [C.POINTER(T4DProblem)]
-    lib.t4d_rasterize_forward.restype = C.c_int
-    lib.t4d_rasterize_forward.argtypes = [C.POINTER(T4DProblem), C.POINTER(T4DForwardIO), C.POINTER(T4DStatus),
-                                          C.c_void_p]
-    lib.t4d_rasterize_backward.restype = C.c_int
-    lib.t4d_rasterize_backward.argtypes = [C.POINTER(T4DProblem), C.POINTER(T4DBackwardIO), C.c_void_p]
-    lib.t4d_fetch_status.restype = C.c_int
-    lib.t4d_fetch_status.argtypes = [C.POINTER(T4DProblem), C.c_void_p, C.POINTER(T4DStatus), C.c_void_p]
-    lib.t4d_mark_visible.restype = C.c_int
-    lib.t4d_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.t4d_debug_state_layout.restype = C.c_int
-    lib.t4d_debug_state_layout.argtypes = [C.POINTER(T4DProblem), C.c_int, C.POINTER(C.c_uint64), C.c_int]
-    lib.t4d_view_dot_scratch_bytes.restype = C.c_size_t
-    lib.t4d_view_dot_scratch_bytes.argtypes = [C.c_int32]
-    lib.t4d_sum_views.restype = C.c_int
-    lib.t4d_sum_views.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
-    lib.t4d_view_dot.restype = C.c_int
-    lib.t4d_view_dot.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.t4d_texture_bake_scratch_bytes.restype = C.c_size_t
-    lib.t4d_texture_bake_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int64]
-    lib.t4d_texture_bake.restype = C.c_int
-    lib.t4d_texture_bake.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                     C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64,
-                                     C.POINTER(C.c_int64), C.c_void_p]
-    lib.t4d_texture_render_colors.restype = C.c_int
-    lib.t4d_texture_render_colors.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 7 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                              C.c_int64, C.POINTER(C.c_int64), C.c_void_p]
-    lib.t4d_photometric_scratch_bytes.restype = C.c_size_t
-    lib.t4d_photometric_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.t4d_photometric_loss.restype = C.c_int
-    lib.t4d_photometric_loss.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10 + [C.c_size_t, C.c_void_p]
-    lib.t4d_masked_l1_scratch_bytes.restype = C.c_size_t
-    lib.t4d_masked_l1_scratch_bytes.argtypes = [C.c_int32]
-    lib.t4d_masked_l1_loss.restype = C.c_int
-    lib.t4d_masked_l1_loss.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]
-    lib.t4d_label_mask_target.restype = C.c_int
-    lib.t4d_label_mask_target.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_float), C.c_int32, C.c_void_p, C.c_float,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.t4d_soft_color_scratch_bytes.restype = C.c_size_t
-    lib.t4d_soft_color_scratch_bytes.argtypes = []
-    lib.t4d_soft_color_loss.restype = C.c_int
-    lib.t4d_soft_color_loss.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
-                                        C.c_size_t, C.c_void_p]
-    lib.t4d_priors_record_layout.restype = C.c_int64
-    lib.t4d_priors_record_layout.argtypes = [C.POINTER(T4DPriors), C.POINTER(C.c_int64)]
-    lib.t4d_priors_scratch_bytes.restype = C.c_size_t
-    lib.t4d_priors_scratch_bytes.argtypes = [C.POINTER(T4DPriors)]
-    lib.t4d_priors_eval.restype = C.c_int
-    lib.t4d_priors_eval.argtypes = [C.POINTER(T4DPriors), C.c_int32] + [C.c_void_p] * 7 + [C.c_uint32, C.c_void_p, C.c_void_p,
-                                                                                            C.c_size_t, C.c_void_p]
-    lib.t4d_dense_scratch_bytes.restype = C.c_size_t
-    lib.t4d_dense_scratch_bytes.argtypes = [C.POINTER(T4DDenseMesh)]
-    lib.t4d_dense_build.restype = C.c_int
-    lib.t4d_dense_build.argtypes = [C.POINTER(T4DDenseMesh), C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.t4d_knn_scratch_bytes.restype = C.c_size_t
-    lib.t4d_knn_scratch_bytes.argtypes = [C.c_int64, C.c_int32]
-    lib.t4d_knn_mean_sq_dist.restype = C.c_int
-    lib.t4d_knn_mean_sq_dist.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.t4d_png_max_bytes.restype = C.c_size_t
-    lib.t4d_png_max_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.t4d_png_scratch_bytes.restype = C.c_size_t
-    lib.t4d_png_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.t4d_png_encode.restype = C.c_int
-    lib.t4d_png_encode.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
-                                   C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.t4d_adam_pin_step.restype = C.c_int
-    lib.t4d_adam_pin_step.argtypes = [C.POINTER(T4DAdamTensor), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]
-    lib.t4d_adam_step_counters.restype = C.c_int64
-    lib.t4d_adam_step_counters.argtypes = [C.POINTER(T4DAdamTensor), C.c_int32]
-    lib.t4d_adam_pin_step_graph.restype = C.c_int
-    lib.t4d_adam_pin_step_graph.argtypes = [C.POINTER(T4DAdamTensor), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int64,
-                                            C.c_void_p, C.c_void_p]
-    lib.t4d_dense_interpolate.restype = C.c_int
-    lib.t4d_dense_interpolate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32,
-                                          C.c_void_p, C.c_void_p]
-    lib.t4d_activate_forward.restype = C.c_int
-    lib.t4d_activate_forward.argtypes = [C.c_int64] + [C.c_void_p] * 7
-    lib.t4d_activate_backward.restype = C.c_int
-    lib.t4d_activate_backward.argtypes = [C.c_int64] + [C.c_void_p] * 10
-    lib.t4d_profile_begin.restype = C.c_int
-    lib.t4d_profile_end.restype = C.c_int
-    lib.t4d_profile_end.argtypes = [C.POINTER(T4DKernelTime), C.c_int, C.POINTER(C.c_int)]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.t4d_abi_version() != T4D_ABI_VERSION:
         raise ExtensionMissing(f"ABI mismatch: library {lib.t4d_abi_version()} vs python {T4D_ABI_VERSION}; rebuild")
     _lib = lib
@@ -231,11 +187,36 @@ def profile_end() -> dict:
     """{kernel name: (total_ms, launches)} since profile_begin()."""
     arr = (T4DKernelTime * 16)()
     n = C.c_int(0)
-    rc = load().t4d_profile_end(arr, 16, C.byref(n))
-    if rc != T4D_OK:
-        raise RuntimeError(f"t4d_profile_end failed: {last_error()}")
+    call("t4d_profile_end", arr, 16, C.byref(n))
     return {arr[i].name.decode(): (arr[i].total_ms, arr[i].launches) for i in range(n.value)}
 
 
 def last_error() -> str:
     return load().t4d_last_error().decode(errors="replace")
+
+
+# ---- what the wrappers of the other modules share --------------------------------------------------------------------------
+def ptr(t):
+    """A tensor's data pointer as an argument of the library (None: NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(device) -> int:
+    """hipStream_t of torch's current stream on `device` (the private getter is ~20x cheaper than building a Stream object)."""
+    try:
+        return torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch.cuda.current_device())
+    except AttributeError:                                   # pragma: no cover - older/newer torch without the private hook
+        return torch.cuda.current_stream(device).cuda_stream
+
+
+def error(name: str, rc=None, exc=RuntimeError) -> Exception:
+    """The exception for a refused call of entry point `name`: its return code (None: a size query that returned 0) and the
+    library's message."""
+    return exc(f"{name} failed{'' if rc is None else f' (code {rc})'}: {last_error()}")
+
+
+def call(name: str, *args) -> None:
+    """Call entry point `name`; a non-zero return code raises error(name, rc)."""
+    rc = getattr(load(), name)(*args)
+    if rc != T4D_OK:
+        raise error(name, rc)

@@ -9,6 +9,9 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib
+from ._lib import ptr
+
 
 def _check_raw(**tensors):
     """The raw entry points hand data pointers to the library: contiguous float32 HIP tensors only ([P,4] / [P,1] / [P,3])."""
@@ -28,39 +31,27 @@ def _check_raw(**tensors):
 def activate_forward(unnorm_rotations, logit_opacities, log_scales):
     """rotations, opacities, scales = normalize(unnorm_rotations), sigmoid(logit_opacities), exp(log_scales) in ONE launch
     (t4d_activate_forward); no autograd - contiguous fp32 HIP tensors in, new tensors out."""
-    import ctypes as C
-    from . import _lib
-    lib = _lib.load()
     dev = unnorm_rotations.device
     if dev.type != "cuda":
         raise RuntimeError("params2rendervar_fused runs on the GPU only (no CPU fallback)")
     ur, lo, ls = unnorm_rotations, logit_opacities, log_scales
     _check_raw(ur=ur, lo=lo, ls=ls)
     rot, op, sc = torch.empty_like(ur), torch.empty_like(lo), torch.empty_like(ls)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    rc = lib.t4d_activate_forward(ur.shape[0], p(ur), p(lo), p(ls), p(rot), p(op), p(sc), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"t4d_activate_forward failed (code {rc}): {_lib.last_error()}")
+    _lib.call("t4d_activate_forward", ur.shape[0], ptr(ur), ptr(lo), ptr(ls), ptr(rot), ptr(op), ptr(sc), _lib.stream(dev))
     return rot, op, sc
 
 
 def activate_backward(unnorm_rotations, opacities, scales, g_rot, g_op, g_sc, need=(True, True, True)):
     """The vector-Jacobian products of activate_forward in one launch (t4d_activate_backward): `opacities` / `scales` are the
     forward OUTPUTS, a None cotangent counts as zeros; returns (d_unnorm_rotations, d_logit_opacities, d_log_scales)."""
-    import ctypes as C
-    from . import _lib
-    lib = _lib.load()
     ur, op, sc = unnorm_rotations, opacities, scales
     dev = ur.device
     _check_raw(ur=ur, op=op, sc=sc, g_rot=g_rot, g_op=g_op, g_sc=g_sc)
     d_ur = torch.empty_like(ur) if need[0] else None
     d_lo = torch.empty_like(op) if need[1] else None
     d_ls = torch.empty_like(sc) if need[2] else None
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    rc = lib.t4d_activate_backward(ur.shape[0], p(ur), p(op), p(sc), p(g_rot), p(g_op), p(g_sc), p(d_ur), p(d_lo), p(d_ls),
-                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"t4d_activate_backward failed (code {rc}): {_lib.last_error()}")
+    _lib.call("t4d_activate_backward", ur.shape[0], ptr(ur), ptr(op), ptr(sc), ptr(g_rot), ptr(g_op), ptr(g_sc), ptr(d_ur), ptr(d_lo),
+              ptr(d_ls), _lib.stream(dev))
     return d_ur, d_lo, d_ls
 
 

@@ -17,9 +17,7 @@
 #include <math.h>
 
 #include "../../include/topo4d_raster.h"
-
-#define T4D_EXPORT extern "C" __attribute__((visibility("default")))
-int t4d_internal_fail(int code, const char *fmt, const char *a);
+#include "t4d_host.h"
 
 namespace {
 
@@ -226,8 +224,6 @@ struct KnnLayout {
 
 constexpr int kScanBlock = 1024;
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 KnnLayout knn_layout(int64_t n)
 {
     KnnLayout L;
@@ -236,16 +232,16 @@ KnnLayout knn_layout(int64_t n)
     L.table = t;
     L.nblocks_scan = (t + kScanBlock - 1) / kScanBlock;
     size_t o = 0;
-    L.bbox = o;   o += align256(sizeof(double) * 6 * 1024);         // per-block min / max partials, then the grid
-    L.keys = o;   o += align256(sizeof(uint64_t) * t);
-    L.cnt = o;    o += align256(sizeof(int32_t) * t);
-    L.start = o;  o += align256(sizeof(int32_t) * t);
-    L.cursor = o; o += align256(sizeof(int32_t) * t);
-    L.slot = o;   o += align256(sizeof(int32_t) * n);
-    L.spts = o;   o += align256(sizeof(double) * 3 * n);
-    L.sidx = o;   o += align256(sizeof(int32_t) * n);
-    L.bsum = o;   o += align256(sizeof(int32_t) * (L.nblocks_scan + 1));
-    L.fall = o;   o += align256(sizeof(int32_t) * (n + 1));         // [0]: count, then the open queries
+    L.bbox = o;   o += align_up(sizeof(double) * 6 * 1024);         // per-block min / max partials, then the grid
+    L.keys = o;   o += align_up(sizeof(uint64_t) * t);
+    L.cnt = o;    o += align_up(sizeof(int32_t) * t);
+    L.start = o;  o += align_up(sizeof(int32_t) * t);
+    L.cursor = o; o += align_up(sizeof(int32_t) * t);
+    L.slot = o;   o += align_up(sizeof(int32_t) * n);
+    L.spts = o;   o += align_up(sizeof(double) * 3 * n);
+    L.sidx = o;   o += align_up(sizeof(int32_t) * n);
+    L.bsum = o;   o += align_up(sizeof(int32_t) * (L.nblocks_scan + 1));
+    L.fall = o;   o += align_up(sizeof(int32_t) * (n + 1));         // [0]: count, then the open queries
     L.total = o + 256;                                              // + the Grid record
     return L;
 }
@@ -543,7 +539,7 @@ unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 T4D_EXPORT size_t t4d_dense_scratch_bytes(const T4DDenseMesh *m)
 {
     if (!dense_valid(m)) {
-        t4d_internal_fail(T4D_ERR_ARG, "t4d_dense_scratch_bytes: bad mesh descriptor%s", "");
+        t4d_fail(T4D_ERR_ARG, "t4d_dense_scratch_bytes: bad mesh descriptor");
         return 0;
     }
     return 256;
@@ -551,8 +547,8 @@ T4D_EXPORT size_t t4d_dense_scratch_bytes(const T4DDenseMesh *m)
 
 T4D_EXPORT int t4d_dense_build(const T4DDenseMesh *m, void *scratch, size_t scratch_bytes, void *hip_stream)
 {
-    if (!dense_valid(m) || !scratch) return t4d_internal_fail(T4D_ERR_ARG, "t4d_dense_build: bad arguments%s", "");
-    if (scratch_bytes < 256) return t4d_internal_fail(T4D_ERR_STATE_SIZE, "t4d_dense_build: scratch too small%s", "");
+    if (!dense_valid(m) || !scratch) return t4d_fail(T4D_ERR_ARG, "t4d_dense_build: bad arguments");
+    if (scratch_bytes < 256) return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_dense_build: scratch too small");
     hipStream_t stream = (hipStream_t)hip_stream;
     DenseStatus *st = (DenseStatus *)scratch;
     hipLaunchKernelGGL(k_zero_status, dim3(1), dim3(1), 0, stream, st);
@@ -561,16 +557,14 @@ T4D_EXPORT int t4d_dense_build(const T4DDenseMesh *m, void *scratch, size_t scra
     if (cells > 0) hipLaunchKernelGGL(k_dense_grid, dim3(blocks(cells, kBlock)), dim3(kBlock), 0, stream, *m, st);
     const int64_t copies = (int64_t)m->n_vert + m->n_uv + m->n_tri + m->n_rest;
     if (copies > 0) hipLaunchKernelGGL(k_dense_copy, dim3(blocks(copies, kBlock)), dim3(kBlock), 0, stream, *m, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_dense_build launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_dense_build");
 }
 
 // helpers.py:147-157 (o3d_knn) followed by `.mean(-1)` (train.py:131-132, :245-246): see include/topo4d_raster.h
 T4D_EXPORT size_t t4d_knn_scratch_bytes(int64_t n, int32_t k)
 {
     if (k < 1 || k > T4D_KNN_MAX_K || n < (int64_t)k + 1 || n > INT32_MAX / 2) {
-        t4d_internal_fail(T4D_ERR_ARG, "t4d_knn_scratch_bytes: need 1 <= k <= T4D_KNN_MAX_K and k < n < 2^30%s", "");
+        t4d_fail(T4D_ERR_ARG, "t4d_knn_scratch_bytes: need 1 <= k <= T4D_KNN_MAX_K and k < n < 2^30");
         return 0;
     }
     return knn_layout(n).total;
@@ -580,9 +574,9 @@ T4D_EXPORT int t4d_knn_mean_sq_dist(const double *points, int64_t n, int32_t k, 
                                     size_t scratch_bytes, void *hip_stream)
 {
     if (!points || !mean || !scratch || k < 1 || k > T4D_KNN_MAX_K || n < (int64_t)k + 1 || n > INT32_MAX / 2)
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_knn_mean_sq_dist: bad arguments%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_knn_mean_sq_dist: bad arguments");
     const KnnLayout L = knn_layout(n);
-    if (scratch_bytes < L.total) return t4d_internal_fail(T4D_ERR_STATE_SIZE, "t4d_knn_mean_sq_dist: scratch too small%s", "");
+    if (scratch_bytes < L.total) return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_knn_mean_sq_dist: scratch too small");
     hipStream_t stream = (hipStream_t)hip_stream;
     char *b = (char *)scratch;
     double *part = (double *)(b + L.bbox);
@@ -603,12 +597,10 @@ T4D_EXPORT int t4d_knn_mean_sq_dist(const double *points, int64_t n, int32_t k, 
     hipLaunchKernelGGL(k_scan_add, dim3((unsigned)L.nblocks_scan), dim3(kScanBlock), 0, stream, start, cursor, bsum, L.table);
     hipLaunchKernelGGL(k_scatter, dim3(blocks(n, kBlock)), dim3(kBlock), 0, stream, points, n, slot, cursor, spts, sidx);
     hipError_t e = hipMemsetAsync(fall, 0, sizeof(int32_t), stream);
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_knn_mean_sq_dist memset: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return t4d_fail(T4D_ERR_HIP, "t4d_knn_mean_sq_dist memset: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(k_knn_grid, dim3(blocks(n, kBlock)), dim3(kBlock), 0, stream, grid, keys, start, cnt, mask, spts, sidx, n,
                        (int)k, mean, fall);
     hipLaunchKernelGGL(k_knn_brute, dim3(256), dim3(kBlock), 0, stream, spts, sidx, n, (int)k, fall, mean);
     if (log_scales) hipLaunchKernelGGL(k_log_scales, dim3(blocks(n, kBlock)), dim3(kBlock), 0, stream, mean, n, log_scales);
-    e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_knn_mean_sq_dist launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_knn_mean_sq_dist");
 }

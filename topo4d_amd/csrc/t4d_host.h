@@ -1,0 +1,42 @@
+// Host-side helpers shared by the library's translation units other than t4d_raster.hip, which owns the error message
+// (g_err) and defines t4d_internal_fail.  Nothing here is part of the ABI or runs on the device.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stddef.h>
+#include <stdio.h>
+
+#include "../../include/topo4d_raster.h"
+
+#define T4D_EXPORT extern "C" __attribute__((visibility("default")))
+
+// t4d_raster.hip: stores the message t4d_last_error() returns and gives back `code` (hidden: not exported)
+int t4d_internal_fail(int code, const char *fmt, const char *a);
+
+// t4d_internal_fail with a printf-style message (the same 512-byte limit)
+__attribute__((format(printf, 2, 3))) static inline int t4d_fail(int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return t4d_internal_fail(code, "%s", buf);
+}
+
+// the return value of entry point `entry` after its launches: T4D_OK, or T4D_ERR_HIP with "<entry> launch: <HIP error>"
+static inline int t4d_launch_status(const char *entry)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? T4D_OK : t4d_fail(T4D_ERR_HIP, "%s launch: %s", entry, hipGetErrorString(e));
+}
+
+// return T4D_ERR_HIP with "<call>: <HIP error>" from the enclosing function when a HIP runtime call fails
+#define T4D_HIP_CHECK(call)                                                                          \
+    do {                                                                                             \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess) return t4d_fail(T4D_ERR_HIP, #call ": %s", hipGetErrorString(e_));    \
+    } while (0)
+
+static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }

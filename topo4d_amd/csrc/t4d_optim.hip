@@ -13,10 +13,8 @@
 #include <string.h>
 
 #include "../../include/topo4d_raster.h"
+#include "t4d_host.h"
 #include "t4d_activations.h"
-
-#define T4D_EXPORT extern "C" __attribute__((visibility("default")))
-int t4d_internal_fail(int code, const char *fmt, const char *a);
 
 namespace {
 
@@ -83,9 +81,9 @@ int adam_launch(const T4DAdamTensor *tensors, int32_t n_tensors, float beta1, fl
                 const float *lr_dev, void *hip_stream)
 {
     if (!tensors || n_tensors < 1 || n_tensors > kMaxTensors)
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_adam_pin_step: 1..T4D_ADAM_MAX_TENSORS tensors%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_adam_pin_step: 1..T4D_ADAM_MAX_TENSORS tensors");
     if ((step_dev == nullptr) != (lr_dev == nullptr))
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_adam_pin_step_graph: step_dev and lr_dev go together%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_adam_pin_step_graph: step_dev and lr_dev go together");
     AdamArgs A;
     memset(&A, 0, sizeof(A));
     A.n = n_tensors; A.beta1 = beta1; A.beta2 = beta2; A.eps = eps;
@@ -94,8 +92,8 @@ int adam_launch(const T4DAdamTensor *tensors, int32_t n_tensors, float beta1, fl
     for (int k = 0; k < n_tensors; k++) {
         const T4DAdamTensor &t = tensors[k];
         if (!t.param || t.rows < 0 || t.width < 1 || (t.grad && (!t.exp_avg || !t.exp_avg_sq)) || ((t.pin_mask == nullptr) != (t.pin_values == nullptr)))
-            return t4d_internal_fail(T4D_ERR_ARG, "t4d_adam_pin_step: inconsistent tensor descriptor%s", "");
-        if (!step_dev && t.grad && t.step < 1) return t4d_internal_fail(T4D_ERR_ARG, "t4d_adam_pin_step: step must be >= 1%s", "");
+            return t4d_fail(T4D_ERR_ARG, "t4d_adam_pin_step: inconsistent tensor descriptor");
+        if (!step_dev && t.grad && t.step < 1) return t4d_fail(T4D_ERR_ARG, "t4d_adam_pin_step: step must be >= 1");
         A.t[k] = t;
         const double st = t.grad ? (double)t.step : 1.0;
         const double bc1 = 1.0 - pow((double)beta1, st), bc2 = 1.0 - pow((double)beta2, st);
@@ -106,15 +104,13 @@ int adam_launch(const T4DAdamTensor *tensors, int32_t n_tensors, float beta1, fl
     }
     A.first_block[n_tensors] = blocks;
     if (blocks == 0) return T4D_OK;
-    if (blocks > 0x7fffffffLL) return t4d_internal_fail(T4D_ERR_ARG, "t4d_adam_pin_step: too many elements%s", "");
+    if (blocks > 0x7fffffffLL) return t4d_fail(T4D_ERR_ARG, "t4d_adam_pin_step: too many elements");
     if (step_dev) {
         hipLaunchKernelGGL(k_adam_pin<true>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)hip_stream, A);
     } else {
         hipLaunchKernelGGL(k_adam_pin<false>, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)hip_stream, A);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_adam_pin_step launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_adam_pin_step");
 }
 
 }  // namespace
@@ -136,11 +132,11 @@ T4D_EXPORT int64_t t4d_adam_step_counters(const T4DAdamTensor *tensors, int32_t 
 T4D_EXPORT int t4d_adam_pin_step_graph(const T4DAdamTensor *tensors, int32_t n_tensors, float beta1, float beta2, float eps,
                                        int32_t *step_dev, int64_t n_step_counters, const float *lr_dev, void *hip_stream)
 {
-    if (!step_dev || !lr_dev) return t4d_internal_fail(T4D_ERR_ARG, "t4d_adam_pin_step_graph: step_dev and lr_dev are required%s", "");
+    if (!step_dev || !lr_dev) return t4d_fail(T4D_ERR_ARG, "t4d_adam_pin_step_graph: step_dev and lr_dev are required");
     // the launch writes one counter per workgroup: an array sized for other shapes (a tensor replaced by a larger one) would be
     // written out of bounds, and every later tensor would read another tensor's counters
     if (n_step_counters != t4d_adam_step_counters(tensors, n_tensors))
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_adam_pin_step_graph: n_step_counters does not match t4d_adam_step_counters() of these tensors%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_adam_pin_step_graph: n_step_counters does not match t4d_adam_step_counters() of these tensors");
     return adam_launch(tensors, n_tensors, beta1, beta2, eps, step_dev, lr_dev, hip_stream);
 }
 
@@ -179,14 +175,12 @@ T4D_EXPORT int t4d_dense_interpolate(const float *attribute, const int32_t *quad
                                      void *hip_stream)
 {
     if (!attribute || !out || n_coarse < 0 || n_dense < 0 || width < 1 || (n_dense > 0 && (!quad_faces || !vertex_father || !weight)))
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_dense_interpolate: bad arguments%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_dense_interpolate: bad arguments");
     const long long total = (n_coarse + n_dense) * width;
     if (total == 0) return T4D_OK;
     hipLaunchKernelGGL(k_dense_interp, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, attribute,
                        quad_faces, vertex_father, weight, (long long)n_coarse, (long long)n_dense, (int)width, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_dense_interpolate launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_dense_interpolate");
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -226,14 +220,12 @@ T4D_EXPORT int t4d_activate_forward(int64_t P, const float *unnorm_rotations, co
                                     float *rotations, float *opacities, float *scales, void *hip_stream)
 {
     if (P < 0 || (P > 0 && (!unnorm_rotations || !logit_opacities || !log_scales || !rotations || !opacities || !scales)))
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_activate_forward: bad arguments%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_activate_forward: bad arguments");
     if (P == 0) return T4D_OK;
     hipLaunchKernelGGL(k_activate_fwd, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, (long long)P,
                        reinterpret_cast<const float4 *>(unnorm_rotations), logit_opacities, log_scales,
                        reinterpret_cast<float4 *>(rotations), opacities, scales);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_activate_forward launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_activate_forward");
 }
 
 T4D_EXPORT int t4d_activate_backward(int64_t P, const float *unnorm_rotations, const float *opacities, const float *scales,
@@ -242,15 +234,13 @@ T4D_EXPORT int t4d_activate_backward(int64_t P, const float *unnorm_rotations, c
 {
     // (a NULL cotangent counts as zeros, a NULL output is not wanted: only the forward's inputs / outputs are required)
     if (P < 0 || (P > 0 && (!unnorm_rotations || !opacities || !scales)))
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_activate_backward: bad arguments%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_activate_backward: bad arguments");
     if (P == 0) return T4D_OK;
     hipLaunchKernelGGL(k_activate_bwd, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, (long long)P,
                        reinterpret_cast<const float4 *>(unnorm_rotations), opacities, scales,
                        reinterpret_cast<const float4 *>(dL_drotations), dL_dopacities, dL_dscales,
                        reinterpret_cast<float4 *>(dL_dunnorm_rotations), dL_dlogit_opacities, dL_dlog_scales);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_activate_backward launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_activate_backward");
 }
 
 
@@ -297,7 +287,7 @@ T4D_EXPORT int t4d_sum_views(int32_t n_views, int32_t n_tensors, const float *co
                              void *hip_stream)
 {
     if (n_views < 1 || n_tensors < 1 || n_tensors > T4D_SUM_MAX_TENSORS || !src || !dst || !n_per_view)
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_sum_views: bad arguments%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_sum_views: bad arguments");
     SumArgs a;
     memset(&a, 0, sizeof(a));
     a.V = n_views;
@@ -311,9 +301,7 @@ T4D_EXPORT int t4d_sum_views(int32_t n_views, int32_t n_tensors, const float *co
     }
     a.first_block[a.count] = blocks;
     if (a.count == 0) return T4D_OK;
-    if (blocks > 0x7fffffffLL) return t4d_internal_fail(T4D_ERR_ARG, "t4d_sum_views: too many elements%s", "");
+    if (blocks > 0x7fffffffLL) return t4d_fail(T4D_ERR_ARG, "t4d_sum_views: too many elements");
     hipLaunchKernelGGL(k_sum_views, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)hip_stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_sum_views launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_sum_views");
 }

@@ -20,9 +20,7 @@
 #include <stdlib.h>
 
 #include "../../include/topo4d_raster.h"
-
-#define T4D_EXPORT extern "C" __attribute__((visibility("default")))
-int t4d_internal_fail(int code, const char *fmt, const char *a);
+#include "t4d_host.h"
 
 namespace {
 
@@ -443,8 +441,6 @@ __global__ __launch_bounds__(kBlock) void k_photo_final(const PhP P)
     }
 }
 
-inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
 // ---------------------------------------------------------------------------------------------------------
 // Masked L1 of the dense (texture) pass, reference train.py:394-405 (get_loss_dense, use_mask=True):
 //     masked_index = filtered_mask == 1;   loss = sum_{masked} |im - gt| / masked_index.sum()
@@ -521,10 +517,10 @@ T4D_EXPORT int t4d_masked_l1_loss(int32_t n_views, int32_t H, int32_t W, const f
 {
     static_assert(kMlBlocks == 128, "k_masked_l1_grad sums two partials per lane of one wave");
     if (n_views < 1 || H < 1 || W < 1 || !im || !gt || !mask || !loss || !dL_dim || !scratch)
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_masked_l1_loss: bad arguments%s", "");
-    if (n_views > 65535) return t4d_internal_fail(T4D_ERR_ARG, "t4d_masked_l1_loss: too many views%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_masked_l1_loss: bad arguments");
+    if (n_views > 65535) return t4d_fail(T4D_ERR_ARG, "t4d_masked_l1_loss: too many views");
     if (scratch_bytes < t4d_masked_l1_scratch_bytes(n_views))
-        return t4d_internal_fail(T4D_ERR_STATE_SIZE, "t4d_masked_l1_loss: scratch too small%s", "");
+        return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_masked_l1_loss: scratch too small");
     const size_t n = (size_t)3 * H * W;
     float *part_sum = (float *)scratch;
     uint32_t *part_cnt = (uint32_t *)((char *)scratch + align_up((size_t)n_views * kMlBlocks * 4));
@@ -533,9 +529,7 @@ T4D_EXPORT int t4d_masked_l1_loss(int32_t n_views, int32_t H, int32_t W, const f
     const unsigned gblocks = (unsigned)((n + (size_t)kBlock * 8 - 1) / ((size_t)kBlock * 8));
     hipLaunchKernelGGL(k_masked_l1_grad, dim3(gblocks < 1 ? 1 : gblocks, n_views), dim3(kBlock), 0, stream, im, gt, mask, n,
                        (const float *)part_sum, (const uint32_t *)part_cnt, view_weight, loss, dL_dim);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_masked_l1_loss launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_masked_l1_loss");
 }
 
 // strips and row segments for an H x W image.  A strip of kFT threads yields kFT - 20 output columns: the launch picks the
@@ -601,19 +595,19 @@ T4D_EXPORT int t4d_photometric_loss(int32_t n_views, int32_t H, int32_t W, const
                                     float *dL_dcam_c, void *scratch, size_t scratch_bytes, void *hip_stream)
 {
     if (n_views < 1 || H < 1 || W < 1 || !im || !gt || !loss || !dL_dim || !scratch)
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_photometric_loss: bad arguments%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_photometric_loss: bad arguments");
     if ((cam_m == nullptr) != (cam_c == nullptr) || (dL_dcam_m == nullptr) != (dL_dcam_c == nullptr))
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_photometric_loss: cam_m/cam_c (and their gradients) come in pairs%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_photometric_loss: cam_m/cam_c (and their gradients) come in pairs");
     if (scratch_bytes < t4d_photometric_scratch_bytes(n_views, H, W))
-        return t4d_internal_fail(T4D_ERR_STATE_SIZE, "t4d_photometric_loss: scratch too small%s", "");
-    if ((size_t)n_views * 3 > 65535) return t4d_internal_fail(T4D_ERR_ARG, "t4d_photometric_loss: too many views%s", "");
+        return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_photometric_loss: scratch too small");
+    if ((size_t)n_views * 3 > 65535) return t4d_fail(T4D_ERR_ARG, "t4d_photometric_loss: too many views");
     PhP P;
     memset(&P, 0, sizeof(P));
     P.V = n_views; P.H = H; P.W = W;
     int ft = 0;
     photo_tiling(n_views, H, W, &P.tx, &P.ty, &P.tw, &P.th, &ft);
-    if (P.ty > 65535) return t4d_internal_fail(T4D_ERR_ARG, "t4d_photometric_loss: image too tall%s", "");
-    if ((size_t)H * W > ((size_t)1 << 30)) return t4d_internal_fail(T4D_ERR_ARG, "t4d_photometric_loss: more than 2^30 pixels per plane%s", "");
+    if (P.ty > 65535) return t4d_fail(T4D_ERR_ARG, "t4d_photometric_loss: image too tall");
+    if ((size_t)H * W > ((size_t)1 << 30)) return t4d_fail(T4D_ERR_ARG, "t4d_photometric_loss: more than 2^30 pixels per plane");
     P.im = im; P.gt = gt; P.cam_m = cam_m; P.cam_c = cam_c; P.weight = view_weight;
     P.loss = loss; P.dL_dim = dL_dim; P.dL_dm = dL_dcam_m; P.dL_dc = dL_dcam_c;
     const size_t tiles = (size_t)P.tx * P.ty * n_views * 3;
@@ -633,7 +627,5 @@ T4D_EXPORT int t4d_photometric_loss(int32_t n_views, int32_t H, int32_t W, const
     else if (ft == 192) hipLaunchKernelGGL(k_photo_stream<192>, grid, dim3(192), 0, stream, P);
     else hipLaunchKernelGGL(k_photo_stream<256>, grid, dim3(256), 0, stream, P);
     hipLaunchKernelGGL(k_photo_final, dim3(n_views), dim3(kBlock), 0, stream, P);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_photometric_loss launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_photometric_loss");
 }

@@ -24,9 +24,7 @@
 #include <math.h>
 
 #include "../../include/topo4d_raster.h"
-
-#define T4D_EXPORT extern "C" __attribute__((visibility("default")))
-int t4d_internal_fail(int code, const char *fmt, const char *a);
+#include "t4d_host.h"
 
 namespace {
 
@@ -77,16 +75,14 @@ struct PngLayout {
     size_t filt, slots, info, offs, total;
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 PngLayout png_layout(const Shape &s)
 {
     PngLayout L;
     size_t o = 0;
-    L.filt = o;  o += align256((size_t)s.n);
-    L.slots = o; o += align256((size_t)s.segs * kSlot);
-    L.info = o;  o += align256((size_t)s.segs * sizeof(SegInfo));
-    L.offs = o;  o += align256((size_t)s.segs * sizeof(int64_t));
+    L.filt = o;  o += align_up((size_t)s.n);
+    L.slots = o; o += align_up((size_t)s.segs * kSlot);
+    L.info = o;  o += align_up((size_t)s.segs * sizeof(SegInfo));
+    L.offs = o;  o += align_up((size_t)s.segs * sizeof(int64_t));
     L.total = o;
     return L;
 }
@@ -702,7 +698,7 @@ __global__ __launch_bounds__(kBlock) void k_png_assemble(Shape s, const uint8_t 
 T4D_EXPORT size_t t4d_png_max_bytes(int32_t h, int32_t w, int32_t c)
 {
     if (!shape_ok(h, w, c)) {
-        t4d_internal_fail(T4D_ERR_ARG, "t4d_png_max_bytes: need h, w >= 1, c in {1, 3, 4} and h*(1+w*c) <= 2^38%s", "");
+        t4d_fail(T4D_ERR_ARG, "t4d_png_max_bytes: need h, w >= 1, c in {1, 3, 4} and h*(1+w*c) <= 2^38");
         return 0;
     }
     return (size_t)max_bytes(make_shape(h, w, c));
@@ -711,7 +707,7 @@ T4D_EXPORT size_t t4d_png_max_bytes(int32_t h, int32_t w, int32_t c)
 T4D_EXPORT size_t t4d_png_scratch_bytes(int32_t h, int32_t w, int32_t c)
 {
     if (!shape_ok(h, w, c)) {
-        t4d_internal_fail(T4D_ERR_ARG, "t4d_png_scratch_bytes: need h, w >= 1, c in {1, 3, 4} and h*(1+w*c) <= 2^38%s", "");
+        t4d_fail(T4D_ERR_ARG, "t4d_png_scratch_bytes: need h, w >= 1, c in {1, 3, 4} and h*(1+w*c) <= 2^38");
         return 0;
     }
     return png_layout(make_shape(h, w, c)).total;
@@ -721,12 +717,12 @@ T4D_EXPORT int t4d_png_encode(const void *image, int32_t is_float32, int32_t h, 
                               int64_t *out_bytes, void *scratch, size_t scratch_bytes, void *hip_stream)
 {
     if (!image || !out || !out_bytes || !scratch || (is_float32 != 0 && is_float32 != 1) || !shape_ok(h, w, c))
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_png_encode: bad arguments%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_png_encode: bad arguments");
     const Shape s = make_shape(h, w, c);
     if (out_capacity < (size_t)max_bytes(s))
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_png_encode: out_capacity below t4d_png_max_bytes%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_png_encode: out_capacity below t4d_png_max_bytes");
     const PngLayout L = png_layout(s);
-    if (scratch_bytes < L.total) return t4d_internal_fail(T4D_ERR_STATE_SIZE, "t4d_png_encode: scratch too small%s", "");
+    if (scratch_bytes < L.total) return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_png_encode: scratch too small");
     hipStream_t stream = (hipStream_t)hip_stream;
     char *b = (char *)scratch;
     uint8_t *filt = (uint8_t *)(b + L.filt), *slots = (uint8_t *)(b + L.slots);
@@ -738,7 +734,5 @@ T4D_EXPORT int t4d_png_encode(const void *image, int32_t is_float32, int32_t h, 
     hipLaunchKernelGGL(k_png_finalize, dim3(1), dim3(kBlock), 0, stream, s, info, offs, out, (int64_t)out_capacity, out_bytes);
     hipLaunchKernelGGL(k_png_assemble, dim3((unsigned)s.segs), dim3(kBlock), 0, stream, s, slots, info, offs, out,
                        (int64_t)out_capacity);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_png_encode launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_png_encode");
 }

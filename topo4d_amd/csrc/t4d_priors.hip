@@ -18,9 +18,7 @@
 #include <string.h>
 
 #include "../../include/topo4d_raster.h"
-
-#define T4D_EXPORT extern "C" __attribute__((visibility("default")))
-int t4d_internal_fail(int code, const char *fmt, const char *a);
+#include "t4d_host.h"
 
 namespace {
 
@@ -474,7 +472,7 @@ T4D_EXPORT int64_t t4d_priors_record_layout(const T4DPriors *pr, int64_t *base)
 T4D_EXPORT size_t t4d_priors_scratch_bytes(const T4DPriors *pr)
 {
     if (!valid(pr)) {
-        t4d_internal_fail(T4D_ERR_ARG, "t4d_priors_scratch_bytes: bad topology%s", "");
+        t4d_fail(T4D_ERR_ARG, "t4d_priors_scratch_bytes: bad topology");
         return 0;
     }
     return scratch_layout(pr).total;
@@ -486,11 +484,11 @@ T4D_EXPORT int t4d_priors_eval(const T4DPriors *pr, int32_t is_initial, const fl
 {
     if (!valid(pr) || !means3D || !unnorm_rotations || !log_scales || !d_means3D || !d_unnorm_rotations || !d_log_scales || !losses ||
         !scratch || (flags & ~(uint32_t)T4D_PRIORS_ACCUMULATE))
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_priors_eval: bad arguments%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_priors_eval: bad arguments");
     if (((uintptr_t)unnorm_rotations | (uintptr_t)pr->prev_inv_rot) & 15)
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_priors_eval: quaternion arrays must be 16-byte aligned%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_priors_eval: quaternion arrays must be 16-byte aligned");
     const Layout L = scratch_layout(pr);
-    if (scratch_bytes < L.total) return t4d_internal_fail(T4D_ERR_STATE_SIZE, "t4d_priors_eval: scratch too small%s", "");
+    if (scratch_bytes < L.total) return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_priors_eval: scratch too small");
     const Segs S = make_segs(pr, is_initial ? 1 : 0);
     char *base = (char *)scratch;
     Ptr p;
@@ -505,7 +503,5 @@ T4D_EXPORT int t4d_priors_eval(const T4DPriors *pr, int32_t is_initial, const fl
     hipLaunchKernelGGL(k_priors_vertices, dim3((unsigned)((pr->P + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, *pr, S, p,
                        (int)(is_initial != 0), d_means3D, d_unnorm_rotations, d_log_scales, upstream,
                        (int)(flags & T4D_PRIORS_ACCUMULATE), losses);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_priors_eval launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_priors_eval");
 }

@@ -15,9 +15,7 @@
 #include <string.h>
 
 #include "../../include/topo4d_raster.h"
-
-#define T4D_EXPORT extern "C" __attribute__((visibility("default")))
-int t4d_internal_fail(int code, const char *fmt, const char *a);
+#include "t4d_host.h"
 
 namespace {
 
@@ -106,8 +104,8 @@ T4D_EXPORT int t4d_label_mask_target(int32_t n_views, int32_t H, int32_t W, cons
 {
     if (n_views < 1 || H < 1 || W < 1 || !mask_image || !label_colors || n_labels < 0 || n_labels > T4D_MAX_MASK_LABELS ||
         (target && !gt) || (!filtered_mask && !target))
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_label_mask_target: bad arguments%s", "");
-    if (n_views > 65535) return t4d_internal_fail(T4D_ERR_ARG, "t4d_label_mask_target: too many views%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_label_mask_target: bad arguments");
+    if (n_views > 65535) return t4d_fail(T4D_ERR_ARG, "t4d_label_mask_target: too many views");
     LabelArgs L;
     memset(&L, 0, sizeof(L));
     L.n = n_labels;
@@ -115,12 +113,10 @@ T4D_EXPORT int t4d_label_mask_target(int32_t n_views, int32_t H, int32_t W, cons
         for (int c = 0; c < 3; c++) L.color[k][c] = label_colors[3 * k + c];
     const size_t plane = (size_t)H * W;
     const size_t blocks = (plane + kBlock - 1) / kBlock;
-    if (blocks > 0x7fffffffull) return t4d_internal_fail(T4D_ERR_ARG, "t4d_label_mask_target: image too large%s", "");
+    if (blocks > 0x7fffffffull) return t4d_fail(T4D_ERR_ARG, "t4d_label_mask_target: image too large");
     hipLaunchKernelGGL(k_label_mask_target, dim3((unsigned)blocks, n_views), dim3(kBlock), 0, (hipStream_t)hip_stream, mask_image, L, gt,
                        scale, plane, filtered_mask, target);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_label_mask_target launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_label_mask_target");
 }
 
 T4D_EXPORT size_t t4d_soft_color_scratch_bytes(void) { return kScBlocks * sizeof(float); }
@@ -129,9 +125,9 @@ T4D_EXPORT int t4d_soft_color_loss(int64_t rows, int32_t width, const float *x, 
                                    float *grad, int32_t accumulate, void *scratch, size_t scratch_bytes, void *hip_stream)
 {
     if (rows < 1 || width < 1 || !x || !y || !loss || !scratch)
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_soft_color_loss: bad arguments%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_soft_color_loss: bad arguments");
     if (scratch_bytes < t4d_soft_color_scratch_bytes())
-        return t4d_internal_fail(T4D_ERR_STATE_SIZE, "t4d_soft_color_loss: scratch too small%s", "");
+        return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_soft_color_loss: scratch too small");
     const size_t n = (size_t)rows * width;
     size_t blocks = (n + kBlock - 1) / kBlock;
     if (blocks > kScBlocks) blocks = kScBlocks;
@@ -140,7 +136,5 @@ T4D_EXPORT int t4d_soft_color_loss(int64_t rows, int32_t width, const float *x, 
     hipStream_t stream = (hipStream_t)hip_stream;
     hipLaunchKernelGGL(k_soft_color, dim3((unsigned)blocks), dim3(kBlock), 0, stream, x, y, n, gw, grad, (int)accumulate, (float *)scratch);
     hipLaunchKernelGGL(k_soft_color_final, dim3(1), dim3(kScBlocks), 0, stream, (const float *)scratch, (int)blocks, (float)rows, loss);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, "t4d_soft_color_loss launch: %s", hipGetErrorString(e));
-    return T4D_OK;
+    return t4d_launch_status("t4d_soft_color_loss");
 }

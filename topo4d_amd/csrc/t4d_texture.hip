@@ -22,9 +22,7 @@
 #include <string.h>
 
 #include "../../include/topo4d_raster.h"
-
-#define T4D_EXPORT extern "C" __attribute__((visibility("default")))
-int t4d_internal_fail(int code, const char *fmt, const char *a);
+#include "t4d_host.h"
 
 namespace {
 
@@ -505,8 +503,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FRESH ? 
     }
 }
 
-inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
 struct TexLayout { size_t total_, bin_count, bin_cursor, zero_end, bin_off, chunk_sum, list, bytes; };
 
 TexLayout tex_layout(int h, int w, int64_t cap)
@@ -539,13 +535,13 @@ int texture_bake_impl(const bool fresh, const float *bg, const float *vertices, 
                       void *scratch, size_t scratch_bytes, int64_t pair_capacity, int64_t *pairs_needed, void *hip_stream)
 {
     if (!vertices || !triangles || !colors || !image || !depth_buffer || !scratch || nver < 1 || ntri < 0 || h < 1 || w < 1 || c < 1)
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_texture_bake: bad arguments%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_texture_bake: bad arguments");
     if (row_begin < 0 || row_end > h || row_begin >= row_end)
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_texture_bake: row band must satisfy 0 <= begin < end <= h%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_texture_bake: row band must satisfy 0 <= begin < end <= h");
     if (pair_capacity < 1 || pair_capacity > 0x7fffffffLL)
-        return t4d_internal_fail(T4D_ERR_ARG, "t4d_texture_bake: pair_capacity out of range%s", "");
+        return t4d_fail(T4D_ERR_ARG, "t4d_texture_bake: pair_capacity out of range");
     const TexLayout L = tex_layout(h, w, pair_capacity);
-    if (scratch_bytes < L.bytes) return t4d_internal_fail(T4D_ERR_STATE_SIZE, "t4d_texture_bake: scratch too small%s", "");
+    if (scratch_bytes < L.bytes) return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_texture_bake: scratch too small");
     hipStream_t stream = (hipStream_t)hip_stream;
     char *sc = (char *)scratch;
     TexP P;
@@ -565,31 +561,25 @@ int texture_bake_impl(const bool fresh, const float *bg, const float *vertices, 
     P.list = (uint4 *)(sc + L.list);
     P.image = image; P.depth = depth_buffer; P.bg = bg;
     if (pairs_needed) *pairs_needed = 0;
-#define TEX_HIP(call)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) return t4d_internal_fail(T4D_ERR_HIP, #call ": %s", hipGetErrorString(e_)); \
-    } while (0)
-    TEX_HIP(hipMemsetAsync(sc, 0, L.zero_end, stream));
+    T4D_HIP_CHECK(hipMemsetAsync(sc, 0, L.zero_end, stream));
     unsigned long long total = 0;
     if (ntri > 0) {
         const int gt = (ntri + kBlock - 1) / kBlock;
         hipLaunchKernelGGL(k_tex_bin<false>, dim3(gt), dim3(kBlock), 0, stream, P);
         if (P.n_chunks > 1) hipLaunchKernelGGL(k_tex_chunk_sums, dim3(P.n_chunks), dim3(kScanChunk), 0, stream, P);
         hipLaunchKernelGGL(k_tex_scan, dim3(P.n_chunks), dim3(kScanChunk), 0, stream, P);
-        TEX_HIP(hipMemcpyAsync(&total, P.total, 8, hipMemcpyDeviceToHost, stream));
-        TEX_HIP(hipStreamSynchronize(stream));          // once per bake (a per-frame export step, not the training loop)
+        T4D_HIP_CHECK(hipMemcpyAsync(&total, P.total, 8, hipMemcpyDeviceToHost, stream));
+        T4D_HIP_CHECK(hipStreamSynchronize(stream));          // once per bake (a per-frame export step, not the training loop)
         if (pairs_needed) *pairs_needed = (int64_t)total;
         if (total > (unsigned long long)pair_capacity)
-            return t4d_internal_fail(T4D_ERR_PAIR_OVERFLOW, "t4d_texture_bake: pair_capacity too small%s", "");
+            return t4d_fail(T4D_ERR_PAIR_OVERFLOW, "t4d_texture_bake: pair_capacity too small");
         hipLaunchKernelGGL(k_tex_bin<true>, dim3(gt), dim3(kBlock), 0, stream, P);
     } else if (!fresh) {
         return T4D_OK;
     }
     if (fresh) hipLaunchKernelGGL(k_tex_render<true>, dim3(P.bx * P.by), dim3(kBlock), 0, stream, P);
     else hipLaunchKernelGGL(k_tex_render<false>, dim3(P.bx * P.by), dim3(kBlock), 0, stream, P);
-    TEX_HIP(hipGetLastError());
-#undef TEX_HIP
+    T4D_HIP_CHECK(hipGetLastError());
     return T4D_OK;
 }
 }  // namespace

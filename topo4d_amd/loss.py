@@ -19,6 +19,9 @@ from typing import Optional, Sequence
 
 import torch
 
+from . import _lib
+from ._lib import ptr
+
 
 # ------------------------------------------------------------------------------------------------------------
 # fused HIP version (t4d_photometric_loss): forward + gradient in one launch set for a batch of views
@@ -27,8 +30,6 @@ def photometric_loss_raw(im, gt, cam_m=None, cam_c=None, d_cam_m=None, d_cam_c=N
     """t4d_photometric_loss without autograd: contiguous fp32 HIP tensors im, gt [V,3,H,W], cam_m / cam_c [V,3] or None.
     Returns (loss [V], dL/dim [V,3,H,W], dL/dcam_m, dL/dcam_c); `d_cam_m` / `d_cam_c`: [V,3] tensors that receive the camera
     gradients (e.g. rows of a persistent gradient buffer), allocated here when None."""
-    import ctypes as C
-    from . import _lib
     lib = _lib.load()
     if not im.is_cuda:
         raise RuntimeError("topo4d_amd has no CPU path: tensors must live on a HIP device")
@@ -48,12 +49,8 @@ def photometric_loss_raw(im, gt, cam_m=None, cam_c=None, d_cam_m=None, d_cam_c=N
         d_cam_c = torch.empty(V, 3, dtype=torch.float32, device=dev)
     nbytes = lib.t4d_photometric_scratch_bytes(V, H, W)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    rc = lib.t4d_photometric_loss(V, H, W, p(im), p(gt), p(cam_m), p(cam_c), None, p(loss), p(d_im),
-                                  p(d_cam_m) if have_cam else None, p(d_cam_c) if have_cam else None,
-                                  p(scratch), nbytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"t4d_photometric_loss failed (code {rc}): {_lib.last_error()}")
+    _lib.call("t4d_photometric_loss", V, H, W, ptr(im), ptr(gt), ptr(cam_m), ptr(cam_c), None, ptr(loss), ptr(d_im),
+              ptr(d_cam_m) if have_cam else None, ptr(d_cam_c) if have_cam else None, ptr(scratch), nbytes, _lib.stream(dev))
     return loss, d_im, (d_cam_m if have_cam else None), (d_cam_c if have_cam else None)
 
 
@@ -94,8 +91,6 @@ def photometric_loss(im: torch.Tensor, gt: torch.Tensor, cam_m: torch.Tensor = N
 class _FusedMaskedL1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, im, gt, mask):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         if not im.is_cuda:
             raise RuntimeError("topo4d_amd has no CPU path: tensors must live on a HIP device")
@@ -107,11 +102,8 @@ class _FusedMaskedL1(torch.autograd.Function):
         d_im = torch.empty_like(im_c)
         nbytes = lib.t4d_masked_l1_scratch_bytes(V)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        rc = lib.t4d_masked_l1_loss(V, H, W, p(im_c), p(gt_c), p(m_c), None, p(loss), p(d_im), p(scratch), nbytes,
-                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"t4d_masked_l1_loss failed (code {rc}): {_lib.last_error()}")
+        _lib.call("t4d_masked_l1_loss", V, H, W, ptr(im_c), ptr(gt_c), ptr(m_c), None, ptr(loss), ptr(d_im), ptr(scratch), nbytes,
+                  _lib.stream(dev))
         ctx.save_for_backward(d_im)
         return loss
 
@@ -143,8 +135,6 @@ def label_mask_target(mask_image: torch.Tensor, label_colors, gt: Optional[torch
     the V cameras of a frame [V,3,H,W] in ONE launch.  `label_colors`: [n,3] colours of the selected labels (a tensor, array or
     nested list; the reference's are uint8: helpers.py:806 `cmap[cmap_index[label]]`), in the channel order of the mask image.
     Returns (filtered_mask or None, target or None), shaped like the inputs; bit-identical to the reference's torch ops."""
-    from . import _lib
-    lib = _lib.load()
     if not mask_image.is_cuda:
         raise RuntimeError("topo4d_amd has no CPU path: tensors must live on a HIP device")
     one = mask_image.dim() == 3
@@ -167,11 +157,7 @@ def label_mask_target(mask_image: torch.Tensor, label_colors, gt: Optional[torch
     target = torch.empty_like(m) if g is not None else None
     if filtered is None and target is None:
         raise ValueError("label_mask_target: nothing to compute (no gt and want_mask False)")
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    rc = lib.t4d_label_mask_target(V, H, W, p(m), host, n, p(g), float(scale), p(filtered), p(target),
-                                   C.c_void_p(torch.cuda.current_stream(m.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"t4d_label_mask_target failed (code {rc}): {_lib.last_error()}")
+    _lib.call("t4d_label_mask_target", V, H, W, ptr(m), host, n, ptr(g), float(scale), ptr(filtered), ptr(target), _lib.stream(m.device))
     if one:
         filtered = None if filtered is None else filtered[0]
         target = None if target is None else target[0]
@@ -193,7 +179,6 @@ def get_mask(target_labels, mask, cmap_index, target_colors) -> torch.Tensor:
 def soft_color_loss_raw(x: torch.Tensor, y: torch.Tensor, weight: float, grad: Optional[torch.Tensor] = None, accumulate: bool = False):
     """t4d_soft_color_loss without autograd: returns (UNWEIGHTED l1_loss_v2 as a device scalar, grad).  `grad` [rows,width]
     receives (accumulate: is increased by) (weight / rows) * sign(x - y); allocated here when None."""
-    from . import _lib
     lib = _lib.load()
     if not x.is_cuda:
         raise RuntimeError("topo4d_amd has no CPU path: tensors must live on a HIP device")
@@ -207,11 +192,8 @@ def soft_color_loss_raw(x: torch.Tensor, y: torch.Tensor, weight: float, grad: O
     loss = torch.empty((), dtype=torch.float32, device=x.device)
     nbytes = lib.t4d_soft_color_scratch_bytes()
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    rc = lib.t4d_soft_color_loss(x.shape[0], x.shape[1], p(x), p(y), float(weight), p(loss), p(grad), int(bool(accumulate)), p(scratch),
-                                 nbytes, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"t4d_soft_color_loss failed (code {rc}): {_lib.last_error()}")
+    _lib.call("t4d_soft_color_loss", x.shape[0], x.shape[1], ptr(x), ptr(y), float(weight), ptr(loss), ptr(grad), int(bool(accumulate)),
+              ptr(scratch), nbytes, _lib.stream(x.device))
     return loss, grad
 
 

@@ -9,12 +9,12 @@ after every step.  step() is ONE kernel launch (`t4d_adam_pin_step`) for all ten
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional
 
 import torch
 
 from . import _lib
+from ._lib import ptr
 
 
 class FusedAdamPins:
@@ -157,12 +157,10 @@ class FusedAdamPins:
         """Write the pinned rows of the named tensors (default: every tensor that has pins) WITHOUT an optimiser step: ONE launch
         of the same kernel with no gradients.  The texture loop pins dense_rgb_colors BEFORE each render and not after the step
         (train.py:731-734), the geometry loop after it (train.py:676-700: step())."""
-        lib = _lib.load()
         todo = [g for g in self.param_groups if g["name"] in self._pins and (names is None or g["name"] in names)]
         if not todo:
             return
         arr = (_lib.T4DAdamTensor * len(todo))()
-        ptr = lambda t: C.c_void_p(t.data_ptr())
         for k, g in enumerate(todo):
             p = g["params"][0]
             if not p.is_cuda:
@@ -173,15 +171,11 @@ class FusedAdamPins:
             mask, vals = self._pins[g["name"]]
             arr[k] = _lib.T4DAdamTensor(ptr(p), None, None, None, ptr(mask), ptr(vals), rows, p.numel() // max(rows, 1), 0.0, 0, 0)
         dev = todo[0]["params"][0].device
-        rc = lib.t4d_adam_pin_step(arr, len(todo), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"t4d_adam_pin_step failed (code {rc}): {_lib.last_error()}")
+        _lib.call("t4d_adam_pin_step", arr, len(todo), float(self.betas[0]), float(self.betas[1]), float(self.eps), _lib.stream(dev))
 
     @torch.no_grad()
     def step(self, pins: bool = True) -> None:
         """Adam for every tensor that has a gradient, then (pins=True) the pinned rows of every tensor - one launch."""
-        lib = _lib.load()
         from . import rasterizer
         if rasterizer._PENDING and not torch.cuda.is_current_stream_capturing():
             # "auto" sync mode of the rasterizer: a render whose pair arena overflowed raises HERE at the latest, before the step
@@ -210,20 +204,17 @@ class FusedAdamPins:
                 keep.append(grad)
             st = self.state.get(p, {})
             mask, vals = self._pins.get(g["name"], (None, None)) if pins else (None, None)
-            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
             arr[k] = _lib.T4DAdamTensor(ptr(p), ptr(grad), ptr(st.get("exp_avg")) if grad is not None else None,
                                         ptr(st.get("exp_avg_sq")) if grad is not None else None, ptr(mask), ptr(vals), rows,
                                         width, float(g["lr"]), int(st.get("step", 0)) if grad is not None else 0,
                                         _lib.T4D_ADAM_CLEAR_GRAD if (grad is not None and g["name"] in self.clear_grad) else 0)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _lib.stream(dev)
         if self.capturable:
             if not torch.cuda.is_current_stream_capturing():
                 self.sync_hyper()
             step_dev, lr_dev = self._hyper(dev)
-            rc = lib.t4d_adam_pin_step_graph(arr, len(self.param_groups), float(self.betas[0]), float(self.betas[1]),
-                                             float(self.eps), C.c_void_p(step_dev.data_ptr()), self._layout[1], C.c_void_p(lr_dev.data_ptr()), stream)
+            _lib.call("t4d_adam_pin_step_graph", arr, len(self.param_groups), float(self.betas[0]), float(self.betas[1]),
+                      float(self.eps), ptr(step_dev), self._layout[1], ptr(lr_dev), stream)
         else:
-            rc = lib.t4d_adam_pin_step(arr, len(self.param_groups), float(self.betas[0]), float(self.betas[1]),
-                                       float(self.eps), stream)
-        if rc != 0:
-            raise RuntimeError(f"t4d_adam_pin_step failed (code {rc}): {_lib.last_error()}")
+            _lib.call("t4d_adam_pin_step", arr, len(self.param_groups), float(self.betas[0]), float(self.betas[1]),
+                      float(self.eps), stream)

@@ -10,12 +10,10 @@ the array `texture.bake_texture` returns.  Only the finished file crosses to the
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
-from ._lib import T4D_OK
+from ._lib import ptr
 
 _PINNED = {}
 
@@ -30,7 +28,7 @@ def max_encoded_bytes(h: int, w: int, c: int) -> int:
     _shape(int(h), int(w), int(c))
     n = _lib.load().t4d_png_max_bytes(int(h), int(w), int(c))
     if n == 0:
-        raise ValueError(f"t4d_png_max_bytes: {_lib.last_error()}")
+        raise _lib.error("t4d_png_max_bytes", exc=ValueError)
     return int(n)
 
 
@@ -71,12 +69,8 @@ def encode_png(image: torch.Tensor) -> bytes:
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
     length = torch.empty(1, dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    rc = lib.t4d_png_encode(C.c_void_p(img.data_ptr()), 1 if img.dtype == torch.float32 else 0, h, w, c, C.c_void_p(out.data_ptr()),
-                            cap, C.c_void_p(length.data_ptr()), C.c_void_p(scratch.data_ptr()), nscratch,
-                            C.c_void_p(stream.cuda_stream))
-    if rc != T4D_OK:
-        raise RuntimeError(f"t4d_png_encode failed (code {rc}): {_lib.last_error()}")
+    _lib.call("t4d_png_encode", ptr(img), 1 if img.dtype == torch.float32 else 0, h, w, c, ptr(out), cap, ptr(length), ptr(scratch),
+              nscratch, _lib.stream(dev))
     n = int(length.item())                                        # the one synchronisation
     if n <= 0 or n > cap:
         raise RuntimeError(f"t4d_png_encode: bad output length {n} (capacity {cap})")

@@ -23,6 +23,9 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _lib
+from ._lib import ptr
+
 # loss slots of t4d_priors_eval (include/topo4d_raster.h T4D_PRIOR_*), then the total
 TERMS = ("scale", "scale_max", "rigid", "rot", "iso", "flat", "flat_lip_bottom", "flat_eye", "flat_face_bottom", "flat_lip_socket",
          "flat_lid_top", "flat_lid_bottom", "flat_lip", "flat_mouth")
@@ -183,7 +186,6 @@ class TopologyPriors:
     def _pack(self):
         if self._struct is not None:
             return self._struct
-        from . import _lib
         s = _lib.T4DPriors()
         s.P, s.K = self.P, self.K
         p = lambda t: t.data_ptr() if t.numel() else None
@@ -207,7 +209,6 @@ class TopologyPriors:
 
     def record_layout(self):
         """(n_records, {term: first record}) as the library computes it (t4d_priors_record_layout)."""
-        from . import _lib
         base = (C.c_int64 * 9)()
         n = _lib.load().t4d_priors_record_layout(C.byref(self._pack()), base)
         return int(n), dict(zip(EDGE_TERMS + REGION_TERMS, [int(b) for b in base]))
@@ -222,7 +223,6 @@ class TopologyPriors:
         the next evaluation overwrites).  `grads` = (d_means3D, d_unnorm_rotations, d_log_scales) receive upstream * dL/d(raw
         tensor), ADDED to what they hold (accumulate) or written over it; None: `self.grads`, overwritten.  `upstream`: an
         optional device scalar multiplier of the gradients."""
-        from . import _lib
         lib = _lib.load()
         x, q, ls = (params[k].detach() for k in ("means3D", "unnorm_rotations", "log_scales"))
         dev = self.device
@@ -244,14 +244,11 @@ class TopologyPriors:
         if self._scratch is None:
             nbytes = lib.t4d_priors_scratch_bytes(C.byref(s))
             if nbytes == 0:
-                raise RuntimeError(f"t4d_priors_scratch_bytes failed: {_lib.last_error()}")
+                raise _lib.error("t4d_priors_scratch_bytes")
             self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        rc = lib.t4d_priors_eval(C.byref(s), int(bool(is_initial_timestep)), p(x), p(q), p(ls), p(grads[0]), p(grads[1]), p(grads[2]),
-                                 p(upstream), _lib.T4D_PRIORS_ACCUMULATE if accumulate else 0, p(self.losses), p(self._scratch),
-                                 self._scratch.numel(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"t4d_priors_eval failed (code {rc}): {_lib.last_error()}")
+        _lib.call("t4d_priors_eval", C.byref(s), int(bool(is_initial_timestep)), ptr(x), ptr(q), ptr(ls), ptr(grads[0]), ptr(grads[1]),
+                  ptr(grads[2]), ptr(upstream), _lib.T4D_PRIORS_ACCUMULATE if accumulate else 0, ptr(self.losses), ptr(self._scratch),
+                  self._scratch.numel(), _lib.stream(dev))
         return self.losses[len(TERMS)], self.detail(is_initial_timestep)
 
     def as_extra_loss(self, is_initial_timestep: bool):

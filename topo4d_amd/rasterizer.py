@@ -27,7 +27,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import (T4D_ABI_VERSION, T4D_ERR_PAIR_OVERFLOW, T4D_FLAG_CHECKED, T4D_FLAG_DEBUG_SYNC, T4D_FLAG_NO_LONG_BINS,
                    T4D_FLAG_PREFILTERED, T4D_OK, T4D_VIEW_FLOATS, T4DBackwardIO, T4DForwardIO, T4DProblem,
-                   T4DStatus)
+                   T4DStatus, ptr)
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -379,10 +379,6 @@ def _check_common(settings: Sequence[GaussianRasterizationSettings]):
 # ------------------------------------------------------------------------------------------------------------
 # low-level batch object (no autograd): what bench.py times and the autograd Function drives
 # ------------------------------------------------------------------------------------------------------------
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _f32c(t: Optional[torch.Tensor], name: str, device) -> Optional[torch.Tensor]:
     if t is None or t.numel() == 0:
         return None
@@ -391,14 +387,6 @@ def _f32c(t: Optional[torch.Tensor], name: str, device) -> Optional[torch.Tensor
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
-
-
-def _raw_stream(device) -> int:
-    """hipStream_t of torch's current stream on `device` (the private getter is ~20x cheaper than building a Stream object)."""
-    try:
-        return torch._C._cuda_getCurrentRawStream(device.index if device.index is not None else torch.cuda.current_device())
-    except AttributeError:                                   # pragma: no cover - older/newer torch without the private hook
-        return torch.cuda.current_stream(device).cuda_stream
 
 
 class _Plan:
@@ -489,9 +477,6 @@ class ViewBatch:
                 flags |= _lib.T4D_FLAG_SHORT_BINS
         return flags
 
-    def _stream(self):
-        return _raw_stream(self.device)
-
     # -- forward ---------------------------------------------------------------------------------------------
     def forward(self, means3D, opacities, scales=None, rotations=None, colors_precomp=None, shs=None,
                 cov3D_precomp=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -563,7 +548,7 @@ class ViewBatch:
         self.plan = plan
         status = plan.status
         lib = self.lib
-        stream = _raw_stream(dev)
+        stream = _lib.stream(dev)
         pending = None
         for _attempt in range(6):
             flags = self._flags(P, checked)
@@ -595,7 +580,7 @@ class ViewBatch:
             if rc == T4D_ERR_PAIR_OVERFLOW:
                 cap = _round_capacity(status.max_pairs_per_view)
                 continue
-            raise RuntimeError(f"t4d_rasterize_forward failed (code {rc}): {_lib.last_error()}")
+            raise _lib.error("t4d_rasterize_forward", rc)
         else:
             raise RuntimeError("pair arena kept overflowing; this should be impossible")
         if checked:
@@ -677,18 +662,18 @@ class ViewBatch:
                 poll_truncation(wait_for=pending)
             if pending.done and pending.overflow:
                 raise _truncation_error((pending.need, pending.cap))
-        rc = lib.t4d_rasterize_backward(C.byref(prob), plan.bio_ref, _raw_stream(dev))
+        rc = lib.t4d_rasterize_backward(C.byref(prob), plan.bio_ref, _lib.stream(dev))
         if rc != T4D_OK:
-            raise RuntimeError(f"t4d_rasterize_backward failed (code {rc}): {_lib.last_error()}")
+            raise _lib.error("t4d_rasterize_backward", rc)
         self._keepalive = (scratch, dL_dcolor, dL_ddepth, dL_dalpha)
         return g
 
     def fetch_status(self) -> T4DStatus:
         """Synchronising read of the forward's binning status (pairs needed, overflow flag)."""
         st = T4DStatus()
-        rc = self.lib.t4d_fetch_status(C.byref(self.prob), _ptr(self.state), C.byref(st), self._stream())
+        rc = self.lib.t4d_fetch_status(C.byref(self.prob), ptr(self.state), C.byref(st), _lib.stream(self.device))
         if rc != T4D_OK:
-            raise RuntimeError(f"t4d_fetch_status failed (code {rc}): {_lib.last_error()}")
+            raise _lib.error("t4d_fetch_status", rc)
         return st
 
 
@@ -703,10 +688,7 @@ def view_dot(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = Non
     if out is None:
         out = torch.empty(V, dtype=torch.float32, device=a.device)
     scratch = torch.empty(lib.t4d_view_dot_scratch_bytes(V), dtype=torch.uint8, device=a.device)
-    rc = lib.t4d_view_dot(V, n, _ptr(a), _ptr(b), _ptr(out), _ptr(scratch),
-                          C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream))
-    if rc != T4D_OK:
-        raise RuntimeError(f"t4d_view_dot failed (code {rc}): {_lib.last_error()}")
+    _lib.call("t4d_view_dot", V, n, ptr(a), ptr(b), ptr(out), ptr(scratch), _lib.stream(a.device))
     return out
 
 
@@ -776,7 +758,6 @@ class _RasterizeViews(torch.autograd.Function):
 
 def _sum_views(g, V: int, need_means2D: bool):
     """dict of per-view gradients [V,P,...] -> dict of view-summed gradients [P,...] (None stays None), one launch."""
-    lib = _lib.load()
     names = [k for k, t in g.items() if t is not None and (k != "means2D" or need_means2D)]
     out = {k: None for k in g}
     if not names:
@@ -787,9 +768,7 @@ def _sum_views(g, V: int, need_means2D: bool):
     src = (C.c_void_p * n)(*[g[k].data_ptr() for k in names])
     dst = (C.c_void_p * n)(*[out[k].data_ptr() for k in names])
     cnt = (C.c_int64 * n)(*[out[k].numel() for k in names])
-    rc = lib.t4d_sum_views(V, n, src, dst, cnt, _raw_stream(g[names[0]].device))
-    if rc != T4D_OK:
-        raise RuntimeError(f"t4d_sum_views failed (code {rc}): {_lib.last_error()}")
+    _lib.call("t4d_sum_views", V, n, src, dst, cnt, _lib.stream(g[names[0]].device))
     return out
 
 
@@ -872,14 +851,10 @@ class GaussianRasterizer(nn.Module):
         with torch.no_grad():
             if not positions.is_cuda:
                 raise RuntimeError("topo4d_amd has no CPU path: tensors must live on a HIP device")
-            lib = _lib.load()
             pos = positions.float().contiguous()
             views = pack_views([self.raster_settings], pos.device)
             out = torch.empty(pos.shape[0], dtype=torch.uint8, device=pos.device)
-            rc = lib.t4d_mark_visible(int(pos.shape[0]), _ptr(pos), _ptr(views), _ptr(out),
-                                      C.c_void_p(torch.cuda.current_stream(pos.device).cuda_stream))
-            if rc != T4D_OK:
-                raise RuntimeError(f"t4d_mark_visible failed (code {rc}): {_lib.last_error()}")
+            _lib.call("t4d_mark_visible", int(pos.shape[0]), ptr(pos), ptr(views), ptr(out), _lib.stream(pos.device))
             return out.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import T4D_ERR_PAIR_OVERFLOW, T4D_OK
+from ._lib import T4D_ERR_PAIR_OVERFLOW, T4D_OK, ptr
 
 _CAP = {}
 
@@ -70,21 +70,18 @@ def render_colors(vertices, triangles, colors, h: int, w: int, c: int = 3, BG=No
     key = (device.index, int(t.shape[0]), h, w)
     cap = _CAP.get(key, max(65536, 4 * int(t.shape[0])))
     need = C.c_int64(0)
-    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    stream = _lib.stream(device)
     for _ in range(4):
         nbytes = lib.t4d_texture_bake_scratch_bytes(h, w, cap)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        rc = lib.t4d_texture_render_colors(C.c_void_p(v.data_ptr()), C.c_void_p(t.data_ptr()), C.c_void_p(col.data_ptr()),
-                                           None if bg is None else C.c_void_p(bg.data_ptr()),
-                                           int(v.shape[0]), int(t.shape[0]), h, w, c, r0, r1, C.c_void_p(image.data_ptr()),
-                                           C.c_void_p(depth.data_ptr()), C.c_void_p(scratch.data_ptr()), nbytes, cap,
-                                           C.byref(need), stream)
+        rc = lib.t4d_texture_render_colors(ptr(v), ptr(t), ptr(col), ptr(bg), int(v.shape[0]), int(t.shape[0]), h, w, c, r0, r1,
+                                           ptr(image), ptr(depth), ptr(scratch), nbytes, cap, C.byref(need), stream)
         if rc == T4D_OK:
             break
         if rc == T4D_ERR_PAIR_OVERFLOW:
             cap = int(need.value * 1.25) + 1024
             continue
-        raise RuntimeError(f"t4d_texture_render_colors failed (code {rc}): {_lib.last_error()}")
+        raise _lib.error("t4d_texture_render_colors", rc)
     else:
         raise RuntimeError("texture bake: pair capacity kept overflowing")
     _CAP[key] = cap
@@ -136,7 +133,6 @@ def compute_vertex_attribute_by_weight(variables, attribute: torch.Tensor) -> to
     the dict."""
     if not attribute.is_cuda:
         raise RuntimeError("topo4d_amd has no CPU path: tensors must live on a HIP device")
-    lib = _lib.load()
     dev = attribute.device
     cache = variables.setdefault("_t4d_dense_cache", {})
     if cache.get("device") != dev:
@@ -151,9 +147,6 @@ def compute_vertex_attribute_by_weight(variables, attribute: torch.Tensor) -> to
     n_dense = n_total - n_coarse
     assert n_dense == cache["father"].numel() == cache["weight"].shape[0]
     out = torch.empty(n_total, width, dtype=torch.float32, device=dev)
-    p = lambda t: C.c_void_p(t.data_ptr())
-    rc = lib.t4d_dense_interpolate(p(attr), p(cache["quads"]), p(cache["father"]), p(cache["weight"]), n_coarse, n_dense, width,
-                                   p(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != T4D_OK:
-        raise RuntimeError(f"t4d_dense_interpolate failed (code {rc}): {_lib.last_error()}")
+    _lib.call("t4d_dense_interpolate", ptr(attr), ptr(cache["quads"]), ptr(cache["father"]), ptr(cache["weight"]), n_coarse, n_dense,
+              width, ptr(out), _lib.stream(dev))
     return out
