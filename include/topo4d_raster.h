@@ -416,6 +416,46 @@ size_t t4d_png_scratch_bytes(int32_t h, int32_t w, int32_t c);
 int t4d_png_encode(const void *image, int32_t is_float32, int32_t h, int32_t w, int32_t c, uint8_t *out, size_t out_capacity,
                    int64_t *out_bytes /* device */, void *scratch, size_t scratch_bytes, void *hip_stream);
 
+/* face.obj of helpers.save_mesh (helpers.py:963-990) on the device (topo4d_amd/objexport.py, csrc/t4d_obj.hip).  Every pointer
+ * but `transform` is device memory; none of these synchronises the stream.
+ *
+ * t4d_obj_vertex_faces: the vertex -> corner CSR of faces [n_faces,3] (once per topology): offsets [n_vert+1], entries [3*n_faces]
+ * (corner ids 3*face + k, ascending within a vertex), status [2] = {corners with an index outside [0, n_vert), vertices no face
+ * references}.  Scratch: t4d_obj_csr_scratch_bytes.
+ * t4d_obj_vertex_normals: trimesh 4.4.1 Trimesh(vertices, faces).vertex_normals in float64 - angle-weighted unit face normals
+ * summed in ascending face order, unitised - from vertices [n_vert,3] (float32, or float64 with is_float64 = 1) and the CSR of
+ * the same faces.  normals [n_vert,3] float64.  Scratch: t4d_obj_normals_scratch_bytes.
+ * t4d_obj_frame_vertices: save_mesh's vertices, out [n_vert,3] float64 = v @ Rg^T + tg, transform (HOST) = Rg row-major then tg
+ * (12 doubles); v = float64(means3D) when normals is NULL (frame 1), else means3D pushed along the normal by
+ * clamp(sqrt(1 / sum((R^-1 n)^2 / exp(log_scales)^2)), 0, 1e-3) in float32, R = build_rotation(rotations) (external.py:26-43).
+ * t4d_obj_format_doubles: repr(float(x)) of values [n] into chars [n, T4D_OBJ_FLOAT_CHARS] (not terminated), lengths [n].
+ * t4d_obj_float_lines: "v x y z\n" (kind T4D_OBJ_V, values [rows,3]) or "vt u v\n" (T4D_OBJ_VT, [rows,2]) lines, every value as
+ * repr(float) - the f-strings of write_obj_with_uv (helpers.py:258-272) - into out, and the byte count to *out_bytes.
+ * t4d_obj_face_lines: "f v+1/uv+1 ...\n" per face; face k's corners are [face_off[k], face_off[k+1]) of v_idx / uv_idx [n_corners]
+ * (face_off [n_faces+1] non-decreasing from 0 to n_corners).
+ * Output capacity: t4d_obj_text_max_bytes(kind, rows, corners) (rows = lines, corners used by T4D_OBJ_F only); scratch:
+ * t4d_obj_text_scratch_bytes with the same arguments. */
+#define T4D_OBJ_V 0
+#define T4D_OBJ_VT 1
+#define T4D_OBJ_F 2
+#define T4D_OBJ_FLOAT_CHARS 24
+size_t t4d_obj_csr_scratch_bytes(int32_t n_vert);
+int t4d_obj_vertex_faces(const int32_t *faces, int64_t n_faces, int32_t n_vert, int32_t *offsets, int32_t *entries, int32_t *status,
+                         void *scratch, size_t scratch_bytes, void *hip_stream);
+size_t t4d_obj_normals_scratch_bytes(int64_t n_faces);
+int t4d_obj_vertex_normals(const void *vertices, int32_t is_float64, int32_t n_vert, const int32_t *faces, int64_t n_faces,
+                           const int32_t *offsets, const int32_t *entries, double *normals, void *scratch, size_t scratch_bytes,
+                           void *hip_stream);
+int t4d_obj_frame_vertices(const float *means3D, const float *log_scales, const float *rotations, const double *normals,
+                           int32_t n_vert, const double *transform, double *out, void *hip_stream);
+int t4d_obj_format_doubles(const double *values, int64_t n, uint8_t *chars, uint8_t *lengths, void *hip_stream);
+size_t t4d_obj_text_max_bytes(int32_t kind, int64_t rows, int64_t corners);
+size_t t4d_obj_text_scratch_bytes(int32_t kind, int64_t rows, int64_t corners);
+int t4d_obj_float_lines(int32_t kind, const double *values, int64_t rows, uint8_t *out, size_t out_capacity, int64_t *out_bytes,
+                        void *scratch, size_t scratch_bytes, void *hip_stream);
+int t4d_obj_face_lines(const int64_t *face_off, const int64_t *v_idx, const int64_t *uv_idx, int64_t n_faces, int64_t n_corners,
+                       uint8_t *out, size_t out_capacity, int64_t *out_bytes, void *scratch, size_t scratch_bytes, void *hip_stream);
+
 /* Optional per-kernel timing with HIP events recorded on the stream the kernels are launched on.  Between
  * t4d_profile_begin() and t4d_profile_end() every kernel launch of this library is bracketed by two events;
  * t4d_profile_end() synchronises them and returns, per kernel, the summed elapsed time and the launch count.

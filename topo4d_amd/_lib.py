@@ -143,6 +143,16 @@ SIGNATURES = {
     "t4d_png_max_bytes": (_SZ, [_I32] * 3),
     "t4d_png_scratch_bytes": (_SZ, [_I32] * 3),
     "t4d_png_encode": (_INT, [_VP] + [_I32] * 4 + [_VP, _SZ, _VP, _VP, _SZ, _VP]),
+    "t4d_obj_csr_scratch_bytes": (_SZ, [_I32]),
+    "t4d_obj_vertex_faces": (_INT, [_VP, _I64, _I32] + [_VP] * 4 + [_SZ, _VP]),
+    "t4d_obj_normals_scratch_bytes": (_SZ, [_I64]),
+    "t4d_obj_vertex_normals": (_INT, [_VP, _I32, _I32, _VP, _I64] + [_VP] * 4 + [_SZ, _VP]),
+    "t4d_obj_frame_vertices": (_INT, [_VP] * 4 + [_I32, C.POINTER(C.c_double), _VP, _VP]),
+    "t4d_obj_format_doubles": (_INT, [_VP, _I64, _VP, _VP, _VP]),
+    "t4d_obj_text_max_bytes": (_SZ, [_I32, _I64, _I64]),
+    "t4d_obj_text_scratch_bytes": (_SZ, [_I32, _I64, _I64]),
+    "t4d_obj_float_lines": (_INT, [_I32, _VP, _I64, _VP, _SZ, _VP, _VP, _SZ, _VP]),
+    "t4d_obj_face_lines": (_INT, [_VP] * 3 + [_I64, _I64, _VP, _SZ, _VP, _VP, _SZ, _VP]),
     "t4d_profile_begin": (_INT, []),
     "t4d_profile_end": (_INT, [C.POINTER(T4DKernelTime), _INT, C.POINTER(_INT)]),
     "t4d_debug_state_layout": (_INT, [_PROB, _INT, C.POINTER(C.c_uint64), _INT]),
