@@ -456,6 +456,55 @@ int t4d_obj_float_lines(int32_t kind, const double *values, int64_t rows, uint8_
 int t4d_obj_face_lines(const int64_t *face_off, const int64_t *v_idx, const int64_t *uv_idx, int64_t n_faces, int64_t n_corners,
                        uint8_t *out, size_t out_capacity, int64_t *out_bytes, void *scratch, size_t scratch_bytes, void *hip_stream);
 
+/* ---- Ingest: a frame's views from file bytes to float32 targets (csrc/t4d_ingest.hip; topo4d_amd/ingest.py) ----
+ * T4DJpegImage: one baseline JPEG (SOF0/SOF1, 8-bit Huffman, 3 components YCbCr, luma sampling 1x1, 2x1 or 2x2 with 1x1 chroma,
+ * one interleaved scan) as the host parsed its headers.  Its entropy-coded segment (stuffed, RSTn markers included, up to the
+ * marker that ends it) is data[data_offset, data_offset + data_bytes) of the batch's device buffer; the segments of a batch are
+ * packed back to back in image order (data_offset = the sum of the previous data_bytes).  quant: the DQT tables in natural
+ * order; huff_bits/huff_vals: DHT tables, slots 0-3 DC tables 0-3 and 4-7 AC tables 0-3; comp_*: the table ids of Y, Cb, Cr.
+ * The image is written as uint8 [height, width, 3] RGB at out + out_offset, byte-identical to libjpeg-turbo's ISLOW IDCT,
+ * fancy upsampling and YCbCr->RGB.
+ *
+ * t4d_jpeg_decode: images (host) and d_images (a device copy of the same array), n of them.  chunk_bits (0: the default 4096,
+ * else >= 64) is the length of a lane's chunk in the self-synchronising decode of images without restart intervals.
+ * status[i] (device) receives 0 or an OR of 1 (entropy segment ended early), 2 (more MCUs than the frame holds), 4 (a code no
+ * Huffman table holds, or a DHT table that over-fills the code space), 8 (RSTn markers missing, extra or out of sequence).
+ * No read outside data[data_offset, data_offset + data_bytes) is made whatever the bytes hold. */
+typedef struct T4DJpegImage {
+    int32_t width, height;
+    int32_t h_samp, v_samp;
+    int32_t restart_interval;               /* MCUs per restart interval, 0: none */
+    int32_t reserved0;
+    int64_t data_offset, data_bytes;
+    int64_t out_offset;
+    uint8_t comp_quant[3], comp_dc[3], comp_ac[3];
+    uint8_t reserved1[7];
+    uint16_t quant[4][64];
+    uint8_t huff_bits[8][16];
+    uint8_t huff_vals[8][256];
+} T4DJpegImage;
+size_t t4d_jpeg_scratch_bytes(const T4DJpegImage *images, int32_t n, int32_t chunk_bits);
+int t4d_jpeg_decode(const T4DJpegImage *images, const T4DJpegImage *d_images, int32_t n, const uint8_t *data, int32_t chunk_bits,
+                    uint8_t *out, size_t out_capacity, int32_t *status, void *scratch, size_t scratch_bytes, void *hip_stream);
+
+/* T4DWarpView: skimage.transform.warp(image, matrix, order=1, mode="constant", cval, clip=True) of one uint8 HWC image read as
+ * image / 255.0 in float64, rounded to float32 and written as [channels, out_rows, out_cols] to dst.  src: rows x cols x
+ * channels samples, src_pitch bytes per row (a crop of a wider image: src_pitch > cols * channels).  matrix: the first two rows
+ * of the inverse map, output (col, row) -> source (col, row).  The output is clipped to the input's [min, max], widened to
+ * cval where cval lies outside it and inside the warped values' range (_clip_warp_output).
+ * t4d_warp_views: views (host) and d_views (a device copy), one launch set for all of them. */
+typedef struct T4DWarpView {
+    const uint8_t *src;
+    float *dst;
+    int32_t rows, cols, channels, src_pitch;
+    int32_t out_rows, out_cols;
+    double matrix[6];
+    double cval;
+} T4DWarpView;
+size_t t4d_warp_scratch_bytes(int32_t n_views);
+int t4d_warp_views(const T4DWarpView *views, const T4DWarpView *d_views, int32_t n_views, void *scratch, size_t scratch_bytes,
+                   void *hip_stream);
+
 /* Optional per-kernel timing with HIP events recorded on the stream the kernels are launched on.  Between
  * t4d_profile_begin() and t4d_profile_end() every kernel launch of this library is bracketed by two events;
  * t4d_profile_end() synchronises them and returns, per kernel, the summed elapsed time and the launch count.

@@ -100,6 +100,19 @@ class T4DDenseMesh(C.Structure):
             "dense_vertex", "vertex_father", "vertex_weight", "dense_uvs", "faces", "uv_faces")]
 
 
+class T4DJpegImage(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "h_samp", "v_samp", "restart_interval", "reserved0")] + [
+        (n, C.c_int64) for n in ("data_offset", "data_bytes", "out_offset")] + [
+        (n, C.c_uint8 * 3) for n in ("comp_quant", "comp_dc", "comp_ac")] + [
+        ("reserved1", C.c_uint8 * 7), ("quant", (C.c_uint16 * 64) * 4), ("huff_bits", (C.c_uint8 * 16) * 8),
+        ("huff_vals", (C.c_uint8 * 256) * 8)]
+
+
+class T4DWarpView(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)] + [(n, C.c_int32) for n in (
+        "rows", "cols", "channels", "src_pitch", "out_rows", "out_cols")] + [("matrix", C.c_double * 6), ("cval", C.c_double)]
+
+
 _VP, _I32, _I64, _F32, _SZ, _INT = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t, C.c_int
 _PROB = C.POINTER(T4DProblem)
 
@@ -153,6 +166,10 @@ SIGNATURES = {
     "t4d_obj_text_scratch_bytes": (_SZ, [_I32, _I64, _I64]),
     "t4d_obj_float_lines": (_INT, [_I32, _VP, _I64, _VP, _SZ, _VP, _VP, _SZ, _VP]),
     "t4d_obj_face_lines": (_INT, [_VP] * 3 + [_I64, _I64, _VP, _SZ, _VP, _VP, _SZ, _VP]),
+    "t4d_jpeg_scratch_bytes": (_SZ, [C.POINTER(T4DJpegImage), _I32, _I32]),
+    "t4d_jpeg_decode": (_INT, [C.POINTER(T4DJpegImage), _VP, _I32, _VP, _I32, _VP, _SZ, _VP, _VP, _SZ, _VP]),
+    "t4d_warp_scratch_bytes": (_SZ, [_I32]),
+    "t4d_warp_views": (_INT, [C.POINTER(T4DWarpView), _VP, _I32, _VP, _SZ, _VP]),
     "t4d_profile_begin": (_INT, []),
     "t4d_profile_end": (_INT, [C.POINTER(T4DKernelTime), _INT, C.POINTER(_INT)]),
     "t4d_debug_state_layout": (_INT, [_PROB, _INT, C.POINTER(C.c_uint64), _INT]),
