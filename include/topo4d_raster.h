@@ -415,6 +415,15 @@ size_t t4d_png_max_bytes(int32_t h, int32_t w, int32_t c);
 size_t t4d_png_scratch_bytes(int32_t h, int32_t w, int32_t c);
 int t4d_png_encode(const void *image, int32_t is_float32, int32_t h, int32_t w, int32_t c, uint8_t *out, size_t out_capacity,
                    int64_t *out_bytes /* device */, void *scratch, size_t scratch_bytes, void *hip_stream);
+/* The same encoder for a render as torchvision's save_image writes it (train.py's progress snapshots, topo4d_amd/progress.py):
+ * image [3,h,w] float32 on the device, contiguous, channel-planar; the file is RGB (colour type 2).  Each value is quantised as
+ * x.mul(255).add_(0.5).clamp_(0, 255).to("cpu", torch.uint8): y = x*255 rounded to float32, then y + 0.5 rounded to float32 as a
+ * separate rounding (never one fused multiply-add), then clamped to [0, 255] with NaN kept, then truncated toward zero to uint8
+ * with NaN -> 0 (ATen's x86-64 conversion).  Output, out_capacity, scratch and error codes as t4d_png_encode with c = 3
+ * (t4d_png_max_bytes(h, w, 3), t4d_png_scratch_bytes(h, w, 3)); arguments are checked before anything touches a device.  Does not
+ * synchronise the stream. */
+int t4d_png_encode_chw(const float *image, int32_t h, int32_t w, uint8_t *out, size_t out_capacity, int64_t *out_bytes /* device */,
+                       void *scratch, size_t scratch_bytes, void *hip_stream);
 
 /* face.obj of helpers.save_mesh (helpers.py:963-990) on the device (topo4d_amd/objexport.py, csrc/t4d_obj.hip).  Every pointer
  * but `transform` is device memory; none of these synchronises the stream.

@@ -156,6 +156,7 @@ SIGNATURES = {
     "t4d_png_max_bytes": (_SZ, [_I32] * 3),
     "t4d_png_scratch_bytes": (_SZ, [_I32] * 3),
     "t4d_png_encode": (_INT, [_VP] + [_I32] * 4 + [_VP, _SZ, _VP, _VP, _SZ, _VP]),
+    "t4d_png_encode_chw": (_INT, [_VP] + [_I32] * 2 + [_VP, _SZ, _VP, _VP, _SZ, _VP]),
     "t4d_obj_csr_scratch_bytes": (_SZ, [_I32]),
     "t4d_obj_vertex_faces": (_INT, [_VP, _I64, _I32] + [_VP] * 4 + [_SZ, _VP]),
     "t4d_obj_normals_scratch_bytes": (_SZ, [_I64]),

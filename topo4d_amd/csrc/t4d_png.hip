@@ -1,4 +1,5 @@
-// t4d_png.hip — lossless PNG encoder for baked UV textures (write_texture(..., encoder="gpu")), on the device.
+// t4d_png.hip — lossless PNG encoder for baked UV textures (write_texture(..., encoder="gpu")) and progress renders
+// (progress.save_image), on the device.
 //
 // The file is a plain PNG: signature, IHDR (8-bit, no interlace, colour type 0 / 2 / 6 for C = 1 / 3 / 4), a 2-byte IDAT with
 // the zlib header, one IDAT per segment, a 4-byte IDAT with the Adler-32 trailer, IEND.  The IDAT payloads joined are one zlib
@@ -7,8 +8,9 @@
 // of literals and distance-1 runs (or one stored block where that is smaller), closed by an empty stored block so the next segment
 // starts byte-aligned.  Four launches:
 //
-//  * k_png_filter   one workgroup per row: quantise (float32 exactly as numpy's (x*255).astype(uint8) on x86-64), score the five
-//                   filters, write filter byte + filtered row to scratch.
+//  * k_png_filter   one workgroup per row: quantise (float32 [h,w,c] exactly as numpy's (x*255).astype(uint8) on x86-64, or a
+//                   float32 [3,h,w] render exactly as torchvision's save_image), score the five filters, write filter byte +
+//                   filtered row to scratch.
 //  * k_png_encode   one workgroup per segment: segment into LDS; the parse into literals and distance-1 runs is fixed by the
 //                   maximal equal-byte runs (every thread walks its own slice, with run bounds carried in by block scans);
 //                   histograms by LDS integer atomics; length-limited Huffman codes (15 / 7 bits); bits OR'ed into LDS words at
@@ -126,10 +128,35 @@ __device__ __forceinline__ uint32_t quant(float x)
     return (uint32_t)(int32_t)y & 0xFFu;
 }
 
-template <bool F32>
-__device__ __forceinline__ uint32_t pix(const void *img, int64_t i)
+// torchvision's save_image: x.mul(255).add_(0.5).clamp_(0, 255) on the device, then .to("cpu", torch.uint8).  Two roundings, a
+// clamp that keeps NaN, and ATen's x86-64 float -> uint8 conversion of the clamped value: truncation toward zero, NaN -> 0.
+// hipcc contracts a*b+c into one v_fma_f32 (one rounding) by default, even through __fmul_rn / __fadd_rn: the pragma keeps the
+// multiply and the add apart.  (A scan of every float32 in [-0.003, 1.003] found no byte the fused form changes; outside that range
+// both clamp.  The pragma keeps the arithmetic torch's all the same.)
+__device__ __forceinline__ uint32_t quant_tv(float x)
 {
-    if (F32) return quant(((const float *)img)[i]);
+#pragma clang fp contract(off)
+    const float m = x * 255.0f;
+    const float y = m + 0.5f;
+    if (!(y > 0.0f)) return 0u;                                       // also NaN
+    if (y >= 255.0f) return 255u;
+    return (uint32_t)y;
+}
+
+// input forms of k_png_filter
+enum PixMode { kU8 = 0, kF32 = 1, kF32Chw = 2 };
+
+// byte x of row r of the [h, w*c] image: [h,w,c] uint8 or float32 (numpy's cast), or a contiguous [3,h,w] float32 (torchvision's
+// rounding), whose byte x is plane x % 3, column x / 3
+template <int MODE>
+__device__ __forceinline__ uint32_t pix(const void *img, const Shape &s, int64_t r, int64_t x)
+{
+    if (MODE == kF32Chw) {
+        const int64_t col = x / 3, plane = x - 3 * col;
+        return quant_tv(((const float *)img)[(plane * s.h + r) * s.w + col]);
+    }
+    const int64_t i = r * ((int64_t)s.w * s.c) + x;
+    if (MODE == kF32) return quant(((const float *)img)[i]);
     return ((const uint8_t *)img)[i];
 }
 
@@ -146,20 +173,19 @@ __device__ __forceinline__ uint32_t sabs8(uint32_t r)             // |(int8)r|
     return (uint32_t)(v < 0 ? -v : v);
 }
 
-template <bool F32>
+template <int MODE>
 __global__ __launch_bounds__(kBlock) void k_png_filter(const void *img, Shape s, uint8_t *filt)
 {
     __shared__ unsigned long long red[5][kBlock];
     const int64_t r = blockIdx.x;
     const int64_t wc = (int64_t)s.w * s.c;
     const int c = s.c;
-    const int64_t cur0 = r * wc, prev0 = (r - 1) * wc;
     unsigned long long sum[5] = {0, 0, 0, 0, 0};
     for (int64_t x = threadIdx.x; x < wc; x += kBlock) {
-        const uint32_t v = pix<F32>(img, cur0 + x);
-        const uint32_t a = x >= c ? pix<F32>(img, cur0 + x - c) : 0u;
-        const uint32_t b = r > 0 ? pix<F32>(img, prev0 + x) : 0u;
-        const uint32_t cc = (r > 0 && x >= c) ? pix<F32>(img, prev0 + x - c) : 0u;
+        const uint32_t v = pix<MODE>(img, s, r, x);
+        const uint32_t a = x >= c ? pix<MODE>(img, s, r, x - c) : 0u;
+        const uint32_t b = r > 0 ? pix<MODE>(img, s, r - 1, x) : 0u;
+        const uint32_t cc = (r > 0 && x >= c) ? pix<MODE>(img, s, r - 1, x - c) : 0u;
         sum[0] += sabs8(v);
         sum[1] += sabs8(v - a);
         sum[2] += sabs8(v - b);
@@ -179,10 +205,10 @@ __global__ __launch_bounds__(kBlock) void k_png_filter(const void *img, Shape s,
     uint8_t *out = filt + r * s.row;
     if (threadIdx.x == 0) out[0] = (uint8_t)best;
     for (int64_t x = threadIdx.x; x < wc; x += kBlock) {
-        const uint32_t v = pix<F32>(img, cur0 + x);
-        const uint32_t a = x >= c ? pix<F32>(img, cur0 + x - c) : 0u;
-        const uint32_t b = r > 0 ? pix<F32>(img, prev0 + x) : 0u;
-        const uint32_t cc = (r > 0 && x >= c) ? pix<F32>(img, prev0 + x - c) : 0u;
+        const uint32_t v = pix<MODE>(img, s, r, x);
+        const uint32_t a = x >= c ? pix<MODE>(img, s, r, x - c) : 0u;
+        const uint32_t b = r > 0 ? pix<MODE>(img, s, r - 1, x) : 0u;
+        const uint32_t cc = (r > 0 && x >= c) ? pix<MODE>(img, s, r - 1, x - c) : 0u;
         const uint32_t pred = best == 0 ? 0u : best == 1 ? a : best == 2 ? b : best == 3 ? ((a + b) >> 1) : paeth(a, b, cc);
         out[1 + x] = (uint8_t)(v - pred);
     }
@@ -693,6 +719,21 @@ __global__ __launch_bounds__(kBlock) void k_png_assemble(Shape s, const uint8_t 
     for (uint32_t i = t; i < si.bytes; i += kBlock) p[8 + i] = src[i];
 }
 
+// the three launches after k_png_filter, on the filtered rows at scratch + L.filt
+void launch_deflate(const Shape &s, const PngLayout &L, void *scratch, uint8_t *out, size_t out_capacity, int64_t *out_bytes,
+                    hipStream_t stream)
+{
+    char *b = (char *)scratch;
+    const uint8_t *filt = (const uint8_t *)(b + L.filt);
+    uint8_t *slots = (uint8_t *)(b + L.slots);
+    SegInfo *info = (SegInfo *)(b + L.info);
+    int64_t *offs = (int64_t *)(b + L.offs);
+    hipLaunchKernelGGL(k_png_encode, dim3((unsigned)s.segs), dim3(kBlock), 0, stream, filt, s, slots, info);
+    hipLaunchKernelGGL(k_png_finalize, dim3(1), dim3(kBlock), 0, stream, s, info, offs, out, (int64_t)out_capacity, out_bytes);
+    hipLaunchKernelGGL(k_png_assemble, dim3((unsigned)s.segs), dim3(kBlock), 0, stream, s, slots, info, offs, out,
+                       (int64_t)out_capacity);
+}
+
 }  // namespace
 
 T4D_EXPORT size_t t4d_png_max_bytes(int32_t h, int32_t w, int32_t c)
@@ -724,15 +765,26 @@ T4D_EXPORT int t4d_png_encode(const void *image, int32_t is_float32, int32_t h, 
     const PngLayout L = png_layout(s);
     if (scratch_bytes < L.total) return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_png_encode: scratch too small");
     hipStream_t stream = (hipStream_t)hip_stream;
-    char *b = (char *)scratch;
-    uint8_t *filt = (uint8_t *)(b + L.filt), *slots = (uint8_t *)(b + L.slots);
-    SegInfo *info = (SegInfo *)(b + L.info);
-    int64_t *offs = (int64_t *)(b + L.offs);
-    if (is_float32) hipLaunchKernelGGL(k_png_filter<true>, dim3((unsigned)h), dim3(kBlock), 0, stream, image, s, filt);
-    else hipLaunchKernelGGL(k_png_filter<false>, dim3((unsigned)h), dim3(kBlock), 0, stream, image, s, filt);
-    hipLaunchKernelGGL(k_png_encode, dim3((unsigned)s.segs), dim3(kBlock), 0, stream, filt, s, slots, info);
-    hipLaunchKernelGGL(k_png_finalize, dim3(1), dim3(kBlock), 0, stream, s, info, offs, out, (int64_t)out_capacity, out_bytes);
-    hipLaunchKernelGGL(k_png_assemble, dim3((unsigned)s.segs), dim3(kBlock), 0, stream, s, slots, info, offs, out,
-                       (int64_t)out_capacity);
+    uint8_t *filt = (uint8_t *)((char *)scratch + L.filt);
+    if (is_float32) hipLaunchKernelGGL(k_png_filter<kF32>, dim3((unsigned)h), dim3(kBlock), 0, stream, image, s, filt);
+    else hipLaunchKernelGGL(k_png_filter<kU8>, dim3((unsigned)h), dim3(kBlock), 0, stream, image, s, filt);
+    launch_deflate(s, L, scratch, out, out_capacity, out_bytes, stream);
     return t4d_launch_status("t4d_png_encode");
+}
+
+T4D_EXPORT int t4d_png_encode_chw(const float *image, int32_t h, int32_t w, uint8_t *out, size_t out_capacity, int64_t *out_bytes,
+                                  void *scratch, size_t scratch_bytes, void *hip_stream)
+{
+    if (!image || !out || !out_bytes || !scratch || !shape_ok(h, w, 3))
+        return t4d_fail(T4D_ERR_ARG, "t4d_png_encode_chw: bad arguments (NULL buffer, or h, w < 1 or h*(1+3w) > 2^38)");
+    const Shape s = make_shape(h, w, 3);
+    if (out_capacity < (size_t)max_bytes(s))
+        return t4d_fail(T4D_ERR_ARG, "t4d_png_encode_chw: out_capacity below t4d_png_max_bytes(h, w, 3)");
+    const PngLayout L = png_layout(s);
+    if (scratch_bytes < L.total) return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_png_encode_chw: scratch below t4d_png_scratch_bytes(h, w, 3)");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(k_png_filter<kF32Chw>, dim3((unsigned)h), dim3(kBlock), 0, stream, (const void *)image, s,
+                       (uint8_t *)((char *)scratch + L.filt));
+    launch_deflate(s, L, scratch, out, out_capacity, out_bytes, stream);
+    return t4d_launch_status("t4d_png_encode_chw");
 }

@@ -335,7 +335,7 @@ def _with_priors(extra_loss: Optional[Callable], priors, is_initial_timestep: bo
 def optimise_views(params, dataset: List[dict], optimizer, n_iters: int, seed: int = 0, loss_fn: Optional[Callable] = None,
                    extra_loss: Optional[Callable] = None, max_2D_radius: Optional[torch.Tensor] = None,
                    explicit: Optional[bool] = None, use_mask: bool = False, is_initial_timestep: bool = True, label_colors=None,
-                   priors=None):
+                   priors=None, report: Optional[Callable[[int], None]] = None):
     """train.py:661-673 for `n_iters` iterations.  Returns the list of per-iteration losses (device scalars, no sync).
     `use_mask`, `is_initial_timestep`: get_loss's branch (train.py:315-327; Topo4D runs use_mask=True, i.e. the masked target in
     every frame after the first - `label_colors` as in prepare_masked_targets, which is called here once).
@@ -344,7 +344,10 @@ def optimise_views(params, dataset: List[dict], optimizer, n_iters: int, seed: i
     arithmetic, a third of the host time; `extra_loss` terms (the regularisers of train.py:330-368) are differentiated on their
     own and their gradients added.  `priors` (priors.TopologyPriors): the topology regularisers of get_loss (train.py:328-368)
     for the frame kind `is_initial_timestep` says, fused into every iteration (explicit: added into the gradient buffers after the
-    rasterizer's backward; otherwise through their autograd.Function)."""
+    rasterizer's backward; otherwise through their autograd.Function).
+    `report(i)`: called under no_grad with the iteration index after iteration i's optimiser step, pins and radius bookkeeping -
+    where train.py:702 calls report_progress, e.g. `lambda i: progress.report_progress(params, dataset, t + 1, i, bar, ...)`.  A
+    reporter that renders leaves the loop's losses and parameters unchanged bit for bit."""
     rng = Random(seed)
     todo: list = []
     losses = []
@@ -358,7 +361,7 @@ def optimise_views(params, dataset: List[dict], optimizer, n_iters: int, seed: i
         before = set(optimizer.clear_grad)
         cam_grads = _adopt_cam_grads(params, optimizer)
         try:
-            for _ in range(n_iters):
+            for it in range(n_iters):
                 curr, todo = get_batch(todo, dataset, rng)
                 l, radius, grads, _, _ = explicit_iteration(params, curr, cam_grads, target=curr['masked_im'] if masked else None,
                                                             extra_loss=extra_loss, priors=priors,
@@ -369,11 +372,14 @@ def optimise_views(params, dataset: List[dict], optimizer, n_iters: int, seed: i
                 optimizer.zero_grad(set_to_none=True)
                 _bookkeep(radius, max_2D_radius)
                 losses.append(l)
+                if report is not None:
+                    with torch.no_grad():
+                        report(it)
         finally:
             optimizer.clear_grad = before
         return losses
     extra_loss = _with_priors(extra_loss, priors, is_initial_timestep)
-    for _ in range(n_iters):
+    for it in range(n_iters):
         curr, todo = get_batch(todo, dataset, rng)
         l, radius, _ = photometric_iteration(params, curr, loss_fn, extra_loss, use_mask=use_mask,
                                              is_initial_timestep=is_initial_timestep, label_colors=label_colors)
@@ -382,6 +388,8 @@ def optimise_views(params, dataset: List[dict], optimizer, n_iters: int, seed: i
             optimizer.step()
             optimizer.zero_grad(set_to_none=True)
             _bookkeep(radius, max_2D_radius)
+            if report is not None:
+                report(it)
         losses.append(l.detach())
     return losses
 
@@ -389,13 +397,15 @@ def optimise_views(params, dataset: List[dict], optimizer, n_iters: int, seed: i
 def optimise_dense_views(params, variables, dataset: List[dict], optimizer, n_iters: int, seed: int = 0,
                          loss_fn: Optional[Callable] = None, soft_color_fn: Optional[Callable] = None,
                          pre_iteration: Optional[Callable] = None, max_2D_radius: Optional[torch.Tensor] = None,
-                         explicit: Optional[bool] = None, soft_color_weight: float = SOFT_COLOR_WEIGHT):
+                         explicit: Optional[bool] = None, soft_color_weight: float = SOFT_COLOR_WEIGHT,
+                         report: Optional[Callable[[int], None]] = None):
     """The texture loop, train.py:729-741, for `n_iters` iterations (args.dense_opt_num = 301 per frame): pins on
     dense_rgb_colors BEFORE each render (train.py:731-734) -> get_loss_dense(use_mask=False) -> backward -> Adam.
     `variables['dense_init_colors']`: the soft-colour anchor (train.py:258,502).
     Pins: with a FusedAdamPins optimiser, the rows set by `optimizer.set_pin('dense_rgb_colors', index, 0.0)` are written before
     every render (apply_pins) and NOT after the step - the reference leaves the last step's values in those rows (they are what
     save_mesh exports); any other optimiser: pass `pre_iteration`, a callable run under no_grad before every render.
+    `report(i)`: as in optimise_views - after iteration i's step, under no_grad (train.py:742 calls report_progress_dense there).
     Returns the list of per-iteration total losses (device scalars)."""
     from .optim import FusedAdamPins
     rng = Random(seed)
@@ -407,7 +417,7 @@ def optimise_dense_views(params, variables, dataset: List[dict], optimizer, n_it
         raise ValueError("explicit=True needs the fused losses, no pre_iteration callable, a FusedAdamPins optimiser and the parameters " + ", ".join(_DENSE_KEYS))
     chain = can if explicit is None else explicit
     init = variables['dense_init_colors']
-    for _ in range(n_iters):
+    for it in range(n_iters):
         curr, todo = get_batch(todo, dataset, rng)
         with torch.no_grad():
             if pre_iteration is not None:
@@ -429,6 +439,8 @@ def optimise_dense_views(params, variables, dataset: List[dict], optimizer, n_it
                 optimizer.step()
             optimizer.zero_grad(set_to_none=True)
             _bookkeep(radius, max_2D_radius)
+            if report is not None:
+                report(it)
         losses.append(l)
     return losses
 
@@ -446,6 +458,10 @@ class GraphedViews:
         gv.check()                                         # once in a while: raises if a replay outgrew its pair arena
         gv.load_frame(next_dataset)                        # next frame: new target images into the recorded buffers
                                                            # (dense=True: ALSO the re-bound dense_init_colors / dense_means3D, below)
+
+    Progress snapshots (train.py:702 / :742): call the reporter yourself between two steps, after the step of iteration `it` -
+    `progress.report_progress(params, dataset, t + 1, it, bar, ...)` renders eagerly from the parameters the replays update in place
+    (step() has no `report=` of its own: a recorded graph cannot call back into Python).
 
     `use_mask` / `is_initial_timestep` / `label_colors`: get_loss's branch, as optimise_views.  `priors`: the fused topology
     regularisers of that frame kind, recorded in every camera's graph (begin_frame writes the state they read in place, so the

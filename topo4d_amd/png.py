@@ -1,12 +1,16 @@
 """
-Lossless PNG encoding of a device image on the GPU, over `t4d_png_encode` (include/topo4d_raster.h, csrc/t4d_png.hip).
+Lossless PNG encoding of a device image on the GPU, over `t4d_png_encode` and `t4d_png_encode_chw` (include/topo4d_raster.h,
+csrc/t4d_png.hip).
 
     encode_png(image) -> bytes        uint8 or float32 [H,W] / [H,W,C], C in {1, 3, 4}, on a HIP device
-    write_png(path, image)
+    encode_png(image, chw=True)       float32 [3,H,W] (a render), quantised as torchvision's save_image (t4d_png_encode_chw)
+    write_png(path, image, chw=False)
     max_encoded_bytes(h, w, c)        the output bound the encoder allocates (a function of the shape alone)
 
-float32 is quantised exactly as numpy's `(x * 255).astype(np.uint8)` on x86-64, so `encode_png(render_colors(...))` decodes to
-the array `texture.bake_texture` returns.  Only the finished file crosses to the host.  There is no CPU path.
+float32 [H,W,C] is quantised exactly as numpy's `(x * 255).astype(np.uint8)` on x86-64, so `encode_png(render_colors(...))`
+decodes to the array `texture.bake_texture` returns.  float32 [3,H,W] with chw=True is quantised exactly as torchvision's
+`x.mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to("cpu", torch.uint8)`, so `encode_png(im, chw=True)` is the file
+`save_image(im, ...)` writes, pixel for pixel.  Only the finished file crosses to the host.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -49,6 +53,20 @@ def _check(image) -> tuple:
     return h, w, c
 
 
+def _check_chw(image) -> tuple:
+    if not isinstance(image, torch.Tensor):
+        raise ValueError("encode_png(chw=True) expects a torch tensor")
+    if image.dtype != torch.float32:
+        raise ValueError(f"encode_png(chw=True) expects float32, got {image.dtype}")
+    if image.dim() != 3 or int(image.shape[0]) != 3:
+        raise ValueError(f"encode_png(chw=True) expects a [3,H,W] image, got shape {tuple(image.shape)}")
+    h, w = int(image.shape[1]), int(image.shape[2])
+    _shape(h, w, 3)
+    if not image.is_cuda:
+        raise RuntimeError("topo4d_amd has no CPU path: encode_png needs the image on a HIP device")
+    return h, w, 3
+
+
 def _pinned(nbytes: int) -> torch.Tensor:
     buf = _PINNED.get("host")
     if buf is None or buf.numel() < nbytes:
@@ -57,10 +75,11 @@ def _pinned(nbytes: int) -> torch.Tensor:
     return buf
 
 
-def encode_png(image: torch.Tensor) -> bytes:
-    """The PNG file of `image` (see the module docstring).  Runs on torch's current stream; synchronises once to read the length,
-    then copies exactly that many bytes through a reused pinned buffer."""
-    h, w, c = _check(image)
+def encode_png(image: torch.Tensor, chw: bool = False) -> bytes:
+    """The PNG file of `image` (see the module docstring; `chw`: a [3,H,W] float32 render, as torchvision's save_image writes it).
+    Runs on torch's current stream; synchronises once to read the length, then copies exactly that many bytes through a reused
+    pinned buffer."""
+    h, w, c = _check_chw(image) if chw else _check(image)
     lib = _lib.load()
     dev = image.device
     img = image.contiguous()
@@ -69,18 +88,23 @@ def encode_png(image: torch.Tensor) -> bytes:
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
     scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
     length = torch.empty(1, dtype=torch.int64, device=dev)
-    _lib.call("t4d_png_encode", ptr(img), 1 if img.dtype == torch.float32 else 0, h, w, c, ptr(out), cap, ptr(length), ptr(scratch),
-              nscratch, _lib.stream(dev))
+    if chw:
+        name = "t4d_png_encode_chw"
+        _lib.call(name, ptr(img), h, w, ptr(out), cap, ptr(length), ptr(scratch), nscratch, _lib.stream(dev))
+    else:
+        name = "t4d_png_encode"
+        _lib.call(name, ptr(img), 1 if img.dtype == torch.float32 else 0, h, w, c, ptr(out), cap, ptr(length), ptr(scratch),
+                  nscratch, _lib.stream(dev))
     n = int(length.item())                                        # the one synchronisation
     if n <= 0 or n > cap:
-        raise RuntimeError(f"t4d_png_encode: bad output length {n} (capacity {cap})")
+        raise RuntimeError(f"{name}: bad output length {n} (capacity {cap})")
     host = _pinned(n)
     host[:n].copy_(out[:n])
     return host[:n].numpy().tobytes()
 
 
-def write_png(path, image: torch.Tensor) -> None:
-    """encode_png(image) written to `path`."""
-    data = encode_png(image)
+def write_png(path, image: torch.Tensor, chw: bool = False) -> None:
+    """encode_png(image, chw) written to `path`."""
+    data = encode_png(image, chw)
     with open(path, "wb") as f:
         f.write(data)
