@@ -514,6 +514,42 @@ size_t t4d_warp_scratch_bytes(int32_t n_views);
 int t4d_warp_views(const T4DWarpView *views, const T4DWarpView *d_views, int32_t n_views, void *scratch, size_t scratch_bytes,
                    void *hip_stream);
 
+/* ---- Coarse setup: initialize_params' coarse half and initialize_losses' topology (csrc/t4d_setup.hip; topo4d_amd/coarse.py) ----
+ * t4d_setup_vertex_colors: compute_vertex_colors (helpers.py:181-209).  image: uint8 [height, width, channels] (3 or 4);
+ * corner_uv [n_corners,2] float64: the UV of triangle corner 3*face+k; offsets / entries: t4d_obj_vertex_faces' CSR of the same
+ * triangles.  Per corner get_color_from_texture (helpers.py:300-333) in float64; per vertex the integer mean of its corners
+ * -> colors [n_vert,3] int32, rgb_colors [n_vert,3] float32 = float32(colors / 255.0).  status [3] (device): corners whose
+ * column / row lands outside the image (getpixel would raise; nothing is read), the first such corner (INT32_MAX: none),
+ * vertices in no corner.  Scratch: t4d_setup_colors_scratch_bytes.
+ * t4d_setup_quaternions: external.build_quaterion (external.py:45-61) in float32 of float32(normals [n,3] float64) -> [n,4].
+ * t4d_setup_one_ring: train.py:177-200 for the padded neighbor_indices [n_vert,K] int64 and eye_del [n_vert] (1: in
+ * eye_del_masks) -> neighbor_weight, neighbor_dist [n_vert,K] float32; status [1]: indices outside [0, n_vert).
+ * t4d_setup_region_weights: out = neighbor_weight with `out[mask_m, :] *= factors[m]` (float32) for m = 0..n_masks-1 in order,
+ * each at most once per row; mask m is rows[mask_off[m], mask_off[m+1]) (mask_off on the HOST, d_mask_off its device copy;
+ * rows outside [0, n_vert) are ignored).  Scratch: t4d_setup_region_scratch_bytes.
+ * t4d_setup_flatten_edges: the FlattenLoss / SoftFlattenLoss constructors (loss_util.py:114-170, 262-318) over faces [F,3] int32
+ * and their t4d_obj_vertex_faces CSR, for the candidate edges [n_edges,2] in the host's set order.  out [4, n_edges] int64
+ * holds v0s, v1s, v2s, v3s in its first *n_out (device) columns.  status [2] (device): edge ends outside [0, n_vert), faces with
+ * no third corner.  Scratch: t4d_setup_edges_scratch_bytes.
+ * t4d_setup_neighbor_mask: FlattenLoss_v2's mask (loss_util.py:232-241): mask [n_vert,K,3] int64 = (k < neighbor_num[v]). */
+#define T4D_SETUP_MAX_MASKS 32
+size_t t4d_setup_colors_scratch_bytes(int64_t n_corners);
+int t4d_setup_vertex_colors(const uint8_t *image, int32_t width, int32_t height, int32_t channels, const double *corner_uv,
+                            int64_t n_corners, const int32_t *offsets, const int32_t *entries, int32_t n_vert, int32_t *colors,
+                            float *rgb_colors, int32_t *status, void *scratch, size_t scratch_bytes, void *hip_stream);
+int t4d_setup_quaternions(const double *normals, int32_t n, float *quaternions, void *hip_stream);
+int t4d_setup_one_ring(const float *means3D, int32_t n_vert, int32_t K, const int64_t *neighbor_indices, const uint8_t *eye_del,
+                       float *neighbor_weight, float *neighbor_dist, int32_t *status, void *hip_stream);
+size_t t4d_setup_region_scratch_bytes(int32_t n_vert);
+int t4d_setup_region_weights(const float *neighbor_weight, int32_t n_vert, int32_t K, const int32_t *rows, const int32_t *d_mask_off,
+                             const int32_t *mask_off, int32_t n_masks, const float *factors, float *out, void *scratch,
+                             size_t scratch_bytes, void *hip_stream);
+size_t t4d_setup_edges_scratch_bytes(int64_t n_edges);
+int t4d_setup_flatten_edges(const int32_t *faces, int32_t n_vert, const int32_t *offsets, const int32_t *entries, const int32_t *edges,
+                            int64_t n_edges, int64_t *out, int64_t *n_out, int32_t *status, void *scratch, size_t scratch_bytes,
+                            void *hip_stream);
+int t4d_setup_neighbor_mask(const int64_t *neighbor_num, int32_t n_vert, int32_t K, int64_t *mask, void *hip_stream);
+
 /* Optional per-kernel timing with HIP events recorded on the stream the kernels are launched on.  Between
  * t4d_profile_begin() and t4d_profile_end() every kernel launch of this library is bracketed by two events;
  * t4d_profile_end() synchronises them and returns, per kernel, the summed elapsed time and the launch count.

@@ -171,6 +171,15 @@ SIGNATURES = {
     "t4d_jpeg_decode": (_INT, [C.POINTER(T4DJpegImage), _VP, _I32, _VP, _I32, _VP, _SZ, _VP, _VP, _SZ, _VP]),
     "t4d_warp_scratch_bytes": (_SZ, [_I32]),
     "t4d_warp_views": (_INT, [C.POINTER(T4DWarpView), _VP, _I32, _VP, _SZ, _VP]),
+    "t4d_setup_colors_scratch_bytes": (_SZ, [_I64]),
+    "t4d_setup_vertex_colors": (_INT, [_VP] + [_I32] * 3 + [_VP, _I64, _VP, _VP, _I32] + [_VP] * 4 + [_SZ, _VP]),
+    "t4d_setup_quaternions": (_INT, [_VP, _I32, _VP, _VP]),
+    "t4d_setup_one_ring": (_INT, [_VP, _I32, _I32] + [_VP] * 6),
+    "t4d_setup_region_scratch_bytes": (_SZ, [_I32]),
+    "t4d_setup_region_weights": (_INT, [_VP, _I32, _I32, _VP, _VP, C.POINTER(_I32), _I32, _VP, _VP, _VP, _SZ, _VP]),
+    "t4d_setup_edges_scratch_bytes": (_SZ, [_I64]),
+    "t4d_setup_flatten_edges": (_INT, [_VP, _I32, _VP, _VP, _VP, _I64] + [_VP] * 4 + [_SZ, _VP]),
+    "t4d_setup_neighbor_mask": (_INT, [_VP, _I32, _I32, _VP, _VP]),
     "t4d_profile_begin": (_INT, []),
     "t4d_profile_end": (_INT, [C.POINTER(T4DKernelTime), _INT, C.POINTER(_INT)]),
     "t4d_debug_state_layout": (_INT, [_PROB, _INT, C.POINTER(C.c_uint64), _INT]),
