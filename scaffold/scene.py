@@ -15,6 +15,8 @@ from typing import Dict, List
 import numpy as np
 import torch
 
+from topo4d_amd.cameras import parsing_colormap_bgr  # noqa: F401  (scaffold's callers import it from here)
+
 from .reference_boundary import setup_camera
 
 # BASELINE.json configs -> (n_lat, n_lon, H, W, sh_degree)
@@ -140,21 +142,6 @@ def frame_displacement(means3D: torch.Tensor, t: int, n_frames: int = 64, seed: 
 # ---- face-parsing label images (the `mask` entry of get_dataset, train.py:84-92) ------------------------------------
 PARSING_LABELS = ("background", "skin", "l_eyebrow", "r_eyebrow", "l_eye", "r_eye", "nose", "upper_lip", "inner_mouth",
                   "lower_lip", "hair", "l_ear", "r_ear", "glasses")          # train.py:50-55 `cmap_index`, by index
-
-
-def parsing_colormap_bgr(n_label: int = 14) -> np.ndarray:
-    """uint8 [n_label,3]: the colour of every parsing label in the channel order of the mask images - what helpers.py:806
-    builds (`label_colormap(14)[:, [2, 1, 0]]`: the pascal-VOC bit-interleaved colormap, helpers.py:783-797, with its columns
-    reversed).  Bits 0/1/2 of (id >> 3j) go to bit 7-j of r/g/b.  Pinned by golden G9's `label_colors`."""
-    cmap = np.zeros((n_label, 3), dtype=np.uint8)
-    for label in range(n_label):
-        rgb = [0, 0, 0]
-        for j in range(8):
-            chunk = label >> (3 * j)
-            for c in range(3):
-                rgb[c] |= ((chunk >> c) & 1) << (7 - j)
-        cmap[label] = rgb[::-1]
-    return cmap
 
 
 def make_label_image(H: int, W: int, seed: int = 0) -> torch.Tensor:

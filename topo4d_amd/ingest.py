@@ -528,6 +528,8 @@ def get_dataset(data_dir, seq, frame, cameras, use_mask=False, blacklist=[], *, 
     are the dict and the function train.py takes from its own module and from helpers; setup_camera is called as train.py:98
     calls it.  'im' and 'mask' hold the values of the reference's tensors, contiguous [C,H,W] instead of permuted views."""
     views = [_read_view(p, m) for p, m in frame_files(data_dir, seq, frame, use_mask, blacklist)]
+    if not views:
+        return []                                   # a frame past the end of the sequence (train.py:654 stops there)
     return _assemble(views, cameras, use_mask, rotate_mask, setup_camera, device, chunk_bits)
 
 
@@ -566,6 +568,8 @@ class FramePrefetcher:
     def get(self, frame: int):
         self.prefetch(frame)
         views = [f.result() for f in self.pending.pop(frame)]
+        if not views:
+            return []
         return _assemble(views, self.cameras, self.use_mask, self.rotate_mask, self.setup_camera, self.device)
 
     def close(self) -> None:

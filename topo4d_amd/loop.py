@@ -335,8 +335,10 @@ def _with_priors(extra_loss: Optional[Callable], priors, is_initial_timestep: bo
 def optimise_views(params, dataset: List[dict], optimizer, n_iters: int, seed: int = 0, loss_fn: Optional[Callable] = None,
                    extra_loss: Optional[Callable] = None, max_2D_radius: Optional[torch.Tensor] = None,
                    explicit: Optional[bool] = None, use_mask: bool = False, is_initial_timestep: bool = True, label_colors=None,
-                   priors=None, report: Optional[Callable[[int], None]] = None):
+                   priors=None, report: Optional[Callable[[int], None]] = None, rng: Optional[Random] = None):
     """train.py:661-673 for `n_iters` iterations.  Returns the list of per-iteration losses (device scalars, no sync).
+    `rng`: the random.Random that get_batch draws the cameras from (default Random(seed)): a run that shares one generator
+    between its loops draws the reference's camera sequence (train.py's get_batch uses the module-level `random`).
     `use_mask`, `is_initial_timestep`: get_loss's branch (train.py:315-327; Topo4D runs use_mask=True, i.e. the masked target in
     every frame after the first - `label_colors` as in prepare_masked_targets, which is called here once).
     `explicit` (default: when possible - fused loss, a FusedAdamPins optimiser, the scale + rotation / RGB parametrisation): the
@@ -348,7 +350,7 @@ def optimise_views(params, dataset: List[dict], optimizer, n_iters: int, seed: i
     `report(i)`: called under no_grad with the iteration index after iteration i's optimiser step, pins and radius bookkeeping -
     where train.py:702 calls report_progress, e.g. `lambda i: progress.report_progress(params, dataset, t + 1, i, bar, ...)`.  A
     reporter that renders leaves the loop's losses and parameters unchanged bit for bit."""
-    rng = Random(seed)
+    rng = Random(seed) if rng is None else rng
     todo: list = []
     losses = []
     masked = use_mask and not is_initial_timestep
@@ -398,7 +400,7 @@ def optimise_dense_views(params, variables, dataset: List[dict], optimizer, n_it
                          loss_fn: Optional[Callable] = None, soft_color_fn: Optional[Callable] = None,
                          pre_iteration: Optional[Callable] = None, max_2D_radius: Optional[torch.Tensor] = None,
                          explicit: Optional[bool] = None, soft_color_weight: float = SOFT_COLOR_WEIGHT,
-                         report: Optional[Callable[[int], None]] = None):
+                         report: Optional[Callable[[int], None]] = None, rng: Optional[Random] = None):
     """The texture loop, train.py:729-741, for `n_iters` iterations (args.dense_opt_num = 301 per frame): pins on
     dense_rgb_colors BEFORE each render (train.py:731-734) -> get_loss_dense(use_mask=False) -> backward -> Adam.
     `variables['dense_init_colors']`: the soft-colour anchor (train.py:258,502).
@@ -406,9 +408,9 @@ def optimise_dense_views(params, variables, dataset: List[dict], optimizer, n_it
     every render (apply_pins) and NOT after the step - the reference leaves the last step's values in those rows (they are what
     save_mesh exports); any other optimiser: pass `pre_iteration`, a callable run under no_grad before every render.
     `report(i)`: as in optimise_views - after iteration i's step, under no_grad (train.py:742 calls report_progress_dense there).
-    Returns the list of per-iteration total losses (device scalars)."""
+    `rng`: as in optimise_views.  Returns the list of per-iteration total losses (device scalars)."""
     from .optim import FusedAdamPins
-    rng = Random(seed)
+    rng = Random(seed) if rng is None else rng
     todo: list = []
     losses = []
     fused_opt = isinstance(optimizer, FusedAdamPins)
