@@ -1,0 +1,241 @@
+"""
+Score a finished run: `python -m topo4d_amd.evaluate -e EXP -s SEQ [-id ... -did ... -od ...] [--frames 1-10] [--views A,B]
+[--set low|dense|both] [--save_renders]`.
+
+For every frame of <od>/<exp>/<seq>: read %06d/face.obj (save_mesh's vertices: the training frame mapped by the trans_g of
+cameras.get_cameras, whose inverse maps them back, in float64) and %06d/face.png (PIL, on the host; frame t+1's files are read on a thread
+while frame t is scored), load the frame's views as training does (ingest.get_dataset, face-parsing masks where they exist),
+render the textured mesh into every camera (meshrender.MeshRenderer) and compare it with the photograph
+(meshrender.image_metrics).  The pixel mask drops the labels training masks out of its photometric loss (get_loss: inner_mouth,
+loss.get_mask).  Writes <od>/<exp>/<seq>/eval.json; with --save_renders also %06d/mesh_<cam>.png.  Works on output trees of the
+reference's train.py as well: the layout and save_mesh's formats are the same.
+"""
+from __future__ import annotations
+
+import argparse
+import functools
+import json
+import math
+import os
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, List, Optional
+
+import numpy as np
+import torch
+
+from . import cameras as C
+from . import meshrender
+
+MASK_LABELS = ["inner_mouth"]                 # train.py get_loss's target_labels
+
+
+def _frames(spec: str) -> List[int]:
+    out = []
+    for part in spec.split(","):
+        part = part.strip()
+        if not part:
+            continue
+        if "-" in part:
+            a, b = part.split("-", 1)
+            out.extend(range(int(a), int(b) + 1))
+        else:
+            out.append(int(part))
+    if not out or min(out) < 1:
+        raise argparse.ArgumentTypeError(f"--frames: {spec!r} is not a list or range of frames >= 1")
+    return out
+
+
+def _read_frame_files(frame_dir: str):
+    """(FaceObj or None, uint8 [H,W,3] texture or None) of one frame directory: the host half, run on the prefetch thread."""
+    obj_path, png_path = os.path.join(frame_dir, "face.obj"), os.path.join(frame_dir, "face.png")
+    if not os.path.exists(obj_path):
+        return None, None
+    obj = meshrender.read_face_obj(obj_path)
+    tex = None
+    if os.path.exists(png_path):
+        from PIL import Image
+        tex = np.ascontiguousarray(np.array(Image.open(png_path).convert("RGB")))
+    return obj, tex
+
+
+def training_vertices(vertices: np.ndarray, trans_g) -> np.ndarray:
+    """face.obj's vertices back in the training frame, in float64.  save_mesh writes its variables['trans_g'] inverted and applied
+    to means3D (helpers.py:981-983); variables['trans_g'] is itself the inverse of the trans_g that cameras.get_cameras returns
+    (train.py:124-126), so the file holds trans_g applied to means3D and inv(trans_g) maps it back."""
+    v = np.asarray(vertices, dtype=np.float64)
+    if trans_g is None:
+        return v
+    inv = np.linalg.inv(np.asarray(trans_g, dtype=np.float64))
+    return v @ inv[:3, :3].T + inv[:3, 3]
+
+
+def pixel_masks(dataset) -> Optional[torch.Tensor]:
+    """[V,1,H,W]: 1 where the photograph is scored; None when the views carry no parsing mask."""
+    if not dataset or any(e.get("mask") is None for e in dataset):
+        return None
+    from .loss import label_mask_target
+    cmap = C.parsing_colormap_bgr(14)
+    colors = cmap[[C.CMAP_INDEX[l] for l in MASK_LABELS]]
+    masks = torch.stack([e["mask"] for e in dataset])
+    filtered, _ = label_mask_target(masks, colors)
+    return (1.0 - filtered[:, :1]).contiguous()
+
+
+def evaluate_frame(renderer: meshrender.MeshRenderer, vertices: torch.Tensor, dataset, masks: Optional[torch.Tensor] = None,
+                   keep_renders: bool = False):
+    """Render and score every view of `dataset` (get_dataset's entries).  vertices [N,3] in the training frame, on the renderer's
+    device; masks [V,1,H,W] or None.  Returns {cam_name: {metric: value, ..., "covered": pixels}} and, with keep_renders,
+    {cam_name: image [3,H,W]} too.  Views of one size go in one launch."""
+    groups: Dict[tuple, List[int]] = {}
+    for k, e in enumerate(dataset):
+        groups.setdefault((int(e["cam"].image_height), int(e["cam"].image_width)), []).append(k)
+    scores, renders = {}, {}
+    for (H, W), ks in groups.items():
+        image, _, index = renderer.render(vertices, [dataset[k]["cam"] for k in ks])
+        target = torch.stack([dataset[k]["im"] for k in ks]).to(torch.float32)
+        m = None if masks is None else masks[ks]
+        vals = meshrender.image_metrics(image, target, index, m).cpu().numpy()
+        covered = (index >= 0).reshape(len(ks), -1).sum(1).cpu().numpy()
+        for j, k in enumerate(ks):
+            name = dataset[k]["cam_name"]
+            row = {n: float(vals[j, q]) for q, n in enumerate(meshrender.METRIC_NAMES)}
+            row["count"] = int(row["count"])
+            row["covered"] = int(covered[j])
+            scores[name] = row
+            if keep_renders:
+                renders[name] = image[j]
+    return (scores, renders) if keep_renders else scores
+
+
+def _finite(x):
+    return x if isinstance(x, (int, bool)) or (isinstance(x, float) and math.isfinite(x)) else None
+
+
+def _summary(frames: dict) -> dict:
+    per = {n: [] for n in ("psnr_full", "l1", "mse", "psnr", "ssim")}
+    for fr in frames.values():
+        for row in fr.get("views", {}).values():
+            for n in per:
+                if row.get(n) is not None:
+                    per[n].append(row[n])
+    out = {"frames": len([f for f in frames.values() if "views" in f])}
+    for n, xs in per.items():
+        out[f"mean_{n}"] = float(np.mean(xs)) if xs else None
+    worst = [(f, min((r["psnr"] for r in fr["views"].values() if r.get("psnr") is not None), default=None))
+             for f, fr in frames.items() if fr.get("views")]
+    worst = [w for w in worst if w[1] is not None]
+    out["worst_frame_psnr"] = min(worst, key=lambda w: w[1])[0] if worst else None
+    return out
+
+
+def score_set(args, which: str, device) -> dict:
+    from . import ingest
+    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
+    data_dir = args.input_dir if which == "low" else args.dense_input_dir
+    # the calibration and the camera list come from the geometry inputs for both sets, as train.py takes them
+    cameras, _, trans_g = C.get_cameras(args.input_dir, args.seq, resize_factor=args.down_ratio if which == "low" else 1)
+    names = [n.split(".")[0] for n in cameras]
+    chosen = names if args.views is None else [n for n in names if n in args.views]
+    if args.views is not None and len(chosen) != len(args.views):
+        raise SystemExit(f"--views: {sorted(set(args.views) - set(names))} not among the cameras of {data_dir}/{args.seq}")
+    skip = [n for n in cameras if n.split(".")[0] not in chosen]           # full file names: a prefix that matches only itself
+    trained = {n: not any(n.startswith(b) for b in C.BLACKLIST) for n in chosen}
+    cam_fn = functools.partial(C.setup_camera, device=device)
+    frames = args.frames or sorted(int(d) for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
+    result = {}
+
+    def mask_dir_ok(t):
+        md = os.path.join(data_dir, args.seq, "mask", "%06d" % t)
+        return all(os.path.exists(os.path.join(md, n + ".png")) for n in chosen)
+
+    pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="t4d-eval")
+    pf = {flag: ingest.FramePrefetcher(data_dir, args.seq, cameras, use_mask=flag, blacklist=skip, rotate_mask=C.ROTATE_MASK,
+                                       setup_camera=cam_fn, device=device) for flag in (False, True)}
+    try:
+        pending = {}
+
+        def prefetch(t):
+            if t not in pending:
+                pending[t] = (pool.submit(_read_frame_files, os.path.join(run_dir, "%06d" % t)), mask_dir_ok(t))
+                pf[pending[t][1]].prefetch(t)
+
+        for i, t in enumerate(frames):
+            prefetch(t)
+            if i + 1 < len(frames):
+                prefetch(frames[i + 1])
+            fut, use_mask = pending.pop(t)
+            obj, tex = fut.result()
+            dataset = pf[use_mask].get(t)
+            key = "%06d" % t
+            if obj is None:
+                result[key] = {"skipped": "no face.obj"}
+                continue
+            if not dataset:
+                result[key] = {"skipped": "no views"}
+                continue
+            faces, uv_faces = meshrender.triangulate(obj.faces_ori, obj.uv_faces_ori)
+            texture = tex if tex is not None else np.full((2, 2, 3), 128, np.uint8)
+            renderer = meshrender.MeshRenderer(faces, uv_faces, obj.uvs, texture, device=device)
+            verts = torch.from_numpy(training_vertices(obj.vertices, trans_g)).to(device)
+            masks = pixel_masks(dataset)
+            scores, renders = evaluate_frame(renderer, verts, dataset, masks, keep_renders=True)
+            for name, row in scores.items():
+                row["trained"] = trained.get(name, True)
+                for n in list(row):
+                    if isinstance(row[n], float):
+                        row[n] = _finite(row[n])
+            result[key] = {"texture": tex is not None, "masked": masks is not None, "views": scores}
+            if args.save_renders:
+                from .png import write_png
+                tag = "" if args.set != "both" else f"_{which}"
+                for name, img in renders.items():
+                    write_png(os.path.join(run_dir, key, f"mesh{tag}_{name}.png"), img, chw=True)
+    finally:
+        pool.shutdown(wait=True)
+        for p in pf.values():
+            p.close()
+    return {"frames": result, "summary": _summary(result)}
+
+
+def build_parser() -> argparse.ArgumentParser:
+    from .train import build_parser as train_parser
+    base = train_parser()
+    p = argparse.ArgumentParser(prog="python -m topo4d_amd.evaluate",
+                                description="Render each frame's face.obj + face.png into the capture views and score it.")
+    for a in base._actions:                                   # -e/-s/-id/-did/-od/-dr exactly as topo4d_amd.train has them
+        if a.dest in ("exp", "seq", "input_dir", "dense_input_dir", "output_dir", "down_ratio"):
+            p.add_argument(*a.option_strings, type=a.type, default=a.default, help=a.help)
+    p.add_argument("--frames", type=_frames, default=None, help="Frames to score: '1-10', '1,5,9' (default: every frame directory).")
+    p.add_argument("--views", type=lambda s: [v.strip() for v in s.split(",") if v.strip()], default=None,
+                   help="Cameras to score, comma-separated (default: every camera, blacklisted ones included).")
+    p.add_argument("--set", choices=("low", "dense", "both"), default="low",
+                   help="Views to score against: the geometry inputs (-id), the texture inputs (-did), or both.")
+    p.add_argument("--save_renders", action="store_true", help="Also write %%06d/mesh_<cam>.png.")
+    return p
+
+
+def evaluate(args, device=None) -> dict:
+    dev = torch.device(device if device is not None else "cuda")
+    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
+    if not os.path.isdir(run_dir):
+        raise SystemExit(f"no run at {run_dir}")
+    sets = ["low", "dense"] if args.set == "both" else [args.set]
+    with torch.cuda.device(dev):
+        out = {"exp": args.exp, "seq": args.seq, "blacklist": sorted(C.BLACKLIST), "mask_labels": MASK_LABELS}
+        for which in sets:
+            out[which] = score_set(args, which, dev)
+    with open(os.path.join(run_dir, "eval.json"), "w") as f:
+        json.dump(out, f, indent=1)
+    return out
+
+
+def main(argv=None) -> None:
+    args = build_parser().parse_args(argv)
+    out = evaluate(args)
+    for which in ("low", "dense"):
+        if which in out:
+            print(which, json.dumps(out[which]["summary"]))
+
+
+if __name__ == "__main__":
+    main()
