@@ -1,84 +1,158 @@
 // t4d_raster_render_bwd.h - part of the translation unit t4d_raster.hip (included there, inside its anonymous namespace; not a
-// stand-alone header).  A.4: the ten-sum DPP transpose-reduce and the backward render kernel (whole tiles or depth segments).
+// stand-alone header).  A.4: the separable moment reduction over a DPP row and the backward render kernel (whole tiles or depth segments).
 // See t4d_raster.hip for the overview, the constants, the state layout and the kernel parameter block.
 // ---------------------------------------------------------------------------------------------------------
-// Reduction of TEN values over each 16-lane DPP row ("transpose-reduce"): at every butterfly level two partial-sum
-// vectors are folded into one, each half of the lanes keeping a different value, so the work halves per level
-// instead of staying at 10 adds x 4 levels.  Levels: xor8 by row_ror:8, xor4 by two bank-masked row shifts, xor2 /
-// xor1 by quad_perm.  The four rows of a wave reduce four different splats at the same time.
+// The backward's pixel map.  Waves, DPP rows and sub-blocks are the forward's (tile_pixel); only the place of a pixel INSIDE its
+// 4x4 sub-block differs: lane i of a row takes pixel (x, y) = (i >> 2, i & 3), so that the four x of one y sit in the four
+// banks of the row (bank = four consecutive lanes = bits b3 b2 of i) and the four y of one x inside one bank (bits b1 b0).
+// Everything per pixel is read by pixel address; what the forward leaves BY THREAD (the snapshots of the segmented builds) is
+// read through fwd_thread_of.
 // ---------------------------------------------------------------------------------------------------------
-// In-place butterfly over ten VGPRs, written as one asm block: bank-masked DPP adds do the "keep one half, send the
-// other" selection of the transpose for free (v_cndmask + v_mov_dpp pairs otherwise), and the instruction order keeps
-// every DPP read at least two instructions behind the write of its source (the gfx9 VALU->DPP hazard), so no s_nop is
-// needed inside; the leading s_nop covers inputs produced just before the block.
-//   level xor8 (row_ror:8):  r[2m] <- r[2m + b3] summed over the pair          (banks 2,3 = lanes with b3 set)
-//   level xor4 (row_shl/shr:4): r1 <- c_{b2}, r3 <- c_{2+b2}, r5 <- c_4        (banks 0,2 read lane+4; banks 1,3 lane-4)
-//   levels xor2, xor1 (quad_perm): no bank masks at this granularity (a bank is four consecutive lanes), so the transposing
-//   is done with selects on the constant lane masks b1 / b0: xor2 folds (r1, r3) into one register and r5 into itself, xor1
-//   folds those two into ONE - seven instructions, and the caller needs no selection (plain butterflies on the three
-//   registers plus the caller's two selects were eight).
-// Returns, in lane i = (b3 b2 b1 b0) of a row: the sum of value  2*b2 + b3  (b1 b0 = 00),  4 + 2*b2 + b3  (b1 b0 = 10),
-// 8 + b3  (b0 = 1; four lanes per half row hold it, row10_index picks b2 = b1 = 0).
-// Operands: values 2 and 5 are read-only inputs whose sums go to fresh registers (o2, o5): r[1], r[2] (and r[3], r[5]) are the
-// halves of ONE packed-multiply result, and tying both halves of a register pair to in/out operands costs a v_mov each.
-template <bool NINE>          // NINE: r[9] is known to be zero (no depth cotangent): its banked add is skipped
-__device__ __forceinline__ float reduce10_row(float (&r)[10])
+__device__ __forceinline__ void tile_pixel_bwd(int tid, int tx, int ty, int &px, int &py)
 {
-    float o2, o5, ta, tb;
-#define T4D_RED_HEAD                                                                                  \
-        "s_nop 1\n\t"                                                                                 \
-        "v_add_f32_dpp %[r0], %[r0], %[r0] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"                  \
-        "v_add_f32_dpp %[o2], %[r2], %[r2] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"                  \
-        "v_add_f32_dpp %[r4], %[r4], %[r4] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"                  \
-        "v_add_f32_dpp %[r6], %[r6], %[r6] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"                  \
-        "v_add_f32_dpp %[r8], %[r8], %[r8] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"                  \
-        "v_add_f32_dpp %[r0], %[r1], %[r1] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                  \
-        "v_add_f32_dpp %[o2], %[r3], %[r3] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                  \
-        "v_add_f32_dpp %[r4], %[r5], %[r5] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                  \
-        "v_add_f32_dpp %[r6], %[r7], %[r7] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-#define T4D_RED_TAIL                                                                                  \
-        "v_add_f32_dpp %[r1], %[r0], %[r0] row_shl:4 row_mask:0xf bank_mask:0x5\n\t"                  \
-        "v_add_f32_dpp %[r3], %[r4], %[r4] row_shl:4 row_mask:0xf bank_mask:0x5\n\t"                  \
-        "v_add_f32_dpp %[o5], %[r8], %[r8] row_shl:4 row_mask:0xf bank_mask:0x5\n\t"                  \
-        "v_add_f32_dpp %[r1], %[o2], %[o2] row_shr:4 row_mask:0xf bank_mask:0xa\n\t"                  \
-        "v_add_f32_dpp %[r3], %[r6], %[r6] row_shr:4 row_mask:0xf bank_mask:0xa\n\t"                  \
-        "v_add_f32_dpp %[o5], %[r8], %[r8] row_shr:4 row_mask:0xf bank_mask:0xa\n\t"                  \
-        "v_cndmask_b32_e64 %[tb], %[r3], %[r1], %[m1]\n\t"              /* b1 ? r1 : r3  (goes to the partner) */ \
-        "v_cndmask_b32_e64 %[ta], %[r1], %[r3], %[m1]\n\t"              /* b1 ? r3 : r1  (stays)               */ \
-        "v_add_f32_dpp %[o5], %[o5], %[o5] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"        \
-        "v_add_f32_dpp %[ta], %[tb], %[ta] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"        \
-        "v_cndmask_b32_e64 %[tb], %[o5], %[ta], %[m0]\n\t"              /* b0 ? x : y  (goes to the partner)   */ \
-        "v_cndmask_b32_e64 %[ta], %[ta], %[o5], %[m0]\n\t"              /* b0 ? y : x  (stays)                 */ \
-        "s_nop 0\n\t"                                                                                 \
-        "v_add_f32_dpp %[ta], %[tb], %[ta] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
-#define T4D_RED_OUT [r0] "+v"(r[0]), [r1] "+v"(r[1]), [o2] "=&v"(o2), [r3] "+v"(r[3]), [r4] "+v"(r[4]), [o5] "=&v"(o5), \
-                    [r6] "+v"(r[6]), [r8] "+v"(r[8]), [ta] "=&v"(ta), [tb] "=&v"(tb)
-#define T4D_RED_MASKS [m1] "s"(0xccccccccccccccccull), [m0] "s"(0xaaaaaaaaaaaaaaaaull)
-    if (NINE) {
-        // r8 then holds the xor8 sum of value 8 in BOTH halves of the row; only the b3 = 0 lane is used (row10_index)
-        asm(T4D_RED_HEAD T4D_RED_TAIL : T4D_RED_OUT : [r2] "v"(r[2]), [r5] "v"(r[5]), [r7] "v"(r[7]), T4D_RED_MASKS);
-    } else {
-        asm(T4D_RED_HEAD
-            "v_add_f32_dpp %[r8], %[r9], %[r9] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
-            T4D_RED_TAIL
-            : T4D_RED_OUT : [r2] "v"(r[2]), [r5] "v"(r[5]), [r7] "v"(r[7]), [r9] "v"(r[9]), T4D_RED_MASKS);
-    }
-    return ta;
-#undef T4D_RED_HEAD
-#undef T4D_RED_TAIL
-#undef T4D_RED_OUT
-#undef T4D_RED_MASKS
+    const int w = tid >> 6, r = (tid >> 4) & 3, i = tid & 15;
+    px = tx * T4D_TILE_X + ((w & 1) << 3) + ((r & 1) << 2) + (i >> 2);
+    py = ty * T4D_TILE_Y + ((w >> 1) << 3) + ((r >> 1) << 2) + (i & 3);
 }
 
-// which of the ten sums lane i of a row holds after reduce10_row; -1 = none (or a duplicate)
+// the forward's thread of the pixel this backward thread holds (same wave, same row, x and y swapped inside the row)
+__device__ __forceinline__ int fwd_thread_of(int tid) { return (tid & ~15) | ((tid & 3) << 2) | ((tid >> 2) & 3); }
+
+// ---------------------------------------------------------------------------------------------------------
+// Reduction of a step's sums over each 16-lane DPP row, SEPARABLY: x first, then y.
+// A lane holds e = G dL/dalpha and w = alpha T of its pixel.  Six of the ten sums of a record are moments of e about the splat
+// centre; about a FIXED origin (the centre of the wave's 8x8 block: pixel = origin + (X, Y), |X|, |Y| <= 3.5, lane constants)
+// they are linear in the raw moments  M_ab = sum e X^a Y^b, a + b <= 2, and a raw moment separates: sum e X^a over x, times Y^b,
+// summed over y.  So only SIX values per lane enter the x stage - e, e X, e X^2 and the three w dL/dC - instead of ten products,
+// and the y weights are applied to x-sums.  The slabs accumulate raw moments; the shift to the splat centre is done once per
+// staged splat and wave where the record is written (moments_about_centre).
+//   x stage (banks): "transpose-reduce" - at every butterfly level two partial-sum vectors are folded into one, each half of the
+//     banks keeping a different value.  xor8 by row_ror:8: (e X^2 | c0) -> a, (c1 | c2) -> b, (e | e X) -> c, the second of each
+//     pair in banks 2,3.  xor4 by bank-masked row shifts: a and b fold into ONE register (bank (b3 b2): e X^2, c1, c0, c2), c folds
+//     into itself: banks 0,1 hold the x-sum of e, banks 2,3 that of e X - every bank one more copy than the fold needs, which
+//     is what the y stage wants: the x-sum of e is needed under three weights (1, Y, Y^2), that of e X under two (1, Y).
+//   y stage (inside a bank, quad_perm): the xor2 fold of the weighted copies needs no selects - "keep Ka on lanes with b1 = 0 and
+//     Kb on the others, send the opposite" is a multiply by a lane constant (ks) and a DPP multiply-add by another (kg), the
+//     weights folded in:  bank 0: (1 | Y) -> M00, M01   bank 1: (Y^2 | -) -> M02   bank 2: (1 | Y) -> M10, M11.  The other register
+//     takes a plain xor2 add; xor1 folds the two with selects on the constant lane mask b0.
+// Per step: 1 truncation of e (moment_e) + 4 products + 10 banked adds + 6 in the y stage (a plain xor2 add, the weight multiply
+// and multiply-add, two selects, the xor1 add) = 21 vector instructions against 5 + 22 for ten products reduced one by one
+// (config 2, 24 views: 252 -> 240 us); with a depth cotangent the seventh value (w dL/dD) is summed over x on its own (2) and
+// folded in at xor2 with selects (+2).
+// Written as one asm block: the instruction order keeps every DPP read at least two instructions behind the write of its source
+// (the gfx9 VALU->DPP hazard), so no s_nop is needed between the levels; the leading s_nop covers inputs produced just before the
+// block.  All inputs are read-only, the three temporaries are fresh registers (tying halves of packed products to in/out operands
+// costs a v_mov each).
+// Returns, in lane i = (b3 b2 b1 b0) of a row, the sum row10_index(i) names.
+// ---------------------------------------------------------------------------------------------------------
+struct RowWeights { float X, ks, kg; };   // lane constants: x about the wave's block centre, and the y-weight patterns (see above)
+
+__device__ __forceinline__ RowWeights row_weights(const int lane)
+{
+    const int r = lane >> 4, i = lane & 15, bank = i >> 2, b1 = (i >> 1) & 1;
+    RowWeights k;
+    k.X = (float)(((r & 1) << 2) + (i >> 2)) - 3.5f;
+    const float y0 = (float)((r >> 1) << 2) - 3.5f;
+    const float Y = y0 + (float)(i & 3), Yp = y0 + (float)((i & 3) ^ 2);      // own y and that of the xor2 partner
+    auto Ka = [&](float y) { return bank == 1 ? y * y : (bank == 3 ? 0.f : 1.f); };      // weights of the sums kept on b1 = 0
+    auto Kb = [&](float y) { return (bank & 1) ? 0.f : y; };                              // ... on b1 = 1
+    k.ks = b1 ? Kb(Y) : Ka(Y);
+    k.kg = b1 ? Kb(Yp) : Ka(Yp);           // applied to the PARTNER's value where it arrives
+    return k;
+}
+
+template <bool NINE>          // NINE: no depth cotangent - the seventh value is not reduced
+__device__ __forceinline__ float reduce_moments_row(const float e, const float ex, const float exx, const float c0, const float c1,
+                                                    const float c2, const float cd, const RowWeights &k)
+{
+    float a, b, c;
+#define T4D_RED_X                                                                                     \
+        "s_nop 1\n\t"                                                                                 \
+        "v_add_f32_dpp %[a], %[v0], %[v0] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"                   \
+        "v_add_f32_dpp %[b], %[v2], %[v2] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"                   \
+        "v_add_f32_dpp %[c], %[v4], %[v4] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"                   \
+        "v_add_f32_dpp %[a], %[v1], %[v1] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                   \
+        "v_add_f32_dpp %[b], %[v3], %[v3] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                   \
+        "v_add_f32_dpp %[c], %[v5], %[v5] row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+#define T4D_RED_X4                                                                                    \
+        "v_add_f32_dpp %[a], %[a], %[a] row_shl:4 row_mask:0xf bank_mask:0x5\n\t"                     \
+        "v_add_f32_dpp %[a], %[b], %[b] row_shr:4 row_mask:0xf bank_mask:0xa\n\t"                     \
+        "v_add_f32_dpp %[b], %[c], %[c] row_shl:4 row_mask:0xf bank_mask:0x5\n\t"                     \
+        "v_add_f32_dpp %[b], %[c], %[c] row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+#define T4D_RED_OUT [a] "=&v"(a), [b] "=&v"(b), [c] "=&v"(c)
+#define T4D_RED_IN [v0] "v"(exx), [v1] "v"(c0), [v2] "v"(c1), [v3] "v"(c2), [v4] "v"(e), [v5] "v"(ex), [ks] "v"(k.ks), [kg] "v"(k.kg), \
+                   [m0] "s"(0xaaaaaaaaaaaaaaaaull)
+    if (NINE) {
+        asm(T4D_RED_X T4D_RED_X4
+            "v_add_f32_dpp %[a], %[a], %[a] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_mul_f32_e32 %[c], %[b], %[ks]\n\t"
+            "v_fmac_f32_dpp %[c], %[b], %[kg] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_e64 %[b], %[a], %[c], %[m0]\n\t"             /* b0 ? moments : others  (goes to the partner) */
+            "v_cndmask_b32_e64 %[c], %[c], %[a], %[m0]\n\t"             /* b0 ? others : moments  (stays)               */
+            "s_nop 0\n\t"
+            "v_add_f32_dpp %[c], %[b], %[c] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+            : T4D_RED_OUT : T4D_RED_IN);
+        return c;
+    } else {
+        float d;                // the x-sum of w dL/dD, in every bank; folded in at xor2 with selects: the lanes with b1 = 1 keep it
+        asm(T4D_RED_X
+            "v_add_f32_dpp %[d], %[v6], %[v6] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+            T4D_RED_X4
+            "v_add_f32_dpp %[d], %[d], %[d] row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_e64 %[c], %[d], %[a], %[m1]\n\t"             /* b1 ? others : depth  (goes to the partner) */
+            "v_cndmask_b32_e64 %[d], %[a], %[d], %[m1]\n\t"             /* b1 ? depth : others  (stays)               */
+            "v_mul_f32_e32 %[a], %[b], %[ks]\n\t"
+            "v_fmac_f32_dpp %[a], %[b], %[kg] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %[d], %[c], %[d] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_cndmask_b32_e64 %[b], %[d], %[a], %[m0]\n\t"             /* b0 ? moments : others  (goes to the partner) */
+            "v_cndmask_b32_e64 %[a], %[a], %[d], %[m0]\n\t"             /* b0 ? others : moments  (stays)               */
+            "s_nop 0\n\t"
+            "v_add_f32_dpp %[a], %[b], %[a] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+            : T4D_RED_OUT, [d] "=&v"(d) : T4D_RED_IN, [v6] "v"(cd), [m1] "s"(0xccccccccccccccccull));
+        return a;
+    }
+#undef T4D_RED_X
+#undef T4D_RED_X4
+#undef T4D_RED_OUT
+#undef T4D_RED_IN
+}
+
+// which of the ten sums (slab entry / record order) lane i of a row holds after reduce_moments_row; -1 = none (or a duplicate)
 __device__ __forceinline__ int row10_index(const int lane)
 {
-    const int b0 = lane & 1, b1 = (lane >> 1) & 1, b2 = (lane >> 2) & 1, b3 = (lane >> 3) & 1;
-    if (!b0 && !b1) return 2 * b2 + b3;
-    if (!b0 && b1) return 4 + 2 * b2 + b3;
-    if (b0 && !b1 && !b2) return 8 + b3;
-    return -1;
+    const int b0 = lane & 1, b1 = (lane >> 1) & 1, bank = (lane >> 2) & 3;
+    if (!b0) {
+        if (bank == 0) return b1 ? 2 : 0;        // M01 : M00
+        if (bank == 1) return b1 ? -1 : 5;       //       M02
+        if (bank == 2) return b1 ? 4 : 1;        // M11 : M10
+        return -1;
+    }
+    if (!b1) return bank == 0 ? 3 : (bank == 1 ? 7 : (bank == 2 ? 6 : 8));      // M20, sum w dL/dC1, C0, C2
+    return bank == 0 ? 9 : -1;                                                  // sum w dL/dD (with a depth cotangent only)
 }
+
+// A slab entry's raw moments about the origin o become the record's sums about the splat centre; p = centre - o.
+//   sum e dx = p.x M00 - M10    sum e dx dx = p.x^2 M00 - 2 p.x M10 + M20    sum e dx dy = p.x p.y M00 - p.x M01 - p.y M10 + M11
+// The shift cancels, and a record must stay accurate RELATIVE TO ITSELF where everything in it is tiny: a splat whose opacity is
+// within a few ulp of 1/255 is drawn on the one pixel its centre sits on, |d| ~ 1e-6, and every gradient of such a scene is made
+// of sums like e d.  Two things keep those exact: e enters the moments with 18 significant bits (moment_e), so that its products
+// with X, X^2, Y, Y^2, X Y (at most 6 bits) are exact floats and a sum with a single contributing pixel IS e X^a Y^b; and the
+// shift is evaluated in double precision, factored so that every step but the last fused multiply-add is exact for such a sum:
+// p.x M00 - M10 = e dx, p.x M10 - M20 = e X dx, and p.x (e dx) - (e X dx) = e dx dx rounds once.  Sums over many pixels carry
+// float rounding of the moments instead, about 1e-5 of the largest entry at worst (tools/experiments/model_bwd_moment_numerics.py).
+// Once per staged splat and wave: noise in the instruction count.
+__device__ __forceinline__ void moments_about_centre(float (&m)[10], const float pxf, const float pyf)
+{
+    const double px = pxf, py = pyf, M00 = m[0], M10 = m[1], M01 = m[2], M20 = m[3], M11 = m[4], M02 = m[5];
+    const double sx = fma(px, M00, -M10), sy = fma(py, M00, -M01);
+    m[1] = (float)sx; m[2] = (float)sy;
+    m[3] = (float)fma(px, sx, -fma(px, M10, -M20));
+    m[4] = (float)fma(px, sy, -fma(py, M10, -M11));
+    m[5] = (float)fma(py, sy, -fma(py, M01, -M02));
+}
+
+// e as the moments take it: 18 significant bits (truncated), see moments_about_centre
+__device__ __forceinline__ float moment_e(const float e) { return __uint_as_float(__float_as_uint(e) & 0xffffffc0u); }
 
 __device__ __forceinline__ uint32_t row_max_u32(uint32_t v)      // every lane gets the maximum over its 16-lane row
 {
@@ -93,7 +167,8 @@ __device__ __forceinline__ uint32_t row_max_u32(uint32_t v)      // every lane g
 // A.4 backward replay.  No global atomics: one kGP-float record per (Gaussian,tile) pair.
 // record (raw sums over the tile's pixels, e = G * dL/dalpha, d = splat centre - pixel):
 //   [0] sum e   [1,2] sum e*d   [3,4,5] sum e*dx*dx, e*dx*dy, e*dy*dy   [6,7,8] sum alpha*T*dL/dC   [9] sum alpha*T*dL/dD
-// Inside the workgroup every wave owns an LDS slab of ten sums per staged splat; a row's reduced sums are added to it
+// Inside the workgroup every wave owns an LDS slab of ten sums per staged splat - [1..5] there as RAW moments about the centre of
+// the wave's 8x8 block (reduce_moments_row), shifted to the splat centre when the record is written; a row's reduced sums are added to it
 // by plain read-add-write (no LDS float atomics: they retire ~3 cycles per lane here), rows that hold the same splat
 // in the same step taking turns, and the slabs of the four waves are summed in wave order when the batch is written
 // out.  Every addition order is fixed, so the gradients are bit-reproducible.
@@ -163,10 +238,11 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
     constexpr int kNull = kBwdBatch;
 
     const int tid = threadIdx.x;
-    const int wave = tid >> 6, lane = tid & 63, row = lane >> 4;
-    // without a depth cotangent the ninth pair is not transposed (reduce10_row<true>): the lane that would hold sum 9 holds a
-    // second copy of sum 8 and must stay out
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, row = lane >> 4;      // wave: a scalar
+    // without a depth cotangent the seventh value is not reduced (reduce_moments_row<true>): the lane that would hold sum 9 holds a
+    // second copy of sum 3 and must stay out
     const int my_slot = (!DA && row10_index(lane & 15) == 9) ? -1 : row10_index(lane & 15);
+    const RowWeights rw = row_weights(lane);
     if (tid == 0) {
 #pragma unroll
         for (int k = 0; k < kEnt / 8; k++) reinterpret_cast<float2 *>(s_rec + kNull * kEnt)[k] = make_float2(0.f, 0.f);
@@ -231,7 +307,7 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
     const float *vr = kp.views + (size_t)v * T4D_VIEW_FLOATS;
 
     int px, py;
-    tile_pixel(tid, tx, ty, px, py);
+    tile_pixel_bwd(tid, tx, ty, px, py);
     const bool inside = px < kp.W && py < kp.H;
     const v2f pix_f = { (float)px, (float)py };
     const size_t HW = (size_t)kp.H * kp.W, pix = (size_t)py * kp.W + px;
@@ -267,7 +343,7 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
         // finished wave, so nothing is read for such a pixel).
         const uint32_t p = (uint32_t)(seg_j + 1) * kSeg;
         if (last_contributor > p) {
-            const float *sb = kp.snap + ((size_t)v * kp.slots_per_view + seg_slot0(kp, off, (uint32_t)t_)) * (kSnapFloats * kBlock) + tid;
+            const float *sb = kp.snap + ((size_t)v * kp.slots_per_view + seg_slot0(kp, off, (uint32_t)t_)) * (kSnapFloats * kBlock) + fwd_thread_of(tid);
             const float *sp = sb + (size_t)seg_j * (kSnapFloats * kBlock), *sf = sb + (size_t)(nb - 1) * (kSnapFloats * kBlock);
             const float Tp = sp[0];
             float suf = fmaf(sf[kBlock] - sp[kBlock], dp0, fmaf(sf[2 * kBlock] - sp[2 * kBlock], dp1, (sf[3 * kBlock] - sp[3 * kBlock]) * dp2));
@@ -396,7 +472,6 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
             for (int k = 0; k < nsteps; k += 4) {
                 const uint32_t ee[4] = { pk.x & 0xffffu, pk.x >> 16, pk.y & 0xffffu, pk.y >> 16 };
                 pk = *reinterpret_cast<const uint2 *>(list + k + 4);          // the lists are padded: always readable
-                v2f ds[4];
                 float Gs[4], alphas[4];
                 float4 cds[4];
                 bool contribs[4];
@@ -404,17 +479,16 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
                 for (int u = 0; u < 4; u++) {            // four independent evaluations (ILP)
                     const float2 *rec = reinterpret_cast<const float2 *>(rec_b + ee[u]);
                     const float2 q01 = rec[0], q23 = rec[1], c01 = rec[2], c23 = rec[3];
-                    ds[u] = *reinterpret_cast<const v2f *>(rec + 4) - pix_f;
+                    const v2f d = *reinterpret_cast<const v2f *>(rec + 4) - pix_f;
                     cds[u] = make_float4(c01.x, c01.y, c23.x, c23.y);
                     float p2;
-                    eval_splat(make_float4(q01.x, q01.y, q23.x, q23.y), ds[u], p2, Gs[u], alphas[u]);
+                    eval_splat(make_float4(q01.x, q01.y, q23.x, q23.y), d, p2, Gs[u], alphas[u]);
                     contribs[u] = (int)ee[u] < lc_rel && !(p2 > 0.0f) && !(alphas[u] < T4D_ALPHA_MIN);
                 }
                 const uint32_t cbits = (uint32_t)(conflict_s[kChunks == 1 ? 0 : (k >> 6)] >> (k & 63));
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     const bool contrib = contribs[u];
-                    const v2f d = ds[u];
                     const float G = Gs[u], alpha = alphas[u];
                     float *dst = reinterpret_cast<float *>(slab + (LAT ? (ee[u] & slab_and) : ee[u]));
                     const float old = *dst;              // early read of the slab value this step adds to
@@ -453,10 +527,11 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
                         // in the last bit)
                         acc = fmaf(alpha, qma, acc);
                     }
-                    // lanes that do not contribute carry e = w = 0, so their ten products are exact zeros
-                    const v2f ed = e * d, edd = ed * d, wdp = w * dp01;
-                    float r[10] = { e, ed.x, ed.y, edd.x, ed.x * d.y, edd.y, wdp.x, wdp.y, w * dp2, DA ? w * ddep : 0.f };
-                    const float tot = reduce10_row<!DA>(r);
+                    // lanes that do not contribute carry e = w = 0, so their products are exact zeros
+                    e = moment_e(e);
+                    const float ex = e * rw.X;
+                    const v2f wdp = w * dp01;
+                    const float tot = reduce_moments_row<!DA>(e, ex, ex * rw.X, wdp.x, wdp.y, w * dp2, DA ? w * ddep : 0.f, rw);
                     // Plain read-add-write into the wave's slab (ds_add_f32 retires ~3 cycles per LANE on this part).  Idle
                     // rows add their zeros to the null splat's row, which nobody reads.
                     const bool add = my_slot >= 0;
@@ -481,15 +556,29 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
             float a[10];
 #pragma unroll
             for (int k = 0; k < 10; k++) a[k] = 0.f;
+            // a batch nobody walked staged nothing: its slabs are zero and stay zero under any (finite) shift
+            const float2 pc = live ? reinterpret_cast<const float2 *>(s_rec + tid * kEnt)[4] : make_float2(0.f, 0.f);
+#pragma unroll 1
+            for (int w = 0; w < 4; w++) {
+                // the wave's raw moments (the latency build: of its four rows' slabs), then their shift from the centre of the
+                // wave's 8x8 block to the splat centre; both differences below are exact
+                float m[10];
 #pragma unroll
-            for (int w = 0; w < kSlabs; w++) {
-                float2 *src = reinterpret_cast<float2 *>(&s_acc[w][tid][0]);
+                for (int k = 0; k < 10; k++) m[k] = 0.f;
 #pragma unroll
-                for (int k = 0; k < 5; k++) {
-                    const float2 b2 = src[k];
-                    a[2 * k] += b2.x; a[2 * k + 1] += b2.y;
-                    src[k] = make_float2(0.f, 0.f);                  // leave the slab zeroed for the next batch
+                for (int s = 0; s < kSlabs / 4; s++) {
+                    float2 *src = reinterpret_cast<float2 *>(&s_acc[w * (kSlabs / 4) + s][tid][0]);
+#pragma unroll
+                    for (int k = 0; k < 5; k++) {
+                        const float2 b2 = src[k];
+                        m[2 * k] += b2.x; m[2 * k + 1] += b2.y;
+                        src[k] = make_float2(0.f, 0.f);              // leave the slab zeroed for the next batch
+                    }
                 }
+                moments_about_centre(m, pc.x - ((float)(tx * T4D_TILE_X + ((w & 1) << 3)) + 3.5f),
+                                        pc.y - ((float)(ty * T4D_TILE_Y + ((w >> 1) << 3)) + 3.5f));
+#pragma unroll
+                for (int k = 0; k < 10; k++) a[k] += m[k];
             }
             const uint32_t pr = s_pair[tid];
             if (pr < kp.cap) {
