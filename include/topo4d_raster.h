@@ -583,6 +583,36 @@ size_t t4d_image_metrics_scratch_bytes(int32_t n_views, int32_t h, int32_t w);
 int t4d_image_metrics(int32_t n_views, int32_t h, int32_t w, const float *render, const float *target, const float *mask,
                       const int32_t *coverage, double *out, void *scratch, size_t scratch_bytes, void *hip_stream);
 
+/* Exact closest point on a triangle soup, or on a bare point cloud, for many query points (csrc/t4d_closest.hip): what
+ * topo4d_amd/scanscore.py scores a frame's face.obj against its multi-view-stereo scan with.  It stands in for
+ * trimesh.proximity.closest_point / open3d's RaycastingScene.compute_closest_points on the host; the reference project has no
+ * counterpart.  All buffers are device memory unless stated; every call takes the stream last.
+ * The primitives are the n_faces triangles `faces` (int32 [n_faces,3], every index in [0, n_vert): the caller checks) of
+ * `vertices` (float64 [n_vert,3]), or, with n_faces == 0, the n_vert points themselves.  bbox (host, 6 doubles: min xyz, max xyz
+ * of the vertices) and mean_extent (host: the mean over the primitives of the longest side of their axis-aligned box, 0 for
+ * points) fix the uniform grid; the same values go to the size query and to the build.
+ * t4d_closest_index_bytes: bytes of the index buffer for lists of up to entry_capacity (primitive, cell) entries; 0 on bad
+ * arguments.  t4d_closest_build: fills `index`; on T4D_ERR_PAIR_OVERFLOW *entries_needed (host) holds the capacity to retry
+ * with.  Synchronises the stream.  The index holds a copy of the primitives: vertices and faces may be freed afterwards.
+ * t4d_closest_query: per query point (float64 [n_queries,3]) d2 (float64, squared distance), prim_index (int32) and closest
+ * (float64 [n_queries,3]) of the nearest primitive; among primitives of equal d2 the lowest index.  max_dist < 0 or +inf: no
+ * limit; otherwise a query is matched iff d2 <= max_dist * max_dist, and an unmatched one gets d2 = +inf, prim_index = -1,
+ * closest = 0.  flags: T4D_CLOSEST_INPUT_ORDER walks the queries in input order instead of grouped by grid cell (the same
+ * results; kept for measurement).  Uses a work area inside `index`: one query at a time per index.  The result equals a
+ * float64 brute force over all primitives with the arithmetic of tests/scanscore_ref.py, bit for bit.
+ * t4d_closest_signed: signed_dist[i] = sqrt(d2[i]) with the sign of (p - closest) . ((b - a) x (c - a)) of the chosen
+ * triangle; 0 where that is 0, for point primitives and for unmatched queries. */
+#define T4D_CLOSEST_INPUT_ORDER 1
+size_t t4d_closest_index_bytes(int64_t n_vert, int64_t n_faces, const double *bbox, double mean_extent, int64_t entry_capacity);
+int t4d_closest_build(const double *vertices, int64_t n_vert, const int32_t *faces, int64_t n_faces, const double *bbox,
+                      double mean_extent, void *index, size_t index_bytes, int64_t entry_capacity, int64_t *entries_needed,
+                      void *hip_stream);
+size_t t4d_closest_query_scratch_bytes(int64_t n_queries);
+int t4d_closest_query(void *index, size_t index_bytes, const double *points, int64_t n_queries, double max_dist, int32_t flags,
+                      double *d2, int32_t *prim_index, double *closest, void *scratch, size_t scratch_bytes, void *hip_stream);
+int t4d_closest_signed(const void *index, size_t index_bytes, const double *points, int64_t n_queries, const double *d2,
+                       const int32_t *prim_index, const double *closest, double *signed_dist, void *hip_stream);
+
 /* Optional per-kernel timing with HIP events recorded on the stream the kernels are launched on.  Between
  * t4d_profile_begin() and t4d_profile_end() every kernel launch of this library is bracketed by two events;
  * t4d_profile_end() synchronises them and returns, per kernel, the summed elapsed time and the launch count.

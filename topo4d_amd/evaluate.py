@@ -1,6 +1,7 @@
 """
 Score a finished run: `python -m topo4d_amd.evaluate -e EXP -s SEQ [-id ... -did ... -od ...] [--frames 1-10] [--views A,B]
-[--set low|dense|both] [--save_renders]`.
+[--set low|dense|both|none] [--save_renders] [--scans DIR [--scan_max_dist X] [--scan_unit S] [--scan_thresholds a,b,c]
+[--scan_transform FILE] [--save_scan_errors]]`.
 
 For every frame of <od>/<exp>/<seq>: read %06d/face.obj (save_mesh's vertices: the training frame mapped by the trans_g of
 cameras.get_cameras, whose inverse maps them back, in float64) and %06d/face.png (PIL, on the host; frame t+1's files are read on a thread
@@ -9,6 +10,10 @@ render the textured mesh into every camera (meshrender.MeshRenderer) and compare
 (meshrender.image_metrics).  The pixel mask drops the labels training masks out of its photometric loss (get_loss: inner_mouth,
 loss.get_mask).  Writes <od>/<exp>/<seq>/eval.json; with --save_renders also %06d/mesh_<cam>.png.  Works on output trees of the
 reference's train.py as well: the layout and save_mesh's formats are the same.
+
+With --scans DIR every frame's face.obj is also measured against that frame's 3D scan, DIR/%06d.ply or else DIR/%06d.obj
+(scanscore.score_scan: scan -> mesh and mesh -> scan distances).  face.obj is compared as written: save_mesh writes world
+coordinates, the frame Metashape exports its scans in.  eval.json gains the key "scan"; --set none scores scans alone.
 """
 from __future__ import annotations
 
@@ -197,6 +202,92 @@ def score_set(args, which: str, device) -> dict:
     return {"frames": result, "summary": _summary(result)}
 
 
+def _read_scan_files(run_dir: str, scan_dir: str, t: int, transform):
+    """(FaceObj or None, Scan or None) of frame t: the host half, run on the prefetch thread."""
+    from . import scanscore
+    obj_path = os.path.join(run_dir, "%06d" % t, "face.obj")
+    obj = meshrender.read_face_obj(obj_path) if os.path.exists(obj_path) else None
+    scan = None
+    for ext in (".ply", ".obj"):
+        path = os.path.join(scan_dir, "%06d%s" % (t, ext))
+        if os.path.exists(path):
+            scan = scanscore.read_scan(path)
+            break
+    if scan is not None and transform is not None:
+        scan = scanscore.Scan(scan.vertices @ transform[:3, :3].T + transform[:3, 3], scan.faces)
+    return obj, scan
+
+
+def _scan_summary(frames: dict) -> dict:
+    scored = {f: fr for f, fr in frames.items() if "scan_to_mesh" in fr}
+    out = {"frames": len(scored)}
+    for d in ("scan_to_mesh", "mesh_to_scan"):
+        rows = [fr[d] for fr in scored.values() if fr[d].get("count")]
+        part = {n: float(np.mean([r[n] for r in rows])) if rows else None for n in ("mean", "rms")}
+        keys = list(rows[0]["within"]) if rows else []
+        part["within"] = {k: float(np.mean([r["within"][k] for r in rows])) for k in keys}
+        out[d] = part
+    worst = [(f, fr["scan_to_mesh"]["mean"]) for f, fr in scored.items() if fr["scan_to_mesh"].get("count")]
+    out["worst_frame"] = max(worst, key=lambda w: w[1])[0] if worst else None
+    return out
+
+
+def score_scans(args, device) -> dict:
+    """The "scan" block of eval.json: per frame the two directions of scanscore.score_scan, and their summary."""
+    from . import scanscore
+    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
+    frames = args.frames or sorted(int(d) for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
+    transform = None
+    if args.scan_transform is not None:
+        transform = np.loadtxt(args.scan_transform, dtype=np.float64)
+        if transform.shape != (4, 4) or not np.isfinite(transform).all():
+            raise SystemExit(f"--scan_transform: {args.scan_transform} does not hold a finite 4x4 matrix")
+    result = {}
+    pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="t4d-eval-scan")
+    try:
+        pending = {}
+
+        def prefetch(t):
+            if t not in pending:
+                pending[t] = pool.submit(_read_scan_files, run_dir, args.scans, t, transform)
+
+        for i, t in enumerate(frames):
+            prefetch(t)
+            if i + 1 < len(frames):
+                prefetch(frames[i + 1])
+            obj, scan = pending.pop(t).result()
+            key = "%06d" % t
+            if obj is None:
+                result[key] = {"skipped": "no face.obj"}
+                continue
+            if scan is None:
+                result[key] = {"skipped": "no scan"}
+                continue
+            faces, _ = meshrender.triangulate(obj.faces_ori, obj.uv_faces_ori)
+            score = scanscore.score_scan(obj.vertices, faces, scan, max_dist=args.scan_max_dist, thresholds=args.scan_thresholds,
+                                         unit=args.scan_unit, device=device, per_element=args.save_scan_errors)
+            arrays = score.pop("arrays", None)
+            if arrays is not None:
+                np.savez(os.path.join(run_dir, key, "scan_score.npz"), **arrays)
+            row = {"scan_vertices": int(len(scan.vertices)), "scan_faces": 0 if scan.faces is None else int(len(scan.faces))}
+            for d, stats in score.items():
+                row[d] = {n: (_finite(v) if isinstance(v, float) else v) for n, v in stats.items()}
+            result[key] = row
+    finally:
+        pool.shutdown(wait=True)
+    return {"unit": args.scan_unit, "max_dist": args.scan_max_dist, "frames": result, "summary": _scan_summary(result)}
+
+
+def _floats(spec: str) -> List[float]:
+    try:
+        out = [float(x) for x in spec.split(",") if x.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{spec!r} is not a comma-separated list of numbers") from None
+    if not out or len(out) > 8 or any(not (x >= 0.0) for x in out):
+        raise argparse.ArgumentTypeError(f"{spec!r}: need 1 to 8 thresholds >= 0")
+    return out
+
+
 def build_parser() -> argparse.ArgumentParser:
     from .train import build_parser as train_parser
     base = train_parser()
@@ -208,9 +299,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--frames", type=_frames, default=None, help="Frames to score: '1-10', '1,5,9' (default: every frame directory).")
     p.add_argument("--views", type=lambda s: [v.strip() for v in s.split(",") if v.strip()], default=None,
                    help="Cameras to score, comma-separated (default: every camera, blacklisted ones included).")
-    p.add_argument("--set", choices=("low", "dense", "both"), default="low",
-                   help="Views to score against: the geometry inputs (-id), the texture inputs (-did), or both.")
+    p.add_argument("--set", choices=("low", "dense", "both", "none"), default="low",
+                   help="Views to score against: the geometry inputs (-id), the texture inputs (-did), both, or none (scans only).")
     p.add_argument("--save_renders", action="store_true", help="Also write %%06d/mesh_<cam>.png.")
+    p.add_argument("--scans", default=None, metavar="DIR",
+                   help="Also score each frame's face.obj against its 3D scan DIR/%%06d.ply (else DIR/%%06d.obj).")
+    p.add_argument("--scan_max_dist", type=float, default=None,
+                   help="Scan scoring: leave out pairs farther apart than this, in file units (default: none left out).")
+    p.add_argument("--scan_unit", type=float, default=1.0, help="Scan scoring: reported unit per file unit, e.g. 1000 for metres -> mm.")
+    p.add_argument("--scan_thresholds", type=_floats, default=[0.5, 1.0, 2.0],
+                   help="Scan scoring: report the fraction of distances under each, in reported units (default 0.5,1,2).")
+    p.add_argument("--scan_transform", default=None, metavar="FILE", help="Scan scoring: a 4x4 text matrix applied to every scan.")
+    p.add_argument("--save_scan_errors", action="store_true",
+                   help="Scan scoring: also write %%06d/scan_score.npz (face_count, face_mean, vertex_dist).")
     return p
 
 
@@ -219,11 +320,18 @@ def evaluate(args, device=None) -> dict:
     run_dir = os.path.join(args.output_dir, args.exp, args.seq)
     if not os.path.isdir(run_dir):
         raise SystemExit(f"no run at {run_dir}")
-    sets = ["low", "dense"] if args.set == "both" else [args.set]
+    sets = {"both": ["low", "dense"], "none": []}.get(args.set, [args.set])
+    scans = getattr(args, "scans", None)
+    if scans is not None and not os.path.isdir(scans):
+        raise SystemExit(f"--scans: no directory {scans}")
+    if not sets and scans is None:
+        raise SystemExit("--set none scores nothing without --scans")
     with torch.cuda.device(dev):
         out = {"exp": args.exp, "seq": args.seq, "blacklist": sorted(C.BLACKLIST), "mask_labels": MASK_LABELS}
         for which in sets:
             out[which] = score_set(args, which, dev)
+        if scans is not None:
+            out["scan"] = score_scans(args, dev)
     with open(os.path.join(run_dir, "eval.json"), "w") as f:
         json.dump(out, f, indent=1)
     return out
@@ -235,6 +343,8 @@ def main(argv=None) -> None:
     for which in ("low", "dense"):
         if which in out:
             print(which, json.dumps(out[which]["summary"]))
+    if "scan" in out:
+        print("scan", json.dumps(out["scan"]["summary"]))
 
 
 if __name__ == "__main__":
