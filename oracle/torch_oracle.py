@@ -343,7 +343,12 @@ def rasterize_with_grads(view: View, means3D, opacities, scales, rotations, colo
     names = ["means3D", "means2D", "opacities", "scales", "rotations", "colors_precomp", "shs", "cov3D_precomp"]
     leaves = [m3, m2, op, sc, ro, cp, sh, cv]
     have = [(n, l) for n, l in zip(names, leaves) if l is not None]
-    gs = torch.autograd.grad(loss, [l for _, l in have], allow_unused=True)
+    if torch.is_tensor(loss) and loss.requires_grad:
+        gs = torch.autograd.grad(loss, [l for _, l in have], allow_unused=True)
+    else:
+        # no Gaussian reaches a pixel (all culled): the outputs are constants - background, zero depth and alpha - and every
+        # gradient is zero, as oracle/raster_oracle.c returns for such a view
+        gs = [None] * len(have)
     grads = {n: (g if g is not None else torch.zeros_like(l)) for (n, l), g in zip(have, gs)}
     outs = dict(color=color.detach(), radii=radii, depth=depth.detach(), alpha=alpha.detach(),
                 final_T=aux["final_T"], n_contrib=aux["n_contrib"], aux=aux)

@@ -134,3 +134,23 @@ def test_mark_visible_and_empty_scene():
     rv2["means3D"] = torch.tensor(far)
     r, _ = util.c_oracle_render(cams[0], rv2)
     assert r.num_rendered == 0 and (r.radii == 0).all() and np.abs(r.color).max() == 0
+
+
+def test_float64_oracle_on_a_view_that_sees_nothing():
+    """No Gaussian visible: rasterize_with_grads used to raise "element 0 of tensors does not require grad".  Like the C oracle
+    it returns the background, zero depth and alpha, and zero gradients."""
+    rv, cams = util.make_scene(6, 10, 32, 32, 1, opacity="B", seed=1)
+    cam = cams[0]._replace(bg=torch.tensor([0.25, 0.5, 0.75]))
+    rv["means3D"] = rv["means3D"] + torch.tensor([0.0, 0.0, 50.0])
+    dc, dd, da = scene.output_cotangents(1, 32, 32, seed=3, depth_alpha=True)
+    for cot in ((dc[0], dd[0], da[0]), (dc[0], None, None), (None, None, None)):
+        outs, grads = util.torch_oracle_render(cam, rv, *cot)
+        assert (outs["color"] == cam.bg.double()[:, None, None]).all()
+        assert not outs["depth"].any() and not outs["alpha"].any() and not outs["radii"].any() and not outs["n_contrib"].any()
+        assert set(KEYS) <= set(grads)
+        for k in KEYS:
+            assert grads[k].shape[0] == rv["means3D"].shape[0] and grads[k].dtype == torch.float64 and not grads[k].any(), k
+    r, g = util.c_oracle_render(cam, rv, dc[0], dd[0], da[0])
+    assert r.num_rendered == 0 and (r.color == cam.bg.numpy()[:, None, None]).all() and not r.depth.any() and not r.alpha.any()
+    for k in KEYS:
+        assert not g[k].any(), k
