@@ -514,6 +514,34 @@ size_t t4d_warp_scratch_bytes(int32_t n_views);
 int t4d_warp_views(const T4DWarpView *views, const T4DWarpView *d_views, int32_t n_views, void *scratch, size_t scratch_bytes,
                    void *hip_stream);
 
+/* T4DLensView: one capture view undistorted by Metashape's frame-camera model, turned and (optionally) box-filtered down in ONE
+ * resampling of a uint8 HWC photograph read as image / 255.0 in float64 (csrc/t4d_lens.h holds the map and the sampling;
+ * csrc/t4d_undistort.hip the kernel).  src, rows, cols, channels, src_pitch, dst, out_rows, out_cols as in T4DWarpView.
+ * Over a virtual image U of out_rows*supersample x out_cols*supersample:
+ *   1. matrix (as in T4DWarpView) takes U's pixel (col, row) to index coordinates (C, R) of the undistorted sensor image;
+ *   2. lens = {f, cxa, cya, k1, k2, k3, k4, p1, p2, b1, b2} (pixels of the photograph in src; cxa = width/2 + cx) takes them to
+ *      index coordinates (C_src, R_src) of the photograph:  x = ((C + 0.5) - cxa) / f, y likewise, r2 = x*x + y*y,
+ *      rad = r2*(k1 + r2*(k2 + r2*(k3 + r2*k4))), dx = x*rad + p1*(r2 + 2*x*x) + 2*p2*x*y, dy = y*rad + p2*(r2 + 2*y*y) + 2*p1*x*y,
+ *      C_src = C + f*dx + b1*(x + dx) + b2*(y + dy), R_src = R + f*dy (all coefficients zero: (C, R) exactly);
+ *   3. the sample is skimage's order-1 interpolation there (taps outside the photograph are cval), or with nearest != 0 the
+ *      single tap at floor(coordinate + 0.5) (label masks); a coordinate more than a sample outside the photograph, or not
+ *      finite, gives cval itself;
+ *   4. dst[ch, r, c] = float32(sum of U over the supersample x supersample block, row-major, / supersample^2).
+ * There is no clip step.  t4d_undistort_views: views (host) and d_views (a device copy), one launch for all of them. */
+typedef struct T4DLensView {
+    const uint8_t *src;
+    float *dst;
+    int32_t rows, cols, channels, src_pitch;
+    int32_t out_rows, out_cols;
+    int32_t supersample;                    /* 1..T4D_LENS_MAX_SUPERSAMPLE */
+    int32_t nearest;                        /* 0 or 1 */
+    double matrix[6];
+    double lens[11];
+    double cval;
+} T4DLensView;
+#define T4D_LENS_MAX_SUPERSAMPLE 64
+int t4d_undistort_views(const T4DLensView *views, const T4DLensView *d_views, int32_t n_views, void *hip_stream);
+
 /* ---- Coarse setup: initialize_params' coarse half and initialize_losses' topology (csrc/t4d_setup.hip; topo4d_amd/coarse.py) ----
  * t4d_setup_vertex_colors: compute_vertex_colors (helpers.py:181-209).  image: uint8 [height, width, channels] (3 or 4);
  * corner_uv [n_corners,2] float64: the UV of triangle corner 3*face+k; offsets / entries: t4d_obj_vertex_faces' CSR of the same

@@ -113,6 +113,15 @@ class T4DWarpView(C.Structure):
         "rows", "cols", "channels", "src_pitch", "out_rows", "out_cols")] + [("matrix", C.c_double * 6), ("cval", C.c_double)]
 
 
+T4D_LENS_MAX_SUPERSAMPLE = 64
+
+
+class T4DLensView(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)] + [(n, C.c_int32) for n in (
+        "rows", "cols", "channels", "src_pitch", "out_rows", "out_cols", "supersample", "nearest")] + [
+        ("matrix", C.c_double * 6), ("lens", C.c_double * 11), ("cval", C.c_double)]
+
+
 _VP, _I32, _I64, _F32, _SZ, _INT = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t, C.c_int
 _PROB = C.POINTER(T4DProblem)
 
@@ -171,6 +180,7 @@ SIGNATURES = {
     "t4d_jpeg_decode": (_INT, [C.POINTER(T4DJpegImage), _VP, _I32, _VP, _I32, _VP, _SZ, _VP, _VP, _SZ, _VP]),
     "t4d_warp_scratch_bytes": (_SZ, [_I32]),
     "t4d_warp_views": (_INT, [C.POINTER(T4DWarpView), _VP, _I32, _VP, _SZ, _VP]),
+    "t4d_undistort_views": (_INT, [C.POINTER(T4DLensView), _VP, _I32, _VP]),
     "t4d_setup_colors_scratch_bytes": (_SZ, [_I64]),
     "t4d_setup_vertex_colors": (_INT, [_VP] + [_I32] * 3 + [_VP, _I64, _VP, _VP, _I32] + [_VP] * 4 + [_SZ, _VP]),
     "t4d_setup_quaternions": (_INT, [_VP, _I32, _VP, _VP]),

@@ -5,6 +5,8 @@ train.py hard-codes (train.py:28-55) with the parsing colormap of helpers.py:725
 
     load_camera(calib_fname, img_name, ...)     one camera's dict + the chunk's component transform (trans_g)
     get_cameras(data_dir, seq, resize_factor)   every camera of frame 000001, at `resize_factor` and at full size
+    load_lens(calib, img_name, resize_factor)   one camera's lens (Metashape's frame model: f, cx, cy, k1-k4, p1, p2, b1, b2)
+    get_lenses(data_dir, seq, resize_factor)    every camera's lens, keyed like get_cameras' dicts (ingest undistorts with them)
     setup_camera(cam, w, h, k, w2c, ...)        GaussianRasterizationSettings (golden G1)
     ROTATE_MASK, BLACKLIST, CMAP_INDEX          train.py:28-55
     label_colormap(n_label)                     helpers.py:725-798
@@ -12,6 +14,7 @@ train.py hard-codes (train.py:28-55) with the parsing colormap of helpers.py:725
 
 Golden G16 (tools/gen_golden_cameras.py) holds the reference's load_camera outputs for a 24-camera cameras.xml: every array
 here equals them bit for bit except radial_distortion, a least-squares fit that nothing downstream reads (within 1e-9).
+The lens itself is read by load_lens, which the reference has no counterpart of: it expects undistorted photographs.
 
 Metashape stores per camera a camera-to-world transform with x right, y down, z forwards.  The reference turns its camera axes
 to OpenGL's (y and z negated), rolls the camera by -rt * 90 degrees about its optical axis for the views train.py turns upright
@@ -22,6 +25,7 @@ from __future__ import annotations
 import math
 import os
 import xml.etree.ElementTree as ET
+from dataclasses import dataclass, replace
 from glob import glob
 from typing import Dict, Optional
 
@@ -196,11 +200,12 @@ def load_camera(calib_fname, img_name, resize_factor=1, to_meters=False, rt=0):
     return _camera(chunk, img_name, resize_factor, rt), component_transform(chunk)
 
 
-def get_cameras(data_dir, seq, resize_factor=8, rotate_mask: Optional[Dict[str, int]] = None):
+def get_cameras(data_dir, seq, resize_factor=8, rotate_mask: Optional[Dict[str, int]] = None, *, views_dir=None):
     """train.py:58-71: (cameras at `resize_factor`, cameras at full size, trans_g) for every view of frame 000001 (sorted *.jpg,
-    then sorted *.png), keyed by file name with its extension."""
+    then sorted *.png), keyed by file name with its extension.  views_dir: the root whose <seq>/000001 lists the views (default
+    data_dir, which holds cameras.xml) - for a run whose geometry inputs are made from the full-size photographs."""
     rotate_mask = ROTATE_MASK if rotate_mask is None else rotate_mask
-    fdir = os.path.join(data_dir, seq, "000001")
+    fdir = os.path.join(data_dir if views_dir is None else views_dir, seq, "000001")
     names = sorted(glob(os.path.join(fdir, "*.jpg"))) + sorted(glob(os.path.join(fdir, "*.png")))
     chunk = _chunk(os.path.join(data_dir, seq, "cameras.xml"))
     trans_g = component_transform(chunk)
@@ -211,6 +216,96 @@ def get_cameras(data_dir, seq, resize_factor=8, rotate_mask: Optional[Dict[str, 
         cams[fname] = _camera(chunk, stem, resize_factor, rotate_mask[stem])
         cams_ori[fname] = _camera(chunk, stem, 1, rotate_mask[stem])
     return cams, cams_ori, trans_g
+
+
+# ---- the lens of a camera (Metashape's frame-camera model; the reference reads none of it) ---------------------------------------
+LENS_COEFFICIENTS = ("k1", "k2", "k3", "k4", "p1", "p2", "b1", "b2")
+
+
+@dataclass(frozen=True)
+class Lens:
+    """One sensor's calibration in pixels of an image of width x height (the sensor before any turn): cxa = width/2 + cx and
+    cya = height/2 + cy from the image's top-left corner.  K and P are dimensionless; f, cxa, cya, b1 and b2 scale with the
+    image.  ingest.undistort_views holds the formulas."""
+    f: float
+    cxa: float
+    cya: float
+    k1: float = 0.0
+    k2: float = 0.0
+    k3: float = 0.0
+    k4: float = 0.0
+    p1: float = 0.0
+    p2: float = 0.0
+    b1: float = 0.0
+    b2: float = 0.0
+    width: int = 0
+    height: int = 0
+
+    @property
+    def is_pinhole(self) -> bool:
+        """Every coefficient is zero: the photograph is its own undistorted image."""
+        return not any(getattr(self, n) != 0.0 for n in LENS_COEFFICIENTS)
+
+    def numbers(self):
+        """f, cxa, cya, k1..k4, p1, p2, b1, b2: T4DLensView's `lens`."""
+        return (self.f, self.cxa, self.cya) + tuple(getattr(self, n) for n in LENS_COEFFICIENTS)
+
+    def scaled(self, resize_factor) -> "Lens":
+        """The lens of the same photograph stored at 1/resize_factor size (width and height floored, as load_camera's)."""
+        if resize_factor == 1:
+            return self
+        s = resize_factor
+        return replace(self, f=self.f / s, cxa=self.cxa / s, cya=self.cya / s, b1=self.b1 / s, b2=self.b2 / s,
+                       width=math.floor(self.width / s), height=math.floor(self.height / s))
+
+
+def _lens(chunk: ET.Element, img_name: str, resize_factor) -> Lens:
+    cams = chunk.find("cameras")
+    node = next((c for c in (cams.findall("camera") if cams is not None else []) if c.get("label") == img_name), None)
+    if node is None:
+        raise ValueError(f"cameras.xml: no camera labelled {img_name!r}")
+    if node.get("sensor_id") is None:
+        raise ValueError(f"cameras.xml: camera {img_name!r} has no sensor_id")
+    sensor_id = int(node.get("sensor_id"))
+    sensors = chunk.find("sensors")
+    sensor = next((s for s in (sensors.findall("sensor") if sensors is not None else []) if int(s.get("id")) == sensor_id), None)
+    if sensor is None or sensor.find("resolution") is None or sensor.find("calibration") is None \
+            or sensor.find("calibration").find("f") is None:
+        raise ValueError(f"cameras.xml: camera {img_name!r} names sensor {sensor_id}, which is missing or has no resolution / f")
+    cal = sensor.find("calibration")
+    for kind in (sensor.get("type"), cal.get("type")):
+        if kind is not None and kind != "frame":
+            raise ValueError(f"cameras.xml: camera {img_name!r}: sensor {sensor_id} is a {kind!r} camera; only Metashape's "
+                             "'frame' lens model is implemented")
+    res = sensor.find("resolution")
+    width, height = int(res.get("width")), int(res.get("height"))
+    value = lambda tag: float(cal.find(tag).text) if cal.find(tag) is not None else 0.0
+    lens = Lens(f=value("f"), cxa=width / 2.0 + value("cx"), cya=height / 2.0 + value("cy"),
+                **{n: value(n) for n in LENS_COEFFICIENTS}, width=width, height=height)
+    return lens.scaled(resize_factor)
+
+
+def load_lens(calib, img_name, resize_factor=1) -> Lens:
+    """The lens of camera `img_name` of a Metashape cameras.xml (a path or a parsed tree), for photographs stored at
+    1/resize_factor size.  Missing coefficient tags are 0.  A missing camera or sensor raises ValueError naming the camera, and
+    so does a sensor whose type is not 'frame' (fisheye and the other camera types have other formulas)."""
+    return _lens(_chunk(calib), img_name, resize_factor)
+
+
+def _view_names(data_dir, seq):
+    fdir = os.path.join(data_dir, seq, "000001")
+    return [os.path.basename(p) for p in sorted(glob(os.path.join(fdir, "*.jpg"))) + sorted(glob(os.path.join(fdir, "*.png")))]
+
+
+def get_lenses(data_dir, seq, resize_factor=8, *, views_dir=None):
+    """(lenses at `resize_factor`, lenses at full size) for every view of frame 000001, keyed like get_cameras' dicts.
+    views_dir: the root whose <seq>/000001 lists the views (default data_dir, which holds cameras.xml)."""
+    chunk = _chunk(os.path.join(data_dir, seq, "cameras.xml"))
+    lenses, lenses_ori = {}, {}
+    for fname in _view_names(data_dir if views_dir is None else views_dir, seq):
+        lenses_ori[fname] = _lens(chunk, fname.split(".")[0], 1)
+        lenses[fname] = lenses_ori[fname].scaled(resize_factor)
+    return lenses, lenses_ori
 
 
 # ---- the rasterizer's camera ------------------------------------------------------------------------------------------------------

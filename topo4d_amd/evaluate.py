@@ -139,6 +139,9 @@ def score_set(args, which: str, device) -> dict:
     data_dir = args.input_dir if which == "low" else args.dense_input_dir
     # the calibration and the camera list come from the geometry inputs for both sets, as train.py takes them
     cameras, _, trans_g = C.get_cameras(args.input_dir, args.seq, resize_factor=args.down_ratio if which == "low" else 1)
+    lenses = None
+    if getattr(args, "undistort", False):                      # the photographs are undistorted as training loaded them
+        lenses = C.get_lenses(args.input_dir, args.seq, args.down_ratio)[0 if which == "low" else 1]
     names = [n.split(".")[0] for n in cameras]
     chosen = names if args.views is None else [n for n in names if n in args.views]
     if args.views is not None and len(chosen) != len(args.views):
@@ -155,7 +158,7 @@ def score_set(args, which: str, device) -> dict:
 
     pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="t4d-eval")
     pf = {flag: ingest.FramePrefetcher(data_dir, args.seq, cameras, use_mask=flag, blacklist=skip, rotate_mask=C.ROTATE_MASK,
-                                       setup_camera=cam_fn, device=device) for flag in (False, True)}
+                                       setup_camera=cam_fn, device=device, lenses=lenses) for flag in (False, True)}
     try:
         pending = {}
 
@@ -302,6 +305,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--set", choices=("low", "dense", "both", "none"), default="low",
                    help="Views to score against: the geometry inputs (-id), the texture inputs (-did), both, or none (scans only).")
     p.add_argument("--save_renders", action="store_true", help="Also write %%06d/mesh_<cam>.png.")
+    p.add_argument("--undistort", action="store_true",
+                   help="Undistort the photographs by the lens calibration of cameras.xml, as topo4d_amd.train --undistort does.")
     p.add_argument("--scans", default=None, metavar="DIR",
                    help="Also score each frame's face.obj against its 3D scan DIR/%%06d.ply (else DIR/%%06d.obj).")
     p.add_argument("--scan_max_dist", type=float, default=None,

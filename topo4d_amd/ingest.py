@@ -1,6 +1,8 @@
 """
 A frame's views from files to float32 device targets, as the reference's `get_dataset` (train.py:73-103) loads them, over
-`t4d_jpeg_decode` and `t4d_warp_views` (include/topo4d_raster.h, csrc/t4d_ingest.hip).
+`t4d_jpeg_decode` and `t4d_warp_views` (include/topo4d_raster.h, csrc/t4d_ingest.hip), and - which the reference cannot -
+undistorted by the lens calibration of cameras.xml and box-filtered down in the same resampling (`t4d_undistort_views`,
+csrc/t4d_undistort.hip, csrc/t4d_lens.h).
 
     parse_jpeg(data) -> JpegHeader        the host half of the decoder: markers, tables, whether the GPU decoder takes the file
     decode_jpeg(list_of_bytes)            uint8 [H,W,3] device tensors, byte-identical to np.asarray(Image.open(f))
@@ -8,8 +10,12 @@ A frame's views from files to float32 device targets, as the reference's `get_da
     load_images(paths, angles, crop=None, out=None)
                                           float32 [C,H',W'] device tensors equal to torch.tensor(rotate(img / 255.0, angle,
                                           resize=True)).float().permute(2, 0, 1)
+    undistort_views(sources, matrices, shapes, lenses, ...)
+                                          Metashape's frame-camera model, the turn and an s x s box filter in one resampling
     get_dataset(data_dir, seq, frame, cameras, use_mask=False, blacklist=[], *, rotate_mask, setup_camera)
     FramePrefetcher                       reads frame t+1's files in a background pool while frame t trains
+    load_images, get_dataset and FramePrefetcher take lenses= ({file name: cameras.Lens}), supersample= and mask_dir=; with
+    their defaults (None, 1, None) nothing changes, and a view whose lens has no distortion still takes t4d_warp_views
 
 The GPU decoder takes baseline (SOF0/SOF1) 8-bit Huffman JPEGs with 3 YCbCr components, luma sampling 1x1, 2x1 or 2x2 and 1x1
 chroma, in one interleaved scan, with or without restart intervals.  Every other file (progressive, arithmetic-coded, 12-bit,
@@ -416,6 +422,61 @@ def warp_views(sources: Sequence[torch.Tensor], matrices, shapes, crops=None, ou
     return outs
 
 
+def undistort_views(sources: Sequence[torch.Tensor], matrices, shapes, lenses, crops=None, out=None, supersample=1,
+                    nearest=False, cval: float = 0.0) -> List[torch.Tensor]:
+    """uint8 [H,W,C] (or [H,W]) device photographs undistorted by Metashape's frame-camera model (cameras.Lens), turned and box-
+    filtered down in one resampling, one launch for all: float32 [C,out_rows,out_cols] (include/topo4d_raster.h T4DLensView).
+    matrices: [3,3] maps from the pixel (col, row) of the virtual image U, out_rows*s x out_cols*s, to index coordinates of the
+    undistorted sensor image (rotate_matrix of the whole sensor); shapes: (out_rows, out_cols); lenses: per view a cameras.Lens
+    (or its 11 numbers) in pixels of that source; supersample s and nearest: one value for all or one per view.  Each output
+    pixel is the mean of s x s order-1 samples of source / 255.0 (nearest: the tap at floor(coordinate + 0.5), for label masks);
+    samples outside the source are cval.  Nothing is clipped."""
+    n = len(sources)
+    if n == 0:
+        return []
+    dev = sources[0].device
+    crops = list(crops) if crops is not None else [None] * n
+    outs = list(out) if out is not None else [None] * n
+    per_view = lambda x: list(x) if isinstance(x, (list, tuple)) else [x] * n
+    ss, nn = per_view(supersample), per_view(nearest)
+    if not (len(matrices) == len(shapes) == len(lenses) == len(ss) == len(nn) == len(crops) == len(outs) == n):
+        raise ValueError("undistort_views: one matrix, shape, lens (crop, out, supersample, nearest) per source")
+    views = (_lib.T4DLensView * n)()
+    keep = []
+    for i, src in enumerate(sources):
+        if src.dtype != torch.uint8 or src.dim() not in (2, 3) or src.device != dev:
+            raise ValueError("undistort_views: sources must be uint8 [H,W] or [H,W,C] on one device")
+        s = src if src.dim() == 3 else src.unsqueeze(-1)
+        s = s.contiguous()
+        keep.append(s)
+        hh, ww, cc = (int(x) for x in s.shape)
+        rows, cols = (hh, ww) if crops[i] is None else (min(hh, int(crops[i][0])), min(ww, int(crops[i][1])))
+        oh, ow = (int(x) for x in shapes[i])
+        o = outs[i]
+        if o is None:
+            o = torch.empty((cc, oh, ow), dtype=torch.float32, device=dev)
+        elif o.shape != (cc, oh, ow) or o.dtype != torch.float32 or not o.is_contiguous() or o.device != dev:
+            raise ValueError(f"undistort_views: out[{i}] must be a contiguous float32 {(cc, oh, ow)} tensor on {dev}")
+        outs[i] = o
+        m = np.asarray(matrices[i], np.float64)
+        numbers = lenses[i].numbers() if hasattr(lenses[i], "numbers") else tuple(float(x) for x in lenses[i])
+        if len(numbers) != 11:
+            raise ValueError("undistort_views: a lens is f, cxa, cya, k1, k2, k3, k4, p1, p2, b1, b2")
+        v = views[i]
+        v.src, v.dst = s.data_ptr(), o.data_ptr()
+        v.rows, v.cols, v.channels, v.src_pitch = rows, cols, cc, ww * cc
+        v.out_rows, v.out_cols = oh, ow
+        v.supersample, v.nearest = int(ss[i]), int(bool(nn[i]))
+        for k in range(6):
+            v.matrix[k] = float(m[k // 3, k % 3])
+        for k in range(11):
+            v.lens[k] = float(numbers[k])
+        v.cval = float(cval)
+    d_views = _to_device_bytes(bytes(views), dev)
+    _lib.call("t4d_undistort_views", views, ptr(d_views), n, _lib.stream(dev))
+    return outs
+
+
 def _rotate_all(images, angles, crops, out):
     mats, shapes = [], []
     for img, a, cr in zip(images, angles, crops):
@@ -428,10 +489,52 @@ def _rotate_all(images, angles, crops, out):
     return warp_views(images, mats, shapes, crops, out)
 
 
-def load_images(paths: Sequence[str], angles: Sequence[float], crop=None, out=None, device=None, chunk_bits=None):
+def _resample_all(images, angles, crops, out, lenses, supersample, nearest):
+    """_rotate_all with a lens (cameras.Lens or None), a supersample and a nearest flag per image.  An image without distortion
+    (no lens, or every coefficient zero) and with supersample 1 goes through t4d_warp_views, as it does without lenses at all;
+    the others are undistorted, turned and averaged in one resampling (undistort_views): the matrix is rotate_matrix of the
+    sensor, and the output is its shape floor-divided by the supersample."""
+    from .cameras import Lens
+    n = len(images)
+    outs = list(out) if out is not None else [None] * n
+    plain = [i for i in range(n) if (lenses[i] is None or lenses[i].is_pinhole) and supersample[i] == 1]
+    lensed = [i for i in range(n) if i not in set(plain)]
+    pick = lambda seq, idx: [seq[i] for i in idx]
+    if plain:
+        for i, o in zip(plain, _rotate_all(pick(images, plain), pick(angles, plain), pick(crops, plain), pick(outs, plain))):
+            outs[i] = o
+    if lensed:
+        mats, shapes, ls = [], [], []
+        for i in lensed:
+            rows, cols = int(images[i].shape[0]), int(images[i].shape[1])
+            if crops[i] is not None:
+                rows, cols = min(rows, int(crops[i][0])), min(cols, int(crops[i][1]))
+            lens = lenses[i] if lenses[i] is not None else Lens(f=1.0, cxa=cols / 2.0, cya=rows / 2.0, width=cols, height=rows)
+            if (lens.height, lens.width) != (rows, cols):
+                raise ValueError(f"view {i}: the image is {rows} x {cols} but its lens is calibrated for {lens.height} x "
+                                 f"{lens.width}: pass the lenses of this resolution (cameras.get_lenses, Lens.scaled)")
+            m, shp = rotate_matrix(rows, cols, float(angles[i]))
+            s = int(supersample[i])
+            if s < 1 or shp[0] // s < 1 or shp[1] // s < 1:
+                raise ValueError(f"view {i}: supersample {s} of a {shp[0]} x {shp[1]} view")
+            mats.append(m)
+            shapes.append((shp[0] // s, shp[1] // s))
+            ls.append(lens)
+        res = undistort_views(pick(images, lensed), mats, shapes, ls, pick(crops, lensed), pick(outs, lensed),
+                              supersample=pick(supersample, lensed), nearest=pick(nearest, lensed))
+        for i, o in zip(lensed, res):
+            outs[i] = o
+    return outs
+
+
+def load_images(paths: Sequence[str], angles: Sequence[float], crop=None, out=None, device=None, chunk_bits=None, *,
+                lenses=None, supersample=1, mask_dir=None):
     """torch.tensor(rotate(np.array(Image.open(p))[:h, :w] / 255.0, angle, resize=True)).float().permute(2, 0, 1) for each path,
     as contiguous float32 device tensors.  crop: per path (h, w) or None (or None for all); out: per path a float32 tensor to
-    write into (e.g. the buffers a GraphedViews reads), or None."""
+    write into (e.g. the buffers a GraphedViews reads), or None.
+    lenses: cameras.Lens per path (a sequence, or a dict keyed by file name as cameras.get_lenses returns) - the photographs are
+    undistorted and turned in one resampling; supersample s: every output pixel is the mean of s x s samples and the output is
+    the turned shape floor-divided by s.  mask_dir is accepted for symmetry with get_dataset (no masks are read here)."""
     n = len(paths)
     crops = [None] * n if crop is None else list(crop)
     files, imgs = [], [None] * n
@@ -440,7 +543,18 @@ def load_images(paths: Sequence[str], angles: Sequence[float], crop=None, out=No
             files.append(f.read())
     decoded = decode_jpeg(files, chunk_bits=chunk_bits, device=device,
                           headers=[_header_or_none(b) for b in files], host_images=imgs)
-    return _rotate_all(decoded, angles, crops, out)
+    if lenses is None and supersample == 1:
+        return _rotate_all(decoded, angles, crops, out)
+    if isinstance(lenses, dict):
+        lenses = [_lens_of(lenses, os.path.basename(p)) for p in paths]
+    lenses = [None] * n if lenses is None else list(lenses)
+    return _resample_all(decoded, list(angles), crops, out, lenses, [int(supersample)] * n, [False] * n)
+
+
+def _lens_of(lenses: dict, name: str):
+    if name not in lenses:
+        raise ValueError(f"no lens for view {name!r} (lenses are keyed by file name, as cameras.get_lenses returns them)")
+    return lenses[name]
 
 
 def _header_or_none(data: bytes):
@@ -458,10 +572,11 @@ _NotJpeg = _NotJpegHeader()
 
 
 # ---- get_dataset -----------------------------------------------------------------------------------------------------------------
-def frame_files(data_dir, seq, frame, use_mask=False, blacklist=()):
+def frame_files(data_dir, seq, frame, use_mask=False, blacklist=(), mask_dir=None):
     """[(image path, mask path or None)] of one frame in the reference's order: sorted *.jpg then sorted *.png of
     <data_dir>/<seq>/<frame:06d>, minus names starting with a blacklisted prefix; the mask of <name>.<ext> is
-    <data_dir>/<seq>/mask/<frame:06d>/<name>.png."""
+    <mask_dir>/<seq>/mask/<frame:06d>/<name>.png (mask_dir: default data_dir)."""
+    mask_dir = data_dir if mask_dir is None else mask_dir
     fdir = os.path.join(data_dir, seq, "%06d" % frame)
     names = sorted(_glob.glob(os.path.join(fdir, "*.jpg"))) + sorted(_glob.glob(os.path.join(fdir, "*.png")))
     names = [p for p in names if not any(os.path.basename(p).startswith(b) for b in blacklist)]
@@ -471,7 +586,7 @@ def frame_files(data_dir, seq, frame, use_mask=False, blacklist=()):
         if use_mask:
             base = os.path.basename(p)
             stem = base.rsplit(".", 1)[0] if "." in base else base
-            mask = os.path.join(data_dir, seq, "mask", "%06d" % frame, stem + ".png")
+            mask = os.path.join(mask_dir, seq, "mask", "%06d" % frame, stem + ".png")
         out.append((p, mask))
     return out
 
@@ -497,7 +612,8 @@ def _read_view(path: str, mask_path: Optional[str]) -> _HostView:
     return _HostView(path, data, header, image, mask)
 
 
-def _assemble(views: List[_HostView], cameras, use_mask, rotate_mask, setup_camera, device, chunk_bits=None):
+def _assemble(views: List[_HostView], cameras, use_mask, rotate_mask, setup_camera, device, chunk_bits=None, lenses=None,
+              supersample=1):
     """The device half of get_dataset: decode, warp, cameras; launches on the caller's thread and stream."""
     dev = _device(device)
     decoded = decode_jpeg([v.data for v in views], chunk_bits=chunk_bits, device=dev, headers=[v.header for v in views],
@@ -509,8 +625,11 @@ def _assemble(views: List[_HostView], cameras, use_mask, rotate_mask, setup_came
         for v, img, a in zip(views, decoded, angles):
             srcs.append(torch.from_numpy(np.ascontiguousarray(v.mask)).to(dev))
             angs.append(a)
-            crops.append((int(img.shape[0]), int(img.shape[1])))
-    warped = _rotate_all(srcs, angs, crops, None)
+            crops.append((int(img.shape[0]) // int(supersample), int(img.shape[1]) // int(supersample)))
+    if lenses is None and supersample == 1:
+        warped = _rotate_all(srcs, angs, crops, None)
+    else:
+        warped = _resample_all(srcs, angs, crops, None, *_view_lenses(names, decoded, srcs, lenses, int(supersample)))
     dataset = []
     for idx, nm in enumerate(names):
         cam = cameras[nm]
@@ -522,15 +641,40 @@ def _assemble(views: List[_HostView], cameras, use_mask, rotate_mask, setup_came
     return dataset
 
 
+def _view_lenses(names, decoded, srcs, lenses, s):
+    """(lenses, supersamples, nearest flags) of _assemble's sources: the photographs, then (with masks) their masks.  A mask
+    stands for the photograph at 1/s size: it is cropped to the photograph's rows // s x cols // s, takes the lens scaled to
+    that size, a supersample of 1 and, where the lens distorts, nearest-tap sampling, so that no two label colours blend."""
+    n = len(names)
+    photo = [None if lenses is None else _lens_of(lenses, nm) for nm in names]
+    ls, ss, nn = list(photo), [s] * n, [False] * n
+    for k in range(n, len(srcs)):
+        img, mask, lens = decoded[k - n], srcs[k], photo[k - n]
+        rows, cols = int(img.shape[0]) // s, int(img.shape[1]) // s
+        if int(mask.shape[0]) < rows or int(mask.shape[1]) < cols:
+            raise ValueError(f"the mask of {names[k - n]!r} is {tuple(mask.shape[:2])}, smaller than its view at 1/{s} size "
+                             f"({rows} x {cols})")
+        ls.append(None if lens is None else lens.scaled(s))
+        ss.append(1)
+        nn.append(lens is not None and not lens.is_pinhole)
+    return ls, ss, nn
+
+
 def get_dataset(data_dir, seq, frame, cameras, use_mask=False, blacklist=[], *, rotate_mask: Dict[str, int],
-                setup_camera: Callable, device=None, chunk_bits=None):
+                setup_camera: Callable, device=None, chunk_bits=None, lenses=None, supersample=1, mask_dir=None):
     """The reference's get_dataset (train.py:73-103) with the decode and the rotation on the GPU.  rotate_mask and setup_camera
     are the dict and the function train.py takes from its own module and from helpers; setup_camera is called as train.py:98
-    calls it.  'im' and 'mask' hold the values of the reference's tensors, contiguous [C,H,W] instead of permuted views."""
-    views = [_read_view(p, m) for p, m in frame_files(data_dir, seq, frame, use_mask, blacklist)]
+    calls it.  'im' and 'mask' hold the values of the reference's tensors, contiguous [C,H,W] instead of permuted views.
+    lenses: {file name: cameras.Lens} in pixels of the photographs read (cameras.get_lenses) - every view is undistorted and
+    turned in one resampling, and its mask goes through the same map with nearest-tap sampling.  supersample s: the photographs
+    are s times the size `cameras` describes and every target pixel is the mean of s x s samples (masks stay at the target's
+    size).  A mask is taken to be at the target's resolution, the photograph's divided by `supersample`, and its lens is
+    scaled by that factor; a mask tree at any other resolution than that is refused (ValueError), not rescaled.  mask_dir: the
+    root of <seq>/mask/ (default data_dir).  With the defaults nothing of this runs."""
+    views = [_read_view(p, m) for p, m in frame_files(data_dir, seq, frame, use_mask, blacklist, mask_dir)]
     if not views:
         return []                                   # a frame past the end of the sequence (train.py:654 stops there)
-    return _assemble(views, cameras, use_mask, rotate_mask, setup_camera, device, chunk_bits)
+    return _assemble(views, cameras, use_mask, rotate_mask, setup_camera, device, chunk_bits, lenses, supersample)
 
 
 def pool_size() -> int:
@@ -553,8 +697,9 @@ class FramePrefetcher:
     """
 
     def __init__(self, data_dir, seq, cameras, use_mask=False, blacklist=(), *, rotate_mask, setup_camera, device=None,
-                 workers: Optional[int] = None):
+                 workers: Optional[int] = None, lenses=None, supersample=1, mask_dir=None):
         self.data_dir, self.seq, self.cameras = data_dir, seq, cameras
+        self.lenses, self.supersample, self.mask_dir = lenses, supersample, mask_dir
         self.use_mask, self.blacklist = use_mask, tuple(blacklist)
         self.rotate_mask, self.setup_camera, self.device = rotate_mask, setup_camera, device
         self.pool = ThreadPoolExecutor(max_workers=workers or pool_size(), thread_name_prefix="t4d-ingest")
@@ -562,7 +707,7 @@ class FramePrefetcher:
 
     def prefetch(self, frame: int) -> None:
         if frame not in self.pending:
-            files = frame_files(self.data_dir, self.seq, frame, self.use_mask, self.blacklist)
+            files = frame_files(self.data_dir, self.seq, frame, self.use_mask, self.blacklist, self.mask_dir)
             self.pending[frame] = [self.pool.submit(_read_view, p, m) for p, m in files]
 
     def get(self, frame: int):
@@ -570,7 +715,8 @@ class FramePrefetcher:
         views = [f.result() for f in self.pending.pop(frame)]
         if not views:
             return []
-        return _assemble(views, self.cameras, self.use_mask, self.rotate_mask, self.setup_camera, self.device)
+        return _assemble(views, self.cameras, self.use_mask, self.rotate_mask, self.setup_camera, self.device,
+                         lenses=self.lenses, supersample=self.supersample)
 
     def close(self) -> None:
         for futs in self.pending.values():

@@ -16,7 +16,10 @@ writes the same output tree as the reference's `python train.py ...`: <output_di
     outputs            params2cpu / save_params / write_loss_json, objexport.save_mesh        train.py:744-755
 
 The one deliberate difference: --log_views takes a comma-separated list of camera names (the reference's `type=list` splits
-its argument into characters).
+its argument into characters).  Two flags the reference does not have: --undistort undistorts every photograph and mask by the
+lens calibration of cameras.xml while it is loaded (cameras.get_lenses, ingest.undistort_views; the reference needs photographs
+exported undistorted), and --low_from_full makes the geometry inputs from the full-size photographs as down_ratio x down_ratio
+means, so that -id holds cameras.xml, the mesh and the masks only.  Without them nothing changes.
 
 The region "freezes" of train.py:676-700 are FusedAdamPins pins, written by the step kernel itself; the pin set changes at
 most twice per frame (the dynamic-eye pins end at iteration int(0.7 n) of frame 0) and the learning rates once (the colour
@@ -299,8 +302,12 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
     dev = coarse._device(device)
     clock = _Clock(timings, dev)
     with torch.cuda.device(dev), clock("setup"):
-        cameras, _, trans_g = C.get_cameras(args.input_dir, args.seq, resize_factor=args.down_ratio)     # train.py:595
-        cameras_dense, _, trans_g = C.get_cameras(args.input_dir, args.seq, resize_factor=1)              # train.py:596
+        undistort, low_from_full = getattr(args, "undistort", False), getattr(args, "low_from_full", False)
+        views_dir = args.dense_input_dir if low_from_full else None          # the calibration of input_dir, the view list of this
+        cameras, _, trans_g = C.get_cameras(args.input_dir, args.seq, resize_factor=args.down_ratio, views_dir=views_dir)   # train.py:595
+        cameras_dense, _, trans_g = C.get_cameras(args.input_dir, args.seq, resize_factor=1, views_dir=views_dir)          # train.py:596
+        lenses, lenses_dense = (None, None) if not undistort else C.get_lenses(
+            args.input_dir, args.seq, args.down_ratio, views_dir=views_dir)
         params, variables = coarse.initialize_params(args, trans_g, facial_regions=facial_regions, device=dev)  # :597
         optimizer = initialize_optimizer(params)                                                           # :600
         variables, losses, loss_weights, _ = coarse.initialize_losses(variables)                           # :601
@@ -308,10 +315,16 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
         pins = RegionPins(params, variables["facial_regions"])                                             # :619-629
         inner_mouth = C.parsing_colormap_bgr(14)[[C.CMAP_INDEX["inner_mouth"]]]                           # :633, helpers.py:806
         cam_fn = functools.partial(C.setup_camera, device=dev)
-        pf = ingest.FramePrefetcher(args.input_dir, args.seq, cameras, use_mask=USE_MASK, blacklist=C.BLACKLIST,
-                                    rotate_mask=C.ROTATE_MASK, setup_camera=cam_fn, device=dev)
+        if low_from_full:                  # the geometry targets are down_ratio x down_ratio means of the full-size photographs
+            pf = ingest.FramePrefetcher(args.dense_input_dir, args.seq, cameras, use_mask=USE_MASK, blacklist=C.BLACKLIST,
+                                        rotate_mask=C.ROTATE_MASK, setup_camera=cam_fn, device=dev, lenses=lenses_dense,
+                                        supersample=args.down_ratio, mask_dir=args.input_dir)
+        else:
+            pf = ingest.FramePrefetcher(args.input_dir, args.seq, cameras, use_mask=USE_MASK, blacklist=C.BLACKLIST,
+                                        rotate_mask=C.ROTATE_MASK, setup_camera=cam_fn, device=dev, lenses=lenses)
         pf_dense = ingest.FramePrefetcher(args.dense_input_dir, args.seq, cameras_dense, use_mask=USE_MASK_DENSE,
-                                          blacklist=C.BLACKLIST, rotate_mask=C.ROTATE_MASK, setup_camera=cam_fn, device=dev)
+                                          blacklist=C.BLACKLIST, rotate_mask=C.ROTATE_MASK, setup_camera=cam_fn, device=dev,
+                                          lenses=lenses_dense)
     rng = Random(seed)
     output_params = []
     state = {"params": params, "variables": variables, "optimizer": optimizer, "priors": priors, "pins": pins, "frames": 0}
@@ -443,6 +456,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('-lv', '--log_views', type=_view_list, default=["K98707293"],
                    help="Views of the saved renderings, comma-separated.")
     p.add_argument('-cf', '--ckp_freq', type=int, default=5, help="Frequence of saving gaussian attributes.")
+    # the two flags the reference does not have stay out of the namespace unless given (read with getattr)
+    p.add_argument('--undistort', action='store_true', default=argparse.SUPPRESS,
+                   help="Undistort every photograph (and its mask) by the lens calibration of cameras.xml while it is loaded; "
+                        "without it the photographs must have been exported undistorted.")
+    p.add_argument('--low_from_full', action='store_true', default=argparse.SUPPRESS,
+                   help="Make the geometry inputs from $dense_input_dir's photographs (down_ratio x down_ratio means) instead "
+                        "of reading $input_dir's; $input_dir then holds cameras.xml, the mesh and the masks only.")
     return p
 
 
