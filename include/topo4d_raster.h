@@ -403,6 +403,35 @@ int t4d_texture_render_colors(const float *vertices, const int32_t *triangles, c
                               float *image, float *depth_buffer, void *scratch, size_t scratch_bytes, int64_t pair_capacity,
                               int64_t *pairs_needed, void *hip_stream);
 
+/* Texture finishing (topo4d_amd/texfinish.py, csrc/t4d_texfinish.hip): a gutter round the UV islands of a baked texture and
+ * smaller levels that ignore the black background.  Every pointer is device memory; images are uint8 [h,w,c], c in {1, 3, 4};
+ * a coverage is uint8 [h,w], non-zero = covered, and every coverage written holds 0 or 1; 1 <= h, w <= 65536.  Inputs and outputs
+ * are separate buffers.  Arguments are checked before anything touches a device; none of these synchronises the stream.  All
+ * arithmetic after the quantisation is integer, so the results do not depend on the launch shape.
+ *
+ * t4d_texture_coverage: coverage = depth > -999999.0f for the depth buffer float32 [h,w] of t4d_texture_render_colors /
+ * t4d_texture_bake, which leave exactly -999999 where no triangle wrote (mesh_core.cpp:216).  A texel of the image's outermost
+ * two-texel ring that the reference writes by extrapolation (mesh_core.cpp:211) has a depth and so counts as covered.
+ * t4d_texture_quantize: float32 [h,w,c] -> uint8 by the rule of t4d_png_encode's float path: numpy's (x*255).astype(np.uint8) on
+ * x86-64 (truncation toward zero to int32, low byte kept, NaN -> 0).
+ * t4d_texture_erode: `rounds` (0..4) rounds; in each, a texel stays covered only if it and its 4-neighbours inside the image are
+ * covered (neighbours outside the image count as covered).  0 rounds normalise the coverage to 0 / 1.
+ * t4d_texture_pad: covered texels are copied through.  An uncovered texel (x, y) takes the value of the covered texel (x', y')
+ * with (x-x')^2 + (y-y')^2 <= radius^2 (a disc; radius 0..64) that has the lexicographically smallest (d^2, y', x'), and its output
+ * coverage is 1; with no such texel it keeps its input value and its output coverage is 0.  radius 0 is a copy.  Scratch:
+ * t4d_texture_pad_scratch_bytes(h, w) (0 and a message for a bad shape); T4D_ERR_STATE_SIZE when it is smaller.
+ * t4d_texture_halve: h and w even (T4D_ERR_ARG otherwise); outputs [h/2,w/2,c] and [h/2,w/2].  For each 2x2 block cnt = its covered
+ * texels and, per channel, s = the sum over them: the output is (2 s + cnt) / (2 cnt) in integer arithmetic (round half up), 0 when
+ * cnt = 0; the output coverage is cnt > 0.  Uncovered texels never enter an average. */
+int t4d_texture_coverage(const float *depth, int32_t h, int32_t w, uint8_t *coverage, void *hip_stream);
+int t4d_texture_quantize(const float *image, int32_t h, int32_t w, int32_t c, uint8_t *out, void *hip_stream);
+int t4d_texture_erode(const uint8_t *coverage, int32_t h, int32_t w, int32_t rounds, uint8_t *out, void *hip_stream);
+size_t t4d_texture_pad_scratch_bytes(int32_t h, int32_t w);
+int t4d_texture_pad(const uint8_t *image, const uint8_t *coverage, int32_t h, int32_t w, int32_t c, int32_t radius,
+                    uint8_t *out_image, uint8_t *out_coverage, void *scratch, size_t scratch_bytes, void *hip_stream);
+int t4d_texture_halve(const uint8_t *image, const uint8_t *coverage, int32_t h, int32_t w, int32_t c, uint8_t *out_image,
+                      uint8_t *out_coverage, void *hip_stream);
+
 /* Lossless PNG encoder for a device image (write_texture(..., encoder="gpu"): the last CPU step of save_mesh, helpers.py:953-960).
  * image [h,w,c] on the device, uint8 (is_float32 = 0) or float32 (is_float32 = 1, quantised exactly like numpy's
  * (x*255).astype(np.uint8) on x86-64: truncation toward zero to int32, low byte kept, NaN -> 0); c in {1, 3, 4} gives colour

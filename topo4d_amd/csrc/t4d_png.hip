@@ -27,6 +27,7 @@
 
 #include "../../include/topo4d_raster.h"
 #include "t4d_host.h"
+#include "t4d_quant.h"
 
 namespace {
 
@@ -119,14 +120,7 @@ __device__ __forceinline__ int len_index(int l)                  // 3..258 -> 0.
 // ---------------------------------------------------------------------------------------------------------------------------
 // quantise + filter
 // ---------------------------------------------------------------------------------------------------------------------------
-// numpy's float32 -> uint8 cast on x86-64: truncate toward zero to int32 (cvttss2si: NaN and |y| >= 2^31 give INT_MIN), keep the
-// low byte.  A multiply alone: nothing to contract.
-__device__ __forceinline__ uint32_t quant(float x)
-{
-    const float y = x * 255.0f;
-    if (!(fabsf(y) < 2147483648.0f)) return 0u;
-    return (uint32_t)(int32_t)y & 0xFFu;
-}
+// numpy's float32 -> uint8 cast on x86-64: t4d_quant_u8 (t4d_quant.h, shared with t4d_texture_quantize)
 
 // torchvision's save_image: x.mul(255).add_(0.5).clamp_(0, 255) on the device, then .to("cpu", torch.uint8).  Two roundings, a
 // clamp that keeps NaN, and ATen's x86-64 float -> uint8 conversion of the clamped value: truncation toward zero, NaN -> 0.
@@ -156,7 +150,7 @@ __device__ __forceinline__ uint32_t pix(const void *img, const Shape &s, int64_t
         return quant_tv(((const float *)img)[(plane * s.h + r) * s.w + col]);
     }
     const int64_t i = r * ((int64_t)s.w * s.c) + x;
-    if (MODE == kF32) return quant(((const float *)img)[i]);
+    if (MODE == kF32) return t4d_quant_u8(((const float *)img)[i]);
     return ((const uint8_t *)img)[i];
 }
 

@@ -1,7 +1,7 @@
 """
 Score a finished run: `python -m topo4d_amd.evaluate -e EXP -s SEQ [-id ... -did ... -od ...] [--frames 1-10] [--views A,B]
 [--set low|dense|both|none] [--save_renders] [--scans DIR [--scan_max_dist X] [--scan_unit S] [--scan_thresholds a,b,c]
-[--scan_transform FILE] [--save_scan_errors]]`.
+[--scan_transform FILE] [--save_scan_errors]] [--tex_pad R [--tex_erode E]]`.
 
 For every frame of <od>/<exp>/<seq>: read %06d/face.obj (save_mesh's vertices: the training frame mapped by the trans_g of
 cameras.get_cameras, whose inverse maps them back, in float64) and %06d/face.png (PIL, on the host; frame t+1's files are read on a thread
@@ -14,6 +14,10 @@ reference's train.py as well: the layout and save_mesh's formats are the same.
 With --scans DIR every frame's face.obj is also measured against that frame's 3D scan, DIR/%06d.ply or else DIR/%06d.obj
 (scanscore.score_scan: scan -> mesh and mesh -> scan distances).  face.obj is compared as written: save_mesh writes world
 coordinates, the frame Metashape exports its scans in.  eval.json gains the key "scan"; --set none scores scans alone.
+
+With --tex_pad R every face.png is padded in memory before it is sampled (texfinish.finish: a gutter of R texels round the UV
+islands of face.obj, whose coverage is first eroded --tex_erode rounds, 1 by default), so that the bilinear taps on the UV seams
+no longer mix in the file's black background.  The files stay as they are; eval.json gains "tex_pad" and "tex_erode".
 """
 from __future__ import annotations
 
@@ -183,6 +187,11 @@ def score_set(args, which: str, device) -> dict:
                 continue
             faces, uv_faces = meshrender.triangulate(obj.faces_ori, obj.uv_faces_ori)
             texture = tex if tex is not None else np.full((2, 2, 3), 128, np.uint8)
+            if tex is not None and getattr(args, "tex_pad", None) is not None:
+                from . import texfinish
+                th, tw = int(tex.shape[0]), int(tex.shape[1])
+                texture = texfinish.finish(torch.from_numpy(tex).to(device), texfinish.coverage_from_obj(obj, th, tw, device=device),
+                                           pad=args.tex_pad, erode=getattr(args, "tex_erode", 1))[th]
             renderer = meshrender.MeshRenderer(faces, uv_faces, obj.uvs, texture, device=device)
             verts = torch.from_numpy(training_vertices(obj.vertices, trans_g)).to(device)
             masks = pixel_masks(dataset)
@@ -307,6 +316,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--save_renders", action="store_true", help="Also write %%06d/mesh_<cam>.png.")
     p.add_argument("--undistort", action="store_true",
                    help="Undistort the photographs by the lens calibration of cameras.xml, as topo4d_amd.train --undistort does.")
+    p.add_argument("--tex_pad", type=int, default=None, metavar="R",
+                   help="Pad the UV islands of every face.png by R texels (0..64) in memory before sampling it (texfinish.finish).")
+    p.add_argument("--tex_erode", type=int, default=1, metavar="E",
+                   help="With --tex_pad: rounds of erosion (0..4) of the face.obj coverage before padding (default 1).")
     p.add_argument("--scans", default=None, metavar="DIR",
                    help="Also score each frame's face.obj against its 3D scan DIR/%%06d.ply (else DIR/%%06d.obj).")
     p.add_argument("--scan_max_dist", type=float, default=None,
@@ -331,8 +344,17 @@ def evaluate(args, device=None) -> dict:
         raise SystemExit(f"--scans: no directory {scans}")
     if not sets and scans is None:
         raise SystemExit("--set none scores nothing without --scans")
+    tex_pad = getattr(args, "tex_pad", None)
+    if tex_pad is not None:
+        from . import texfinish
+        try:
+            texfinish.check_options(tex_pad, getattr(args, "tex_erode", 1), (), 1)
+        except ValueError as e:
+            raise SystemExit(f"--tex_pad / --tex_erode: {e}") from None
     with torch.cuda.device(dev):
         out = {"exp": args.exp, "seq": args.seq, "blacklist": sorted(C.BLACKLIST), "mask_labels": MASK_LABELS}
+        if tex_pad is not None:
+            out["tex_pad"], out["tex_erode"] = int(tex_pad), int(getattr(args, "tex_erode", 1))
         for which in sets:
             out[which] = score_set(args, which, dev)
         if scans is not None:

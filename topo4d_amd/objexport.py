@@ -293,8 +293,11 @@ class MeshExporter:
         dense = dense_rgb_colors.detach().clamp(0.0, 1.0)
         return torch.cat([dense[:self.n_vert][self._seam], dense[self.n_vert:]], dim=0)
 
-    def save_mesh(self, out_dir, params: dict, frame: int, res: int = 1024, gen_texture: bool = True, encoder: str = "gpu") -> None:
-        """helpers.save_mesh for this topology: out_dir/face.obj and, with gen_texture, out_dir/face.png."""
+    def save_mesh(self, out_dir, params: dict, frame: int, res: int = 1024, gen_texture: bool = True, encoder: str = "gpu",
+                  pad: int = 0, erode: int = 0, sizes=()) -> None:
+        """helpers.save_mesh for this topology: out_dir/face.obj and, with gen_texture, out_dir/face.png.  pad / erode / sizes:
+        texture.write_texture's finishing (a gutter round the UV islands, face_<size>.png for smaller levels); the defaults
+        write the reference's file."""
         os.makedirs(out_dir, exist_ok=True)
         data = self.obj_bytes(params, frame)
         with open(os.path.join(out_dir, "face.obj"), "wb") as f:
@@ -302,15 +305,17 @@ class MeshExporter:
         if gen_texture:
             from .texture import write_texture
             write_texture(os.path.join(out_dir, "face.png"), self.variables["dense_uvs"], self.seam_colors(params["dense_rgb_colors"]),
-                          self.variables["dense_uv_faces"], res=res, device=self.dev, encoder=encoder)
+                          self.variables["dense_uv_faces"], res=res, device=self.dev, encoder=encoder, pad=pad, erode=erode,
+                          sizes=sizes)
 
 
 _TOPOLOGY_KEYS = ("faces", "faces_ori", "uvs_ori", "uv_faces_ori", "trans_g")
 
 
-def save_mesh(out_dir, params: dict, variables: dict, frame: int, res: int = 1024, gen_texture: bool = True) -> None:
+def save_mesh(out_dir, params: dict, variables: dict, frame: int, res: int = 1024, gen_texture: bool = True, pad: int = 0,
+              erode: int = 0, sizes=()) -> None:
     """The drop-in for helpers.save_mesh (train.py:755): a MeshExporter per topology (the same variables objects and vertex
-    count), face.png through texture.write_texture(..., encoder="gpu")."""
+    count), face.png through texture.write_texture(..., encoder="gpu"); pad / erode / sizes as MeshExporter.save_mesh."""
     n_vert = int(params["means3D"].shape[0])
     objs = tuple(variables[k] for k in _TOPOLOGY_KEYS)
     for key, exporter in _EXPORTERS:
@@ -319,4 +324,4 @@ def save_mesh(out_dir, params: dict, variables: dict, frame: int, res: int = 102
     else:
         exporter = MeshExporter(variables, n_vertices=n_vert, device=params["means3D"].device)
         _EXPORTERS[:] = [((n_vert, objs), exporter)] + _EXPORTERS[:3]
-    exporter.save_mesh(out_dir, params, frame, res=res, gen_texture=gen_texture)
+    exporter.save_mesh(out_dir, params, frame, res=res, gen_texture=gen_texture, pad=pad, erode=erode, sizes=sizes)

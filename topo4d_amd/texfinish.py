@@ -1,0 +1,266 @@
+"""
+Finishing a baked UV texture on the GPU, over csrc/t4d_texfinish.hip (include/topo4d_raster.h states the exact rules):
+
+    coverage_from_depth(depth)                 uint8 [h,w]: depth > -999999, the texels a bake wrote
+    quantize(image_f32)                        float32 [h,w,c] -> uint8, the PNG encoder's rule: numpy's (x*255).astype(np.uint8)
+    erode(coverage, rounds)                    rounds (0..4) of 4-neighbour erosion; image edges do not erode
+    pad(image, coverage, radius)               -> (image, coverage): every uncovered texel within `radius` (0..64, a disc) of a
+                                               covered one takes the nearest covered texel, ties to the smallest (y', x')
+    halve(image, coverage)                     -> (image, coverage): 2x2 means over the covered texels only, round half up
+    finish(image_u8, coverage, pad, erode, sizes)  -> {res: image}: level 0 and the smaller levels, each with its own gutter
+    coverage_from_obj(face_obj, h, w)          the coverage of a face.obj's UV faces, for a tree whose bake is gone
+
+Why: face.png is black outside the UV islands and the mesh vertices on a UV seam sit on an island's border, so every bilinear
+tap there (meshrender's default, and every viewer's) and every mip level a viewer builds mixes black in.  A gutter of the
+island's own border colour removes the seams; levels averaged over covered texels alone keep them out of smaller textures.
+Inherited as it is: the reference bake writes the texels of the image's outermost two-texel ring that fall into a triangle's
+bounding box by extrapolation, inside the triangle or not (mesh_core.cpp:211); they have a depth and count as covered.
+
+Everything is integer arithmetic on device images; nothing here synchronises or copies to the host.  There is no CPU path.
+
+`python -m topo4d_amd.texfinish -e EXP -s SEQ -od DIR [--frames 1-10] --pad R [--erode 1] [--sizes 2048,1024] [--in_place]`
+finishes an output tree that already exists (the reference's too): beside every %06d/face.png it writes face_pad.png and
+face_pad_<res>.png for the sizes, from the coverage of the frame's face.obj (accurate to about a texel at the island borders,
+hence the default --erode 1); --in_place writes face.png and face_<res>.png instead.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+from typing import Dict, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import ptr
+
+MAX_PAD, MAX_ERODE = 64, 4
+
+
+def _image(image, what: str, need_device: bool = True) -> Tuple[torch.Tensor, int, int, int]:
+    if not isinstance(image, torch.Tensor) or image.dtype != torch.uint8 or image.dim() not in (2, 3):
+        raise ValueError(f"{what} must be a uint8 [h,w] or [h,w,c] tensor")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    c = 1 if image.dim() == 2 else int(image.shape[2])
+    if h < 1 or w < 1 or c not in (1, 3, 4):
+        raise ValueError(f"{what} must be [h,w] or [h,w,c] with h, w >= 1 and c in (1, 3, 4); got {tuple(image.shape)}")
+    if need_device and not image.is_cuda:
+        raise RuntimeError(f"topo4d_amd has no CPU path: {what} must live on a HIP device")
+    return image.contiguous(), h, w, c
+
+
+def _coverage(coverage, h: int = None, w: int = None, device=None) -> torch.Tensor:
+    if not isinstance(coverage, torch.Tensor) or coverage.dtype not in (torch.uint8, torch.bool) or coverage.dim() != 2:
+        raise ValueError("coverage must be a uint8 or bool [h,w] tensor")
+    if h is not None and tuple(coverage.shape) != (h, w):
+        raise ValueError(f"coverage {tuple(coverage.shape)} does not match the image's [{h},{w}]")
+    if not coverage.is_cuda or (device is not None and coverage.device != device):
+        raise RuntimeError("topo4d_amd has no CPU path: coverage must live on the image's HIP device")
+    if coverage.dtype == torch.bool:
+        coverage = coverage.to(torch.uint8)
+    return coverage.contiguous()
+
+
+def coverage_from_depth(depth: torch.Tensor) -> torch.Tensor:
+    """uint8 [h,w], 1 where the bake whose depth buffer this is (render_colors(..., return_depth=True)) wrote a texel."""
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 2:
+        raise ValueError("coverage_from_depth expects the float32 [h,w] depth buffer of a bake")
+    if not depth.is_cuda:
+        raise RuntimeError("topo4d_amd has no CPU path: the depth buffer must live on a HIP device")
+    d = depth.contiguous()
+    h, w = int(d.shape[0]), int(d.shape[1])
+    out = torch.empty(h, w, dtype=torch.uint8, device=d.device)
+    _lib.call("t4d_texture_coverage", ptr(d), h, w, ptr(out), _lib.stream(d.device))
+    return out
+
+
+def quantize(image_f32: torch.Tensor) -> torch.Tensor:
+    """float32 [h,w] / [h,w,c] -> uint8 of the same shape, exactly as png.encode_png quantises a float32 image."""
+    if not isinstance(image_f32, torch.Tensor) or image_f32.dtype != torch.float32 or image_f32.dim() not in (2, 3):
+        raise ValueError("quantize expects a float32 [h,w] or [h,w,c] tensor")
+    if not image_f32.is_cuda:
+        raise RuntimeError("topo4d_amd has no CPU path: the image must live on a HIP device")
+    img = image_f32.contiguous()
+    h, w = int(img.shape[0]), int(img.shape[1])
+    c = 1 if img.dim() == 2 else int(img.shape[2])
+    if h < 1 or w < 1 or c not in (1, 3, 4):
+        raise ValueError(f"quantize: need h, w >= 1 and c in (1, 3, 4); got {tuple(img.shape)}")
+    out = torch.empty(img.shape, dtype=torch.uint8, device=img.device)
+    _lib.call("t4d_texture_quantize", ptr(img), h, w, c, ptr(out), _lib.stream(img.device))
+    return out
+
+
+def erode(coverage: torch.Tensor, rounds: int) -> torch.Tensor:
+    """`rounds` rounds of: a texel stays covered only if it and its 4-neighbours inside the image are covered."""
+    rounds = int(rounds)
+    if not 0 <= rounds <= MAX_ERODE:
+        raise ValueError(f"erode: rounds must be in [0, {MAX_ERODE}], got {rounds}")
+    cov = _coverage(coverage)
+    h, w = int(cov.shape[0]), int(cov.shape[1])
+    out = torch.empty_like(cov)
+    _lib.call("t4d_texture_erode", ptr(cov), h, w, rounds, ptr(out), _lib.stream(cov.device))
+    return out
+
+
+def pad(image: torch.Tensor, coverage: torch.Tensor, radius: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(image, coverage) with every uncovered texel within `radius` of a covered one filled from the nearest (see the module)."""
+    radius = int(radius)
+    if not 0 <= radius <= MAX_PAD:
+        raise ValueError(f"pad: radius must be in [0, {MAX_PAD}], got {radius}")
+    img, h, w, c = _image(image, "image")
+    cov = _coverage(coverage, h, w, img.device)
+    nbytes = int(_lib.load().t4d_texture_pad_scratch_bytes(h, w))
+    if nbytes == 0:
+        raise _lib.error("t4d_texture_pad_scratch_bytes", exc=ValueError)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+    out, out_cov = torch.empty_like(img), torch.empty_like(cov)
+    _lib.call("t4d_texture_pad", ptr(img), ptr(cov), h, w, c, radius, ptr(out), ptr(out_cov), ptr(scratch), nbytes,
+              _lib.stream(img.device))
+    return out, out_cov
+
+
+def halve(image: torch.Tensor, coverage: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(image [h/2,w/2(,c)], coverage [h/2,w/2]): per 2x2 block the mean of its covered texels, rounded half up; 0 without any."""
+    img, h, w, c = _image(image, "image")
+    cov = _coverage(coverage, h, w, img.device)
+    if h % 2 or w % 2:
+        raise ValueError(f"halve: h and w must be even, got {h} x {w}")
+    out = torch.empty((h // 2, w // 2) + tuple(img.shape[2:]), dtype=torch.uint8, device=img.device)
+    out_cov = torch.empty(h // 2, w // 2, dtype=torch.uint8, device=img.device)
+    _lib.call("t4d_texture_halve", ptr(img), ptr(cov), h, w, c, ptr(out), ptr(out_cov), _lib.stream(img.device))
+    return out, out_cov
+
+
+_pad, _erode = pad, erode                                     # finish's keyword arguments carry the same names
+
+
+def _levels(res: int, w: int, sizes: Sequence[int]) -> Dict[int, int]:
+    """{size: k} with size = res / 2^k for every entry of `sizes`; ValueError for anything else."""
+    out = {}
+    for s in sizes:
+        s = int(s)
+        k = 0
+        while s > 0 and (s << k) < res:
+            k += 1
+        if s < 1 or (s << k) != res or res % (1 << k) or w % (1 << k):
+            raise ValueError(f"finish: size {s} is not {res} / 2^k (with {res} x {w} divisible by 2^k)")
+        out[s] = k
+    return out
+
+
+def check_options(pad: int, erode: int, sizes: Sequence[int], res: int) -> None:
+    """ValueError for a radius, a round count or a size that finish would refuse (callable without a device)."""
+    if not 0 <= int(pad) <= MAX_PAD:
+        raise ValueError(f"pad must be in [0, {MAX_PAD}], got {pad}")
+    if not 0 <= int(erode) <= MAX_ERODE:
+        raise ValueError(f"erode must be in [0, {MAX_ERODE}], got {erode}")
+    _levels(int(res), int(res), sizes)
+
+
+def finish(image_u8: torch.Tensor, coverage: torch.Tensor, pad: int = 0, erode: int = 0, sizes: Sequence[int] = ()) -> Dict[int, torch.Tensor]:
+    """{res: image} for res = the image's height and every entry of `sizes` (each res / 2^k).  The coverage is eroded `erode`
+    rounds once; level 0 is the image padded by `pad` under that coverage; every further level halves the UNPADDED image and the
+    eroded coverage repeatedly and is then padded by the same `pad`, in its own texels."""
+    _, h, w, _ = _image(image_u8, "image", need_device=False)  # argument errors first, with or without a device
+    levels = _levels(h, w, sizes)
+    pad_r, rounds = int(pad), int(erode)
+    if not 0 <= pad_r <= MAX_PAD or not 0 <= rounds <= MAX_ERODE:
+        raise ValueError(f"finish: pad must be in [0, {MAX_PAD}] and erode in [0, {MAX_ERODE}], got {pad_r}, {rounds}")
+    img = _image(image_u8, "image")[0]
+    cov = _coverage(coverage, h, w, img.device)
+    cov0 = _erode(cov, rounds)
+    out = {}
+    cur, cur_cov = img, cov0
+    for k in range(max(levels.values(), default=0) + 1):
+        if k:
+            cur, cur_cov = halve(cur, cur_cov)
+        size = h >> k
+        if k == 0 or size in levels:
+            out[size] = _pad(cur, cur_cov, pad_r)[0] if pad_r else cur
+    return out
+
+
+def coverage_from_obj(face_obj, h: int, w: int, device="cuda") -> torch.Tensor:
+    """The coverage of an [h,w] texture baked for `face_obj` (meshrender.read_face_obj): its triangulated UV faces rasterised by
+    the bake itself.  A bake of the dense mesh covers the same islands to about a texel at their borders."""
+    from . import meshrender, texture
+    _, uv_tris = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
+    verts = texture.process_uv(face_obj.uvs, h, w)
+    zeros = torch.zeros(len(face_obj.uvs), 3, dtype=torch.float32, device=device)
+    _, depth = texture.render_colors(verts, uv_tris, zeros, h, w, device=device, return_depth=True)
+    return coverage_from_depth(depth)
+
+
+def level_path(path, size: int) -> str:
+    """face.png -> face_<size>.png: the file of a smaller level beside `path`."""
+    root, ext = os.path.splitext(os.fspath(path))
+    return f"{root}_{int(size)}{ext}"
+
+
+def write_levels(path, levels: Dict[int, torch.Tensor]) -> list:
+    """finish's levels as PNG files through png.write_png: the largest at `path`, the others at level_path(path, size)."""
+    from .png import write_png
+    top = max(levels)
+    written = []
+    for size in sorted(levels, reverse=True):
+        p = os.fspath(path) if size == top else level_path(path, size)
+        write_png(p, levels[size])
+        written.append(p)
+    return written
+
+
+# ---- command line ----------------------------------------------------------------------------------------------------------
+def build_parser() -> argparse.ArgumentParser:
+    from .evaluate import _frames
+    from .train import _size_list, build_parser as train_parser
+    p = argparse.ArgumentParser(prog="python -m topo4d_amd.texfinish",
+                                description="Pad the UV islands of every frame's face.png and write smaller levels.")
+    for a in train_parser()._actions:                         # -e/-s/-od exactly as topo4d_amd.train has them
+        if a.dest in ("exp", "seq", "output_dir"):
+            p.add_argument(*a.option_strings, type=a.type, default=a.default, help=a.help)
+    p.add_argument("--frames", type=_frames, default=None, help="Frames to finish: '1-10', '1,5,9' (default: every frame directory).")
+    p.add_argument("--pad", type=int, required=True, metavar="R", help=f"Gutter radius in texels, 0..{MAX_PAD}.")
+    p.add_argument("--erode", type=int, default=1, metavar="E",
+                   help=f"Rounds of erosion of the face.obj coverage before padding, 0..{MAX_ERODE} (default 1).")
+    p.add_argument("--sizes", type=_size_list, default=[], help="Smaller levels to write too, comma-separated: res / 2^k each.")
+    p.add_argument("--in_place", action="store_true", help="Overwrite face.png (and write face_<res>.png) instead of face_pad*.png.")
+    return p
+
+
+def finish_tree(args, device=None) -> list:
+    """The files written for the run <od>/<exp>/<seq>; frames without face.obj or face.png are left alone."""
+    from PIL import Image
+    from . import meshrender
+    dev = torch.device(device if device is not None else "cuda")
+    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
+    if not os.path.isdir(run_dir):
+        raise SystemExit(f"no run at {run_dir}")
+    frames = args.frames or sorted(int(d) for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
+    written = []
+    with torch.cuda.device(dev):
+        for t in frames:
+            frame_dir = os.path.join(run_dir, "%06d" % t)
+            obj_path, png_path = os.path.join(frame_dir, "face.obj"), os.path.join(frame_dir, "face.png")
+            if not (os.path.exists(obj_path) and os.path.exists(png_path)):
+                continue
+            tex = np.ascontiguousarray(np.array(Image.open(png_path).convert("RGB")))
+            try:
+                check_options(args.pad, args.erode, args.sizes, tex.shape[0])
+            except ValueError as e:
+                raise SystemExit(f"{png_path}: {e}") from None
+            image = torch.from_numpy(tex).to(dev)
+            cov = coverage_from_obj(meshrender.read_face_obj(obj_path), tex.shape[0], tex.shape[1], device=dev)
+            levels = finish(image, cov, pad=args.pad, erode=args.erode, sizes=args.sizes)
+            written += write_levels(png_path if args.in_place else os.path.join(frame_dir, "face_pad.png"), levels)
+    return written
+
+
+def main(argv=None) -> None:
+    args = build_parser().parse_args(argv)
+    for p in finish_tree(args):
+        print(p)
+
+
+if __name__ == "__main__":
+    main()

@@ -111,11 +111,24 @@ def bake_texture_sharded(uvs, colors, faces, res: int = 1024, device="cuda") -> 
     return (full.cpu().numpy() * 255).astype(np.uint8)
 
 
-def write_texture(path, uvs, colors, faces, res: int = 1024, device="cuda", encoder: str = "pil") -> None:
+def write_texture(path, uvs, colors, faces, res: int = 1024, device="cuda", encoder: str = "pil", pad: int = 0, erode: int = 0,
+                  sizes=()) -> None:
     """helpers.py:953-960 (`io.imsave` replaced by PIL, which this image has).  encoder="gpu" encodes the device image with
-    png.encode_png instead: no image copy to the host, no numpy pass, no zlib; the file decodes to the same pixels."""
+    png.encode_png instead: no image copy to the host, no numpy pass, no zlib; the file decodes to the same pixels.
+
+    With `pad`, `erode` or `sizes` set the bake is finished on the device first (texfinish.finish: a gutter of `pad` texels round
+    the UV islands under the bake's own coverage eroded `erode` rounds, and a level of res / 2^k texels for every entry of
+    `sizes`): `path` holds level 0 and <stem>_<size>.png the others, all through png.write_png.  Without them the file is the
+    reference's, byte for byte."""
     if encoder not in ("pil", "gpu"):
         raise ValueError(f"write_texture: encoder must be 'pil' or 'gpu', got {encoder!r}")
+    if pad or erode or len(sizes):
+        from . import texfinish
+        texfinish.check_options(pad, erode, sizes, res)
+        image, depth = render_colors(process_uv(uvs, res, res), faces, colors, res, res, c=3, device=device, return_depth=True)
+        levels = texfinish.finish(texfinish.quantize(image), texfinish.coverage_from_depth(depth), pad=pad, erode=erode, sizes=sizes)
+        texfinish.write_levels(path, levels)
+        return
     if encoder == "gpu":
         from .png import write_png
         write_png(path, render_colors(process_uv(uvs, res, res), faces, colors, res, res, c=3, device=device))

@@ -16,10 +16,11 @@ writes the same output tree as the reference's `python train.py ...`: <output_di
     outputs            params2cpu / save_params / write_loss_json, objexport.save_mesh        train.py:744-755
 
 The one deliberate difference: --log_views takes a comma-separated list of camera names (the reference's `type=list` splits
-its argument into characters).  Two flags the reference does not have: --undistort undistorts every photograph and mask by the
+its argument into characters).  Flags the reference does not have: --undistort undistorts every photograph and mask by the
 lens calibration of cameras.xml while it is loaded (cameras.get_lenses, ingest.undistort_views; the reference needs photographs
 exported undistorted), and --low_from_full makes the geometry inputs from the full-size photographs as down_ratio x down_ratio
-means, so that -id holds cameras.xml, the mesh and the masks only.  Without them nothing changes.
+means, so that -id holds cameras.xml, the mesh and the masks only; with --gen_tex, --tex_pad R fills a gutter of R texels round
+the UV islands of face.png and --tex_sizes 4096,2048 also writes face_<size>.png (texfinish.finish).  Without them nothing changes.
 
 The region "freezes" of train.py:676-700 are FusedAdamPins pins, written by the step kernel itself; the pin set changes at
 most twice per frame (the dynamic-eye pins end at iteration int(0.7 n) of frame 0) and the learning rates once (the colour
@@ -299,6 +300,13 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
     if os.path.exists(out_dir):                                                             # train.py:591-593
         print(f"Experiment '{args.exp}' for sequence '{args.seq}' already exists. Exiting.")
         return None
+    tex_pad, tex_sizes = getattr(args, "tex_pad", 0), getattr(args, "tex_sizes", ())
+    if tex_pad or len(tex_sizes):                              # a bad radius or size stops the run here, not at its first export
+        from . import texfinish
+        try:
+            texfinish.check_options(tex_pad, 0, tex_sizes, args.tex_res)
+        except ValueError as e:
+            raise SystemExit(f"--tex_pad / --tex_sizes: {e}") from None
     dev = coarse._device(device)
     clock = _Clock(timings, dev)
     with torch.cuda.device(dev), clock("setup"):
@@ -413,7 +421,8 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
                         save_params(output_params, args)
                         write_loss_json(out_dir, losses, loss_weights)
                     objexport.save_mesh(os.path.join(out_dir, "%06d" % (t + 1)), params, variables, t + 1,
-                                        res=args.tex_res, gen_texture=args.gen_tex and sav_tex)         # train.py:755
+                                        res=args.tex_res, gen_texture=args.gen_tex and sav_tex,          # train.py:755
+                                        pad=tex_pad, sizes=tex_sizes)
                 state["frames"] = t + 1
                 if on_frame is not None:
                     on_frame(t, state)
@@ -426,6 +435,16 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
 # ---- command line ----------------------------------------------------------------------------------------------------------
 def _view_list(s: str) -> List[str]:
     return [v.strip() for v in s.split(",") if v.strip()]
+
+
+def _size_list(s: str) -> List[int]:
+    try:
+        out = [int(v) for v in s.split(",") if v.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{s!r} is not a comma-separated list of sizes") from None
+    if any(v < 1 for v in out):
+        raise argparse.ArgumentTypeError(f"{s!r}: sizes must be positive")
+    return out
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -456,13 +475,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('-lv', '--log_views', type=_view_list, default=["K98707293"],
                    help="Views of the saved renderings, comma-separated.")
     p.add_argument('-cf', '--ckp_freq', type=int, default=5, help="Frequence of saving gaussian attributes.")
-    # the two flags the reference does not have stay out of the namespace unless given (read with getattr)
+    # the flags the reference does not have stay out of the namespace unless given (read with getattr)
     p.add_argument('--undistort', action='store_true', default=argparse.SUPPRESS,
                    help="Undistort every photograph (and its mask) by the lens calibration of cameras.xml while it is loaded; "
                         "without it the photographs must have been exported undistorted.")
     p.add_argument('--low_from_full', action='store_true', default=argparse.SUPPRESS,
                    help="Make the geometry inputs from $dense_input_dir's photographs (down_ratio x down_ratio means) instead "
                         "of reading $input_dir's; $input_dir then holds cameras.xml, the mesh and the masks only.")
+    p.add_argument('--tex_pad', type=int, default=argparse.SUPPRESS, metavar='R',
+                   help="With --gen_tex: fill a gutter of R texels (0..64) round the UV islands of face.png from the nearest "
+                        "baked texel, so that bilinear taps on the seams no longer mix in the black background.")
+    p.add_argument('--tex_sizes', type=_size_list, default=argparse.SUPPRESS,
+                   help="With --gen_tex: texture sizes to write, comma-separated, each tex_res / 2^k: face.png holds tex_res, "
+                        "face_<size>.png the others, averaged over baked texels only.")
     return p
 
 
