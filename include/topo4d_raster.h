@@ -640,6 +640,28 @@ size_t t4d_image_metrics_scratch_bytes(int32_t n_views, int32_t h, int32_t w);
 int t4d_image_metrics(int32_t n_views, int32_t h, int32_t w, const float *render, const float *target, const float *mask,
                       const int32_t *coverage, double *out, void *scratch, size_t scratch_bytes, void *hip_stream);
 
+/* ---- Projection: the capture photographs gathered into a UV texture (csrc/t4d_projtex.hip; topo4d_amd/projtex.py) ----
+ * t4d_project_texture: pos / nrm [tex_h,tex_w,3] float32 (each texel's point in the training world frame and its normal, any
+ * length), coverage [tex_h,tex_w] uint8, views [n_views, T4D_VIEW_FLOATS] packed view records of one size h x w (n_views <= 255),
+ * photos [n_views,3,h,w] float32, depth [n_views,1,h,w] float32 as t4d_mesh_render writes it (0: no triangle).  Outputs: color
+ * [tex_h,tex_w,3] float32, weight [tex_h,tex_w] float32, count [tex_h,tex_w] uint8 (views that contributed).
+ * Per covered texel with a non-zero normal, views in ascending order (float64 without FP contraction in the order written down in
+ * csrc/t4d_projtex.hip; tests/projtex_ref.py reproduces every output bit): t4d_mesh_render's projection gives the pixel (px, py)
+ * and the view depth z; the view is rejected when z <= 0.01, when one of the four bilinear taps at floor(px), floor(py) lies
+ * outside the image, when a tap of depth is 0 (background) or z > depth (1 + depth_tol) (a nearer surface), or when cos < cos_min,
+ * cos the angle between the unit normal and the unit vector to the camera centre -R^T t of the view matrix (never the record's
+ * campos).  Its weight is cos^power (power 0..8, by repeated multiplication) times min(1, m / fade_px), m the distance of (px, py)
+ * to the nearest of the lines x = 0, x = w - 1, y = 0, y = h - 1 (fade_px = 0: no fade); a weight that is not > 0 rejects the view
+ * too.  Its sample is the bilinear mix of the photograph's taps.  T4D_PROJTEX_WEIGHTED: color = sum(w s) / sum(w), weight =
+ * sum(w).  T4D_PROJTEX_BEST: the sample and the weight of the view of largest w, the lowest such view on ties.  Every other texel
+ * gets zeros.  Does not synchronise the stream. */
+#define T4D_PROJTEX_WEIGHTED 0
+#define T4D_PROJTEX_BEST 1
+int t4d_project_texture(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w, const float *views,
+                        int32_t n_views, int32_t h, int32_t w, const float *photos, const float *depth, int32_t power,
+                        double cos_min, double fade_px, double depth_tol, int32_t mode, float *color, float *weight, uint8_t *count,
+                        void *hip_stream);
+
 /* Exact closest point on a triangle soup, or on a bare point cloud, for many query points (csrc/t4d_closest.hip): what
  * topo4d_amd/scanscore.py scores a frame's face.obj against its multi-view-stereo scan with.  It stands in for
  * trimesh.proximity.closest_point / open3d's RaycastingScene.compute_closest_points on the host; the reference project has no

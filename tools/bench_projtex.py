@@ -1,0 +1,119 @@
+#!/usr/bin/env python
+"""Projection of the capture photographs into the UV texture (topo4d_amd/projtex.py, csrc/t4d_projtex.hip).  Prints one JSON line.
+    python tools/bench_projtex.py [--res 8192] [--n 513] [--views 24] [--height 3008] [--width 4096]
+The scene: scaffold.scene.uv_mesh(n) as the UV layout, its vertices lifted onto the front of the scaffold's head-sized ellipsoid,
+seen by scaffold.scene.camera_rig (24 views at 4096 x 3008) with random photographs.  kernel_ms: t4d_project_texture alone between
+HIP events on preallocated buffers (min of 6), for both modes.  frame_ms: what one frame costs from the mesh and the photographs
+on the device to the PNG file as bytes in host memory - the depth render, the two texel maps and the coverage, the projection,
+the quantisation and png.encode_png (min of 3).  parts_ms times three of its steps on their own, each between two device
+synchronisations, so they add up to a little more than the frame, where the steps queue behind one another; quantise_encode
+is timed on the weighted result, the one the frame encodes.  The texture loop this stands beside is timed by tools/bench_train.py."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from scaffold.scene import SEMI_AXES, camera_rig, uv_mesh
+from topo4d_amd import _lib, meshrender, png, projtex, texfinish, texture
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--res", type=int, default=8192)
+ap.add_argument("--n", type=int, default=513)
+ap.add_argument("--views", type=int, default=24)
+ap.add_argument("--height", type=int, default=3008)
+ap.add_argument("--width", type=int, default=4096)
+a = ap.parse_args()
+dev = torch.device("cuda", torch.cuda.current_device())
+lib = _lib.load()
+P = lambda t: C.c_void_p(t.data_ptr())
+
+
+def events_ms(launch, repeats=6):
+    stream = torch.cuda.current_stream()
+    best = 1e9
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        launch(C.c_void_p(stream.cuda_stream))
+        e1.record(stream)
+        e1.synchronize()
+        best = min(best, e0.elapsed_time(e1))
+    return round(best, 3)
+
+
+def wall_ms(fn, repeats=3):
+    fn()
+    runs = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        runs.append(time.perf_counter() - t0)
+    return round(min(runs) * 1e3, 2)
+
+
+res, V, H, W = a.res, a.views, a.height, a.width
+uv_px, tris, _ = uv_mesh(a.n, res, res, seed=0)
+u, v = uv_px[:, 0] / (res - 1), (res - 1 - uv_px[:, 1]) / (res - 1)
+lon, lat = (u - 0.5) * 0.9 * np.pi, (v - 0.5) * 0.9 * np.pi
+unit = np.stack([np.cos(lat) * np.sin(lon), np.sin(lat), np.cos(lat) * np.cos(lon)], 1)
+verts = torch.from_numpy((unit * np.array(SEMI_AXES)).astype(np.float32)).to(dev)
+normals = torch.from_numpy((unit / np.array(SEMI_AXES)).astype(np.float32)).to(dev)
+cams = camera_rig(H, W, V, device=dev)
+photos = torch.rand(V, 3, H, W, device=dev)
+uvs = np.stack([u, v], 1)
+renderer = meshrender.MeshRenderer(tris, tris, uvs, np.zeros((1, 1, 3), np.uint8), device=dev)
+
+
+def depth_maps():
+    return renderer.render(verts, cams)[1]
+
+
+def maps():
+    pos, d = texture.render_colors(uv_px, tris, verts, res, res, device=dev, return_depth=True)
+    nrm = texture.render_colors(uv_px, tris, normals, res, res, device=dev)
+    return pos, nrm, texfinish.coverage_from_depth(d)
+
+
+depth = depth_maps()
+pos, nrm, cov = maps()
+views = meshrender._views(cams, dev)[0]
+color = torch.empty(res, res, 3, dtype=torch.float32, device=dev)
+weight = torch.empty(res, res, dtype=torch.float32, device=dev)
+count = torch.empty(res, res, dtype=torch.uint8, device=dev)
+
+
+def kernel(mode):
+    def launch(s):
+        rc = lib.t4d_project_texture(P(pos), P(nrm), P(cov), res, res, P(views), V, H, W, P(photos), P(depth), 2, 0.1, 16.0, 0.002,
+                                     mode, P(color), P(weight), P(count), s)
+        assert rc == 0, _lib.last_error()
+    return launch
+
+
+def frame():
+    d = depth_maps()
+    p, n, c = maps()
+    col, _, _ = projtex.project(p, n, c, cams, photos, d)
+    return png.encode_png(texfinish.quantize(col))
+
+
+result = {"metric": "photographs projected into the UV texture", "res": res, "views": V, "image": [H, W], "triangles": int(len(tris))}
+result["kernel_ms"] = {"weighted": events_ms(kernel(0)), "best": events_ms(kernel(1))}
+result["covered_fraction"] = round(float((cov != 0).float().mean()), 4)
+result["seen_fraction_of_covered"] = round(float(((count != 0) & (cov != 0)).float().sum() / (cov != 0).float().sum()), 4)
+result["mean_views_per_seen_texel"] = round(float(count[count != 0].float().mean()), 2)
+result["projections_per_s"] = round(float((cov != 0).sum()) * V / (result["kernel_ms"]["weighted"] * 1e-3), 0)
+kernel(0)(C.c_void_p(torch.cuda.current_stream().cuda_stream))        # `color` holds the weighted result again
+result["parts_ms"] = {"depth_render": wall_ms(depth_maps), "texel_maps": wall_ms(maps),
+                      "quantise_encode": wall_ms(lambda: png.encode_png(texfinish.quantize(color)))}
+result["frame_ms"] = wall_ms(frame)
+result["png_bytes"] = len(frame())
+print(json.dumps(result))

@@ -1,7 +1,7 @@
 """
 Score a finished run: `python -m topo4d_amd.evaluate -e EXP -s SEQ [-id ... -did ... -od ...] [--frames 1-10] [--views A,B]
 [--set low|dense|both|none] [--save_renders] [--scans DIR [--scan_max_dist X] [--scan_unit S] [--scan_thresholds a,b,c]
-[--scan_transform FILE] [--save_scan_errors]] [--tex_pad R [--tex_erode E]]`.
+[--scan_transform FILE] [--save_scan_errors]] [--tex_pad R [--tex_erode E]] [--texture NAME]`.
 
 For every frame of <od>/<exp>/<seq>: read %06d/face.obj (save_mesh's vertices: the training frame mapped by the trans_g of
 cameras.get_cameras, whose inverse maps them back, in float64) and %06d/face.png (PIL, on the host; frame t+1's files are read on a thread
@@ -18,6 +18,9 @@ coordinates, the frame Metashape exports its scans in.  eval.json gains the key 
 With --tex_pad R every face.png is padded in memory before it is sampled (texfinish.finish: a gutter of R texels round the UV
 islands of face.obj, whose coverage is first eroded --tex_erode rounds, 1 by default), so that the bilinear taps on the UV seams
 no longer mix in the file's black background.  The files stay as they are; eval.json gains "tex_pad" and "tex_erode".
+
+With --texture NAME that file of every frame directory is sampled instead of face.png, e.g. face_proj.png (projtex); eval.json
+gains "texture_file".
 """
 from __future__ import annotations
 
@@ -54,9 +57,12 @@ def _frames(spec: str) -> List[int]:
     return out
 
 
-def _read_frame_files(frame_dir: str):
+TEXTURE_FILE = "face.png"
+
+
+def _read_frame_files(frame_dir: str, texture: str = TEXTURE_FILE):
     """(FaceObj or None, uint8 [H,W,3] texture or None) of one frame directory: the host half, run on the prefetch thread."""
-    obj_path, png_path = os.path.join(frame_dir, "face.obj"), os.path.join(frame_dir, "face.png")
+    obj_path, png_path = os.path.join(frame_dir, "face.obj"), os.path.join(frame_dir, texture)
     if not os.path.exists(obj_path):
         return None, None
     obj = meshrender.read_face_obj(obj_path)
@@ -168,7 +174,8 @@ def score_set(args, which: str, device) -> dict:
 
         def prefetch(t):
             if t not in pending:
-                pending[t] = (pool.submit(_read_frame_files, os.path.join(run_dir, "%06d" % t)), mask_dir_ok(t))
+                pending[t] = (pool.submit(_read_frame_files, os.path.join(run_dir, "%06d" % t), getattr(args, "texture", TEXTURE_FILE)),
+                              mask_dir_ok(t))
                 pf[pending[t][1]].prefetch(t)
 
         for i, t in enumerate(frames):
@@ -320,6 +327,8 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Pad the UV islands of every face.png by R texels (0..64) in memory before sampling it (texfinish.finish).")
     p.add_argument("--tex_erode", type=int, default=1, metavar="E",
                    help="With --tex_pad: rounds of erosion (0..4) of the face.obj coverage before padding (default 1).")
+    p.add_argument("--texture", default=TEXTURE_FILE, metavar="NAME",
+                   help="The file of every frame directory that is sampled (default face.png), e.g. face_proj.png.")
     p.add_argument("--scans", default=None, metavar="DIR",
                    help="Also score each frame's face.obj against its 3D scan DIR/%%06d.ply (else DIR/%%06d.obj).")
     p.add_argument("--scan_max_dist", type=float, default=None,
@@ -355,6 +364,8 @@ def evaluate(args, device=None) -> dict:
         out = {"exp": args.exp, "seq": args.seq, "blacklist": sorted(C.BLACKLIST), "mask_labels": MASK_LABELS}
         if tex_pad is not None:
             out["tex_pad"], out["tex_erode"] = int(tex_pad), int(getattr(args, "tex_erode", 1))
+        if getattr(args, "texture", TEXTURE_FILE) != TEXTURE_FILE:
+            out["texture_file"] = args.texture
         for which in sets:
             out[which] = score_set(args, which, dev)
         if scans is not None:

@@ -20,7 +20,10 @@ its argument into characters).  Flags the reference does not have: --undistort u
 lens calibration of cameras.xml while it is loaded (cameras.get_lenses, ingest.undistort_views; the reference needs photographs
 exported undistorted), and --low_from_full makes the geometry inputs from the full-size photographs as down_ratio x down_ratio
 means, so that -id holds cameras.xml, the mesh and the masks only; with --gen_tex, --tex_pad R fills a gutter of R texels round
-the UV islands of face.png and --tex_sizes 4096,2048 also writes face_<size>.png (texfinish.finish).  Without them nothing changes.
+the UV islands of face.png and --tex_sizes 4096,2048 also writes face_<size>.png (texfinish.finish); --tex_project writes
+face_proj.png beside every face.obj, the frame's full-size photographs projected into the UV layout (projtex, with or without
+--gen_tex; --mode, --power, --cos_min, --fade_px and --depth_tol as python -m topo4d_amd.projtex takes them).  Without them
+nothing changes.
 
 The region "freezes" of train.py:676-700 are FusedAdamPins pins, written by the step kernel itself; the pin set changes at
 most twice per frame (the dynamic-eye pins end at iteration int(0.7 n) of frame 0) and the learning rates once (the colour
@@ -307,6 +310,10 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
             texfinish.check_options(tex_pad, 0, tex_sizes, args.tex_res)
         except ValueError as e:
             raise SystemExit(f"--tex_pad / --tex_sizes: {e}") from None
+    tex_project = getattr(args, "tex_project", False)
+    if tex_project:
+        from . import meshrender, projtex
+        proj_opts = projtex._check_args(args, args.tex_res)
     dev = coarse._device(device)
     clock = _Clock(timings, dev)
     with torch.cuda.device(dev), clock("setup"):
@@ -347,7 +354,7 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
                         update_optimizer(NEW_LR, optimizer)                                               # :647-650
                 with clock("ingest"):
                     dataset = pf.get(t + 1)                                                               # train.py:653
-                    if args.gen_tex:
+                    if args.gen_tex or tex_project:
                         pf_dense.prefetch(t + 1)
                     pf.prefetch(t + 2)
                 if len(dataset) == 0:                                                                     # :654-655
@@ -384,7 +391,7 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
                     optimizer.clear_pin(name)
 
                 # ---- texture (train.py:714-743) ----
-                sav_tex = True
+                sav_tex, dense = True, None
                 if args.gen_tex:
                     with clock("transition"):
                         update_dense_states(params, variables, first)                                     # train.py:720
@@ -423,6 +430,16 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
                     objexport.save_mesh(os.path.join(out_dir, "%06d" % (t + 1)), params, variables, t + 1,
                                         res=args.tex_res, gen_texture=args.gen_tex and sav_tex,          # train.py:755
                                         pad=tex_pad, sizes=tex_sizes)
+                if tex_project:
+                    if dense is None:
+                        with clock("ingest"):
+                            dense = pf_dense.get(t + 1)
+                            pf_dense.prefetch(t + 2)
+                    if len(dense):
+                        with clock("export"):                    # from the face.obj just written: the file the command line reads
+                            frame_dir = os.path.join(out_dir, "%06d" % (t + 1))
+                            projtex.write_frame(frame_dir, meshrender.read_face_obj(os.path.join(frame_dir, "face.obj")), trans_g,
+                                                dense, args.tex_res, proj_opts, pad=tex_pad, sizes=tex_sizes, device=dev)
                 state["frames"] = t + 1
                 if on_frame is not None:
                     on_frame(t, state)
@@ -488,6 +505,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--tex_sizes', type=_size_list, default=argparse.SUPPRESS,
                    help="With --gen_tex: texture sizes to write, comma-separated, each tex_res / 2^k: face.png holds tex_res, "
                         "face_<size>.png the others, averaged over baked texels only.")
+    p.add_argument('--tex_project', action='store_true', default=argparse.SUPPRESS,
+                   help="Also write face_proj.png beside every face.obj: the frame's full-size photographs projected into the UV "
+                        "layout (topo4d_amd.projtex), with or without --gen_tex; --tex_pad and --tex_sizes apply to it too.")
+    from .projtex import add_options
+    add_options(p, suppress=True)
     return p
 
 
