@@ -661,6 +661,30 @@ int t4d_project_texture(const float *pos, const float *nrm, const uint8_t *cover
                         int32_t n_views, int32_t h, int32_t w, const float *photos, const float *depth, int32_t power,
                         double cos_min, double fade_px, double depth_tol, int32_t mode, float *color, float *weight, uint8_t *count,
                         void *hip_stream);
+/* Equalising the cameras (projtex.pair_stats / solve_gains): exposure and white balance differ from camera to camera, and a blend
+ * of unequal cameras shows a step wherever the set of contributing views changes.
+ * t4d_project_texture_gains: t4d_project_texture with gains [n_views,3] float64 (device; NULL: none): the sample of view v becomes
+ * s[c] = s[c] gains[v][c], one rounded float64 product, before it is blended or kept.  With NULL every output bit is
+ * t4d_project_texture's, which forwards here.
+ * t4d_projtex_pair_stats: what the gains are solved from.  pos, nrm, coverage, power, cos_min, fade_px, depth_tol as above; views
+ * [n_views, T4D_VIEW_FLOATS] with 1 <= n_views <= 32, of any mix of sizes: sizes [n_views,2] int32 (h, w) and the tables photos /
+ * depth of n_views device pointers ([3,h_v,w_v] and [h_v,w_v] float32) are device memory.  A view takes part at a covered texel
+ * with a non-zero normal when t4d_project_texture would accept it there, cos >= stat_cos_min and every channel of its sample
+ * (times gains[v][c] when gains is given) satisfies stat_lo <= s[c] <= stat_hi (a NaN fails; -1024 <= stat_lo <= stat_hi <= 1024):
+ * clipped or black samples follow no gain model.  Its integer sample is q[c] = llrint(s[c] 65536), half to even.  For every
+ * ordered pair (i, j) of views that both take part at a texel, i == j included: pair_count[i][j] += 1, pair_sum[i][j][c] += q_i[c].
+ * pair_count int64 [n_views,n_views] and pair_sum int64 [n_views,n_views,3] (device) are ADDED to: the caller zeroes them, and the
+ * statistics of several frames accumulate.  Integer sums: the result does not depend on the order of accumulation
+ * (tests/projtex_eq_ref.py reproduces every bit).  Neither call synchronises the stream. */
+int t4d_project_texture_gains(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                              const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos, const float *depth,
+                              const double *gains, int32_t power, double cos_min, double fade_px, double depth_tol, int32_t mode,
+                              float *color, float *weight, uint8_t *count, void *hip_stream);
+int t4d_projtex_pair_stats(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                           const float *views, int32_t n_views, const int32_t *sizes, const float *const *photos,
+                           const float *const *depth, int32_t power, double cos_min, double fade_px, double depth_tol,
+                           double stat_cos_min, double stat_lo, double stat_hi, const double *gains, int64_t *pair_count,
+                           int64_t *pair_sum, void *hip_stream);
 
 /* Exact closest point on a triangle soup, or on a bare point cloud, for many query points (csrc/t4d_closest.hip): what
  * topo4d_amd/scanscore.py scores a frame's face.obj against its multi-view-stereo scan with.  It stands in for

@@ -1,13 +1,17 @@
 #!/usr/bin/env python
 """Projection of the capture photographs into the UV texture (topo4d_amd/projtex.py, csrc/t4d_projtex.hip).  Prints one JSON line.
-    python tools/bench_projtex.py [--res 8192] [--n 513] [--views 24] [--height 3008] [--width 4096]
+    python tools/bench_projtex.py [--res 8192] [--n 513] [--views 24] [--height 3008] [--width 4096] [--equalize]
 The scene: scaffold.scene.uv_mesh(n) as the UV layout, its vertices lifted onto the front of the scaffold's head-sized ellipsoid,
 seen by scaffold.scene.camera_rig (24 views at 4096 x 3008) with random photographs.  kernel_ms: t4d_project_texture alone between
 HIP events on preallocated buffers (min of 6), for both modes.  frame_ms: what one frame costs from the mesh and the photographs
 on the device to the PNG file as bytes in host memory - the depth render, the two texel maps and the coverage, the projection,
 the quantisation and png.encode_png (min of 3).  parts_ms times three of its steps on their own, each between two device
 synchronisations, so they add up to a little more than the frame, where the steps queue behind one another; quantise_encode
-is timed on the weighted result, the one the frame encodes.  The texture loop this stands beside is timed by tools/bench_train.py."""
+is timed on the weighted result, the one the frame encodes.  The texture loop this stands beside is timed by tools/bench_train.py.
+--equalize times the camera equalisation instead of the frame, in the same run as kernel_ms: pair_stats_ms is
+t4d_projtex_pair_stats alone on zeroed outputs and project_gains_ms t4d_project_texture_gains (weighted) with the solved gains,
+both between HIP events (min of 6); solve_ms is projtex.solve_gains on the host, the copy of the two tables included (min of 3).
+The photographs are random, so the solved gains say nothing; pair_counts describes the overlap they were solved from."""
 import argparse
 import ctypes as C
 import json
@@ -28,6 +32,7 @@ ap.add_argument("--n", type=int, default=513)
 ap.add_argument("--views", type=int, default=24)
 ap.add_argument("--height", type=int, default=3008)
 ap.add_argument("--width", type=int, default=4096)
+ap.add_argument("--equalize", action="store_true")
 a = ap.parse_args()
 dev = torch.device("cuda", torch.cuda.current_device())
 lib = _lib.load()
@@ -111,6 +116,42 @@ result["covered_fraction"] = round(float((cov != 0).float().mean()), 4)
 result["seen_fraction_of_covered"] = round(float(((count != 0) & (cov != 0)).float().sum() / (cov != 0).float().sum()), 4)
 result["mean_views_per_seen_texel"] = round(float(count[count != 0].float().mean()), 2)
 result["projections_per_s"] = round(float((cov != 0).sum()) * V / (result["kernel_ms"]["weighted"] * 1e-3), 0)
+if a.equalize:
+    pair_count = torch.zeros(V, V, dtype=torch.int64, device=dev)
+    pair_sum = torch.zeros(V, V, 3, dtype=torch.int64, device=dev)
+    sizes = torch.tensor([[H, W]] * V, dtype=torch.int32, device=dev)
+    tables = torch.tensor([[photos[k].data_ptr() for k in range(V)], [depth[k].data_ptr() for k in range(V)]], dtype=torch.int64, device=dev)
+
+    def stats(s):
+        rc = lib.t4d_projtex_pair_stats(P(pos), P(nrm), P(cov), res, res, P(views), V, P(sizes), P(tables[0]), P(tables[1]), 2, 0.1, 16.0,
+                                        0.002, 0.5, 0.02, 0.98, None, P(pair_count), P(pair_sum), s)
+        assert rc == 0, _lib.last_error()
+
+    result["pair_stats_ms"] = events_ms(stats)
+    pair_count.zero_()
+    pair_sum.zero_()
+    stats(C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    runs = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        gains = projtex.solve_gains(pair_count, pair_sum)
+        runs.append(time.perf_counter() - t0)
+    result["solve_ms"] = round(min(runs) * 1e3, 3)
+    g = torch.from_numpy(gains).to(dev)
+
+    def with_gains(s):
+        rc = lib.t4d_project_texture_gains(P(pos), P(nrm), P(cov), res, res, P(views), V, H, W, P(photos), P(depth), P(g), 2, 0.1, 16.0,
+                                           0.002, 0, P(color), P(weight), P(count), s)
+        assert rc == 0, _lib.last_error()
+
+    result["project_gains_ms"] = events_ms(with_gains)
+    result["kernel_ms_again"] = events_ms(kernel(0))             # the plain kernel once more, after the others: the run's own spread
+    off = pair_count.cpu().numpy()[~np.eye(V, dtype=bool)]
+    result["pair_counts"] = {"pairs_with_overlap": int((off > 0).sum() // 2), "max": int(off.max()), "diagonal_mean": int(pair_count.diagonal().float().mean())}
+    result["pair_stats_over_kernel"] = round(result["pair_stats_ms"] / result["kernel_ms"]["weighted"], 2)
+    print(json.dumps(result))
+    sys.exit(0)
 kernel(0)(C.c_void_p(torch.cuda.current_stream().cuda_stream))        # `color` holds the weighted result again
 result["parts_ms"] = {"depth_render": wall_ms(depth_maps), "texel_maps": wall_ms(maps),
                       "quantise_encode": wall_ms(lambda: png.encode_png(texfinish.quantize(color)))}

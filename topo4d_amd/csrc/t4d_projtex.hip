@@ -22,6 +22,8 @@
 //   7. weighted: sw = sw + w, sc = sc + w s, at the end color = float32(sc / sw), weight = float32(sw);
 //      best: the view replaces the kept one when w > the kept w (ties stay with the lower view), color = float32(s), weight = float32(w)
 // count is the number of views that passed 1..5.  A texel nobody sees gets color 0, weight 0, count 0.
+// t4d_project_texture_gains multiplies the sample of step 6 by the view's gain, s = s gains[v][c] (one rounded product), before
+// step 7; k_pair_stats (below) gathers what these gains are solved from.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -40,12 +42,75 @@ constexpr double kNear = 0.01;               // the mesh renderer's near plane
 struct PTP {
     const float *pos, *nrm, *views, *photos, *depth;
     const uint8_t *coverage;
+    const double *gains;                     // [V,3] or NULL
     int th, tw, V, H, W, power, mode;
     double cos_min, fade_px, depth_lim;      // depth_lim = 1 + depth_tol
     float *color, *weight;
     uint8_t *count;
 };
 
+// Steps 1..6 of the rule above for one view of size H x W (photo [3,H,W], depth [H,W], vm its record), shared by k_projtex and
+// k_pair_stats: 0 when the view is rejected; 1 when it is accepted (w and cs are set) but, with `keep`, w is not > keep_above, so
+// that its sample is not wanted (mode "best": a view that cannot win costs no gather of the photograph); 2 with the sample s, times
+// gain[c] when gain is given (one rounded product).
+__device__ __forceinline__ int view_eval(const float *vm, double X, double Y, double Z, double nhx, double nhy, double nhz, int H, int W,
+                                         const float *photo, const float *depth, const double *gain, int power, double cos_min,
+                                         double fade_px, double depth_lim, bool keep, double keep_above, double &w_out, double &cs_out, double s[3])
+{
+#pragma clang fp contract(off)
+    const float *pm = vm + 16;
+    const double Wd = (double)W, Hd = (double)H, xmax = (double)(W - 1), ymax = (double)(H - 1);
+    const size_t plane = (size_t)H * (size_t)W;
+    // 1. projection
+    const double cx = (((double)pm[0] * X + (double)pm[4] * Y) + (double)pm[8] * Z) + (double)pm[12];
+    const double cy = (((double)pm[1] * X + (double)pm[5] * Y) + (double)pm[9] * Z) + (double)pm[13];
+    const double cw = (((double)pm[3] * X + (double)pm[7] * Y) + (double)pm[11] * Z) + (double)pm[15];
+    const double px = ((cx / cw + 1.0) * Wd - 1.0) * 0.5;
+    const double py = ((cy / cw + 1.0) * Hd - 1.0) * 0.5;
+    const double z = (((double)vm[2] * X + (double)vm[6] * Y) + (double)vm[10] * Z) + (double)vm[14];
+    if (!(z > kNear)) return 0;
+    // 2. the four taps inside the image (a NaN fails the comparisons)
+    const double fx0 = floor(px), fy0 = floor(py);
+    if (!(fx0 >= 0.0 && fx0 + 1.0 <= xmax && fy0 >= 0.0 && fy0 + 1.0 <= ymax)) return 0;
+    // 4. facing (before the gathers: it needs no memory)
+    const double t0 = (double)vm[12], t1 = (double)vm[13], t2 = (double)vm[14];
+    const double ex = -(((double)vm[0] * t0 + (double)vm[1] * t1) + (double)vm[2] * t2) - X;
+    const double ey = -(((double)vm[4] * t0 + (double)vm[5] * t1) + (double)vm[6] * t2) - Y;
+    const double ez = -(((double)vm[8] * t0 + (double)vm[9] * t1) + (double)vm[10] * t2) - Z;
+    const double el = sqrt((ex * ex + ey * ey) + ez * ez);
+    const double cs = (nhx * (ex / el) + nhy * (ey / el)) + nhz * (ez / el);
+    if (!(cs >= cos_min)) return 0;
+    // 3. visibility
+    const size_t tap = (size_t)(int)fy0 * (size_t)W + (size_t)(int)fx0;
+    const float *dp = depth + tap;
+    const double d00 = (double)dp[0], d01 = (double)dp[1], d10 = (double)dp[W], d11 = (double)dp[W + 1];
+    if (!(d00 > 0.0 && d01 > 0.0 && d10 > 0.0 && d11 > 0.0)) return 0;
+    if (!(z <= d00 * depth_lim && z <= d01 * depth_lim && z <= d10 * depth_lim && z <= d11 * depth_lim)) return 0;
+    // 5. weight
+    double w = 1.0;
+    for (int k = 0; k < power; ++k) w = w * cs;
+    if (fade_px > 0.0) {
+        const double m = fmin(fmin(px, xmax - px), fmin(py, ymax - py));
+        const double f = m / fade_px;
+        if (f < 1.0) w = w * f;
+    }
+    if (!(w > 0.0)) return 0;
+    w_out = w;
+    cs_out = cs;
+    if (keep && !(w > keep_above)) return 1;
+    // 6. sample
+    const double fx = px - fx0, fy = py - fy0, gx = 1.0 - fx, gy = 1.0 - fy;
+    const float *ph = photo + tap;
+    for (int c = 0; c < 3; ++c) {
+        const float *q = ph + (size_t)c * plane;
+        const double a = gx * (double)q[0] + fx * (double)q[1], b = gx * (double)q[W] + fx * (double)q[W + 1];
+        s[c] = gy * a + fy * b;
+        if (gain) s[c] = s[c] * gain[c];
+    }
+    return 2;
+}
+
+template <bool kGains>                       // (two instances, so that the kernel without gains is the one it was before they existed)
 __global__ __launch_bounds__(kTile * kTile) void k_projtex(const PTP P)
 {
 #pragma clang fp contract(off)
@@ -65,64 +130,25 @@ __global__ __launch_bounds__(kTile * kTile) void k_projtex(const PTP P)
     if (nl > 0.0) {
         const double X = (double)P.pos[3 * at], Y = (double)P.pos[3 * at + 1], Z = (double)P.pos[3 * at + 2];
         const double nhx = nx / nl, nhy = ny / nl, nhz = nz / nl;
-        const double Wd = (double)P.W, Hd = (double)P.H, xmax = (double)(P.W - 1), ymax = (double)(P.H - 1);
         const size_t plane = (size_t)P.H * (size_t)P.W;
+        const bool best = P.mode == T4D_PROJTEX_BEST;
         for (int v = 0; v < P.V; ++v) {
-            const float *vm = P.views + (size_t)v * T4D_VIEW_FLOATS, *pm = vm + 16;
-            // 1. projection
-            const double cx = (((double)pm[0] * X + (double)pm[4] * Y) + (double)pm[8] * Z) + (double)pm[12];
-            const double cy = (((double)pm[1] * X + (double)pm[5] * Y) + (double)pm[9] * Z) + (double)pm[13];
-            const double cw = (((double)pm[3] * X + (double)pm[7] * Y) + (double)pm[11] * Z) + (double)pm[15];
-            const double px = ((cx / cw + 1.0) * Wd - 1.0) * 0.5;
-            const double py = ((cy / cw + 1.0) * Hd - 1.0) * 0.5;
-            const double z = (((double)vm[2] * X + (double)vm[6] * Y) + (double)vm[10] * Z) + (double)vm[14];
-            if (!(z > kNear)) continue;
-            // 2. the four taps inside the image (a NaN fails the comparisons)
-            const double fx0 = floor(px), fy0 = floor(py);
-            if (!(fx0 >= 0.0 && fx0 + 1.0 <= xmax && fy0 >= 0.0 && fy0 + 1.0 <= ymax)) continue;
-            // 4. facing (before the gathers: it needs no memory)
-            const double t0 = (double)vm[12], t1 = (double)vm[13], t2 = (double)vm[14];
-            const double ex = -(((double)vm[0] * t0 + (double)vm[1] * t1) + (double)vm[2] * t2) - X;
-            const double ey = -(((double)vm[4] * t0 + (double)vm[5] * t1) + (double)vm[6] * t2) - Y;
-            const double ez = -(((double)vm[8] * t0 + (double)vm[9] * t1) + (double)vm[10] * t2) - Z;
-            const double el = sqrt((ex * ex + ey * ey) + ez * ez);
-            const double cs = (nhx * (ex / el) + nhy * (ey / el)) + nhz * (ez / el);
-            if (!(cs >= P.cos_min)) continue;
-            // 3. visibility
-            const size_t tap = (size_t)(int)fy0 * (size_t)P.W + (size_t)(int)fx0;
-            const float *dp = P.depth + (size_t)v * plane + tap;
-            const double d00 = (double)dp[0], d01 = (double)dp[1], d10 = (double)dp[P.W], d11 = (double)dp[P.W + 1];
-            if (!(d00 > 0.0 && d01 > 0.0 && d10 > 0.0 && d11 > 0.0)) continue;
-            if (!(z <= d00 * P.depth_lim && z <= d01 * P.depth_lim && z <= d10 * P.depth_lim && z <= d11 * P.depth_lim)) continue;
-            // 5. weight
-            double w = 1.0;
-            for (int k = 0; k < P.power; ++k) w = w * cs;
-            if (P.fade_px > 0.0) {
-                const double m = fmin(fmin(px, xmax - px), fmin(py, ymax - py));
-                const double f = m / P.fade_px;
-                if (f < 1.0) w = w * f;
-            }
-            if (!(w > 0.0)) continue;
+            double w, cs, s[3];
+            const int got = view_eval(P.views + (size_t)v * T4D_VIEW_FLOATS, X, Y, Z, nhx, nhy, nhz, P.H, P.W,
+                                      P.photos + (size_t)v * 3 * plane, P.depth + (size_t)v * plane, kGains ? P.gains + 3 * v : nullptr,
+                                      P.power, P.cos_min, P.fade_px, P.depth_lim, best, sw, w, cs, s);
+            if (!got) continue;
             ++cnt;
-            if (P.mode == T4D_PROJTEX_BEST && !(w > sw)) continue;
-            // 6. sample
-            const double fx = px - fx0, fy = py - fy0, gx = 1.0 - fx, gy = 1.0 - fy;
-            const float *ph = P.photos + (size_t)v * 3 * plane + tap;
-            double s[3];
-            for (int c = 0; c < 3; ++c) {
-                const float *q = ph + (size_t)c * plane;
-                const double a = gx * (double)q[0] + fx * (double)q[1], b = gx * (double)q[P.W] + fx * (double)q[P.W + 1];
-                s[c] = gy * a + fy * b;
-            }
+            if (got == 1) continue;                                         // best: the kept view stays (ties stay with the lower view)
             // 7. accumulate
-            if (P.mode == T4D_PROJTEX_BEST) {
+            if (best) {
                 sw = w; s0 = s[0]; s1 = s[1]; s2 = s[2];
             } else {
                 sw = sw + w;
                 s0 = s0 + w * s[0]; s1 = s1 + w * s[1]; s2 = s2 + w * s[2];
             }
         }
-        if (cnt && P.mode != T4D_PROJTEX_BEST) { s0 = s0 / sw; s1 = s1 / sw; s2 = s2 / sw; }
+        if (cnt && !best) { s0 = s0 / sw; s1 = s1 / sw; s2 = s2 / sw; }
     }
     P.color[3 * at] = (float)s0;
     P.color[3 * at + 1] = (float)s1;
@@ -131,12 +157,149 @@ __global__ __launch_bounds__(kTile * kTile) void k_projtex(const PTP P)
     P.count[at] = (uint8_t)cnt;
 }
 
+// ---- pair statistics: what projtex.solve_gains equalises the cameras from ----------------------------------------------------
+// A view takes part at a texel when it is accepted (steps 1..5), cos >= stat_cos_min and every channel of its sample s (step 6,
+// times its gain) lies in [stat_lo, stat_hi]; q[c] = llrint(s[c] 65536).  For every ordered pair (i, j) of views that both take part
+// at a texel, pair_count[i][j] += 1 and pair_sum[i][j][c] += q_i[c].  Everything summed is an integer, so no order of accumulation
+// changes a bit.
+//
+// One lane per texel, 16x16 tiles as k_projtex, so a wave holds 4 rows of 16 neighbouring texels; a workgroup walks the tiles
+// blockIdx.x, blockIdx.x + gridDim.x, ... and keeps a [V,V,4] int64 table (count, three sums) in LDS that it adds to global memory
+// once at its end, entry by entry with 64-bit vector atomics, the zero entries left out.
+// Per wave and tile, first the view loop: each lane keeps a 32-bit mask of its taking-part views; a ballot gives the view's lane set
+// and a butterfly the sum of its q over that set; lane v of the wave keeps both for view v (V <= 32 < 64).  Then the pairs: for view
+// i lane j sees set_i & set_j; where that equals set_i (neighbouring texels mostly share their view sets) the sum over the pair is
+// the sum over set_i, so lanes j = 0..V-1 add their entries (i, j) in one step with no further cross-lane work.  Only for a view i
+// that has a partner covering part of its set is q_i evaluated again (nothing per lane and view is stored: at 12 bytes per view
+// and lane that would take the LDS the occupancy needs for the gathers), followed by a masked butterfly per such partner.
+constexpr int kStatViews = 32;               // the lane's mask has 32 bits
+constexpr int kStatGrid = 4096;              // workgroups at most: 16 per CU, each flushing its table once
+constexpr double kStatRange = 1024.0;        // |stat_lo|, |stat_hi| at most: q < 2^26, so an int64 holds the sum over 2^37 texels
+constexpr double kStatScale = 65536.0;
+
+struct PSP {
+    const float *pos, *nrm, *views;
+    const uint8_t *coverage;
+    const int32_t *sizes;                    // [V,2] (h, w)
+    const float *const *photos, *const *depth;
+    const double *gains;                     // [V,3] or NULL
+    int th, tw, V, power, tiles_x, tiles;
+    double cos_min, fade_px, depth_lim, stat_cos_min, stat_lo, stat_hi;
+    unsigned long long *pair_count, *pair_sum;
+};
+
+__device__ __forceinline__ long long wave_sum(long long a)
+{
+    for (int m = 1; m < 64; m <<= 1) a += __shfl_xor(a, m, 64);
+    return a;
+}
+
+// whether view v takes part at the lane's texel, and its q
+__device__ __forceinline__ bool stat_eval(const PSP &P, int v, double X, double Y, double Z, double nhx, double nhy, double nhz, long long q[3])
+{
+#pragma clang fp contract(off)
+    const int H = P.sizes[2 * v], W = P.sizes[2 * v + 1];
+    if (H < 1 || W < 1 || H > kMaxDim || W > kMaxDim) return false;
+    double w, cs, s[3];
+    if (view_eval(P.views + (size_t)v * T4D_VIEW_FLOATS, X, Y, Z, nhx, nhy, nhz, H, W, P.photos[v], P.depth[v],
+                  P.gains ? P.gains + 3 * v : nullptr, P.power, P.cos_min, P.fade_px, P.depth_lim, false, 0.0, w, cs, s) != 2)
+        return false;
+    if (!(cs >= P.stat_cos_min)) return false;
+    for (int c = 0; c < 3; ++c)
+        if (!(s[c] >= P.stat_lo && s[c] <= P.stat_hi)) return false;
+    for (int c = 0; c < 3; ++c) q[c] = llrint(s[c] * kStatScale);
+    return true;
+}
+
+__global__ __launch_bounds__(kTile * kTile) void k_pair_stats(const PSP P)
+{
+    __shared__ unsigned long long tab[kStatViews * kStatViews * 4];
+    const int V = P.V, lane = (int)(threadIdx.x & 63);
+    for (int e = (int)threadIdx.x; e < V * V * 4; e += kTile * kTile) tab[e] = 0;
+    __syncthreads();
+    for (int t = (int)blockIdx.x; t < P.tiles; t += (int)gridDim.x) {
+        const int tx = (t % P.tiles_x) * kTile + (int)(threadIdx.x % kTile), ty = (t / P.tiles_x) * kTile + (int)(threadIdx.x / kTile);
+        const size_t at = (size_t)ty * (size_t)P.tw + (size_t)tx;
+        bool live = tx < P.tw && ty < P.th;
+        if (live) live = P.coverage[at] != 0;
+        if (__ballot(live) == 0) continue;                                  // the whole wave, so every lane reaches the shuffles below
+        double X = 0.0, Y = 0.0, Z = 0.0, nhx = 0.0, nhy = 0.0, nhz = 0.0;
+        if (live) {
+            const double nx = (double)P.nrm[3 * at], ny = (double)P.nrm[3 * at + 1], nz = (double)P.nrm[3 * at + 2];
+            const double nl = sqrt((nx * nx + ny * ny) + nz * nz);
+            live = nl > 0.0;
+            X = (double)P.pos[3 * at]; Y = (double)P.pos[3 * at + 1]; Z = (double)P.pos[3 * at + 2];
+            nhx = nx / nl; nhy = ny / nl; nhz = nz / nl;
+        }
+        // the views: the lane's mask; lane v keeps the lane set of view v and the sums of q over it
+        uint32_t mask = 0;
+        unsigned long long set = 0;
+        long long tot0 = 0, tot1 = 0, tot2 = 0;
+        for (int v = 0; v < V; ++v) {
+            long long q[3] = {0, 0, 0};
+            const bool part = live && stat_eval(P, v, X, Y, Z, nhx, nhy, nhz, q);
+            const unsigned long long b = __ballot(part);
+            if (b == 0) continue;
+            if (part) mask |= 1u << v;
+            const long long a0 = wave_sum(part ? q[0] : 0), a1 = wave_sum(part ? q[1] : 0), a2 = wave_sum(part ? q[2] : 0);
+            if (lane == v) { set = b; tot0 = a0; tot1 = a1; tot2 = a2; }
+        }
+        // the pairs
+        for (int i = 0; i < V; ++i) {
+            const unsigned long long si = __shfl(set, i, 64);
+            if (si == 0) continue;
+            const long long t0 = __shfl(tot0, i, 64), t1 = __shfl(tot1, i, 64), t2 = __shfl(tot2, i, 64);
+            const unsigned long long both = si & set;                       // lane j: texels of the wave where i and j take part
+            const bool whole = both == si;
+            if (both != 0 && whole) {                                       // (only lanes j < V hold a set)
+                unsigned long long *e = tab + (size_t)(i * V + lane) * 4;
+                atomicAdd(e, (unsigned long long)__popcll(both));
+                atomicAdd(e + 1, (unsigned long long)t0); atomicAdd(e + 2, (unsigned long long)t1); atomicAdd(e + 3, (unsigned long long)t2);
+            }
+            unsigned long long partial = __ballot(both != 0 && !whole);     // partners j that share only a part of set_i
+            if (partial == 0) continue;
+            long long q[3] = {0, 0, 0};
+            const bool has_i = (mask >> i) & 1u;
+            if (has_i) stat_eval(P, i, X, Y, Z, nhx, nhy, nhz, q);          // the same operations again: the same q
+            while (partial) {
+                const int j = __builtin_ctzll(partial);
+                partial &= partial - 1;
+                const bool in = has_i && ((mask >> j) & 1u);
+                const unsigned long long n = (unsigned long long)__popcll(__ballot(in));
+                const long long a0 = wave_sum(in ? q[0] : 0), a1 = wave_sum(in ? q[1] : 0), a2 = wave_sum(in ? q[2] : 0);
+                if (lane == 0) {
+                    unsigned long long *e = tab + (size_t)(i * V + j) * 4;
+                    atomicAdd(e, n);
+                    atomicAdd(e + 1, (unsigned long long)a0); atomicAdd(e + 2, (unsigned long long)a1); atomicAdd(e + 3, (unsigned long long)a2);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int e = (int)threadIdx.x; e < V * V; e += kTile * kTile) {
+        if (tab[4 * e] == 0) continue;
+        atomicAdd(P.pair_count + e, tab[4 * e]);
+        for (int c = 0; c < 3; ++c)
+            if (tab[4 * e + 1 + c] != 0) atomicAdd(P.pair_sum + 3 * (size_t)e + c, tab[4 * e + 1 + c]);
+    }
+}
+
 }  // namespace
 
-T4D_EXPORT int t4d_project_texture(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
-                                   const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos, const float *depth,
-                                   int32_t power, double cos_min, double fade_px, double depth_tol, int32_t mode, float *color,
-                                   float *weight, uint8_t *count, void *hip_stream)
+static int projtex_check(const char *name, int32_t tex_h, int32_t tex_w, int32_t power, double cos_min, double fade_px, double depth_tol)
+{
+    if (tex_h < 1 || tex_w < 1 || tex_h > kMaxDim || tex_w > kMaxDim)
+        return t4d_fail(T4D_ERR_ARG, "%s: need 1 <= sides <= %d, got a %d x %d texture", name, kMaxDim, tex_h, tex_w);
+    if (power < 0 || power > kMaxPower) return t4d_fail(T4D_ERR_ARG, "%s: power must be in [0, %d], got %d", name, kMaxPower, power);
+    if (!(cos_min >= -1.0 && cos_min <= 1.0) || !(fade_px >= 0.0 && fade_px <= (double)kMaxDim) || !(depth_tol >= 0.0 && depth_tol <= 1.0))
+        return t4d_fail(T4D_ERR_ARG, "%s: need cos_min in [-1, 1], fade_px in [0, %d] and depth_tol in [0, 1]", name, kMaxDim);
+    return T4D_OK;
+}
+
+T4D_EXPORT int t4d_project_texture_gains(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                         const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
+                                         const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
+                                         double depth_tol, int32_t mode, float *color, float *weight, uint8_t *count, void *hip_stream)
 {
     if (!pos || !nrm || !coverage || !views || !photos || !depth || !color || !weight || !count)
         return t4d_fail(T4D_ERR_ARG, "t4d_project_texture: NULL buffer");
@@ -145,17 +308,51 @@ T4D_EXPORT int t4d_project_texture(const float *pos, const float *nrm, const uin
                         tex_h, tex_w, h, w);
     if (n_views < 1 || n_views > kMaxViews)
         return t4d_fail(T4D_ERR_ARG, "t4d_project_texture: n_views must be in [1, %d], got %d", kMaxViews, n_views);
-    if (power < 0 || power > kMaxPower) return t4d_fail(T4D_ERR_ARG, "t4d_project_texture: power must be in [0, %d], got %d", kMaxPower, power);
     if (mode != T4D_PROJTEX_WEIGHTED && mode != T4D_PROJTEX_BEST)
         return t4d_fail(T4D_ERR_ARG, "t4d_project_texture: mode must be T4D_PROJTEX_WEIGHTED or T4D_PROJTEX_BEST, got %d", mode);
-    if (!(cos_min >= -1.0 && cos_min <= 1.0) || !(fade_px >= 0.0 && fade_px <= (double)kMaxDim) || !(depth_tol >= 0.0 && depth_tol <= 1.0))
-        return t4d_fail(T4D_ERR_ARG, "t4d_project_texture: need cos_min in [-1, 1], fade_px in [0, %d] and depth_tol in [0, 1]", kMaxDim);
+    if (const int rc = projtex_check("t4d_project_texture", tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
     PTP P;
-    P.pos = pos; P.nrm = nrm; P.views = views; P.photos = photos; P.depth = depth; P.coverage = coverage;
+    P.pos = pos; P.nrm = nrm; P.views = views; P.photos = photos; P.depth = depth; P.coverage = coverage; P.gains = gains;
     P.th = tex_h; P.tw = tex_w; P.V = n_views; P.H = h; P.W = w; P.power = power; P.mode = mode;
     P.cos_min = cos_min; P.fade_px = fade_px; P.depth_lim = 1.0 + depth_tol;
     P.color = color; P.weight = weight; P.count = count;
     const dim3 grid((unsigned)((tex_w + kTile - 1) / kTile), (unsigned)((tex_h + kTile - 1) / kTile));
-    hipLaunchKernelGGL(k_projtex, grid, dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
+    hipLaunchKernelGGL(gains ? k_projtex<true> : k_projtex<false>, grid, dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
     return t4d_launch_status("t4d_project_texture");
+}
+
+T4D_EXPORT int t4d_project_texture(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                   const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos, const float *depth,
+                                   int32_t power, double cos_min, double fade_px, double depth_tol, int32_t mode, float *color,
+                                   float *weight, uint8_t *count, void *hip_stream)
+{
+    return t4d_project_texture_gains(pos, nrm, coverage, tex_h, tex_w, views, n_views, h, w, photos, depth, nullptr, power, cos_min,
+                                     fade_px, depth_tol, mode, color, weight, count, hip_stream);
+}
+
+T4D_EXPORT int t4d_projtex_pair_stats(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                      const float *views, int32_t n_views, const int32_t *sizes, const float *const *photos,
+                                      const float *const *depth, int32_t power, double cos_min, double fade_px, double depth_tol,
+                                      double stat_cos_min, double stat_lo, double stat_hi, const double *gains, int64_t *pair_count,
+                                      int64_t *pair_sum, void *hip_stream)
+{
+    if (!pos || !nrm || !coverage || !views || !sizes || !photos || !depth || !pair_count || !pair_sum)
+        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_pair_stats: NULL buffer");
+    if (n_views < 1 || n_views > kStatViews)
+        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_pair_stats: n_views must be in [1, %d], got %d", kStatViews, n_views);
+    if (const int rc = projtex_check("t4d_projtex_pair_stats", tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
+    if (!(stat_cos_min >= -1.0 && stat_cos_min <= 1.0) || !(stat_lo >= -kStatRange && stat_lo <= stat_hi && stat_hi <= kStatRange))
+        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_pair_stats: need stat_cos_min in [-1, 1] and -%g <= stat_lo <= stat_hi <= %g", kStatRange,
+                        kStatRange);
+    PSP P;
+    P.pos = pos; P.nrm = nrm; P.views = views; P.coverage = coverage; P.sizes = sizes; P.photos = photos; P.depth = depth; P.gains = gains;
+    P.th = tex_h; P.tw = tex_w; P.V = n_views; P.power = power;
+    P.tiles_x = (tex_w + kTile - 1) / kTile;
+    P.tiles = P.tiles_x * ((tex_h + kTile - 1) / kTile);                   // at most 4096^2
+    P.cos_min = cos_min; P.fade_px = fade_px; P.depth_lim = 1.0 + depth_tol;
+    P.stat_cos_min = stat_cos_min; P.stat_lo = stat_lo; P.stat_hi = stat_hi;
+    P.pair_count = (unsigned long long *)pair_count; P.pair_sum = (unsigned long long *)pair_sum;
+    const int blocks = P.tiles < kStatGrid ? P.tiles : kStatGrid;
+    hipLaunchKernelGGL(k_pair_stats, dim3((unsigned)blocks), dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
+    return t4d_launch_status("t4d_projtex_pair_stats");
 }

@@ -5,6 +5,9 @@ states the per-texel rule; tests/projtex_ref.py restates it in numpy bit for bit
     project(pos, nrm, coverage, cams, photos, depth, ...)   -> (color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8)
     surface_maps(face_obj, vertices, res, device)           -> (pos [h,w,3], nrm [h,w,3], coverage [h,w]) of a face.obj's UV layout
     project_frame(face_obj, vertices, dataset, res, ...)    -> (texture [h,w,3] uint8, weight, count): one frame from its views
+    pair_stats(pos, nrm, coverage, groups, ...)             -> (count [V,V], sums [V,V,3]) int64: what the cameras share, per pair
+    solve_gains(count, sums, ...)                           -> float64 [V,3]: one gain per camera and channel, on the host
+    estimate_gains(face_obj, vertices, dataset, res, ...)   -> (gains, report) of one frame; write_gains / read_gains: proj_gains.json
 
 Every texel is coloured from the cameras that see it: a view counts when the texel's point projects inside its photograph,
 in front of the near plane, is not hidden (the depth map of meshrender.MeshRenderer.render, within depth_tol) and faces the
@@ -13,17 +16,27 @@ faded over fade_px pixels towards the image edge; mode="best" keeps the single v
 conventional choices, not tuned on a capture.  Unlike face.png (the texture loop's Gaussian-filtered
 colour field) this is the photographs themselves.  There is no CPU path.
 
+The cameras of a rig never agree exactly in exposure and white balance, and a blend of unequal cameras shows a step wherever the
+set of contributing views changes.  pair_stats counts, for every pair of cameras, the texels both see and sums each camera's
+samples there (integers, so the result is the same bits in any order); solve_gains finds the gain per camera and channel that
+makes the pairs agree in the least-squares sense (the gain compensation of panorama stitchers, in the log domain), and project /
+project_frame take these gains.  Exposure belongs to the rig, not to a frame: one set of gains serves a whole run.
+
 `python -m topo4d_amd.projtex -e EXP -s SEQ [-id ... -did ... -od ... -dr N] [--frames 1-10] [--views A,B] [--set low|dense]
 [--undistort] [--tex_res R] [--mode weighted|best] [--power P --cos_min C --fade_px F --depth_tol T] [--tex_pad R]
-[--tex_sizes 2048,1024] [--save_weight]` works on an output tree that already exists (the reference's too): it writes
+[--tex_sizes 2048,1024] [--save_weight] [--equalize [--equalize_frames 1-10] | --gains FILE] [--stat_cos_min C --stat_lo L
+--stat_hi H --eq_prior P --eq_min_overlap N]` works on an output tree that already exists (the reference's too): it writes
 %06d/face_proj.png (and face_proj_<size>.png) beside every frame's face.obj, with --save_weight also face_proj_weight.png (the
 8-bit count of contributing views).  By default it projects the full-size photographs of the cameras training uses.
-`python -m topo4d_amd.train --tex_project` writes the same file while the run is made.
+--equalize gathers the pair statistics over --equalize_frames (default: the first frame projected), solves once, writes
+proj_gains.json into the run directory and projects every frame with these gains; --gains FILE takes a saved file instead.
+`python -m topo4d_amd.train --tex_project` writes the same file while the run is made; with --tex_equalize it estimates the gains on the first frame it writes.
 """
 from __future__ import annotations
 
 import argparse
 import functools
+import json
 import os
 from concurrent.futures import ThreadPoolExecutor
 from typing import Tuple
@@ -39,6 +52,10 @@ _MODES = {"weighted": T4D_PROJTEX_WEIGHTED, "best": T4D_PROJTEX_BEST}
 MAX_POWER, MAX_VIEWS = 8, 255
 DEFAULTS = dict(power=2, cos_min=0.1, fade_px=16.0, depth_tol=0.002, mode="weighted")
 FILE_NAME, WEIGHT_NAME = "face_proj.png", "face_proj_weight.png"
+MAX_STAT_VIEWS, MAX_STAT = 32, 1024.0                          # pair_stats: a 32-bit mask of views per texel; |stat_lo|, |stat_hi|
+STAT_DEFAULTS = dict(stat_cos_min=0.5, stat_lo=0.02, stat_hi=0.98)
+SOLVE_DEFAULTS = dict(prior=0.01, min_overlap=64)
+GAINS_NAME = "proj_gains.json"
 
 
 def check_options(power=2, cos_min=0.1, fade_px=16.0, depth_tol=0.002, mode="weighted") -> None:
@@ -55,6 +72,35 @@ def check_options(power=2, cos_min=0.1, fade_px=16.0, depth_tol=0.002, mode="wei
         raise ValueError(f"depth_tol must be in [0, 1], got {depth_tol!r}")
 
 
+def check_stat_options(stat_cos_min=0.5, stat_lo=0.02, stat_hi=0.98) -> None:
+    """ValueError for a parameter pair_stats would refuse (callable without a device)."""
+    if not -1.0 <= float(stat_cos_min) <= 1.0:
+        raise ValueError(f"stat_cos_min must be in [-1, 1], got {stat_cos_min!r}")
+    if not -MAX_STAT <= float(stat_lo) <= float(stat_hi) <= MAX_STAT:
+        raise ValueError(f"need -{MAX_STAT:g} <= stat_lo <= stat_hi <= {MAX_STAT:g}, got {stat_lo!r} and {stat_hi!r}")
+
+
+def check_solve_options(prior=0.01, min_overlap=64) -> None:
+    """ValueError for a parameter solve_gains would refuse."""
+    if not 0.0 <= float(prior) < float("inf"):
+        raise ValueError(f"prior must be finite and >= 0, got {prior!r}")
+    if isinstance(min_overlap, bool) or int(min_overlap) != min_overlap or int(min_overlap) < 1:
+        raise ValueError(f"min_overlap must be a positive integer, got {min_overlap!r}")
+
+
+def _gains(gains, V: int):
+    """None, or gains as a float64 [V,3] host array; ValueError for anything else"""
+    if gains is None:
+        return None
+    g = np.asarray(gains.detach().cpu() if isinstance(gains, torch.Tensor) else gains)
+    if g.shape != (V, 3) or g.dtype.kind not in "fiu":
+        raise ValueError(f"gains must be a real [{V},3] array (one per view and channel), got {g.dtype} {list(g.shape)}")
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    if not np.isfinite(g).all():
+        raise ValueError("gains must be finite")
+    return g
+
+
 def _map(t, what: str, shape, dtype) -> torch.Tensor:
     if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape):
         raise ValueError(f"{what} must be a {str(dtype).split('.')[-1]} tensor of shape {list(shape)}, got "
@@ -64,11 +110,12 @@ def _map(t, what: str, shape, dtype) -> torch.Tensor:
 
 def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, photos: torch.Tensor, depth: torch.Tensor, *,
             power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0, depth_tol: float = 0.002,
-            mode: str = "weighted") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+            mode: str = "weighted", gains=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8).  pos / nrm [h,w,3] float32: each texel's point in the
     training world frame and its normal (any length; a zero normal switches the texel off); coverage [h,w] uint8 or bool;
     cams: a sequence of GaussianRasterizationSettings of one size, or (packed view records, H, W), as MeshRenderer.render takes
-    them; photos [V,3,H,W] float32; depth [V,1,H,W] float32, MeshRenderer.render's (0: empty).  Everything on one HIP device."""
+    them; photos [V,3,H,W] float32; depth [V,1,H,W] float32, MeshRenderer.render's (0: empty).  Everything on one HIP device.  gains [V,3] (None: none): view v's
+    sample is multiplied by gains[v] in the kernel, in float64; no scaled copy of the photographs is made."""
     check_options(power, cos_min, fade_px, depth_tol, mode)
     if not isinstance(pos, torch.Tensor) or pos.dim() != 3 or pos.shape[2] != 3 or pos.shape[0] < 1 or pos.shape[1] < 1:
         raise ValueError(f"pos must be a float32 [h,w,3] tensor, got {list(getattr(pos, 'shape', ()))}")
@@ -85,6 +132,7 @@ def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, 
         raise ValueError(f"at most {MAX_VIEWS} views per call, got {V}")
     _map(photos, "photos", (V, 3, H, W), torch.float32)
     _map(depth, "depth", (V, 1, H, W), torch.float32)
+    g = _gains(gains, V)
     for name, t in (("nrm", nrm), ("coverage", coverage), ("photos", photos), ("depth", depth)):
         if t.device != dev:
             raise ValueError(f"{name} must live on pos's device {dev}, got {t.device}")
@@ -95,9 +143,124 @@ def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, 
     color = torch.empty(h, w, 3, dtype=torch.float32, device=dev)
     weight = torch.empty(h, w, dtype=torch.float32, device=dev)
     count = torch.empty(h, w, dtype=torch.uint8, device=dev)
-    _lib.call("t4d_project_texture", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(depth), int(power),
-              float(cos_min), float(fade_px), float(depth_tol), _MODES[mode], ptr(color), ptr(weight), ptr(count), _lib.stream(dev))
+    g = None if g is None else torch.from_numpy(g).to(dev)
+    _lib.call("t4d_project_texture_gains", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(depth), ptr(g),
+              int(power), float(cos_min), float(fade_px), float(depth_tol), _MODES[mode], ptr(color), ptr(weight), ptr(count),
+              _lib.stream(dev))
     return color, weight, count
+
+
+def pair_stats(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, groups, *, gains=None, out=None, stat_cos_min: float = 0.5,
+               stat_lo: float = 0.02, stat_hi: float = 0.98, power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0,
+               depth_tol: float = 0.002) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(count [V,V], sums [V,V,3]), int64 on the device.  pos, nrm, coverage as project takes them; groups: a list of (cams, photos
+    [v,3,H,W], depth [v,1,H,W]) as project takes them, one per image size, V <= 32 views in all, numbered in the order given.  View v
+    takes part at a texel when project would accept it there (power, cos_min, fade_px, depth_tol), its cosine is >= stat_cos_min
+    and every channel of its sample (times gains[v], [V,3], when given) lies in [stat_lo, stat_hi]: a clipped or black sample follows
+    no gain model.  count[i][j]: the texels where i and j both take part; sums[i][j]: the sum of view i's samples there, as integers
+    in units of 2^-16 (count[i][i], sums[i][i]: over all of view i's texels).  out = (count, sums) of an earlier call is added to and
+    returned: the statistics of several frames.  The three stat_* defaults are conventional choices (a facing limit of 60 degrees,
+    2 % off either end of the range), not tuned on a capture."""
+    check_options(power, cos_min, fade_px, depth_tol)
+    check_stat_options(stat_cos_min, stat_lo, stat_hi)
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 3 or pos.shape[2] != 3 or pos.shape[0] < 1 or pos.shape[1] < 1:
+        raise ValueError(f"pos must be a float32 [h,w,3] tensor, got {list(getattr(pos, 'shape', ()))}")
+    h, w = int(pos.shape[0]), int(pos.shape[1])
+    _map(pos, "pos", (h, w, 3), torch.float32)
+    _map(nrm, "nrm", (h, w, 3), torch.float32)
+    if not isinstance(coverage, torch.Tensor) or coverage.dtype not in (torch.uint8, torch.bool) or tuple(coverage.shape) != (h, w):
+        raise ValueError(f"coverage must be a uint8 or bool [{h},{w}] tensor")
+    dev = pos.device
+    from .meshrender import _views
+    groups = list(groups)
+    if not groups:
+        raise ValueError("pair_stats: no views")
+    records, sizes, keep = [], [], []
+    for cams, photos, depth in groups:
+        views, H, W = _views(cams, dev)
+        v = int(views.shape[0])
+        if not 1 <= H <= 65536 or not 1 <= W <= 65536:
+            raise ValueError(f"image sides must be in [1, 65536], got {H} x {W}")
+        _map(photos, "photos", (v, 3, H, W), torch.float32)
+        _map(depth, "depth", (v, 1, H, W), torch.float32)
+        records.append(views)
+        sizes += [(H, W)] * v
+        keep.append((photos, depth))
+    V = len(sizes)
+    if V > MAX_STAT_VIEWS:
+        raise ValueError(f"at most {MAX_STAT_VIEWS} views per call, got {V}")
+    g = _gains(gains, V)
+    if out is not None:
+        count, sums = out
+        _map(count, "out[0]", (V, V), torch.int64)
+        _map(sums, "out[1]", (V, V, 3), torch.int64)
+        keep.append((count, sums))
+    for name, t in [("nrm", nrm), ("coverage", coverage)] + [("photos, depth and out", t) for pair in keep for t in pair]:
+        if t.device != dev:
+            raise ValueError(f"{name} must live on pos's device {dev}, got {t.device}")
+    if not pos.is_cuda:                                        # argument errors first, with or without a device
+        raise RuntimeError("topo4d_amd has no CPU path: the maps, the photographs and the depth must live on a HIP device")
+    if out is None:
+        count, sums = torch.zeros(V, V, dtype=torch.int64, device=dev), torch.zeros(V, V, 3, dtype=torch.int64, device=dev)
+    elif not (count.is_contiguous() and sums.is_contiguous()):
+        raise ValueError("out must be contiguous")
+    cov = (coverage.to(torch.uint8) if coverage.dtype == torch.bool else coverage).contiguous()
+    pos, nrm = pos.contiguous(), nrm.contiguous()
+    held = [(p.contiguous(), d.contiguous()) for p, d in keep[:len(groups)]]       # alive until the launch is queued on their stream
+    photo_ptrs = [p[k].data_ptr() for p, _ in held for k in range(p.shape[0])]
+    depth_ptrs = [d[k].data_ptr() for _, d in held for k in range(d.shape[0])]
+    tables = torch.tensor([photo_ptrs, depth_ptrs], dtype=torch.int64).to(dev)
+    sizes_t = torch.tensor(sizes, dtype=torch.int32).to(dev)
+    views = torch.cat(records).contiguous()
+    g = None if g is None else torch.from_numpy(g).to(dev)
+    _lib.call("t4d_projtex_pair_stats", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, ptr(sizes_t), ptr(tables[0]), ptr(tables[1]),
+              int(power), float(cos_min), float(fade_px), float(depth_tol), float(stat_cos_min), float(stat_lo), float(stat_hi), ptr(g),
+              ptr(count), ptr(sums), _lib.stream(dev))
+    return count, sums
+
+
+def _solve(count, sums, prior: float, min_overlap: int):
+    check_solve_options(prior, min_overlap)
+    count = np.asarray(count.detach().cpu() if isinstance(count, torch.Tensor) else count)
+    sums = np.asarray(sums.detach().cpu() if isinstance(sums, torch.Tensor) else sums)
+    if count.ndim != 2 or count.shape[0] != count.shape[1] or count.shape[0] < 1 or sums.shape != (*count.shape, 3):
+        raise ValueError(f"count must be [V,V] and sums [V,V,3], got {list(count.shape)} and {list(sums.shape)}")
+    V = count.shape[0]
+    count, sums = count.astype(np.float64), sums.astype(np.float64)
+    gains = np.ones((V, 3))
+    report = dict(pairs=[], rms_before=[], rms_after=[])
+    off = ~np.eye(V, dtype=bool)
+    for c in range(3):
+        s = sums[..., c]
+        use = off & (count >= min_overlap) & (s > 0) & (s.T > 0)
+        N = np.where(use, count, 0.0)
+        with np.errstate(all="ignore"):
+            d = np.where(N > 0, np.log(np.where(use, s, 1.0)) - np.log(np.where(use, s.T, 1.0)), 0.0)
+        n = N.sum(1)
+        A = -N + np.diag((1.0 + prior) * n)
+        b = -(N * d).sum(1)
+        lone = n == 0
+        A[lone, lone] = 1.0
+        l = np.linalg.solve(A, b)
+        l[lone] = 0.0
+        gains[:, c] = np.exp(l)
+        total = N.sum()
+        r = l[:, None] - l[None, :] + d
+        report["pairs"].append(int((N > 0).sum() // 2))
+        report["rms_before"].append(float(np.sqrt((N * d * d).sum() / total)) if total else 0.0)
+        report["rms_after"].append(float(np.sqrt((N * r * r).sum() / total)) if total else 0.0)
+    return gains, report
+
+
+def solve_gains(count, sums, *, prior: float = 0.01, min_overlap: int = 64) -> np.ndarray:
+    """float64 [V,3]: the gain of every camera and channel that makes the pairs of pair_stats agree, on the host in numpy float64.
+    Per channel c, in the log domain: N_ij = count[i][j] for i != j, 0 where it is below min_overlap or where sums[i][j][c] or
+    sums[j][i][c] is not positive; d_ij = log(sums[i][j][c]) - log(sums[j][i][c]), the log ratio of the two cameras' means over the
+    texels they share; l minimises E(l) = sum_{i<j} N_ij (l_i - l_j + d_ij)^2 + prior sum_i n_i l_i^2 with n_i = sum_j N_ij, that
+    is A l = b with A_ii = (1 + prior) n_i, A_ij = -N_ij, b_i = -sum_j N_ij d_ij; a camera with n_i = 0 keeps l_i = 0.  The gain is
+    exp(l).  The prior only fixes the common factor every connected group of cameras is free in, at about 1.  prior = 0.01 and
+    min_overlap = 64 are conventional choices, not tuned on a capture."""
+    return _solve(count, sums, prior, min_overlap)[0]
 
 
 def _size(res) -> Tuple[int, int]:
@@ -148,30 +311,29 @@ def surface_maps(face_obj, vertices: torch.Tensor, res, device=None):
 
 
 def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0,
-                  depth_tol: float = 0.002, mode: str = "weighted", device=None):
+                  depth_tol: float = 0.002, mode: str = "weighted", gains=None, device=None):
     """(texture [h,w,3] uint8, weight [h,w] float32, count [h,w] uint8) of one frame: `dataset` holds ingest.get_dataset's entries
     ("cam", "im"), vertices [N,3] the mesh in the training world frame.  The mesh is rendered once for the depth maps
     (meshrender.MeshRenderer over a 1x1 dummy texture), surface_maps gives the texel maps, project gathers, texfinish.quantize
     rounds as the PNG encoder does.  Views of one size go in one launch; a rig with several sizes (turned cameras) is merged
-    per size: weighted sums add up, "best" keeps the larger weight, the earlier size on ties."""
+    per size: weighted sums add up, "best" keeps the larger weight, the earlier size on ties.  gains [len(dataset),3] (None: none):
+    one row per entry of `dataset`, in its order."""
     from . import meshrender, texfinish
     check_options(power, cos_min, fade_px, depth_tol, mode)
     if not dataset:
         raise ValueError("project_frame: no views")
+    gains = _gains(gains, len(dataset))
     faces, uv_faces = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
     dev = meshrender._device(device if device is not None else (vertices.device if vertices.is_cuda else None))
     renderer = meshrender.MeshRenderer(faces, uv_faces, face_obj.uvs, np.zeros((1, 1, 3), np.uint8), device=dev)
     pos, nrm, cov = surface_maps(face_obj, vertices, res, device=dev)
-    groups = {}
-    for k, e in enumerate(dataset):
-        groups.setdefault((int(e["cam"].image_height), int(e["cam"].image_width)), []).append(k)
     total = None
-    for ks in groups.values():
+    for ks in _size_groups(dataset).values():
         cams = [dataset[k]["cam"] for k in ks]
         _, depth, _ = renderer.render(vertices, cams)
         photos = torch.stack([dataset[k]["im"] for k in ks]).to(torch.float32)
         color, weight, count = project(pos, nrm, cov, cams, photos, depth, power=power, cos_min=cos_min, fade_px=fade_px,
-                                       depth_tol=depth_tol, mode=mode)
+                                       depth_tol=depth_tol, mode=mode, gains=None if gains is None else gains[ks])
         if total is None:
             total = [color, weight, count]
             continue
@@ -187,17 +349,108 @@ def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power: int 
     return texfinish.quantize(color), weight, count
 
 
+def _size_groups(dataset) -> dict:
+    groups = {}
+    for k, e in enumerate(dataset):
+        groups.setdefault((int(e["cam"].image_height), int(e["cam"].image_width)), []).append(k)
+    return groups
+
+
+def frame_stats(face_obj, vertices: torch.Tensor, dataset, res, *, out=None, stat_cos_min: float = 0.5, stat_lo: float = 0.02,
+                stat_hi: float = 0.98, power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0, depth_tol: float = 0.002,
+                mode: str = "weighted", device=None):
+    """pair_stats of one frame, its views numbered as in `dataset`: the maps of surface_maps, the depth renders of project_frame.
+    out: the statistics of earlier frames of the same cameras, added to.  (mode is accepted and ignored, so that one dictionary
+    of projection options serves project_frame and this.)"""
+    from . import meshrender
+    check_options(power, cos_min, fade_px, depth_tol, mode)
+    check_stat_options(stat_cos_min, stat_lo, stat_hi)
+    if not dataset:
+        raise ValueError("frame_stats: no views")
+    if len(dataset) > MAX_STAT_VIEWS:
+        raise ValueError(f"at most {MAX_STAT_VIEWS} views can be equalised, got {len(dataset)}")
+    faces, uv_faces = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
+    dev = meshrender._device(device if device is not None else (vertices.device if vertices.is_cuda else None))
+    renderer = meshrender.MeshRenderer(faces, uv_faces, face_obj.uvs, np.zeros((1, 1, 3), np.uint8), device=dev)
+    pos, nrm, cov = surface_maps(face_obj, vertices, res, device=dev)
+    groups, order = [], []
+    for ks in _size_groups(dataset).values():
+        cams = [dataset[k]["cam"] for k in ks]
+        groups.append((cams, torch.stack([dataset[k]["im"] for k in ks]).to(torch.float32), renderer.render(vertices, cams)[1]))
+        order += ks
+    count, sums = pair_stats(pos, nrm, cov, groups, stat_cos_min=stat_cos_min, stat_lo=stat_lo, stat_hi=stat_hi, power=power,
+                             cos_min=cos_min, fade_px=fade_px, depth_tol=depth_tol)
+    if order != sorted(order):                                 # several sizes: back from group order to dataset order
+        back = torch.tensor(np.argsort(order), device=dev)
+        count, sums = count[back][:, back], sums[back][:, back]
+    if out is not None:
+        out[0].add_(count)
+        out[1].add_(sums)
+        return out
+    return count.contiguous(), sums.contiguous()
+
+
+def estimate_gains(face_obj, vertices: torch.Tensor, dataset, res, *, prior: float = 0.01, min_overlap: int = 64, device=None, **options):
+    """(gains float64 [len(dataset),3], report) of one frame: frame_stats, then solve_gains.  options: frame_stats's.  report:
+    per channel the number of camera pairs used ("pairs"), the count-weighted rms of the pairs' log ratios d_ij as the cameras come
+    ("rms_before") and of l_i - l_j + d_ij with the gains applied ("rms_after")."""
+    check_solve_options(prior, min_overlap)
+    count, sums = frame_stats(face_obj, vertices, dataset, res, device=device, **options)
+    return _solve(count, sums, prior, min_overlap)
+
+
+def write_gains(path: str, names, gains, report: dict = None, options: dict = None) -> None:
+    """proj_gains.json: {"cameras": names, "gains": [[r, g, b] per camera], "report", "options"}"""
+    names = [str(n) for n in names]
+    g = _gains(gains, len(names))
+    if len(set(names)) != len(names):
+        raise ValueError("write_gains: camera names must be distinct")
+    with open(path, "w") as f:
+        json.dump({"cameras": names, "gains": [[float(x) for x in row] for row in g], "report": report or {}, "options": options or {}},
+                  f, indent=1)
+        f.write("\n")
+
+
+def read_gains(path: str, names=None):
+    """float64 [len(names),3]: the gains of proj_gains.json for the cameras `names`, matched by name; a camera the file does not
+    hold is a ValueError.  names None: (the file's names, its gains)."""
+    with open(path) as f:
+        doc = json.load(f)
+    try:
+        held = [str(n) for n in doc["cameras"]]
+        g = _gains(np.asarray(doc["gains"], dtype=np.float64).reshape(len(held), 3), len(held))
+    except (KeyError, TypeError, ValueError) as e:
+        raise ValueError(f"{path}: not a gains file ({e})") from None
+    if names is None:
+        return held, g
+    row = {n: k for k, n in enumerate(held)}
+    missing = [str(n) for n in names if str(n) not in row]
+    if missing:
+        raise ValueError(f"{path}: no gains for camera(s) {', '.join(missing)}")
+    return g[[row[str(n)] for n in names]]
+
+
+def _names(dataset) -> list:
+    return [e["cam_name"] for e in dataset]
+
+
 def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: int = 0, sizes=(), save_weight: bool = False,
-                device=None) -> list:
+                device=None, gains=None) -> list:
     """One frame's face_proj.png (and face_proj_<size>.png, face_proj_weight.png) in `frame_dir`, from the face.obj read there:
     what the command line and train --tex_project both call.  Returns the files written.  The gutter of `pad` texels is filled
-    from the texels some view contributed to (count > 0), through texfinish.finish."""
+    from the texels some view contributed to (count > 0), through texfinish.finish.  gains: None, or
+    {camera name: [r, g, b]} holding every camera of `dataset`."""
     from . import texfinish
     from .evaluate import training_vertices
     from .png import write_png
     dev = torch.device(device if device is not None else "cuda")
     verts = torch.from_numpy(training_vertices(face_obj.vertices, trans_g)).to(dev)
-    tex, _, count = project_frame(face_obj, verts, dataset, res, device=dev, **options)
+    if gains is not None:
+        missing = [n for n in _names(dataset) if n not in gains]
+        if missing:
+            raise ValueError(f"no gains for camera(s) {', '.join(missing)}")
+        gains = np.asarray([gains[n] for n in _names(dataset)], dtype=np.float64)
+    tex, _, count = project_frame(face_obj, verts, dataset, res, device=dev, gains=gains, **options)
     levels = texfinish.finish(tex, (count > 0).to(torch.uint8), pad=pad, erode=0, sizes=sizes)
     written = texfinish.write_levels(os.path.join(frame_dir, FILE_NAME), levels)
     if save_weight:
@@ -226,6 +479,67 @@ def options_of(args) -> dict:
     return {k: getattr(args, k, v) for k, v in DEFAULTS.items()}
 
 
+def add_eq_options(p: argparse.ArgumentParser, suppress: bool = False) -> None:
+    """The parameters of the equalisation, beside add_options' on both parsers."""
+    d = (lambda v: argparse.SUPPRESS) if suppress else (lambda v: v)
+    p.add_argument("--stat_cos_min", type=float, default=d(STAT_DEFAULTS["stat_cos_min"]),
+                   help="Equalisation: a view's texel counts when the cosine between normal and viewing direction is at least this (default 0.5).")
+    p.add_argument("--stat_lo", type=float, default=d(STAT_DEFAULTS["stat_lo"]),
+                   help="Equalisation: leave out samples with a channel below this: black follows no gain (default 0.02).")
+    p.add_argument("--stat_hi", type=float, default=d(STAT_DEFAULTS["stat_hi"]),
+                   help="Equalisation: leave out samples with a channel above this: clipped (default 0.98).")
+    p.add_argument("--eq_prior", type=float, default=d(SOLVE_DEFAULTS["prior"]),
+                   help="Equalisation: weight of the pull of every gain towards 1, which fixes the common factor (default 0.01).")
+    p.add_argument("--eq_min_overlap", type=int, default=d(SOLVE_DEFAULTS["min_overlap"]),
+                   help="Equalisation: ignore a pair of cameras that shares fewer texels than this (default 64).")
+
+
+def eq_options_of(args) -> Tuple[dict, dict]:
+    """(the stat_* options of pair_stats, the options of solve_gains) of a parse, checked"""
+    stat = {k: getattr(args, k, v) for k, v in STAT_DEFAULTS.items()}
+    solve = dict(prior=getattr(args, "eq_prior", SOLVE_DEFAULTS["prior"]), min_overlap=getattr(args, "eq_min_overlap", SOLVE_DEFAULTS["min_overlap"]))
+    try:
+        check_stat_options(**stat)
+        check_solve_options(**solve)
+    except ValueError as e:
+        raise SystemExit(f"equalisation options: {e}") from None
+    return stat, solve
+
+
+class GainEstimator:
+    """The gains of a run: add(face_obj, trans_g, dataset) gathers one frame's statistics, finish(path) solves, writes
+    proj_gains.json and returns {camera name: gain}.  Every frame must hold the same cameras in the same order."""
+
+    def __init__(self, res, options: dict, stat: dict, solve: dict, device=None):
+        self.res, self.options, self.stat, self.solve, self.dev = res, dict(options), dict(stat), dict(solve), device
+        self.names, self.out, self.frames = None, None, 0
+
+    def add(self, face_obj, trans_g, dataset) -> None:
+        from .evaluate import training_vertices
+        dev = torch.device(self.dev if self.dev is not None else "cuda")
+        if self.names is None:
+            self.names = _names(dataset)
+        elif self.names != _names(dataset):
+            raise ValueError(f"the frames to equalise over hold different cameras: {self.names} and {_names(dataset)}")
+        verts = torch.from_numpy(training_vertices(face_obj.vertices, trans_g)).to(dev)
+        self.out = frame_stats(face_obj, verts, dataset, self.res, out=self.out, device=dev, **self.options, **self.stat)
+        self.frames += 1
+
+    def finish(self, path: str) -> dict:
+        if self.out is None:
+            raise ValueError("no frame to estimate the gains from")
+        gains, report = _solve(self.out[0], self.out[1], **self.solve)
+        report["frames"] = self.frames
+        write_gains(path, self.names, gains, report, {**self.options, **self.stat, **self.solve})
+        return dict(zip(self.names, gains.tolist()))
+
+
+def load_gains(path: str) -> dict:
+    """{camera name: gain} of a proj_gains.json"""
+    names, g = read_gains(path)
+    return dict(zip(names, g.tolist()))
+
+
 def build_parser() -> argparse.ArgumentParser:
     from .evaluate import _frames
     from .train import _size_list, build_parser as train_parser
@@ -242,6 +556,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--undistort", action="store_true",
                    help="Undistort the photographs by the lens calibration of cameras.xml, as topo4d_amd.train --undistort does.")
     add_options(p)
+    p.add_argument("--equalize", action="store_true",
+                   help="Equalise the cameras' exposure and white balance: estimate one gain per camera and channel, write "
+                        "proj_gains.json into the run directory and project every frame with these gains.")
+    p.add_argument("--equalize_frames", type=_frames, default=None,
+                   help="With --equalize: the frames the statistics are gathered over (default: the first frame projected).")
+    p.add_argument("--gains", default=None, metavar="FILE", help="Project with the gains of a saved proj_gains.json instead of estimating.")
+    add_eq_options(p)
     p.add_argument("--tex_pad", type=int, default=0, metavar="R",
                    help="Fill a gutter of R texels (0..64) round the projected texels (texfinish.finish).")
     p.add_argument("--tex_sizes", type=_size_list, default=[],
@@ -275,6 +596,10 @@ def project_tree(args, device=None) -> list:
     if not os.path.isdir(run_dir):
         raise SystemExit(f"no run at {run_dir}")
     opts = _check_args(args, args.tex_res)
+    equalize, gains_file = getattr(args, "equalize", False), getattr(args, "gains", None)
+    if equalize and gains_file:
+        raise SystemExit("--equalize estimates the gains and --gains reads them: give one of the two")
+    stat, solve = eq_options_of(args)
     low = args.set == "low"
     data_dir = args.input_dir if low else args.dense_input_dir
     cameras, _, trans_g = C.get_cameras(args.input_dir, args.seq, resize_factor=args.down_ratio if low else 1)
@@ -300,6 +625,23 @@ def project_tree(args, device=None) -> list:
                     pending[t] = pool.submit(_read_obj, os.path.join(run_dir, "%06d" % t))
                     pf.prefetch(t)
 
+            gains = None
+            try:
+                if gains_file:
+                    gains = load_gains(gains_file)
+                elif equalize:
+                    est = GainEstimator(args.tex_res, opts, stat, solve, device=dev)
+                    for t in getattr(args, "equalize_frames", None) or frames:
+                        obj, dataset = _read_obj(os.path.join(run_dir, "%06d" % t)), pf.get(t)
+                        if obj is None or not dataset:
+                            continue
+                        est.add(obj, trans_g, dataset)
+                        if not getattr(args, "equalize_frames", None):
+                            break                                  # the first frame that can be projected
+                    gains = est.finish(os.path.join(run_dir, GAINS_NAME))
+                    written.append(os.path.join(run_dir, GAINS_NAME))
+            except (OSError, ValueError) as e:
+                raise SystemExit(f"equalisation: {e}") from None
             for i, t in enumerate(frames):
                 prefetch(t)
                 if i + 1 < len(frames):
@@ -308,8 +650,10 @@ def project_tree(args, device=None) -> list:
                 dataset = pf.get(t)
                 if obj is None or not dataset:
                     continue
+                if gains is not None and any(n not in gains for n in _names(dataset)):
+                    raise SystemExit(f"equalisation: no gains for camera(s) {', '.join(n for n in _names(dataset) if n not in gains)}")
                 written += write_frame(os.path.join(run_dir, "%06d" % t), obj, trans_g, dataset, args.tex_res, opts,
-                                       pad=args.tex_pad, sizes=args.tex_sizes, save_weight=args.save_weight, device=dev)
+                                       pad=args.tex_pad, sizes=args.tex_sizes, save_weight=args.save_weight, device=dev, gains=gains)
         finally:
             pool.shutdown(wait=True)
             pf.close()

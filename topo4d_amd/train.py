@@ -22,8 +22,9 @@ exported undistorted), and --low_from_full makes the geometry inputs from the fu
 means, so that -id holds cameras.xml, the mesh and the masks only; with --gen_tex, --tex_pad R fills a gutter of R texels round
 the UV islands of face.png and --tex_sizes 4096,2048 also writes face_<size>.png (texfinish.finish); --tex_project writes
 face_proj.png beside every face.obj, the frame's full-size photographs projected into the UV layout (projtex, with or without
---gen_tex; --mode, --power, --cos_min, --fade_px and --depth_tol as python -m topo4d_amd.projtex takes them).  Without them
-nothing changes.
+--gen_tex; --mode, --power, --cos_min, --fade_px and --depth_tol as python -m topo4d_amd.projtex takes them; --tex_equalize
+estimates one gain per camera and channel on the first frame written, stores proj_gains.json in the run directory and projects
+every frame with it).  Without them nothing changes.
 
 The region "freezes" of train.py:676-700 are FusedAdamPins pins, written by the step kernel itself; the pin set changes at
 most twice per frame (the dynamic-eye pins end at iteration int(0.7 n) of frame 0) and the learning rates once (the colour
@@ -314,6 +315,11 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
     if tex_project:
         from . import meshrender, projtex
         proj_opts = projtex._check_args(args, args.tex_res)
+    tex_equalize, proj_gains = getattr(args, "tex_equalize", False), None
+    if tex_equalize:
+        if not tex_project:
+            raise SystemExit("--tex_equalize equalises the projected texture: it needs --tex_project")
+        eq_stat, eq_solve = projtex.eq_options_of(args)
     dev = coarse._device(device)
     clock = _Clock(timings, dev)
     with torch.cuda.device(dev), clock("setup"):
@@ -438,8 +444,13 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
                     if len(dense):
                         with clock("export"):                    # from the face.obj just written: the file the command line reads
                             frame_dir = os.path.join(out_dir, "%06d" % (t + 1))
-                            projtex.write_frame(frame_dir, meshrender.read_face_obj(os.path.join(frame_dir, "face.obj")), trans_g,
-                                                dense, args.tex_res, proj_opts, pad=tex_pad, sizes=tex_sizes, device=dev)
+                            face_obj = meshrender.read_face_obj(os.path.join(frame_dir, "face.obj"))
+                            if tex_equalize and proj_gains is None:          # the rig's gains, from the first frame written
+                                est = projtex.GainEstimator(args.tex_res, proj_opts, eq_stat, eq_solve, device=dev)
+                                est.add(face_obj, trans_g, dense)
+                                proj_gains = est.finish(os.path.join(out_dir, projtex.GAINS_NAME))
+                            projtex.write_frame(frame_dir, face_obj, trans_g, dense, args.tex_res, proj_opts, pad=tex_pad,
+                                                sizes=tex_sizes, device=dev, gains=proj_gains)
                 state["frames"] = t + 1
                 if on_frame is not None:
                     on_frame(t, state)
@@ -508,8 +519,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--tex_project', action='store_true', default=argparse.SUPPRESS,
                    help="Also write face_proj.png beside every face.obj: the frame's full-size photographs projected into the UV "
                         "layout (topo4d_amd.projtex), with or without --gen_tex; --tex_pad and --tex_sizes apply to it too.")
-    from .projtex import add_options
+    p.add_argument('--tex_equalize', action='store_true', default=argparse.SUPPRESS,
+                   help="With --tex_project: equalise the cameras' exposure and white balance. The gains are estimated on the first "
+                        "frame written, stored as proj_gains.json in the run directory and used for every frame (topo4d_amd.projtex "
+                        "--equalize; --stat_cos_min, --stat_lo, --stat_hi, --eq_prior and --eq_min_overlap as it takes them).")
+    from .projtex import add_eq_options, add_options
     add_options(p, suppress=True)
+    add_eq_options(p, suppress=True)
     return p
 
 
