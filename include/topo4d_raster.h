@@ -685,6 +685,29 @@ int t4d_projtex_pair_stats(const float *pos, const float *nrm, const uint8_t *co
                            const float *const *depth, int32_t power, double cos_min, double fade_px, double depth_tol,
                            double stat_cos_min, double stat_lo, double stat_hi, const double *gains, int64_t *pair_count,
                            int64_t *pair_sum, void *hip_stream);
+/* Two bands (projtex.low_band / project_bands; mode "twoband"): the views never register to the pixel, so a blend of all views
+ * smears the detail and the single best view shows a step where it changes.  The low frequencies are blended over all views and
+ * the detail above them comes from the best view alone (Brown & Lowe's multi-band blending with two bands).  The low-pass runs
+ * on the photographs, not in UV space, where it would run across island borders.
+ * t4d_projtex_low_band: photos [n_views,3,h,w] float32, depth [n_views,1,h,w] float32 (t4d_mesh_render's; the mask is M = depth
+ * > 0), 0 <= radius <= 32 in pixels; low [n_views,3,h,w] float32, not the photographs' own memory.  Per view and channel, in
+ * float64 without FP contraction: A[r][c] = the sum over k = -radius .. radius ascending of photos[r][c + k], taken only where
+ * 0 <= c + k < w and M[r][c + k] (a tap elsewhere is skipped, so a NaN off the mesh stays out), N1[r][c] the number of these
+ * taps; B[r][c] = the sum over k ascending of A[r + k][c] for 0 <= r + k < h, N likewise of N1; low = N > 0 ? float32(B / N) : 0.
+ * Only mesh pixels count, so the background never bleeds into the face at its silhouette; across a self-occlusion edge (nose
+ * over cheek) the box does mix the two surfaces.  With radius 0, low is photos on M and 0 elsewhere.
+ * t4d_project_texture_bands: the inputs of t4d_project_texture_gains and low.  Every view accepted at a texel is sampled as there
+ * (s) and, by the same bilinear mix over the same taps of low and the same gain, in its low band (l).  low_color [tex_h,tex_w,3]
+ * = sum(w l) / sum(w), weight = sum(w), count as there; high [tex_h,tex_w,3] = s - l (one rounded float64 subtraction) and
+ * best_weight [tex_h,tex_w] = w of the view of largest w, the lowest such view on ties.  Every other texel gets zeros.  The
+ * texture is low_color + high.  tests/projtex_bands_ref.py reproduces every bit of both.  Neither call synchronises the stream. */
+int t4d_projtex_low_band(const float *photos, const float *depth, int32_t n_views, int32_t h, int32_t w, int32_t radius, float *low,
+                         void *hip_stream);
+int t4d_project_texture_bands(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                              const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos, const float *low,
+                              const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
+                              double depth_tol, float *low_color, float *weight, uint8_t *count, float *high, float *best_weight,
+                              void *hip_stream);
 
 /* Exact closest point on a triangle soup, or on a bare point cloud, for many query points (csrc/t4d_closest.hip): what
  * topo4d_amd/scanscore.py scores a frame's face.obj against its multi-view-stereo scan with.  It stands in for

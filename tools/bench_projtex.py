@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Projection of the capture photographs into the UV texture (topo4d_amd/projtex.py, csrc/t4d_projtex.hip).  Prints one JSON line.
-    python tools/bench_projtex.py [--res 8192] [--n 513] [--views 24] [--height 3008] [--width 4096] [--equalize]
+    python tools/bench_projtex.py [--res 8192] [--n 513] [--views 24] [--height 3008] [--width 4096] [--equalize | --twoband [--radius 8]]
 The scene: scaffold.scene.uv_mesh(n) as the UV layout, its vertices lifted onto the front of the scaffold's head-sized ellipsoid,
 seen by scaffold.scene.camera_rig (24 views at 4096 x 3008) with random photographs.  kernel_ms: t4d_project_texture alone between
 HIP events on preallocated buffers (min of 6), for both modes.  frame_ms: what one frame costs from the mesh and the photographs
@@ -11,7 +11,11 @@ is timed on the weighted result, the one the frame encodes.  The texture loop th
 --equalize times the camera equalisation instead of the frame, in the same run as kernel_ms: pair_stats_ms is
 t4d_projtex_pair_stats alone on zeroed outputs and project_gains_ms t4d_project_texture_gains (weighted) with the solved gains,
 both between HIP events (min of 6); solve_ms is projtex.solve_gains on the host, the copy of the two tables included (min of 3).
-The photographs are random, so the solved gains say nothing; pair_counts describes the overlap they were solved from."""
+The photographs are random, so the solved gains say nothing; pair_counts describes the overlap they were solved from.
+--twoband times mode "twoband" instead of the frame, in the same run as kernel_ms: low_band_ms is t4d_projtex_low_band over all
+views and project_bands_ms t4d_project_texture_bands, both between HIP events (min of 6); twoband_frame_ms is the frame as above
+with the low bands, the two-band projection and the sum of the bands in the place of the projection, and frame_ms the weighted
+frame of the same run (min of 3 each)."""
 import argparse
 import ctypes as C
 import json
@@ -33,6 +37,8 @@ ap.add_argument("--views", type=int, default=24)
 ap.add_argument("--height", type=int, default=3008)
 ap.add_argument("--width", type=int, default=4096)
 ap.add_argument("--equalize", action="store_true")
+ap.add_argument("--twoband", action="store_true")
+ap.add_argument("--radius", type=int, default=projtex.BAND_DEFAULTS["band_radius"])
 a = ap.parse_args()
 dev = torch.device("cuda", torch.cuda.current_device())
 lib = _lib.load()
@@ -150,6 +156,36 @@ if a.equalize:
     off = pair_count.cpu().numpy()[~np.eye(V, dtype=bool)]
     result["pair_counts"] = {"pairs_with_overlap": int((off > 0).sum() // 2), "max": int(off.max()), "diagonal_mean": int(pair_count.diagonal().float().mean())}
     result["pair_stats_over_kernel"] = round(result["pair_stats_ms"] / result["kernel_ms"]["weighted"], 2)
+    print(json.dumps(result))
+    sys.exit(0)
+if a.twoband:
+    low = torch.empty_like(photos)
+    high = torch.empty_like(color)
+    best_weight = torch.empty_like(weight)
+
+    def low_pass(s):
+        rc = lib.t4d_projtex_low_band(P(photos), P(depth), V, H, W, a.radius, P(low), s)
+        assert rc == 0, _lib.last_error()
+
+    def bands(s):
+        rc = lib.t4d_project_texture_bands(P(pos), P(nrm), P(cov), res, res, P(views), V, H, W, P(photos), P(low), P(depth), None, 2, 0.1,
+                                           16.0, 0.002, P(color), P(weight), P(count), P(high), P(best_weight), s)
+        assert rc == 0, _lib.last_error()
+
+    def twoband_frame():
+        d = depth_maps()
+        p, n, c = maps()
+        lc, _, _, hi, _ = projtex.project_bands(p, n, c, cams, photos, projtex.low_band(photos, d, a.radius), d)
+        return png.encode_png(texfinish.quantize((lc + hi).clamp_(0.0, 1.0)))
+
+    result["radius"] = a.radius
+    result["low_band_ms"] = events_ms(low_pass)
+    result["project_bands_ms"] = events_ms(bands)
+    result["kernel_ms_again"] = events_ms(kernel(0))             # the plain kernel once more, after the others: the run's own spread
+    result["bands_over_kernel"] = round(result["project_bands_ms"] / result["kernel_ms"]["weighted"], 2)
+    del low, high, best_weight
+    result["frame_ms"] = wall_ms(frame)
+    result["twoband_frame_ms"] = wall_ms(twoband_frame)
     print(json.dumps(result))
     sys.exit(0)
 kernel(0)(C.c_void_p(torch.cuda.current_stream().cuda_stream))        # `color` holds the weighted result again

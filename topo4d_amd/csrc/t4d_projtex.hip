@@ -24,6 +24,27 @@
 // count is the number of views that passed 1..5.  A texel nobody sees gets color 0, weight 0, count 0.
 // t4d_project_texture_gains multiplies the sample of step 6 by the view's gain, s = s gains[v][c] (one rounded product), before
 // step 7; k_pair_stats (below) gathers what these gains are solved from.
+//
+// Two bands (t4d_projtex_low_band, t4d_project_texture_bands; the rule is restated in tests/projtex_bands_ref.py): the views never
+// register to the pixel, so "weighted" smears the detail and "best" shows a step where the best view changes.  The low band of
+// every photograph is blended over all views, the detail above it comes from the best view alone.
+// k_low_band, per view and channel, with I the photograph, M = depth > 0 and R the radius (0..32), in float64:
+//   A[r][c] = +0, then for k = -R .. R ascending A = A + I[r][c + k] where 0 <= c + k < W and M[r][c + k]; N1[r][c] counts these taps
+//   (a tap outside M or outside the image is skipped, never multiplied by 0: a NaN there stays out)
+//   B[r][c] = +0, then for k = -R .. R ascending B = B + A[r + k][c] where 0 <= r + k < H; N likewise from N1
+//   low = N > 0 ? float32(B / N) : 0
+// A box over the mesh pixels only, so the background never bleeds into the face at its silhouette; across a self-occlusion edge
+// (nose over cheek) it does mix the two surfaces.  R is in pixels of the photograph.  A workgroup owns a tile of 64 x 32 pixels
+// of one view and channel: it forms A and N1 of the tile's rows -R .. 32 + R in LDS (at R = 32: 96 x 64 doubles, 48 KB), four
+// rows per step through a staged copy of their pixels -R .. 64 + R, then every lane sums its column of A.  The sums are formed
+// tap by tap, never as a running window: that would round differently (the integer counts do slide).
+// k_projtex_bands, per covered texel with a non-zero normal and the views in ascending order: steps 1..6 as above (every accepted
+// view is sampled), then
+//   6b. l = the bilinear mix of step 6 over the same four taps of low, times gains[v][c] when given (one rounded product)
+//   7.  sw = sw + w, sl = sl + w l;  where w > bw (the kept best weight, 0 at first): bw = w, hb = s - l (one rounded subtraction;
+//       ties stay with the lower view)
+// and at the end low_color = float32(sl / sw), weight = float32(sw), high = float32(hb), best_weight = float32(bw), count as
+// above; every other texel gets zeros.  The caller adds the bands: color = low_color + high.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -52,10 +73,11 @@ struct PTP {
 // Steps 1..6 of the rule above for one view of size H x W (photo [3,H,W], depth [H,W], vm its record), shared by k_projtex and
 // k_pair_stats: 0 when the view is rejected; 1 when it is accepted (w and cs are set) but, with `keep`, w is not > keep_above, so
 // that its sample is not wanted (mode "best": a view that cannot win costs no gather of the photograph); 2 with the sample s, times
-// gain[c] when gain is given (one rounded product).
+// gain[c] when gain is given (one rounded product); with `low` ([3,H,W]) also l, the same mix over low's taps (step 6b).
 __device__ __forceinline__ int view_eval(const float *vm, double X, double Y, double Z, double nhx, double nhy, double nhz, int H, int W,
                                          const float *photo, const float *depth, const double *gain, int power, double cos_min,
-                                         double fade_px, double depth_lim, bool keep, double keep_above, double &w_out, double &cs_out, double s[3])
+                                         double fade_px, double depth_lim, bool keep, double keep_above, double &w_out, double &cs_out, double s[3],
+                                         const float *low = nullptr, double *l = nullptr)
 {
 #pragma clang fp contract(off)
     const float *pm = vm + 16;
@@ -106,6 +128,15 @@ __device__ __forceinline__ int view_eval(const float *vm, double X, double Y, do
         const double a = gx * (double)q[0] + fx * (double)q[1], b = gx * (double)q[W] + fx * (double)q[W + 1];
         s[c] = gy * a + fy * b;
         if (gain) s[c] = s[c] * gain[c];
+    }
+    if (low) {                                                              // 6b. the low band under the same taps
+        const float *lp = low + tap;
+        for (int c = 0; c < 3; ++c) {
+            const float *q = lp + (size_t)c * plane;
+            const double a = gx * (double)q[0] + fx * (double)q[1], b = gx * (double)q[W] + fx * (double)q[W + 1];
+            l[c] = gy * a + fy * b;
+            if (gain) l[c] = l[c] * gain[c];
+        }
     }
     return 2;
 }
@@ -284,6 +315,141 @@ __global__ __launch_bounds__(kTile * kTile) void k_pair_stats(const PSP P)
     }
 }
 
+// ---- two bands: the low band of the photographs, and the projection that blends it and keeps the best view's detail -----------
+constexpr int kLowW = 64, kLowH = 32;        // pixels per workgroup of k_low_band: a wave per row, 256 lanes
+constexpr int kLowStep = 4;                  // rows of A formed per step, one per wave
+constexpr int kMaxRadius = 32;
+constexpr int kLowSeg = kLowW + 2 * kMaxRadius;
+
+struct LBP {
+    const float *photos, *depth;
+    float *low;
+    int H, W, R;
+};
+
+static size_t low_band_lds(int R)
+{
+    const size_t rows = (size_t)(kLowH + 2 * R);
+    return rows * kLowW * (sizeof(double) + 1) + (size_t)kLowStep * kLowSeg * sizeof(float);
+}
+
+__global__ __launch_bounds__(kLowW * kLowStep) void k_low_band(const LBP P)
+{
+#pragma clang fp contract(off)
+    extern __shared__ double lds[];
+    const int R = P.R, H = P.H, W = P.W, rows = kLowH + 2 * R, seg = kLowW + 2 * R;
+    double *A = lds;                                                        // [rows][64]: the horizontal sums
+    float *sv = (float *)(A + (size_t)rows * kLowW);                        // [4][128]: the staged pixels of four rows, 0 off the mesh
+    uint8_t *N1 = (uint8_t *)(sv + kLowStep * kLowSeg);                     // [rows][64]: the taps in A (at most 65)
+    const int tid = (int)threadIdx.x, lane = tid % kLowW, wv = tid / kLowW;
+    const int x0 = (int)blockIdx.x * kLowW, y0 = (int)blockIdx.y * kLowH;
+    const size_t plane = (size_t)H * (size_t)W;
+    const float *photo = P.photos + (size_t)blockIdx.z * plane;             // blockIdx.z = 3 view + channel
+    const float *depth = P.depth + (size_t)(blockIdx.z / 3) * plane;
+    const unsigned long long window = 2 * R + 1 >= 64 ? ~0ull : (1ull << (2 * R + 1)) - 1;
+    // A wave forms its row of A from the row's pixels -R .. 64 + R, which it stages itself.  A pixel off the mesh or outside the
+    // image is staged as +0: A starts at +0 and is never -0, so adding +0 leaves every bit as skipping the tap does, and the
+    // pixel itself is not read.  The number of taps is the population of the mask's bits lane .. lane + 2 R.
+    for (int r0 = 0; r0 < rows; r0 += kLowStep) {
+        const int y = y0 - R + r0 + wv;
+        unsigned long long mask[2] = {0ull, 0ull};
+        for (int half = 0; half < 2; ++half) {
+            const int j = lane + half * kLowW, x = x0 - R + j;
+            bool m = false;
+            float val = 0.0f;
+            if (j < seg && y >= 0 && y < H && x >= 0 && x < W) {
+                const size_t at = (size_t)y * (size_t)W + (size_t)x;
+                m = depth[at] > 0.0f;
+                if (m) val = photo[at];
+            }
+            sv[wv * kLowSeg + j] = val;
+            mask[half] = __ballot(m);
+        }
+        const unsigned long long mlo = mask[0], mhi = mask[1];
+        __syncthreads();
+        if (r0 + wv < rows) {
+            const float *pv = sv + wv * kLowSeg + lane;
+            double a = 0.0;
+            for (int k = 0; k <= 2 * R; ++k) a = a + (double)pv[k];
+            const unsigned long long bits = (mlo >> lane) | (lane ? mhi << (64 - lane) : 0ull);      // the mask from pixel `lane` on
+            const int n = __popcll(bits & window) + (R == kMaxRadius ? (int)((mhi >> lane) & 1ull) : 0);
+            A[(size_t)(r0 + wv) * kLowW + lane] = a;
+            N1[(size_t)(r0 + wv) * kLowW + lane] = (uint8_t)n;
+        }
+        __syncthreads();
+    }
+    const int x = x0 + lane;
+    if (x >= W) return;
+    // the vertical pass: a lane sums its column over eight consecutive rows; rows outside the image hold A = +0 and N1 = 0, and
+    // the count, an integer, slides from row to row
+    float *out = P.low + (size_t)blockIdx.z * plane;
+    const int i0 = wv * (kLowH / kLowStep);
+    int n = 0;
+    for (int k = 0; k <= 2 * R; ++k) n += N1[(size_t)(i0 + k) * kLowW + lane];
+    for (int i = i0; i < i0 + kLowH / kLowStep && y0 + i < H; ++i) {
+        const int y = y0 + i;
+        const int klo = R < y ? -R : -y, khi = R < H - 1 - y ? R : H - 1 - y;   // the rows inside the image
+        double b = 0.0;
+        for (int k = klo; k <= khi; ++k) b = b + A[(size_t)(i + k + R) * kLowW + lane];
+        out[(size_t)y * (size_t)W + (size_t)x] = n > 0 ? (float)(b / (double)n) : 0.0f;
+        if (i + 1 < kLowH) n += (int)N1[(size_t)(i + 1 + 2 * R) * kLowW + lane] - (int)N1[(size_t)i * kLowW + lane];
+    }
+}
+
+struct PBP {
+    const float *pos, *nrm, *views, *photos, *low, *depth;
+    const uint8_t *coverage;
+    const double *gains;                     // [V,3] or NULL
+    int th, tw, V, H, W, power;
+    double cos_min, fade_px, depth_lim;
+    float *low_color, *weight, *high, *best_weight;
+    uint8_t *count;
+};
+
+template <bool kGains>
+__global__ __launch_bounds__(kTile * kTile) void k_projtex_bands(const PBP P)
+{
+#pragma clang fp contract(off)
+    const int tx = (int)blockIdx.x * kTile + (int)(threadIdx.x % kTile), ty = (int)blockIdx.y * kTile + (int)(threadIdx.x / kTile);
+    if (tx >= P.tw || ty >= P.th) return;
+    const size_t at = (size_t)ty * (size_t)P.tw + (size_t)tx;
+    double sw = 0.0, bw = 0.0, sl[3] = {0.0, 0.0, 0.0}, hb[3] = {0.0, 0.0, 0.0};
+    int cnt = 0;
+    if (P.coverage[at] != 0) {
+        const double nx = (double)P.nrm[3 * at], ny = (double)P.nrm[3 * at + 1], nz = (double)P.nrm[3 * at + 2];
+        const double nl = sqrt((nx * nx + ny * ny) + nz * nz);
+        if (nl > 0.0) {
+            const double X = (double)P.pos[3 * at], Y = (double)P.pos[3 * at + 1], Z = (double)P.pos[3 * at + 2];
+            const double nhx = nx / nl, nhy = ny / nl, nhz = nz / nl;
+            const size_t plane = (size_t)P.H * (size_t)P.W;
+            for (int v = 0; v < P.V; ++v) {
+                double w, cs, s[3], l[3];
+                if (!view_eval(P.views + (size_t)v * T4D_VIEW_FLOATS, X, Y, Z, nhx, nhy, nhz, P.H, P.W, P.photos + (size_t)v * 3 * plane,
+                               P.depth + (size_t)v * plane, kGains ? P.gains + 3 * v : nullptr, P.power, P.cos_min, P.fade_px,
+                               P.depth_lim, false, 0.0, w, cs, s, P.low + (size_t)v * 3 * plane, l))
+                    continue;
+                ++cnt;
+                // 7. the low band of every view, the detail of the best one
+                sw = sw + w;
+                for (int c = 0; c < 3; ++c) sl[c] = sl[c] + w * l[c];
+                if (w > bw) {
+                    bw = w;
+                    for (int c = 0; c < 3; ++c) hb[c] = s[c] - l[c];
+                }
+            }
+            if (cnt)
+                for (int c = 0; c < 3; ++c) sl[c] = sl[c] / sw;
+        }
+    }
+    for (int c = 0; c < 3; ++c) {
+        P.low_color[3 * at + c] = (float)sl[c];
+        P.high[3 * at + c] = (float)hb[c];
+    }
+    P.weight[at] = (float)sw;
+    P.best_weight[at] = (float)bw;
+    P.count[at] = (uint8_t)cnt;
+}
+
 }  // namespace
 
 static int projtex_check(const char *name, int32_t tex_h, int32_t tex_w, int32_t power, double cos_min, double fade_px, double depth_tol)
@@ -355,4 +521,45 @@ T4D_EXPORT int t4d_projtex_pair_stats(const float *pos, const float *nrm, const 
     const int blocks = P.tiles < kStatGrid ? P.tiles : kStatGrid;
     hipLaunchKernelGGL(k_pair_stats, dim3((unsigned)blocks), dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
     return t4d_launch_status("t4d_projtex_pair_stats");
+}
+
+T4D_EXPORT int t4d_projtex_low_band(const float *photos, const float *depth, int32_t n_views, int32_t h, int32_t w, int32_t radius,
+                                    float *low, void *hip_stream)
+{
+    if (!photos || !depth || !low) return t4d_fail(T4D_ERR_ARG, "t4d_projtex_low_band: NULL buffer");
+    if (h < 1 || w < 1 || h > kMaxDim || w > kMaxDim)
+        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_low_band: need 1 <= sides <= %d, got %d x %d images", kMaxDim, h, w);
+    if (n_views < 1 || n_views > kMaxViews)
+        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_low_band: n_views must be in [1, %d], got %d", kMaxViews, n_views);
+    if (radius < 0 || radius > kMaxRadius)
+        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_low_band: radius must be in [0, %d], got %d", kMaxRadius, radius);
+    if (low == photos) return t4d_fail(T4D_ERR_ARG, "t4d_projtex_low_band: low must not be the photographs themselves");
+    LBP P;
+    P.photos = photos; P.depth = depth; P.low = low; P.H = h; P.W = w; P.R = radius;
+    const dim3 grid((unsigned)((w + kLowW - 1) / kLowW), (unsigned)((h + kLowH - 1) / kLowH), (unsigned)(3 * n_views));
+    hipLaunchKernelGGL(k_low_band, grid, dim3(kLowW * kLowStep), low_band_lds(radius), (hipStream_t)hip_stream, P);
+    return t4d_launch_status("t4d_projtex_low_band");
+}
+
+T4D_EXPORT int t4d_project_texture_bands(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                         const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
+                                         const float *low, const float *depth, const double *gains, int32_t power, double cos_min,
+                                         double fade_px, double depth_tol, float *low_color, float *weight, uint8_t *count,
+                                         float *high, float *best_weight, void *hip_stream)
+{
+    if (!pos || !nrm || !coverage || !views || !photos || !low || !depth || !low_color || !weight || !count || !high || !best_weight)
+        return t4d_fail(T4D_ERR_ARG, "t4d_project_texture_bands: NULL buffer");
+    if (h < 1 || w < 1 || h > kMaxDim || w > kMaxDim)
+        return t4d_fail(T4D_ERR_ARG, "t4d_project_texture_bands: need 1 <= sides <= %d, got %d x %d images", kMaxDim, h, w);
+    if (n_views < 1 || n_views > kMaxViews)
+        return t4d_fail(T4D_ERR_ARG, "t4d_project_texture_bands: n_views must be in [1, %d], got %d", kMaxViews, n_views);
+    if (const int rc = projtex_check("t4d_project_texture_bands", tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
+    PBP P;
+    P.pos = pos; P.nrm = nrm; P.views = views; P.photos = photos; P.low = low; P.depth = depth; P.coverage = coverage; P.gains = gains;
+    P.th = tex_h; P.tw = tex_w; P.V = n_views; P.H = h; P.W = w; P.power = power;
+    P.cos_min = cos_min; P.fade_px = fade_px; P.depth_lim = 1.0 + depth_tol;
+    P.low_color = low_color; P.weight = weight; P.high = high; P.best_weight = best_weight; P.count = count;
+    const dim3 grid((unsigned)((tex_w + kTile - 1) / kTile), (unsigned)((tex_h + kTile - 1) / kTile));
+    hipLaunchKernelGGL(gains ? k_projtex_bands<true> : k_projtex_bands<false>, grid, dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
+    return t4d_launch_status("t4d_project_texture_bands");
 }

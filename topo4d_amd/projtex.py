@@ -3,6 +3,8 @@ The capture photographs projected into a frame's UV texture on the GPU, over csr
 states the per-texel rule; tests/projtex_ref.py restates it in numpy bit for bit):
 
     project(pos, nrm, coverage, cams, photos, depth, ...)   -> (color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8)
+    low_band(photos, depth, radius)                         -> low [V,3,H,W] float32: each photograph's box mean over its mesh pixels
+    project_bands(pos, nrm, coverage, cams, photos, low, depth, ...) -> (low_color, weight, count, high, best_weight): mode "twoband"
     surface_maps(face_obj, vertices, res, device)           -> (pos [h,w,3], nrm [h,w,3], coverage [h,w]) of a face.obj's UV layout
     project_frame(face_obj, vertices, dataset, res, ...)    -> (texture [h,w,3] uint8, weight, count): one frame from its views
     pair_stats(pos, nrm, coverage, groups, ...)             -> (count [V,V], sums [V,V,3]) int64: what the cameras share, per pair
@@ -16,6 +18,16 @@ faded over fade_px pixels towards the image edge; mode="best" keeps the single v
 conventional choices, not tuned on a capture.  Unlike face.png (the texture loop's Gaussian-filtered
 colour field) this is the photographs themselves.  There is no CPU path.
 
+Calibration, the tracked mesh and the lens model are never exact to the pixel, so the views disagree by a pixel or two: "weighted"
+then smears the detail the photographs carry, and "best" shows a step wherever the best view changes, since what equalisation
+leaves (shading, vignetting) is no gain per camera.  mode="twoband" (project_frame, both command lines) takes the next step of
+stitchers and photogrammetry texturing (Brown & Lowe's multi-band blending, Baumberg's two-band texture blending): low_band
+low-passes every photograph with a box of band_radius pixels over its mesh pixels, project_bands blends these low bands over all
+views as "weighted" does and takes the detail above them, photograph minus low band, from the best view alone; the texture is the
+sum.  The low-pass runs on the photographs, since a blur in UV space would run across island borders.  Known limit: across a
+self-occlusion edge (nose over cheek) the box mixes the two surfaces.  band_radius = 8 is a conventional choice, not tuned on a
+capture, and is in pixels of the photograph.
+
 The cameras of a rig never agree exactly in exposure and white balance, and a blend of unequal cameras shows a step wherever the
 set of contributing views changes.  pair_stats counts, for every pair of cameras, the texels both see and sums each camera's
 samples there (integers, so the result is the same bits in any order); solve_gains finds the gain per camera and channel that
@@ -23,7 +35,7 @@ makes the pairs agree in the least-squares sense (the gain compensation of panor
 project_frame take these gains.  Exposure belongs to the rig, not to a frame: one set of gains serves a whole run.
 
 `python -m topo4d_amd.projtex -e EXP -s SEQ [-id ... -did ... -od ... -dr N] [--frames 1-10] [--views A,B] [--set low|dense]
-[--undistort] [--tex_res R] [--mode weighted|best] [--power P --cos_min C --fade_px F --depth_tol T] [--tex_pad R]
+[--undistort] [--tex_res R] [--mode weighted|best|twoband [--band_radius R]] [--power P --cos_min C --fade_px F --depth_tol T] [--tex_pad R]
 [--tex_sizes 2048,1024] [--save_weight] [--equalize [--equalize_frames 1-10] | --gains FILE] [--stat_cos_min C --stat_lo L
 --stat_hi H --eq_prior P --eq_min_overlap N]` works on an output tree that already exists (the reference's too): it writes
 %06d/face_proj.png (and face_proj_<size>.png) beside every frame's face.obj, with --save_weight also face_proj_weight.png (the
@@ -49,8 +61,10 @@ from ._lib import ptr
 
 T4D_PROJTEX_WEIGHTED, T4D_PROJTEX_BEST = 0, 1
 _MODES = {"weighted": T4D_PROJTEX_WEIGHTED, "best": T4D_PROJTEX_BEST}
-MAX_POWER, MAX_VIEWS = 8, 255
+MODES = (*_MODES, "twoband")                                   # "twoband" is project_bands', not a mode of the one kernel
+MAX_POWER, MAX_VIEWS, MAX_BAND_RADIUS = 8, 255, 32
 DEFAULTS = dict(power=2, cos_min=0.1, fade_px=16.0, depth_tol=0.002, mode="weighted")
+BAND_DEFAULTS = dict(band_radius=8)
 FILE_NAME, WEIGHT_NAME = "face_proj.png", "face_proj_weight.png"
 MAX_STAT_VIEWS, MAX_STAT = 32, 1024.0                          # pair_stats: a 32-bit mask of views per texel; |stat_lo|, |stat_hi|
 STAT_DEFAULTS = dict(stat_cos_min=0.5, stat_lo=0.02, stat_hi=0.98)
@@ -60,8 +74,8 @@ GAINS_NAME = "proj_gains.json"
 
 def check_options(power=2, cos_min=0.1, fade_px=16.0, depth_tol=0.002, mode="weighted") -> None:
     """ValueError for a parameter project would refuse (callable without a device)."""
-    if mode not in _MODES:
-        raise ValueError(f"mode must be 'weighted' or 'best', got {mode!r}")
+    if mode not in MODES:
+        raise ValueError(f"mode must be 'weighted', 'best' or 'twoband', got {mode!r}")
     if isinstance(power, bool) or int(power) != power or not 0 <= int(power) <= MAX_POWER:
         raise ValueError(f"power must be an integer in [0, {MAX_POWER}], got {power!r}")
     if not -1.0 <= float(cos_min) <= 1.0:
@@ -70,6 +84,13 @@ def check_options(power=2, cos_min=0.1, fade_px=16.0, depth_tol=0.002, mode="wei
         raise ValueError(f"fade_px must be in [0, 65536], got {fade_px!r}")
     if not 0.0 <= float(depth_tol) <= 1.0:
         raise ValueError(f"depth_tol must be in [0, 1], got {depth_tol!r}")
+
+
+def check_band_options(band_radius=8) -> None:
+    """ValueError for a radius low_band would refuse (callable without a device)."""
+    if isinstance(band_radius, bool) or not isinstance(band_radius, (int, float, np.integer, np.floating)) \
+            or int(band_radius) != band_radius or not 0 <= int(band_radius) <= MAX_BAND_RADIUS:
+        raise ValueError(f"band_radius must be an integer in [0, {MAX_BAND_RADIUS}], got {band_radius!r}")
 
 
 def check_stat_options(stat_cos_min=0.5, stat_lo=0.02, stat_hi=0.98) -> None:
@@ -117,6 +138,8 @@ def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, 
     them; photos [V,3,H,W] float32; depth [V,1,H,W] float32, MeshRenderer.render's (0: empty).  Everything on one HIP device.  gains [V,3] (None: none): view v's
     sample is multiplied by gains[v] in the kernel, in float64; no scaled copy of the photographs is made."""
     check_options(power, cos_min, fade_px, depth_tol, mode)
+    if mode not in _MODES:
+        raise ValueError(f"mode {mode!r} has five outputs and takes the low bands: it is project_bands'")
     if not isinstance(pos, torch.Tensor) or pos.dim() != 3 or pos.shape[2] != 3 or pos.shape[0] < 1 or pos.shape[1] < 1:
         raise ValueError(f"pos must be a float32 [h,w,3] tensor, got {list(getattr(pos, 'shape', ()))}")
     h, w = int(pos.shape[0]), int(pos.shape[1])
@@ -148,6 +171,74 @@ def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, 
               int(power), float(cos_min), float(fade_px), float(depth_tol), _MODES[mode], ptr(color), ptr(weight), ptr(count),
               _lib.stream(dev))
     return color, weight, count
+
+
+def low_band(photos: torch.Tensor, depth: torch.Tensor, radius: int = 8) -> torch.Tensor:
+    """low [V,3,H,W] float32: every photograph's mean over the (2 radius + 1)^2 box, counted over the mesh pixels alone (depth >
+    0), so that the background never bleeds into the face at its silhouette; 0 where the box holds no mesh pixel.  photos [V,3,H,W]
+    float32, depth [V,1,H,W] float32 (MeshRenderer.render's), on one HIP device; radius an integer in [0, 32], in pixels.  A pixel
+    off the mesh is never read (a NaN there stays out); with radius 0 the result is the photographs on the mesh and 0 elsewhere.
+    The box is separable, rows first, in float64 (csrc/t4d_projtex.hip states the order; tests/projtex_bands_ref.py restates it
+    bit for bit).  Known limit: across a self-occlusion edge the box mixes the two surfaces."""
+    check_band_options(radius)
+    if not isinstance(photos, torch.Tensor) or photos.dim() != 4 or photos.shape[1] != 3 or min(photos.shape) < 1:
+        raise ValueError(f"photos must be a float32 [V,3,H,W] tensor, got {list(getattr(photos, 'shape', ()))}")
+    V, _, H, W = (int(x) for x in photos.shape)
+    if V > MAX_VIEWS or H > 65536 or W > 65536:
+        raise ValueError(f"at most {MAX_VIEWS} views of sides up to 65536 per call, got {V} of {H} x {W}")
+    _map(photos, "photos", (V, 3, H, W), torch.float32)
+    _map(depth, "depth", (V, 1, H, W), torch.float32)
+    if depth.device != photos.device:
+        raise ValueError(f"depth must live on photos' device {photos.device}, got {depth.device}")
+    if not photos.is_cuda:                                     # argument errors first, with or without a device
+        raise RuntimeError("topo4d_amd has no CPU path: the photographs and the depth must live on a HIP device")
+    photos, depth = photos.contiguous(), depth.contiguous()
+    low = torch.empty_like(photos)
+    _lib.call("t4d_projtex_low_band", ptr(photos), ptr(depth), V, H, W, int(radius), ptr(low), _lib.stream(photos.device))
+    return low
+
+
+def project_bands(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, photos: torch.Tensor, low: torch.Tensor,
+                  depth: torch.Tensor, *, power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0, depth_tol: float = 0.002,
+                  gains=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(low_color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8, high [h,w,3] float32, best_weight [h,w] float32): the
+    two bands of mode "twoband".  The arguments of project and low [V,3,H,W] float32, low_band's.  Every view that project would
+    accept at a texel gives its sample s and, by the same bilinear mix over the same taps of low, its low band l (both times
+    gains[v] when given).  low_color, weight, count: the blend of the l as mode "weighted" blends the s.  high = s - l and
+    best_weight = the weight of the view mode "best" would keep.  The texture is low_color + high; zeros where no view counts."""
+    check_options(power, cos_min, fade_px, depth_tol)
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 3 or pos.shape[2] != 3 or pos.shape[0] < 1 or pos.shape[1] < 1:
+        raise ValueError(f"pos must be a float32 [h,w,3] tensor, got {list(getattr(pos, 'shape', ()))}")
+    h, w = int(pos.shape[0]), int(pos.shape[1])
+    _map(pos, "pos", (h, w, 3), torch.float32)
+    _map(nrm, "nrm", (h, w, 3), torch.float32)
+    if not isinstance(coverage, torch.Tensor) or coverage.dtype not in (torch.uint8, torch.bool) or tuple(coverage.shape) != (h, w):
+        raise ValueError(f"coverage must be a uint8 or bool [{h},{w}] tensor")
+    dev = pos.device
+    from .meshrender import _views
+    views, H, W = _views(cams, dev)
+    V = int(views.shape[0])
+    if V > MAX_VIEWS:
+        raise ValueError(f"at most {MAX_VIEWS} views per call, got {V}")
+    _map(photos, "photos", (V, 3, H, W), torch.float32)
+    _map(low, "low", (V, 3, H, W), torch.float32)
+    _map(depth, "depth", (V, 1, H, W), torch.float32)
+    g = _gains(gains, V)
+    for name, t in (("nrm", nrm), ("coverage", coverage), ("photos", photos), ("low", low), ("depth", depth)):
+        if t.device != dev:
+            raise ValueError(f"{name} must live on pos's device {dev}, got {t.device}")
+    if not pos.is_cuda:                                        # argument errors first, with or without a device
+        raise RuntimeError("topo4d_amd has no CPU path: the maps, the photographs, their low bands and the depth must live on a HIP device")
+    cov = (coverage.to(torch.uint8) if coverage.dtype == torch.bool else coverage).contiguous()
+    pos, nrm, photos, low, depth = pos.contiguous(), nrm.contiguous(), photos.contiguous(), low.contiguous(), depth.contiguous()
+    low_color, high = (torch.empty(h, w, 3, dtype=torch.float32, device=dev) for _ in range(2))
+    weight, best_weight = (torch.empty(h, w, dtype=torch.float32, device=dev) for _ in range(2))
+    count = torch.empty(h, w, dtype=torch.uint8, device=dev)
+    g = None if g is None else torch.from_numpy(g).to(dev)
+    _lib.call("t4d_project_texture_bands", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(low), ptr(depth),
+              ptr(g), int(power), float(cos_min), float(fade_px), float(depth_tol), ptr(low_color), ptr(weight), ptr(count), ptr(high),
+              ptr(best_weight), _lib.stream(dev))
+    return low_color, weight, count, high, best_weight
 
 
 def pair_stats(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, groups, *, gains=None, out=None, stat_cos_min: float = 0.5,
@@ -311,15 +402,18 @@ def surface_maps(face_obj, vertices: torch.Tensor, res, device=None):
 
 
 def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0,
-                  depth_tol: float = 0.002, mode: str = "weighted", gains=None, device=None):
+                  depth_tol: float = 0.002, mode: str = "weighted", gains=None, device=None, band_radius: int = 8):
     """(texture [h,w,3] uint8, weight [h,w] float32, count [h,w] uint8) of one frame: `dataset` holds ingest.get_dataset's entries
     ("cam", "im"), vertices [N,3] the mesh in the training world frame.  The mesh is rendered once for the depth maps
     (meshrender.MeshRenderer over a 1x1 dummy texture), surface_maps gives the texel maps, project gathers, texfinish.quantize
     rounds as the PNG encoder does.  Views of one size go in one launch; a rig with several sizes (turned cameras) is merged
     per size: weighted sums add up, "best" keeps the larger weight, the earlier size on ties.  gains [len(dataset),3] (None: none):
-    one row per entry of `dataset`, in its order."""
+    one row per entry of `dataset`, in its order.  mode "twoband": per size low_band (band_radius) and project_bands; the low bands
+    merge as "weighted" does, the detail by the larger best weight (the earlier size on ties), and the texture is their sum, one
+    float32 addition, clamped to [0, 1] (where the views disagree the sum overshoots, and the quantisation wraps)."""
     from . import meshrender, texfinish
     check_options(power, cos_min, fade_px, depth_tol, mode)
+    check_band_options(band_radius)
     if not dataset:
         raise ValueError("project_frame: no views")
     gains = _gains(gains, len(dataset))
@@ -327,13 +421,23 @@ def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power: int 
     dev = meshrender._device(device if device is not None else (vertices.device if vertices.is_cuda else None))
     renderer = meshrender.MeshRenderer(faces, uv_faces, face_obj.uvs, np.zeros((1, 1, 3), np.uint8), device=dev)
     pos, nrm, cov = surface_maps(face_obj, vertices, res, device=dev)
-    total = None
+    total, detail = None, None
     for ks in _size_groups(dataset).values():
         cams = [dataset[k]["cam"] for k in ks]
         _, depth, _ = renderer.render(vertices, cams)
         photos = torch.stack([dataset[k]["im"] for k in ks]).to(torch.float32)
-        color, weight, count = project(pos, nrm, cov, cams, photos, depth, power=power, cos_min=cos_min, fade_px=fade_px,
-                                       depth_tol=depth_tol, mode=mode, gains=None if gains is None else gains[ks])
+        if mode == "twoband":
+            color, weight, count, high, best = project_bands(pos, nrm, cov, cams, photos, low_band(photos, depth, band_radius), depth,
+                                                             power=power, cos_min=cos_min, fade_px=fade_px, depth_tol=depth_tol,
+                                                             gains=None if gains is None else gains[ks])
+            if detail is None:
+                detail = [high, best]
+            else:
+                take = best > detail[1]
+                detail = [torch.where(take[..., None], high, detail[0]), torch.where(take, best, detail[1])]
+        else:
+            color, weight, count = project(pos, nrm, cov, cams, photos, depth, power=power, cos_min=cos_min, fade_px=fade_px,
+                                           depth_tol=depth_tol, mode=mode, gains=None if gains is None else gains[ks])
         if total is None:
             total = [color, weight, count]
             continue
@@ -346,6 +450,8 @@ def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power: int 
             mixed = (c0 * w0[..., None] + color * weight[..., None]) / ws.clamp_min(torch.finfo(torch.float32).tiny)[..., None]
             total = [torch.where((ws > 0)[..., None], mixed, torch.zeros_like(mixed)), ws, n0 + count]
     color, weight, count = total
+    if detail is not None:                                     # the sum of two bands can leave [0, 1], and quantize wraps as numpy's cast does
+        color = (color + detail[0]).clamp_(0.0, 1.0)
     return texfinish.quantize(color), weight, count
 
 
@@ -358,12 +464,13 @@ def _size_groups(dataset) -> dict:
 
 def frame_stats(face_obj, vertices: torch.Tensor, dataset, res, *, out=None, stat_cos_min: float = 0.5, stat_lo: float = 0.02,
                 stat_hi: float = 0.98, power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0, depth_tol: float = 0.002,
-                mode: str = "weighted", device=None):
+                mode: str = "weighted", device=None, band_radius: int = 8):
     """pair_stats of one frame, its views numbered as in `dataset`: the maps of surface_maps, the depth renders of project_frame.
-    out: the statistics of earlier frames of the same cameras, added to.  (mode is accepted and ignored, so that one dictionary
-    of projection options serves project_frame and this.)"""
+    out: the statistics of earlier frames of the same cameras, added to.  (mode and band_radius are accepted and ignored, so that
+    one dictionary of projection options serves project_frame and this.)"""
     from . import meshrender
     check_options(power, cos_min, fade_px, depth_tol, mode)
+    check_band_options(band_radius)
     check_stat_options(stat_cos_min, stat_lo, stat_hi)
     if not dataset:
         raise ValueError("frame_stats: no views")
@@ -464,8 +571,9 @@ def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: 
 def add_options(p: argparse.ArgumentParser, suppress: bool = False) -> None:
     """--mode and the four parameters, on the parser of this module and (suppress=True: absent unless given) of train."""
     d = (lambda v: argparse.SUPPRESS) if suppress else (lambda v: v)
-    p.add_argument("--mode", choices=tuple(_MODES), default=d(DEFAULTS["mode"]),
-                   help="Projection: blend the views that see a texel by their weights, or keep the best one (default weighted).")
+    p.add_argument("--mode", choices=MODES, default=d(DEFAULTS["mode"]),
+                   help="Projection: blend the views that see a texel by their weights, keep the best one, or blend the photographs' "
+                        "low band and take the detail from the best view (default weighted).")
     p.add_argument("--power", type=int, default=d(DEFAULTS["power"]), help=f"Projection: weight = cos^power, 0..{MAX_POWER} (default 2).")
     p.add_argument("--cos_min", type=float, default=d(DEFAULTS["cos_min"]),
                    help="Projection: drop a view whose viewing direction makes a cosine below this with the normal (default 0.1).")
@@ -477,6 +585,17 @@ def add_options(p: argparse.ArgumentParser, suppress: bool = False) -> None:
 
 def options_of(args) -> dict:
     return {k: getattr(args, k, v) for k, v in DEFAULTS.items()}
+
+
+def add_band_options(p: argparse.ArgumentParser, suppress: bool = False) -> None:
+    """The parameter of --mode twoband, beside add_options' on both parsers."""
+    d = (lambda v: argparse.SUPPRESS) if suppress else (lambda v: v)
+    p.add_argument("--band_radius", type=int, default=d(BAND_DEFAULTS["band_radius"]), metavar="R",
+                   help=f"With --mode twoband: the low band is the photograph's mean over a box of 2R+1 pixels, 0..{MAX_BAND_RADIUS} (default 8).")
+
+
+def band_options_of(args) -> dict:
+    return {k: getattr(args, k, v) for k, v in BAND_DEFAULTS.items()}
 
 
 def add_eq_options(p: argparse.ArgumentParser, suppress: bool = False) -> None:
@@ -556,6 +675,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--undistort", action="store_true",
                    help="Undistort the photographs by the lens calibration of cameras.xml, as topo4d_amd.train --undistort does.")
     add_options(p)
+    add_band_options(p)
     p.add_argument("--equalize", action="store_true",
                    help="Equalise the cameras' exposure and white balance: estimate one gain per camera and channel, write "
                         "proj_gains.json into the run directory and project every frame with these gains.")
@@ -574,8 +694,11 @@ def build_parser() -> argparse.ArgumentParser:
 def _check_args(args, res: int) -> dict:
     from . import texfinish
     opts = options_of(args)
+    if opts["mode"] == "twoband":                              # (only then: the options are recorded in proj_gains.json)
+        opts.update(band_options_of(args))
     try:
-        check_options(**opts)
+        check_options(**{k: opts[k] for k in DEFAULTS})
+        check_band_options(**band_options_of(args))
         texfinish.check_options(getattr(args, "tex_pad", 0), 0, getattr(args, "tex_sizes", ()), res)
     except ValueError as e:
         raise SystemExit(f"projection options: {e}") from None

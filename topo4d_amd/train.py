@@ -22,7 +22,7 @@ exported undistorted), and --low_from_full makes the geometry inputs from the fu
 means, so that -id holds cameras.xml, the mesh and the masks only; with --gen_tex, --tex_pad R fills a gutter of R texels round
 the UV islands of face.png and --tex_sizes 4096,2048 also writes face_<size>.png (texfinish.finish); --tex_project writes
 face_proj.png beside every face.obj, the frame's full-size photographs projected into the UV layout (projtex, with or without
---gen_tex; --mode, --power, --cos_min, --fade_px and --depth_tol as python -m topo4d_amd.projtex takes them; --tex_equalize
+--gen_tex; --mode, --band_radius, --power, --cos_min, --fade_px and --depth_tol as python -m topo4d_amd.projtex takes them; --tex_equalize
 estimates one gain per camera and channel on the first frame written, stores proj_gains.json in the run directory and projects
 every frame with it).  Without them nothing changes.
 
@@ -523,8 +523,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="With --tex_project: equalise the cameras' exposure and white balance. The gains are estimated on the first "
                         "frame written, stored as proj_gains.json in the run directory and used for every frame (topo4d_amd.projtex "
                         "--equalize; --stat_cos_min, --stat_lo, --stat_hi, --eq_prior and --eq_min_overlap as it takes them).")
-    from .projtex import add_eq_options, add_options
+    from .projtex import add_band_options, add_eq_options, add_options
     add_options(p, suppress=True)
+    add_band_options(p, suppress=True)
     add_eq_options(p, suppress=True)
     return p
 
