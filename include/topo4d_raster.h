@@ -432,6 +432,25 @@ int t4d_texture_pad(const uint8_t *image, const uint8_t *coverage, int32_t h, in
 int t4d_texture_halve(const uint8_t *image, const uint8_t *coverage, int32_t h, int32_t w, int32_t c, uint8_t *out_image,
                       uint8_t *out_coverage, void *hip_stream);
 
+/* Hole filling by push-pull (texfinish.fill, csrc/t4d_texfill.hip), of the same family and under the same conventions: the texels
+ * of a projected texture that no camera saw take a smooth interpolation of the texels round them.  image uint8 [h,w,c]; valid
+ * uint8 [h,w], non-zero = the texel has a colour; domain uint8 [h,w], non-zero = the texel wants a colour, NULL = every texel;
+ * out_image [h,w,c]; out_filled uint8 [h,w], holding 0 or 1.  Pyramid colours are integers in units of 1/256 of an 8-bit step.
+ * Level 0: C0 = 256 image where valid, V0 = valid != 0.
+ * Pull: level k+1 has the size ceil(h_k / 2) x ceil(w_k / 2); for each 2x2 block (children outside the level do not exist) n = its
+ * valid children and s = the sum of their colours per channel: V = n > 0 and C = (2 s + n) / (2 n) in integer division
+ * (t4d_texture_halve's round half up).  Levels continue until the level is 1x1.
+ * No valid texel at all: out_image = image and out_filled = 0.
+ * Push, from the level below the top down to level 0: a texel (x, y) with V = 0 takes
+ * (9 P[py][px] + 3 P[py][nx] + 3 P[ny][px] + P[ny][nx] + 8) >> 4 of the completed level above, P, where px = x >> 1, py = y >> 1,
+ * nx = px + 1 for odd x and px - 1 for even x, ny likewise, both clamped to P's bounds; a texel with V = 1 keeps its pulled colour.
+ * Output: a texel in the domain and not valid gets (C0 + 128) >> 8 and out_filled = 1; every other texel is copied through with
+ * out_filled = 0.  A filled value lies between the smallest and the largest valid value of its channel.
+ * Scratch: t4d_texture_fill_scratch_bytes(h, w, c) (0 and a message for a bad shape); T4D_ERR_STATE_SIZE when it is smaller. */
+size_t t4d_texture_fill_scratch_bytes(int32_t h, int32_t w, int32_t c);
+int t4d_texture_fill(const uint8_t *image, const uint8_t *valid, const uint8_t *domain, int32_t h, int32_t w, int32_t c,
+                     uint8_t *out_image, uint8_t *out_filled, void *scratch, size_t scratch_bytes, void *hip_stream);
+
 /* Lossless PNG encoder for a device image (write_texture(..., encoder="gpu"): the last CPU step of save_mesh, helpers.py:953-960).
  * image [h,w,c] on the device, uint8 (is_float32 = 0) or float32 (is_float32 = 1, quantised exactly like numpy's
  * (x*255).astype(np.uint8) on x86-64: truncation toward zero to int32, low byte kept, NaN -> 0); c in {1, 3, 4} gives colour

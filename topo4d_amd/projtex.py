@@ -10,6 +10,8 @@ states the per-texel rule; tests/projtex_ref.py restates it in numpy bit for bit
     pair_stats(pos, nrm, coverage, groups, ...)             -> (count [V,V], sums [V,V,3]) int64: what the cameras share, per pair
     solve_gains(count, sums, ...)                           -> float64 [V,3]: one gain per camera and channel, on the host
     estimate_gains(face_obj, vertices, dataset, res, ...)   -> (gains, report) of one frame; write_gains / read_gains: proj_gains.json
+    uv_islands(face_obj)                                    -> int [n_uv]: the UV island of every UV vertex, numbered from 1 (host)
+    island_labels(face_obj, h, w, device)                   -> uint8 [h,w]: the island of every texel, 0 outside the coverage
 
 Every texel is coloured from the cameras that see it: a view counts when the texel's point projects inside its photograph,
 in front of the near plane, is not hidden (the depth map of meshrender.MeshRenderer.render, within depth_tol) and faces the
@@ -36,13 +38,19 @@ project_frame take these gains.  Exposure belongs to the rig, not to a frame: on
 
 `python -m topo4d_amd.projtex -e EXP -s SEQ [-id ... -did ... -od ... -dr N] [--frames 1-10] [--views A,B] [--set low|dense]
 [--undistort] [--tex_res R] [--mode weighted|best|twoband [--band_radius R]] [--power P --cos_min C --fade_px F --depth_tol T] [--tex_pad R]
-[--tex_sizes 2048,1024] [--save_weight] [--equalize [--equalize_frames 1-10] | --gains FILE] [--stat_cos_min C --stat_lo L
+[--tex_sizes 2048,1024] [--save_weight] [--tex_fill] [--equalize [--equalize_frames 1-10] | --gains FILE] [--stat_cos_min C --stat_lo L
 --stat_hi H --eq_prior P --eq_min_overlap N]` works on an output tree that already exists (the reference's too): it writes
 %06d/face_proj.png (and face_proj_<size>.png) beside every frame's face.obj, with --save_weight also face_proj_weight.png (the
 8-bit count of contributing views).  By default it projects the full-size photographs of the cameras training uses.
 --equalize gathers the pair statistics over --equalize_frames (default: the first frame projected), solves once, writes
 proj_gains.json into the run directory and projects every frame with these gains; --gains FILE takes a saved file instead.
 `python -m topo4d_amd.train --tex_project` writes the same file while the run is made; with --tex_equalize it estimates the gains on the first frame it writes.
+
+project and project_bands write zeros where no view counts: under the chin, in the nostrils, behind the ears.  --tex_fill (both
+command lines; write_frame(fill=True)) fills these texels island by island with texfinish.fill_islands over island_labels, the
+push-pull interpolation of the island's projected texels, before the gutter and the smaller levels are made; an island no view
+sees at all stays black, and face_proj_weight.png still holds the count, so its zeros inside an island mark what was filled.
+Known limit: the fill interpolates in UV space and knows nothing of the surface, so a large hole comes out smooth, not plausible.
 """
 from __future__ import annotations
 
@@ -401,6 +409,56 @@ def surface_maps(face_obj, vertices: torch.Tensor, res, device=None):
     return pos, nrm, texfinish.coverage_from_obj(face_obj, h, w, device=dev)
 
 
+def uv_islands(face_obj) -> np.ndarray:
+    """int64 [n_uv]: the UV island of every UV vertex (host).  The islands are the connected components of the triangulated
+    uv_faces over shared UV-vertex indices, numbered from 1 in the order of each component's lowest face index; 0 for a UV vertex
+    no face names.  More than 255 islands (a label is a uint8) is a ValueError."""
+    from . import meshrender
+    _, uv_tris = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
+    n_uv = len(face_obj.uvs)
+    if uv_tris.size and (uv_tris.min() < 0 or uv_tris.max() >= n_uv):
+        raise ValueError(f"uv_faces name UV vertex {int(uv_tris.max())} but the mesh has {n_uv}")
+    parent = list(range(n_uv))
+
+    def root(a: int) -> int:
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    for a, b, c in uv_tris.tolist():
+        ra = root(a)
+        for other in (b, c):
+            ro = root(other)
+            if ro != ra:
+                parent[ro] = ra
+    number, ids = {}, np.zeros(n_uv, np.int64)
+    for a, _, _ in uv_tris.tolist():                           # in face order: a component is numbered when its first face comes
+        r = root(a)
+        if r not in number:
+            number[r] = len(number) + 1
+    if len(number) > 255:
+        raise ValueError(f"the UV layout has {len(number)} islands; island_labels holds at most 255")
+    for v in np.unique(uv_tris).tolist():
+        ids[v] = number[root(v)]
+    return ids
+
+
+def island_labels(face_obj, h: int, w: int, device=None) -> torch.Tensor:
+    """uint8 [h,w]: the uv_islands number of the island every texel belongs to, 0 where texfinish.coverage_from_obj is 0.  The
+    numbers are rasterised by texture.render_colors as a vertex attribute: one constant per island, which the interpolation gives
+    back to within rounding, so the nearest integer is exact."""
+    from . import meshrender, texfinish, texture
+    h, w = _size((h, w))
+    ids = uv_islands(face_obj)                                 # argument errors first, with or without a device
+    dev = meshrender._device(device)
+    _, uv_tris = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
+    uv_verts = texture.process_uv(face_obj.uvs, h, w)
+    img = texture.render_colors(uv_verts, uv_tris, ids.astype(np.float32)[:, None], h, w, c=1, device=dev)
+    labels = torch.round(img[..., 0]).clamp_(0, 255).to(torch.uint8)
+    return torch.where(texfinish.coverage_from_obj(face_obj, h, w, device=dev) != 0, labels, torch.zeros_like(labels))
+
+
 def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0,
                   depth_tol: float = 0.002, mode: str = "weighted", gains=None, device=None, band_radius: int = 8):
     """(texture [h,w,3] uint8, weight [h,w] float32, count [h,w] uint8) of one frame: `dataset` holds ingest.get_dataset's entries
@@ -542,11 +600,13 @@ def _names(dataset) -> list:
 
 
 def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: int = 0, sizes=(), save_weight: bool = False,
-                device=None, gains=None) -> list:
+                device=None, gains=None, fill: bool = False) -> list:
     """One frame's face_proj.png (and face_proj_<size>.png, face_proj_weight.png) in `frame_dir`, from the face.obj read there:
     what the command line and train --tex_project both call.  Returns the files written.  The gutter of `pad` texels is filled
     from the texels some view contributed to (count > 0), through texfinish.finish.  gains: None, or
-    {camera name: [r, g, b]} holding every camera of `dataset`."""
+    {camera name: [r, g, b]} holding every camera of `dataset`.  fill: the texels of an island that no view contributed to take the
+    push-pull interpolation of that island's projected texels (texfinish.fill_islands over island_labels) and count as projected
+    for the gutter and the smaller levels; face_proj_weight.png is unchanged, so its zeros inside an island mark what was filled."""
     from . import texfinish
     from .evaluate import training_vertices
     from .png import write_png
@@ -558,7 +618,11 @@ def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: 
             raise ValueError(f"no gains for camera(s) {', '.join(missing)}")
         gains = np.asarray([gains[n] for n in _names(dataset)], dtype=np.float64)
     tex, _, count = project_frame(face_obj, verts, dataset, res, device=dev, gains=gains, **options)
-    levels = texfinish.finish(tex, (count > 0).to(torch.uint8), pad=pad, erode=0, sizes=sizes)
+    seen = (count > 0).to(torch.uint8)
+    if fill:
+        tex, filled = texfinish.fill_islands(tex, seen, island_labels(face_obj, tex.shape[0], tex.shape[1], device=dev))
+        seen |= filled
+    levels = texfinish.finish(tex, seen, pad=pad, erode=0, sizes=sizes)
     written = texfinish.write_levels(os.path.join(frame_dir, FILE_NAME), levels)
     if save_weight:
         path = os.path.join(frame_dir, WEIGHT_NAME)
@@ -688,6 +752,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--tex_sizes", type=_size_list, default=[],
                    help="Smaller levels to write too, comma-separated, each tex_res / 2^k: face_proj_<size>.png.")
     p.add_argument("--save_weight", action="store_true", help="Also write %%06d/face_proj_weight.png: the number of views per texel.")
+    p.add_argument("--tex_fill", action="store_true",
+                   help="Fill the texels of every UV island that no view sees by push-pull from the island's projected texels "
+                        "(texfinish.fill_islands); the gutter and the smaller levels are then built from the filled texture.")
     return p
 
 
@@ -776,7 +843,8 @@ def project_tree(args, device=None) -> list:
                 if gains is not None and any(n not in gains for n in _names(dataset)):
                     raise SystemExit(f"equalisation: no gains for camera(s) {', '.join(n for n in _names(dataset) if n not in gains)}")
                 written += write_frame(os.path.join(run_dir, "%06d" % t), obj, trans_g, dataset, args.tex_res, opts,
-                                       pad=args.tex_pad, sizes=args.tex_sizes, save_weight=args.save_weight, device=dev, gains=gains)
+                                       pad=args.tex_pad, sizes=args.tex_sizes, save_weight=args.save_weight, device=dev, gains=gains,
+                                       fill=getattr(args, "tex_fill", False))
         finally:
             pool.shutdown(wait=True)
             pf.close()

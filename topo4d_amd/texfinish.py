@@ -9,6 +9,15 @@ Finishing a baked UV texture on the GPU, over csrc/t4d_texfinish.hip (include/to
     halve(image, coverage)                     -> (image, coverage): 2x2 means over the covered texels only, round half up
     finish(image_u8, coverage, pad, erode, sizes)  -> {res: image}: level 0 and the smaller levels, each with its own gutter
     coverage_from_obj(face_obj, h, w)          the coverage of a face.obj's UV faces, for a tree whose bake is gone
+    fill(image, valid, domain=None)            -> (image, filled): every texel of `domain` that is not valid takes a smooth
+                                               interpolation of the valid texels: push-pull over a pyramid, csrc/t4d_texfill.hip
+    fill_islands(image, valid, labels)         -> (image, filled): fill per UV island, from that island's valid texels alone
+
+pad is right for a gutter and wrong for a hole: the nearest texel makes blocky streaks with a crease where two fronts meet.  fill is
+for the holes of a projected texture (projtex: the texels no camera sees): the valid texels are averaged down a pyramid over valid
+texels alone (halve's rule, in units of 1/256), and every hole takes the bilinear enlargement of the first level that has a colour
+for it, so a small hole is filled from its rim and a large one from further away.  Known limit: within one island the fill is an
+interpolation in UV space that knows nothing of the surface, so a large hole comes out smooth, not plausible.
 
 Why: face.png is black outside the UV islands and the mesh vertices on a UV seam sit on an island's border, so every bilinear
 tap there (meshrender's default, and every viewer's) and every mip level a viewer builds mixes black in.  A gutter of the
@@ -130,6 +139,68 @@ def halve(image: torch.Tensor, coverage: torch.Tensor) -> Tuple[torch.Tensor, to
     out_cov = torch.empty(h // 2, w // 2, dtype=torch.uint8, device=img.device)
     _lib.call("t4d_texture_halve", ptr(img), ptr(cov), h, w, c, ptr(out), ptr(out_cov), _lib.stream(img.device))
     return out, out_cov
+
+
+def _mask(mask, what: str, h: int, w: int) -> None:
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (h, w):
+        raise ValueError(f"{what} must be a uint8 or bool [{h},{w}] tensor, got {getattr(mask, 'dtype', type(mask))} "
+                         f"{list(getattr(mask, 'shape', ()))}")
+
+
+def _on_device(mask: torch.Tensor, what: str, device) -> torch.Tensor:
+    if mask.device != device:
+        raise RuntimeError(f"topo4d_amd has no CPU path: {what} must live on the image's HIP device")
+    return (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
+
+
+def fill(image: torch.Tensor, valid: torch.Tensor, domain: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(image, filled uint8 [h,w]): every texel of `domain` (None: every texel) that is not `valid` takes the push-pull
+    interpolation of the valid texels (include/topo4d_raster.h states the rule, tests/texfill_ref.py restates it); every other
+    texel is copied through.  filled is 1 at the texels written.  Without any valid texel the image comes back as it is."""
+    _, h, w, c = _image(image, "image", need_device=False)     # argument errors first, with or without a device
+    _mask(valid, "valid", h, w)
+    if domain is not None:
+        _mask(domain, "domain", h, w)
+    img = _image(image, "image")[0]
+    val = _on_device(valid, "valid", img.device)
+    dom = None if domain is None else _on_device(domain, "domain", img.device)
+    nbytes = int(_lib.load().t4d_texture_fill_scratch_bytes(h, w, c))
+    if nbytes == 0:
+        raise _lib.error("t4d_texture_fill_scratch_bytes", exc=ValueError)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+    out = torch.empty_like(img)
+    filled = torch.empty(h, w, dtype=torch.uint8, device=img.device)
+    _lib.call("t4d_texture_fill", ptr(img), ptr(val), ptr(dom), h, w, c, ptr(out), ptr(filled), ptr(scratch), nbytes,
+              _lib.stream(img.device))
+    return out, filled
+
+
+def fill_islands(image: torch.Tensor, valid: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(image, filled): fill per UV island.  labels uint8 [h,w] (projtex.island_labels; 0: no island).  For every label i that holds
+    both a valid texel and a texel to fill, fill(image, valid & (labels == i), labels == i), and the filled texels are merged: an
+    island's colours never enter another island's holes, and an island without any valid texel stays as it is.  Every pass runs on
+    the whole image (a crop would shift the pyramid and change the bits).  The labels that need a pass are found by one read of
+    two flags per label from the device."""
+    _, h, w, _ = _image(image, "image", need_device=False)
+    _mask(valid, "valid", h, w)
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or tuple(labels.shape) != (h, w):
+        raise ValueError(f"labels must be a uint8 [{h},{w}] tensor, got {getattr(labels, 'dtype', type(labels))} "
+                         f"{list(getattr(labels, 'shape', ()))}")
+    img = _image(image, "image")[0]
+    val = _on_device(valid, "valid", img.device) != 0
+    lab = _on_device(labels, "labels", img.device)
+    flat = lab.reshape(-1).to(torch.int64)
+    flags = torch.stack([torch.bincount(flat, weights=val.reshape(-1).to(torch.float64), minlength=256),
+                         torch.bincount(flat, weights=(~val).reshape(-1).to(torch.float64), minlength=256)]).cpu().numpy()
+    out, filled = img.clone(), torch.zeros(h, w, dtype=torch.uint8, device=img.device)
+    for i in range(1, 256):
+        if not (flags[0, i] > 0 and flags[1, i] > 0):
+            continue
+        island = lab == i
+        o, f = fill(img, val & island, island)
+        out = torch.where((f != 0).reshape((h, w) + (1,) * (img.dim() - 2)), o, out)
+        filled |= f
+    return out, filled
 
 
 _pad, _erode = pad, erode                                     # finish's keyword arguments carry the same names

@@ -24,7 +24,8 @@ the UV islands of face.png and --tex_sizes 4096,2048 also writes face_<size>.png
 face_proj.png beside every face.obj, the frame's full-size photographs projected into the UV layout (projtex, with or without
 --gen_tex; --mode, --band_radius, --power, --cos_min, --fade_px and --depth_tol as python -m topo4d_amd.projtex takes them; --tex_equalize
 estimates one gain per camera and channel on the first frame written, stores proj_gains.json in the run directory and projects
-every frame with it).  Without them nothing changes.
+every frame with it; --tex_fill fills the texels of every UV island that no view sees by push-pull from the island's projected
+texels, texfinish.fill_islands).  Without them nothing changes.
 
 The region "freezes" of train.py:676-700 are FusedAdamPins pins, written by the step kernel itself; the pin set changes at
 most twice per frame (the dynamic-eye pins end at iteration int(0.7 n) of frame 0) and the learning rates once (the colour
@@ -320,6 +321,9 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
         if not tex_project:
             raise SystemExit("--tex_equalize equalises the projected texture: it needs --tex_project")
         eq_stat, eq_solve = projtex.eq_options_of(args)
+    tex_fill = getattr(args, "tex_fill", False)
+    if tex_fill and not tex_project:
+        raise SystemExit("--tex_fill fills the holes of the projected texture: it needs --tex_project")
     dev = coarse._device(device)
     clock = _Clock(timings, dev)
     with torch.cuda.device(dev), clock("setup"):
@@ -450,7 +454,7 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
                                 est.add(face_obj, trans_g, dense)
                                 proj_gains = est.finish(os.path.join(out_dir, projtex.GAINS_NAME))
                             projtex.write_frame(frame_dir, face_obj, trans_g, dense, args.tex_res, proj_opts, pad=tex_pad,
-                                                sizes=tex_sizes, device=dev, gains=proj_gains)
+                                                sizes=tex_sizes, device=dev, gains=proj_gains, fill=tex_fill)
                 state["frames"] = t + 1
                 if on_frame is not None:
                     on_frame(t, state)
@@ -523,6 +527,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="With --tex_project: equalise the cameras' exposure and white balance. The gains are estimated on the first "
                         "frame written, stored as proj_gains.json in the run directory and used for every frame (topo4d_amd.projtex "
                         "--equalize; --stat_cos_min, --stat_lo, --stat_hi, --eq_prior and --eq_min_overlap as it takes them).")
+    p.add_argument('--tex_fill', action='store_true', default=argparse.SUPPRESS,
+                   help="With --tex_project: fill the texels of every UV island that no view sees by push-pull from the island's "
+                        "projected texels (topo4d_amd.projtex --tex_fill).")
     from .projtex import add_band_options, add_eq_options, add_options
     add_options(p, suppress=True)
     add_band_options(p, suppress=True)
