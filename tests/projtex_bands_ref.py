@@ -8,14 +8,14 @@ on the host:
     twoband(...)                                                       low_band, project_bands and float32(low_color + high)
 
 Both perform the kernels' operations in the kernels' order over all pixels / texels at once (numpy never fuses a multiply-add), so
-every output bit agrees.  project_bands takes steps 1..6 from tests/projtex_eq_ref.view_samples, which is built from
-tests/projtex_ref.project_texture's code path: once over the photograph for s, once over its low band for l.
+every output bit agrees.  project_bands takes steps 1..6 from tests/projtex_ref.view_samples: once over the photograph for s, once
+over its low band for l.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from tests.projtex_eq_ref import view_samples
+from tests.projtex_ref import view_samples
 
 
 def low_band(photos, depth, radius: int):

@@ -60,29 +60,69 @@ constexpr int kMaxViews = 255;               // count is a uint8
 constexpr int kMaxPower = 8;
 constexpr double kNear = 0.01;               // the mesh renderer's near plane
 
-struct PTP {
-    const float *pos, *nrm, *views, *photos, *depth;
+struct Rule {                                 // what accepts and weighs a view, the same in every kernel
+    int power;
+    double cos_min, fade_px, depth_lim;      // depth_lim = 1 + depth_tol
+};
+
+struct Tex {                                  // what every texel kernel takes: the texel maps, the views' records, the rule
+    const float *pos, *nrm, *views;
     const uint8_t *coverage;
     const double *gains;                     // [V,3] or NULL
-    int th, tw, V, H, W, power, mode;
-    double cos_min, fade_px, depth_lim;      // depth_lim = 1 + depth_tol
+    int th, tw, V;
+    Rule rule;
+};
+
+struct PTP {
+    Tex T;
+    const float *photos, *depth;
+    int H, W, mode;
     float *color, *weight;
     uint8_t *count;
 };
 
-// Steps 1..6 of the rule above for one view of size H x W (photo [3,H,W], depth [H,W], vm its record), shared by k_projtex and
-// k_pair_stats: 0 when the view is rejected; 1 when it is accepted (w and cs are set) but, with `keep`, w is not > keep_above, so
-// that its sample is not wanted (mode "best": a view that cannot win costs no gather of the photograph); 2 with the sample s, times
-// gain[c] when gain is given (one rounded product); with `low` ([3,H,W]) also l, the same mix over low's taps (step 6b).
-__device__ __forceinline__ int view_eval(const float *vm, double X, double Y, double Z, double nhx, double nhy, double nhz, int H, int W,
-                                         const float *photo, const float *depth, const double *gain, int power, double cos_min,
-                                         double fade_px, double depth_lim, bool keep, double keep_above, double &w_out, double &cs_out, double s[3],
-                                         const float *low = nullptr, double *l = nullptr)
+// The lane's texel of the 16x16 tile (tile_x, tile_y): whether it lies inside the texture, and there `at`; whether it is live (inside,
+// covered, with a non-zero normal), and then its point and its normalised normal.  A texel outside the coverage costs one byte read.
+struct Texel {
+    bool inside, live;
+    size_t at;
+    double X, Y, Z, nhx, nhy, nhz;
+};
+
+__device__ __forceinline__ Texel texel_load(const Tex &T, int tile_x, int tile_y)
 {
 #pragma clang fp contract(off)
-    const float *pm = vm + 16;
-    const double Wd = (double)W, Hd = (double)H, xmax = (double)(W - 1), ymax = (double)(H - 1);
-    const size_t plane = (size_t)H * (size_t)W;
+    Texel t = {};
+    const int tx = tile_x * kTile + (int)(threadIdx.x % kTile), ty = tile_y * kTile + (int)(threadIdx.x / kTile);
+    t.inside = tx < T.tw && ty < T.th;
+    t.at = (size_t)ty * (size_t)T.tw + (size_t)tx;
+    if (!t.inside || T.coverage[t.at] == 0) return t;
+    const double nx = (double)T.nrm[3 * t.at], ny = (double)T.nrm[3 * t.at + 1], nz = (double)T.nrm[3 * t.at + 2];
+    const double nl = sqrt((nx * nx + ny * ny) + nz * nz);
+    t.live = nl > 0.0;
+    t.X = (double)T.pos[3 * t.at]; t.Y = (double)T.pos[3 * t.at + 1]; t.Z = (double)T.pos[3 * t.at + 2];
+    t.nhx = nx / nl; t.nhy = ny / nl; t.nhz = nz / nl;
+    return t;
+}
+
+struct View {                                 // one view of size H x W: its record (vm, then pm) and its depth [H,W]
+    const float *vm, *depth;
+    int H, W;
+};
+
+struct Hit {                                  // an accepted view at a texel: weight, cosine, the first of its four taps and the bilinear fractions
+    double w, cs, fx, fy;
+    size_t tap;
+};
+
+// Steps 1..5 of the rule above for one view at a live texel: whether the view is accepted, and then `h`.
+__device__ __forceinline__ bool view_accept(const View &v, const Rule &r, const Texel &t, Hit &h)
+{
+#pragma clang fp contract(off)
+    const float *vm = v.vm, *pm = vm + 16;
+    const int W = v.W;
+    const double X = t.X, Y = t.Y, Z = t.Z;
+    const double Wd = (double)W, Hd = (double)v.H, xmax = (double)(W - 1), ymax = (double)(v.H - 1);
     // 1. projection
     const double cx = (((double)pm[0] * X + (double)pm[4] * Y) + (double)pm[8] * Z) + (double)pm[12];
     const double cy = (((double)pm[1] * X + (double)pm[5] * Y) + (double)pm[9] * Z) + (double)pm[13];
@@ -90,93 +130,82 @@ __device__ __forceinline__ int view_eval(const float *vm, double X, double Y, do
     const double px = ((cx / cw + 1.0) * Wd - 1.0) * 0.5;
     const double py = ((cy / cw + 1.0) * Hd - 1.0) * 0.5;
     const double z = (((double)vm[2] * X + (double)vm[6] * Y) + (double)vm[10] * Z) + (double)vm[14];
-    if (!(z > kNear)) return 0;
+    if (!(z > kNear)) return false;
     // 2. the four taps inside the image (a NaN fails the comparisons)
     const double fx0 = floor(px), fy0 = floor(py);
-    if (!(fx0 >= 0.0 && fx0 + 1.0 <= xmax && fy0 >= 0.0 && fy0 + 1.0 <= ymax)) return 0;
+    if (!(fx0 >= 0.0 && fx0 + 1.0 <= xmax && fy0 >= 0.0 && fy0 + 1.0 <= ymax)) return false;
     // 4. facing (before the gathers: it needs no memory)
     const double t0 = (double)vm[12], t1 = (double)vm[13], t2 = (double)vm[14];
     const double ex = -(((double)vm[0] * t0 + (double)vm[1] * t1) + (double)vm[2] * t2) - X;
     const double ey = -(((double)vm[4] * t0 + (double)vm[5] * t1) + (double)vm[6] * t2) - Y;
     const double ez = -(((double)vm[8] * t0 + (double)vm[9] * t1) + (double)vm[10] * t2) - Z;
     const double el = sqrt((ex * ex + ey * ey) + ez * ez);
-    const double cs = (nhx * (ex / el) + nhy * (ey / el)) + nhz * (ez / el);
-    if (!(cs >= cos_min)) return 0;
+    const double cs = (t.nhx * (ex / el) + t.nhy * (ey / el)) + t.nhz * (ez / el);
+    if (!(cs >= r.cos_min)) return false;
     // 3. visibility
-    const size_t tap = (size_t)(int)fy0 * (size_t)W + (size_t)(int)fx0;
-    const float *dp = depth + tap;
+    h.tap = (size_t)(int)fy0 * (size_t)W + (size_t)(int)fx0;
+    const float *dp = v.depth + h.tap;
     const double d00 = (double)dp[0], d01 = (double)dp[1], d10 = (double)dp[W], d11 = (double)dp[W + 1];
-    if (!(d00 > 0.0 && d01 > 0.0 && d10 > 0.0 && d11 > 0.0)) return 0;
-    if (!(z <= d00 * depth_lim && z <= d01 * depth_lim && z <= d10 * depth_lim && z <= d11 * depth_lim)) return 0;
+    if (!(d00 > 0.0 && d01 > 0.0 && d10 > 0.0 && d11 > 0.0)) return false;
+    if (!(z <= d00 * r.depth_lim && z <= d01 * r.depth_lim && z <= d10 * r.depth_lim && z <= d11 * r.depth_lim)) return false;
     // 5. weight
     double w = 1.0;
-    for (int k = 0; k < power; ++k) w = w * cs;
-    if (fade_px > 0.0) {
+    for (int k = 0; k < r.power; ++k) w = w * cs;
+    if (r.fade_px > 0.0) {
         const double m = fmin(fmin(px, xmax - px), fmin(py, ymax - py));
-        const double f = m / fade_px;
+        const double f = m / r.fade_px;
         if (f < 1.0) w = w * f;
     }
-    if (!(w > 0.0)) return 0;
-    w_out = w;
-    cs_out = cs;
-    if (keep && !(w > keep_above)) return 1;
-    // 6. sample
-    const double fx = px - fx0, fy = py - fy0, gx = 1.0 - fx, gy = 1.0 - fy;
-    const float *ph = photo + tap;
+    if (!(w > 0.0)) return false;
+    h.w = w;
+    h.cs = cs;
+    h.fx = px - fx0;
+    h.fy = py - fy0;
+    return true;
+}
+
+// Step 6 under an accepted view's taps: s = the bilinear mix of img ([3,H,W]: the photograph, or its low band), times gain[c] when
+// gain is given (one rounded product).
+__device__ __forceinline__ void view_sample(const float *img, const View &v, const Hit &h, const double *gain, double s[3])
+{
+#pragma clang fp contract(off)
+    const int W = v.W;
+    const size_t plane = (size_t)v.H * (size_t)W;
+    const double fx = h.fx, fy = h.fy, gx = 1.0 - fx, gy = 1.0 - fy;
     for (int c = 0; c < 3; ++c) {
-        const float *q = ph + (size_t)c * plane;
+        const float *q = img + h.tap + (size_t)c * plane;
         const double a = gx * (double)q[0] + fx * (double)q[1], b = gx * (double)q[W] + fx * (double)q[W + 1];
         s[c] = gy * a + fy * b;
         if (gain) s[c] = s[c] * gain[c];
     }
-    if (low) {                                                              // 6b. the low band under the same taps
-        const float *lp = low + tap;
-        for (int c = 0; c < 3; ++c) {
-            const float *q = lp + (size_t)c * plane;
-            const double a = gx * (double)q[0] + fx * (double)q[1], b = gx * (double)q[W] + fx * (double)q[W + 1];
-            l[c] = gy * a + fy * b;
-            if (gain) l[c] = l[c] * gain[c];
-        }
-    }
-    return 2;
 }
 
 template <bool kGains>                       // (two instances, so that the kernel without gains is the one it was before they existed)
 __global__ __launch_bounds__(kTile * kTile) void k_projtex(const PTP P)
 {
 #pragma clang fp contract(off)
-    const int tx = (int)blockIdx.x * kTile + (int)(threadIdx.x % kTile), ty = (int)blockIdx.y * kTile + (int)(threadIdx.x / kTile);
-    if (tx >= P.tw || ty >= P.th) return;
-    const size_t at = (size_t)ty * (size_t)P.tw + (size_t)tx;
-    if (P.coverage[at] == 0) {                                              // most of a face's UV layout: one byte read, zeros out
-        P.color[3 * at] = 0.0f; P.color[3 * at + 1] = 0.0f; P.color[3 * at + 2] = 0.0f;
-        P.weight[at] = 0.0f;
-        P.count[at] = 0;
-        return;
-    }
+    const Texel t = texel_load(P.T, (int)blockIdx.x, (int)blockIdx.y);
+    if (!t.inside) return;
+    const size_t at = t.at;
     double sw = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
     int cnt = 0;
-    const double nx = (double)P.nrm[3 * at], ny = (double)P.nrm[3 * at + 1], nz = (double)P.nrm[3 * at + 2];
-    const double nl = sqrt((nx * nx + ny * ny) + nz * nz);
-    if (nl > 0.0) {
-        const double X = (double)P.pos[3 * at], Y = (double)P.pos[3 * at + 1], Z = (double)P.pos[3 * at + 2];
-        const double nhx = nx / nl, nhy = ny / nl, nhz = nz / nl;
+    if (t.live) {                                                           // (else, most of a face's UV layout: one byte read, zeros out)
         const size_t plane = (size_t)P.H * (size_t)P.W;
         const bool best = P.mode == T4D_PROJTEX_BEST;
-        for (int v = 0; v < P.V; ++v) {
-            double w, cs, s[3];
-            const int got = view_eval(P.views + (size_t)v * T4D_VIEW_FLOATS, X, Y, Z, nhx, nhy, nhz, P.H, P.W,
-                                      P.photos + (size_t)v * 3 * plane, P.depth + (size_t)v * plane, kGains ? P.gains + 3 * v : nullptr,
-                                      P.power, P.cos_min, P.fade_px, P.depth_lim, best, sw, w, cs, s);
-            if (!got) continue;
+        for (int v = 0; v < P.T.V; ++v) {
+            const View view = {P.T.views + (size_t)v * T4D_VIEW_FLOATS, P.depth + (size_t)v * plane, P.H, P.W};
+            Hit h;
+            if (!view_accept(view, P.T.rule, t, h)) continue;
             ++cnt;
-            if (got == 1) continue;                                         // best: the kept view stays (ties stay with the lower view)
+            if (best && !(h.w > sw)) continue;                              // a view that cannot win is counted but not gathered (ties stay with the lower view)
+            double s[3];
+            view_sample(P.photos + (size_t)v * 3 * plane, view, h, kGains ? P.T.gains + 3 * v : nullptr, s);
             // 7. accumulate
             if (best) {
-                sw = w; s0 = s[0]; s1 = s[1]; s2 = s[2];
+                sw = h.w; s0 = s[0]; s1 = s[1]; s2 = s[2];
             } else {
-                sw = sw + w;
-                s0 = s0 + w * s[0]; s1 = s1 + w * s[1]; s2 = s2 + w * s[2];
+                sw = sw + h.w;
+                s0 = s0 + h.w * s[0]; s1 = s1 + h.w * s[1]; s2 = s2 + h.w * s[2];
             }
         }
         if (cnt && !best) { s0 = s0 / sw; s1 = s1 / sw; s2 = s2 / sw; }
@@ -209,13 +238,11 @@ constexpr double kStatRange = 1024.0;        // |stat_lo|, |stat_hi| at most: q 
 constexpr double kStatScale = 65536.0;
 
 struct PSP {
-    const float *pos, *nrm, *views;
-    const uint8_t *coverage;
+    Tex T;
     const int32_t *sizes;                    // [V,2] (h, w)
     const float *const *photos, *const *depth;
-    const double *gains;                     // [V,3] or NULL
-    int th, tw, V, power, tiles_x, tiles;
-    double cos_min, fade_px, depth_lim, stat_cos_min, stat_lo, stat_hi;
+    int tiles_x, tiles;
+    double stat_cos_min, stat_lo, stat_hi;
     unsigned long long *pair_count, *pair_sum;
 };
 
@@ -226,16 +253,15 @@ __device__ __forceinline__ long long wave_sum(long long a)
 }
 
 // whether view v takes part at the lane's texel, and its q
-__device__ __forceinline__ bool stat_eval(const PSP &P, int v, double X, double Y, double Z, double nhx, double nhy, double nhz, long long q[3])
+__device__ __forceinline__ bool stat_eval(const PSP &P, int v, const Texel &t, long long q[3])
 {
 #pragma clang fp contract(off)
-    const int H = P.sizes[2 * v], W = P.sizes[2 * v + 1];
-    if (H < 1 || W < 1 || H > kMaxDim || W > kMaxDim) return false;
-    double w, cs, s[3];
-    if (view_eval(P.views + (size_t)v * T4D_VIEW_FLOATS, X, Y, Z, nhx, nhy, nhz, H, W, P.photos[v], P.depth[v],
-                  P.gains ? P.gains + 3 * v : nullptr, P.power, P.cos_min, P.fade_px, P.depth_lim, false, 0.0, w, cs, s) != 2)
-        return false;
-    if (!(cs >= P.stat_cos_min)) return false;
+    const View view = {P.T.views + (size_t)v * T4D_VIEW_FLOATS, P.depth[v], P.sizes[2 * v], P.sizes[2 * v + 1]};
+    if (view.H < 1 || view.W < 1 || view.H > kMaxDim || view.W > kMaxDim) return false;
+    Hit h;
+    double s[3];
+    if (!view_accept(view, P.T.rule, t, h) || !(h.cs >= P.stat_cos_min)) return false;
+    view_sample(P.photos[v], view, h, P.T.gains ? P.T.gains + 3 * v : nullptr, s);
     for (int c = 0; c < 3; ++c)
         if (!(s[c] >= P.stat_lo && s[c] <= P.stat_hi)) return false;
     for (int c = 0; c < 3; ++c) q[c] = llrint(s[c] * kStatScale);
@@ -245,30 +271,20 @@ __device__ __forceinline__ bool stat_eval(const PSP &P, int v, double X, double 
 __global__ __launch_bounds__(kTile * kTile) void k_pair_stats(const PSP P)
 {
     __shared__ unsigned long long tab[kStatViews * kStatViews * 4];
-    const int V = P.V, lane = (int)(threadIdx.x & 63);
+    const int V = P.T.V, lane = (int)(threadIdx.x & 63);
     for (int e = (int)threadIdx.x; e < V * V * 4; e += kTile * kTile) tab[e] = 0;
     __syncthreads();
     for (int t = (int)blockIdx.x; t < P.tiles; t += (int)gridDim.x) {
-        const int tx = (t % P.tiles_x) * kTile + (int)(threadIdx.x % kTile), ty = (t / P.tiles_x) * kTile + (int)(threadIdx.x / kTile);
-        const size_t at = (size_t)ty * (size_t)P.tw + (size_t)tx;
-        bool live = tx < P.tw && ty < P.th;
-        if (live) live = P.coverage[at] != 0;
+        const Texel tex = texel_load(P.T, t % P.tiles_x, t / P.tiles_x);
+        const bool live = tex.live;
         if (__ballot(live) == 0) continue;                                  // the whole wave, so every lane reaches the shuffles below
-        double X = 0.0, Y = 0.0, Z = 0.0, nhx = 0.0, nhy = 0.0, nhz = 0.0;
-        if (live) {
-            const double nx = (double)P.nrm[3 * at], ny = (double)P.nrm[3 * at + 1], nz = (double)P.nrm[3 * at + 2];
-            const double nl = sqrt((nx * nx + ny * ny) + nz * nz);
-            live = nl > 0.0;
-            X = (double)P.pos[3 * at]; Y = (double)P.pos[3 * at + 1]; Z = (double)P.pos[3 * at + 2];
-            nhx = nx / nl; nhy = ny / nl; nhz = nz / nl;
-        }
         // the views: the lane's mask; lane v keeps the lane set of view v and the sums of q over it
         uint32_t mask = 0;
         unsigned long long set = 0;
         long long tot0 = 0, tot1 = 0, tot2 = 0;
         for (int v = 0; v < V; ++v) {
             long long q[3] = {0, 0, 0};
-            const bool part = live && stat_eval(P, v, X, Y, Z, nhx, nhy, nhz, q);
+            const bool part = live && stat_eval(P, v, tex, q);
             const unsigned long long b = __ballot(part);
             if (b == 0) continue;
             if (part) mask |= 1u << v;
@@ -291,7 +307,7 @@ __global__ __launch_bounds__(kTile * kTile) void k_pair_stats(const PSP P)
             if (partial == 0) continue;
             long long q[3] = {0, 0, 0};
             const bool has_i = (mask >> i) & 1u;
-            if (has_i) stat_eval(P, i, X, Y, Z, nhx, nhy, nhz, q);          // the same operations again: the same q
+            if (has_i) stat_eval(P, i, tex, q);         // the same operations again: the same q
             while (partial) {
                 const int j = __builtin_ctzll(partial);
                 partial &= partial - 1;
@@ -397,11 +413,9 @@ __global__ __launch_bounds__(kLowW * kLowStep) void k_low_band(const LBP P)
 }
 
 struct PBP {
-    const float *pos, *nrm, *views, *photos, *low, *depth;
-    const uint8_t *coverage;
-    const double *gains;                     // [V,3] or NULL
-    int th, tw, V, H, W, power;
-    double cos_min, fade_px, depth_lim;
+    Tex T;
+    const float *photos, *low, *depth;
+    int H, W;
     float *low_color, *weight, *high, *best_weight;
     uint8_t *count;
 };
@@ -410,36 +424,32 @@ template <bool kGains>
 __global__ __launch_bounds__(kTile * kTile) void k_projtex_bands(const PBP P)
 {
 #pragma clang fp contract(off)
-    const int tx = (int)blockIdx.x * kTile + (int)(threadIdx.x % kTile), ty = (int)blockIdx.y * kTile + (int)(threadIdx.x / kTile);
-    if (tx >= P.tw || ty >= P.th) return;
-    const size_t at = (size_t)ty * (size_t)P.tw + (size_t)tx;
+    const Texel t = texel_load(P.T, (int)blockIdx.x, (int)blockIdx.y);
+    if (!t.inside) return;
+    const size_t at = t.at;
     double sw = 0.0, bw = 0.0, sl[3] = {0.0, 0.0, 0.0}, hb[3] = {0.0, 0.0, 0.0};
     int cnt = 0;
-    if (P.coverage[at] != 0) {
-        const double nx = (double)P.nrm[3 * at], ny = (double)P.nrm[3 * at + 1], nz = (double)P.nrm[3 * at + 2];
-        const double nl = sqrt((nx * nx + ny * ny) + nz * nz);
-        if (nl > 0.0) {
-            const double X = (double)P.pos[3 * at], Y = (double)P.pos[3 * at + 1], Z = (double)P.pos[3 * at + 2];
-            const double nhx = nx / nl, nhy = ny / nl, nhz = nz / nl;
-            const size_t plane = (size_t)P.H * (size_t)P.W;
-            for (int v = 0; v < P.V; ++v) {
-                double w, cs, s[3], l[3];
-                if (!view_eval(P.views + (size_t)v * T4D_VIEW_FLOATS, X, Y, Z, nhx, nhy, nhz, P.H, P.W, P.photos + (size_t)v * 3 * plane,
-                               P.depth + (size_t)v * plane, kGains ? P.gains + 3 * v : nullptr, P.power, P.cos_min, P.fade_px,
-                               P.depth_lim, false, 0.0, w, cs, s, P.low + (size_t)v * 3 * plane, l))
-                    continue;
-                ++cnt;
-                // 7. the low band of every view, the detail of the best one
-                sw = sw + w;
-                for (int c = 0; c < 3; ++c) sl[c] = sl[c] + w * l[c];
-                if (w > bw) {
-                    bw = w;
-                    for (int c = 0; c < 3; ++c) hb[c] = s[c] - l[c];
-                }
+    if (t.live) {
+        const size_t plane = (size_t)P.H * (size_t)P.W;
+        for (int v = 0; v < P.T.V; ++v) {
+            const View view = {P.T.views + (size_t)v * T4D_VIEW_FLOATS, P.depth + (size_t)v * plane, P.H, P.W};
+            const double *gain = kGains ? P.T.gains + 3 * v : nullptr;
+            Hit h;
+            if (!view_accept(view, P.T.rule, t, h)) continue;
+            ++cnt;
+            double s[3], l[3];
+            view_sample(P.photos + (size_t)v * 3 * plane, view, h, gain, s);
+            view_sample(P.low + (size_t)v * 3 * plane, view, h, gain, l);    // 6b. the low band under the same taps
+            // 7. the low band of every view, the detail of the best one
+            sw = sw + h.w;
+            for (int c = 0; c < 3; ++c) sl[c] = sl[c] + h.w * l[c];
+            if (h.w > bw) {
+                bw = h.w;
+                for (int c = 0; c < 3; ++c) hb[c] = s[c] - l[c];
             }
-            if (cnt)
-                for (int c = 0; c < 3; ++c) sl[c] = sl[c] / sw;
         }
+        if (cnt)
+            for (int c = 0; c < 3; ++c) sl[c] = sl[c] / sw;
     }
     for (int c = 0; c < 3; ++c) {
         P.low_color[3 * at + c] = (float)sl[c];
@@ -452,6 +462,16 @@ __global__ __launch_bounds__(kTile * kTile) void k_projtex_bands(const PBP P)
 
 }  // namespace
 
+// What the entry points check alike: the buffers (`buffers`: none of them NULL), the image sides and the number of views.
+static int views_check(const char *name, bool buffers, int32_t n_views, int max_views, int32_t h, int32_t w)
+{
+    if (!buffers) return t4d_fail(T4D_ERR_ARG, "%s: NULL buffer", name);
+    if (h < 1 || w < 1 || h > kMaxDim || w > kMaxDim)
+        return t4d_fail(T4D_ERR_ARG, "%s: need 1 <= sides <= %d, got %d x %d images", name, kMaxDim, h, w);
+    if (n_views < 1 || n_views > max_views) return t4d_fail(T4D_ERR_ARG, "%s: n_views must be in [1, %d], got %d", name, max_views, n_views);
+    return T4D_OK;
+}
+
 static int projtex_check(const char *name, int32_t tex_h, int32_t tex_w, int32_t power, double cos_min, double fade_px, double depth_tol)
 {
     if (tex_h < 1 || tex_w < 1 || tex_h > kMaxDim || tex_w > kMaxDim)
@@ -462,29 +482,32 @@ static int projtex_check(const char *name, int32_t tex_h, int32_t tex_w, int32_t
     return T4D_OK;
 }
 
+static Tex tex_block(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w, const float *views,
+                     int32_t n_views, const double *gains, int32_t power, double cos_min, double fade_px, double depth_tol)
+{
+    return Tex{pos, nrm, views, coverage, gains, tex_h, tex_w, n_views, Rule{power, cos_min, fade_px, 1.0 + depth_tol}};
+}
+
+static dim3 tile_grid(int32_t tex_h, int32_t tex_w)
+{
+    return dim3((unsigned)((tex_w + kTile - 1) / kTile), (unsigned)((tex_h + kTile - 1) / kTile));
+}
+
 T4D_EXPORT int t4d_project_texture_gains(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
                                          const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
                                          const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
                                          double depth_tol, int32_t mode, float *color, float *weight, uint8_t *count, void *hip_stream)
 {
-    if (!pos || !nrm || !coverage || !views || !photos || !depth || !color || !weight || !count)
-        return t4d_fail(T4D_ERR_ARG, "t4d_project_texture: NULL buffer");
-    if (tex_h < 1 || tex_w < 1 || tex_h > kMaxDim || tex_w > kMaxDim || h < 1 || w < 1 || h > kMaxDim || w > kMaxDim)
-        return t4d_fail(T4D_ERR_ARG, "t4d_project_texture: need 1 <= sides <= %d, got a %d x %d texture and %d x %d images", kMaxDim,
-                        tex_h, tex_w, h, w);
-    if (n_views < 1 || n_views > kMaxViews)
-        return t4d_fail(T4D_ERR_ARG, "t4d_project_texture: n_views must be in [1, %d], got %d", kMaxViews, n_views);
+    const char *name = "t4d_project_texture";
+    if (const int rc = views_check(name, pos && nrm && coverage && views && photos && depth && color && weight && count, n_views, kMaxViews, h, w))
+        return rc;
     if (mode != T4D_PROJTEX_WEIGHTED && mode != T4D_PROJTEX_BEST)
-        return t4d_fail(T4D_ERR_ARG, "t4d_project_texture: mode must be T4D_PROJTEX_WEIGHTED or T4D_PROJTEX_BEST, got %d", mode);
-    if (const int rc = projtex_check("t4d_project_texture", tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
-    PTP P;
-    P.pos = pos; P.nrm = nrm; P.views = views; P.photos = photos; P.depth = depth; P.coverage = coverage; P.gains = gains;
-    P.th = tex_h; P.tw = tex_w; P.V = n_views; P.H = h; P.W = w; P.power = power; P.mode = mode;
-    P.cos_min = cos_min; P.fade_px = fade_px; P.depth_lim = 1.0 + depth_tol;
-    P.color = color; P.weight = weight; P.count = count;
-    const dim3 grid((unsigned)((tex_w + kTile - 1) / kTile), (unsigned)((tex_h + kTile - 1) / kTile));
-    hipLaunchKernelGGL(gains ? k_projtex<true> : k_projtex<false>, grid, dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
-    return t4d_launch_status("t4d_project_texture");
+        return t4d_fail(T4D_ERR_ARG, "%s: mode must be T4D_PROJTEX_WEIGHTED or T4D_PROJTEX_BEST, got %d", name, mode);
+    if (const int rc = projtex_check(name, tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
+    const PTP P = {tex_block(pos, nrm, coverage, tex_h, tex_w, views, n_views, gains, power, cos_min, fade_px, depth_tol),
+                   photos, depth, h, w, mode, color, weight, count};
+    hipLaunchKernelGGL(gains ? k_projtex<true> : k_projtex<false>, tile_grid(tex_h, tex_w), dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
+    return t4d_launch_status(name);
 }
 
 T4D_EXPORT int t4d_project_texture(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
@@ -502,43 +525,33 @@ T4D_EXPORT int t4d_projtex_pair_stats(const float *pos, const float *nrm, const 
                                       double stat_cos_min, double stat_lo, double stat_hi, const double *gains, int64_t *pair_count,
                                       int64_t *pair_sum, void *hip_stream)
 {
-    if (!pos || !nrm || !coverage || !views || !sizes || !photos || !depth || !pair_count || !pair_sum)
-        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_pair_stats: NULL buffer");
-    if (n_views < 1 || n_views > kStatViews)
-        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_pair_stats: n_views must be in [1, %d], got %d", kStatViews, n_views);
-    if (const int rc = projtex_check("t4d_projtex_pair_stats", tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
+    const char *name = "t4d_projtex_pair_stats";             // (the image sides are per view, in `sizes` on the device: the kernel looks at them)
+    if (const int rc = views_check(name, pos && nrm && coverage && views && sizes && photos && depth && pair_count && pair_sum, n_views, kStatViews, 1, 1))
+        return rc;
+    if (const int rc = projtex_check(name, tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
     if (!(stat_cos_min >= -1.0 && stat_cos_min <= 1.0) || !(stat_lo >= -kStatRange && stat_lo <= stat_hi && stat_hi <= kStatRange))
-        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_pair_stats: need stat_cos_min in [-1, 1] and -%g <= stat_lo <= stat_hi <= %g", kStatRange,
-                        kStatRange);
-    PSP P;
-    P.pos = pos; P.nrm = nrm; P.views = views; P.coverage = coverage; P.sizes = sizes; P.photos = photos; P.depth = depth; P.gains = gains;
-    P.th = tex_h; P.tw = tex_w; P.V = n_views; P.power = power;
-    P.tiles_x = (tex_w + kTile - 1) / kTile;
-    P.tiles = P.tiles_x * ((tex_h + kTile - 1) / kTile);                   // at most 4096^2
-    P.cos_min = cos_min; P.fade_px = fade_px; P.depth_lim = 1.0 + depth_tol;
-    P.stat_cos_min = stat_cos_min; P.stat_lo = stat_lo; P.stat_hi = stat_hi;
-    P.pair_count = (unsigned long long *)pair_count; P.pair_sum = (unsigned long long *)pair_sum;
-    const int blocks = P.tiles < kStatGrid ? P.tiles : kStatGrid;
+        return t4d_fail(T4D_ERR_ARG, "%s: need stat_cos_min in [-1, 1] and -%g <= stat_lo <= stat_hi <= %g", name, kStatRange, kStatRange);
+    const int tiles_x = (tex_w + kTile - 1) / kTile, tiles = tiles_x * ((tex_h + kTile - 1) / kTile);      // at most 4096^2
+    const PSP P = {tex_block(pos, nrm, coverage, tex_h, tex_w, views, n_views, gains, power, cos_min, fade_px, depth_tol),
+                   sizes, photos, depth, tiles_x, tiles, stat_cos_min, stat_lo, stat_hi,
+                   (unsigned long long *)pair_count, (unsigned long long *)pair_sum};
+    const int blocks = tiles < kStatGrid ? tiles : kStatGrid;
     hipLaunchKernelGGL(k_pair_stats, dim3((unsigned)blocks), dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
-    return t4d_launch_status("t4d_projtex_pair_stats");
+    return t4d_launch_status(name);
 }
 
 T4D_EXPORT int t4d_projtex_low_band(const float *photos, const float *depth, int32_t n_views, int32_t h, int32_t w, int32_t radius,
                                     float *low, void *hip_stream)
 {
-    if (!photos || !depth || !low) return t4d_fail(T4D_ERR_ARG, "t4d_projtex_low_band: NULL buffer");
-    if (h < 1 || w < 1 || h > kMaxDim || w > kMaxDim)
-        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_low_band: need 1 <= sides <= %d, got %d x %d images", kMaxDim, h, w);
-    if (n_views < 1 || n_views > kMaxViews)
-        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_low_band: n_views must be in [1, %d], got %d", kMaxViews, n_views);
-    if (radius < 0 || radius > kMaxRadius)
-        return t4d_fail(T4D_ERR_ARG, "t4d_projtex_low_band: radius must be in [0, %d], got %d", kMaxRadius, radius);
-    if (low == photos) return t4d_fail(T4D_ERR_ARG, "t4d_projtex_low_band: low must not be the photographs themselves");
+    const char *name = "t4d_projtex_low_band";
+    if (const int rc = views_check(name, photos && depth && low, n_views, kMaxViews, h, w)) return rc;
+    if (radius < 0 || radius > kMaxRadius) return t4d_fail(T4D_ERR_ARG, "%s: radius must be in [0, %d], got %d", name, kMaxRadius, radius);
+    if (low == photos) return t4d_fail(T4D_ERR_ARG, "%s: low must not be the photographs themselves", name);
     LBP P;
     P.photos = photos; P.depth = depth; P.low = low; P.H = h; P.W = w; P.R = radius;
     const dim3 grid((unsigned)((w + kLowW - 1) / kLowW), (unsigned)((h + kLowH - 1) / kLowH), (unsigned)(3 * n_views));
     hipLaunchKernelGGL(k_low_band, grid, dim3(kLowW * kLowStep), low_band_lds(radius), (hipStream_t)hip_stream, P);
-    return t4d_launch_status("t4d_projtex_low_band");
+    return t4d_launch_status(name);
 }
 
 T4D_EXPORT int t4d_project_texture_bands(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
@@ -547,19 +560,14 @@ T4D_EXPORT int t4d_project_texture_bands(const float *pos, const float *nrm, con
                                          double fade_px, double depth_tol, float *low_color, float *weight, uint8_t *count,
                                          float *high, float *best_weight, void *hip_stream)
 {
-    if (!pos || !nrm || !coverage || !views || !photos || !low || !depth || !low_color || !weight || !count || !high || !best_weight)
-        return t4d_fail(T4D_ERR_ARG, "t4d_project_texture_bands: NULL buffer");
-    if (h < 1 || w < 1 || h > kMaxDim || w > kMaxDim)
-        return t4d_fail(T4D_ERR_ARG, "t4d_project_texture_bands: need 1 <= sides <= %d, got %d x %d images", kMaxDim, h, w);
-    if (n_views < 1 || n_views > kMaxViews)
-        return t4d_fail(T4D_ERR_ARG, "t4d_project_texture_bands: n_views must be in [1, %d], got %d", kMaxViews, n_views);
-    if (const int rc = projtex_check("t4d_project_texture_bands", tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
-    PBP P;
-    P.pos = pos; P.nrm = nrm; P.views = views; P.photos = photos; P.low = low; P.depth = depth; P.coverage = coverage; P.gains = gains;
-    P.th = tex_h; P.tw = tex_w; P.V = n_views; P.H = h; P.W = w; P.power = power;
-    P.cos_min = cos_min; P.fade_px = fade_px; P.depth_lim = 1.0 + depth_tol;
-    P.low_color = low_color; P.weight = weight; P.high = high; P.best_weight = best_weight; P.count = count;
-    const dim3 grid((unsigned)((tex_w + kTile - 1) / kTile), (unsigned)((tex_h + kTile - 1) / kTile));
-    hipLaunchKernelGGL(gains ? k_projtex_bands<true> : k_projtex_bands<false>, grid, dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
-    return t4d_launch_status("t4d_project_texture_bands");
+    const char *name = "t4d_project_texture_bands";
+    if (const int rc = views_check(name, pos && nrm && coverage && views && photos && low && depth && low_color && weight && count && high && best_weight,
+                                   n_views, kMaxViews, h, w))
+        return rc;
+    if (const int rc = projtex_check(name, tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
+    const PBP P = {tex_block(pos, nrm, coverage, tex_h, tex_w, views, n_views, gains, power, cos_min, fade_px, depth_tol),
+                   photos, low, depth, h, w, low_color, weight, high, best_weight, count};
+    hipLaunchKernelGGL(gains ? k_projtex_bands<true> : k_projtex_bands<false>, tile_grid(tex_h, tex_w), dim3(kTile * kTile), 0,
+                       (hipStream_t)hip_stream, P);
+    return t4d_launch_status(name);
 }

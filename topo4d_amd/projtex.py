@@ -80,18 +80,27 @@ SOLVE_DEFAULTS = dict(prior=0.01, min_overlap=64)
 GAINS_NAME = "proj_gains.json"
 
 
-def check_options(power=2, cos_min=0.1, fade_px=16.0, depth_tol=0.002, mode="weighted") -> None:
-    """ValueError for a parameter project would refuse (callable without a device)."""
-    if mode not in MODES:
-        raise ValueError(f"mode must be 'weighted', 'best' or 'twoband', got {mode!r}")
-    if isinstance(power, bool) or int(power) != power or not 0 <= int(power) <= MAX_POWER:
-        raise ValueError(f"power must be an integer in [0, {MAX_POWER}], got {power!r}")
-    if not -1.0 <= float(cos_min) <= 1.0:
-        raise ValueError(f"cos_min must be in [-1, 1], got {cos_min!r}")
-    if not 0.0 <= float(fade_px) <= 65536.0:
-        raise ValueError(f"fade_px must be in [0, 65536], got {fade_px!r}")
-    if not 0.0 <= float(depth_tol) <= 1.0:
-        raise ValueError(f"depth_tol must be in [0, 1], got {depth_tol!r}")
+def _filled(defaults: dict, **given) -> dict:
+    """`given`, every None replaced by its default"""
+    return {k: defaults[k] if v is None else v for k, v in given.items()}
+
+
+def check_options(power=None, cos_min=None, fade_px=None, depth_tol=None, mode=None) -> dict:
+    """ValueError for a parameter project would refuse (callable without a device); the five options, None: DEFAULTS'."""
+    o = _filled(DEFAULTS, power=power, cos_min=cos_min, fade_px=fade_px, depth_tol=depth_tol, mode=mode)
+    if o["mode"] not in MODES:
+        raise ValueError(f"mode must be 'weighted', 'best' or 'twoband', got {o['mode']!r}")
+    if isinstance(o["power"], bool) or int(o["power"]) != o["power"] or not 0 <= int(o["power"]) <= MAX_POWER:
+        raise ValueError(f"power must be an integer in [0, {MAX_POWER}], got {o['power']!r}")
+    for k, lo, hi in (("cos_min", -1.0, 1.0), ("fade_px", 0.0, 65536.0), ("depth_tol", 0.0, 1.0)):
+        if not lo <= float(o[k]) <= hi:
+            raise ValueError(f"{k} must be in [{lo:g}, {hi:g}], got {o[k]!r}")
+    return o
+
+
+def _rule(o: dict) -> tuple:
+    """the four parameters of the per-view rule as the C entry points take them"""
+    return int(o["power"]), float(o["cos_min"]), float(o["fade_px"]), float(o["depth_tol"])
 
 
 def check_band_options(band_radius=8) -> None:
@@ -101,20 +110,24 @@ def check_band_options(band_radius=8) -> None:
         raise ValueError(f"band_radius must be an integer in [0, {MAX_BAND_RADIUS}], got {band_radius!r}")
 
 
-def check_stat_options(stat_cos_min=0.5, stat_lo=0.02, stat_hi=0.98) -> None:
+def check_stat_options(stat_cos_min=None, stat_lo=None, stat_hi=None) -> dict:
     """ValueError for a parameter pair_stats would refuse (callable without a device)."""
-    if not -1.0 <= float(stat_cos_min) <= 1.0:
-        raise ValueError(f"stat_cos_min must be in [-1, 1], got {stat_cos_min!r}")
-    if not -MAX_STAT <= float(stat_lo) <= float(stat_hi) <= MAX_STAT:
-        raise ValueError(f"need -{MAX_STAT:g} <= stat_lo <= stat_hi <= {MAX_STAT:g}, got {stat_lo!r} and {stat_hi!r}")
+    o = _filled(STAT_DEFAULTS, stat_cos_min=stat_cos_min, stat_lo=stat_lo, stat_hi=stat_hi)
+    if not -1.0 <= float(o["stat_cos_min"]) <= 1.0:
+        raise ValueError(f"stat_cos_min must be in [-1, 1], got {o['stat_cos_min']!r}")
+    if not -MAX_STAT <= float(o["stat_lo"]) <= float(o["stat_hi"]) <= MAX_STAT:
+        raise ValueError(f"need -{MAX_STAT:g} <= stat_lo <= stat_hi <= {MAX_STAT:g}, got {o['stat_lo']!r} and {o['stat_hi']!r}")
+    return o
 
 
-def check_solve_options(prior=0.01, min_overlap=64) -> None:
+def check_solve_options(prior=None, min_overlap=None) -> dict:
     """ValueError for a parameter solve_gains would refuse."""
-    if not 0.0 <= float(prior) < float("inf"):
-        raise ValueError(f"prior must be finite and >= 0, got {prior!r}")
-    if isinstance(min_overlap, bool) or int(min_overlap) != min_overlap or int(min_overlap) < 1:
-        raise ValueError(f"min_overlap must be a positive integer, got {min_overlap!r}")
+    o = _filled(SOLVE_DEFAULTS, prior=prior, min_overlap=min_overlap)
+    if not 0.0 <= float(o["prior"]) < float("inf"):
+        raise ValueError(f"prior must be finite and >= 0, got {o['prior']!r}")
+    if isinstance(o["min_overlap"], bool) or int(o["min_overlap"]) != o["min_overlap"] or int(o["min_overlap"]) < 1:
+        raise ValueError(f"min_overlap must be a positive integer, got {o['min_overlap']!r}")
+    return o
 
 
 def _gains(gains, V: int):
@@ -137,17 +150,8 @@ def _map(t, what: str, shape, dtype) -> torch.Tensor:
     return t
 
 
-def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, photos: torch.Tensor, depth: torch.Tensor, *,
-            power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0, depth_tol: float = 0.002,
-            mode: str = "weighted", gains=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """(color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8).  pos / nrm [h,w,3] float32: each texel's point in the
-    training world frame and its normal (any length; a zero normal switches the texel off); coverage [h,w] uint8 or bool;
-    cams: a sequence of GaussianRasterizationSettings of one size, or (packed view records, H, W), as MeshRenderer.render takes
-    them; photos [V,3,H,W] float32; depth [V,1,H,W] float32, MeshRenderer.render's (0: empty).  Everything on one HIP device.  gains [V,3] (None: none): view v's
-    sample is multiplied by gains[v] in the kernel, in float64; no scaled copy of the photographs is made."""
-    check_options(power, cos_min, fade_px, depth_tol, mode)
-    if mode not in _MODES:
-        raise ValueError(f"mode {mode!r} has five outputs and takes the low bands: it is project_bands'")
+def _texel_maps(pos, nrm, coverage) -> tuple:
+    """(h, w, device) of the texel maps as project, project_bands and pair_stats take them; ValueError for anything else"""
     if not isinstance(pos, torch.Tensor) or pos.dim() != 3 or pos.shape[2] != 3 or pos.shape[0] < 1 or pos.shape[1] < 1:
         raise ValueError(f"pos must be a float32 [h,w,3] tensor, got {list(getattr(pos, 'shape', ()))}")
     h, w = int(pos.shape[0]), int(pos.shape[1])
@@ -155,29 +159,54 @@ def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, 
     _map(nrm, "nrm", (h, w, 3), torch.float32)
     if not isinstance(coverage, torch.Tensor) or coverage.dtype not in (torch.uint8, torch.bool) or tuple(coverage.shape) != (h, w):
         raise ValueError(f"coverage must be a uint8 or bool [{h},{w}] tensor")
-    dev = pos.device
+    return h, w, pos.device
+
+
+def _view_group(dev, cams, depth, **images) -> tuple:
+    """(packed views, V, H, W) of the views of one image size, with their depth maps and `images` (photos=..., project_bands: low=...)"""
     from .meshrender import _views
     views, H, W = _views(cams, dev)
     V = int(views.shape[0])
     if V > MAX_VIEWS:
         raise ValueError(f"at most {MAX_VIEWS} views per call, got {V}")
-    _map(photos, "photos", (V, 3, H, W), torch.float32)
+    for name, t in images.items():
+        _map(t, name, (V, 3, H, W), torch.float32)
     _map(depth, "depth", (V, 1, H, W), torch.float32)
-    g = _gains(gains, V)
-    for name, t in (("nrm", nrm), ("coverage", coverage), ("photos", photos), ("depth", depth)):
+    return views, V, H, W
+
+
+def _on_device(dev, pos, nrm, coverage, others, g) -> tuple:
+    """The last step before a launch, after every argument error: the named tensors `others` live where pos does (ValueError), and
+    that is a HIP device (RuntimeError).  (pos, nrm, coverage as uint8, others' tensors), all contiguous, and the gains uploaded."""
+    for name, t in [("nrm", nrm), ("coverage", coverage), *others]:
         if t.device != dev:
             raise ValueError(f"{name} must live on pos's device {dev}, got {t.device}")
-    if not pos.is_cuda:                                        # argument errors first, with or without a device
+    if dev.type != "cuda":
         raise RuntimeError("topo4d_amd has no CPU path: the maps, the photographs and the depth must live on a HIP device")
-    cov = (coverage.to(torch.uint8) if coverage.dtype == torch.bool else coverage).contiguous()
-    pos, nrm, photos, depth = pos.contiguous(), nrm.contiguous(), photos.contiguous(), depth.contiguous()
+    cov = coverage.to(torch.uint8) if coverage.dtype == torch.bool else coverage
+    return pos.contiguous(), nrm.contiguous(), cov.contiguous(), [t.contiguous() for _, t in others], None if g is None else torch.from_numpy(g).to(dev)
+
+
+def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, photos: torch.Tensor, depth: torch.Tensor, *,
+            power=None, cos_min=None, fade_px=None, depth_tol=None, mode=None, gains=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8).  pos / nrm [h,w,3] float32: each texel's point in the
+    training world frame and its normal (any length; a zero normal switches the texel off); coverage [h,w] uint8 or bool;
+    cams: a sequence of GaussianRasterizationSettings of one size, or (packed view records, H, W), as MeshRenderer.render takes
+    them; photos [V,3,H,W] float32; depth [V,1,H,W] float32, MeshRenderer.render's (0: empty).  Everything on one HIP device.
+    power, cos_min, fade_px, depth_tol, mode: None is DEFAULTS'.  gains [V,3] (None: none): view v's sample is multiplied by
+    gains[v] in the kernel, in float64; no scaled copy of the photographs is made."""
+    o = check_options(power, cos_min, fade_px, depth_tol, mode)
+    if o["mode"] not in _MODES:
+        raise ValueError(f"mode {o['mode']!r} has five outputs and takes the low bands: it is project_bands'")
+    h, w, dev = _texel_maps(pos, nrm, coverage)
+    views, V, H, W = _view_group(dev, cams, depth, photos=photos)
+    g = _gains(gains, V)
+    pos, nrm, cov, (photos, depth), g = _on_device(dev, pos, nrm, coverage, [("photos", photos), ("depth", depth)], g)
     color = torch.empty(h, w, 3, dtype=torch.float32, device=dev)
     weight = torch.empty(h, w, dtype=torch.float32, device=dev)
     count = torch.empty(h, w, dtype=torch.uint8, device=dev)
-    g = None if g is None else torch.from_numpy(g).to(dev)
     _lib.call("t4d_project_texture_gains", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(depth), ptr(g),
-              int(power), float(cos_min), float(fade_px), float(depth_tol), _MODES[mode], ptr(color), ptr(weight), ptr(count),
-              _lib.stream(dev))
+              *_rule(o), _MODES[o["mode"]], ptr(color), ptr(weight), ptr(count), _lib.stream(dev))
     return color, weight, count
 
 
@@ -207,84 +236,50 @@ def low_band(photos: torch.Tensor, depth: torch.Tensor, radius: int = 8) -> torc
 
 
 def project_bands(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, photos: torch.Tensor, low: torch.Tensor,
-                  depth: torch.Tensor, *, power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0, depth_tol: float = 0.002,
+                  depth: torch.Tensor, *, power=None, cos_min=None, fade_px=None, depth_tol=None,
                   gains=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """(low_color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8, high [h,w,3] float32, best_weight [h,w] float32): the
     two bands of mode "twoband".  The arguments of project and low [V,3,H,W] float32, low_band's.  Every view that project would
     accept at a texel gives its sample s and, by the same bilinear mix over the same taps of low, its low band l (both times
     gains[v] when given).  low_color, weight, count: the blend of the l as mode "weighted" blends the s.  high = s - l and
     best_weight = the weight of the view mode "best" would keep.  The texture is low_color + high; zeros where no view counts."""
-    check_options(power, cos_min, fade_px, depth_tol)
-    if not isinstance(pos, torch.Tensor) or pos.dim() != 3 or pos.shape[2] != 3 or pos.shape[0] < 1 or pos.shape[1] < 1:
-        raise ValueError(f"pos must be a float32 [h,w,3] tensor, got {list(getattr(pos, 'shape', ()))}")
-    h, w = int(pos.shape[0]), int(pos.shape[1])
-    _map(pos, "pos", (h, w, 3), torch.float32)
-    _map(nrm, "nrm", (h, w, 3), torch.float32)
-    if not isinstance(coverage, torch.Tensor) or coverage.dtype not in (torch.uint8, torch.bool) or tuple(coverage.shape) != (h, w):
-        raise ValueError(f"coverage must be a uint8 or bool [{h},{w}] tensor")
-    dev = pos.device
-    from .meshrender import _views
-    views, H, W = _views(cams, dev)
-    V = int(views.shape[0])
-    if V > MAX_VIEWS:
-        raise ValueError(f"at most {MAX_VIEWS} views per call, got {V}")
-    _map(photos, "photos", (V, 3, H, W), torch.float32)
-    _map(low, "low", (V, 3, H, W), torch.float32)
-    _map(depth, "depth", (V, 1, H, W), torch.float32)
+    o = check_options(power, cos_min, fade_px, depth_tol)
+    h, w, dev = _texel_maps(pos, nrm, coverage)
+    views, V, H, W = _view_group(dev, cams, depth, photos=photos, low=low)
     g = _gains(gains, V)
-    for name, t in (("nrm", nrm), ("coverage", coverage), ("photos", photos), ("low", low), ("depth", depth)):
-        if t.device != dev:
-            raise ValueError(f"{name} must live on pos's device {dev}, got {t.device}")
-    if not pos.is_cuda:                                        # argument errors first, with or without a device
-        raise RuntimeError("topo4d_amd has no CPU path: the maps, the photographs, their low bands and the depth must live on a HIP device")
-    cov = (coverage.to(torch.uint8) if coverage.dtype == torch.bool else coverage).contiguous()
-    pos, nrm, photos, low, depth = pos.contiguous(), nrm.contiguous(), photos.contiguous(), low.contiguous(), depth.contiguous()
+    pos, nrm, cov, (photos, low, depth), g = _on_device(dev, pos, nrm, coverage, [("photos", photos), ("low", low), ("depth", depth)], g)
     low_color, high = (torch.empty(h, w, 3, dtype=torch.float32, device=dev) for _ in range(2))
     weight, best_weight = (torch.empty(h, w, dtype=torch.float32, device=dev) for _ in range(2))
     count = torch.empty(h, w, dtype=torch.uint8, device=dev)
-    g = None if g is None else torch.from_numpy(g).to(dev)
     _lib.call("t4d_project_texture_bands", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(low), ptr(depth),
-              ptr(g), int(power), float(cos_min), float(fade_px), float(depth_tol), ptr(low_color), ptr(weight), ptr(count), ptr(high),
-              ptr(best_weight), _lib.stream(dev))
+              ptr(g), *_rule(o), ptr(low_color), ptr(weight), ptr(count), ptr(high), ptr(best_weight), _lib.stream(dev))
     return low_color, weight, count, high, best_weight
 
 
-def pair_stats(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, groups, *, gains=None, out=None, stat_cos_min: float = 0.5,
-               stat_lo: float = 0.02, stat_hi: float = 0.98, power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0,
-               depth_tol: float = 0.002) -> Tuple[torch.Tensor, torch.Tensor]:
+def pair_stats(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, groups, *, gains=None, out=None, stat_cos_min=None,
+               stat_lo=None, stat_hi=None, power=None, cos_min=None, fade_px=None, depth_tol=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(count [V,V], sums [V,V,3]), int64 on the device.  pos, nrm, coverage as project takes them; groups: a list of (cams, photos
     [v,3,H,W], depth [v,1,H,W]) as project takes them, one per image size, V <= 32 views in all, numbered in the order given.  View v
     takes part at a texel when project would accept it there (power, cos_min, fade_px, depth_tol), its cosine is >= stat_cos_min
     and every channel of its sample (times gains[v], [V,3], when given) lies in [stat_lo, stat_hi]: a clipped or black sample follows
     no gain model.  count[i][j]: the texels where i and j both take part; sums[i][j]: the sum of view i's samples there, as integers
     in units of 2^-16 (count[i][i], sums[i][i]: over all of view i's texels).  out = (count, sums) of an earlier call is added to and
-    returned: the statistics of several frames.  The three stat_* defaults are conventional choices (a facing limit of 60 degrees,
-    2 % off either end of the range), not tuned on a capture."""
-    check_options(power, cos_min, fade_px, depth_tol)
-    check_stat_options(stat_cos_min, stat_lo, stat_hi)
-    if not isinstance(pos, torch.Tensor) or pos.dim() != 3 or pos.shape[2] != 3 or pos.shape[0] < 1 or pos.shape[1] < 1:
-        raise ValueError(f"pos must be a float32 [h,w,3] tensor, got {list(getattr(pos, 'shape', ()))}")
-    h, w = int(pos.shape[0]), int(pos.shape[1])
-    _map(pos, "pos", (h, w, 3), torch.float32)
-    _map(nrm, "nrm", (h, w, 3), torch.float32)
-    if not isinstance(coverage, torch.Tensor) or coverage.dtype not in (torch.uint8, torch.bool) or tuple(coverage.shape) != (h, w):
-        raise ValueError(f"coverage must be a uint8 or bool [{h},{w}] tensor")
-    dev = pos.device
-    from .meshrender import _views
+    returned: the statistics of several frames.  The three stat_* defaults (None: STAT_DEFAULTS') are conventional choices (a facing
+    limit of 60 degrees, 2 % off either end of the range), not tuned on a capture."""
+    o = check_options(power, cos_min, fade_px, depth_tol)
+    stat = check_stat_options(stat_cos_min, stat_lo, stat_hi)
+    h, w, dev = _texel_maps(pos, nrm, coverage)
     groups = list(groups)
     if not groups:
         raise ValueError("pair_stats: no views")
-    records, sizes, keep = [], [], []
+    records, sizes, held = [], [], []
     for cams, photos, depth in groups:
-        views, H, W = _views(cams, dev)
-        v = int(views.shape[0])
+        views, v, H, W = _view_group(dev, cams, depth, photos=photos)
         if not 1 <= H <= 65536 or not 1 <= W <= 65536:
             raise ValueError(f"image sides must be in [1, 65536], got {H} x {W}")
-        _map(photos, "photos", (v, 3, H, W), torch.float32)
-        _map(depth, "depth", (v, 1, H, W), torch.float32)
         records.append(views)
         sizes += [(H, W)] * v
-        keep.append((photos, depth))
+        held += [("photos, depth and out", photos), ("photos, depth and out", depth)]
     V = len(sizes)
     if V > MAX_STAT_VIEWS:
         raise ValueError(f"at most {MAX_STAT_VIEWS} views per call, got {V}")
@@ -293,33 +288,25 @@ def pair_stats(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, gro
         count, sums = out
         _map(count, "out[0]", (V, V), torch.int64)
         _map(sums, "out[1]", (V, V, 3), torch.int64)
-        keep.append((count, sums))
-    for name, t in [("nrm", nrm), ("coverage", coverage)] + [("photos, depth and out", t) for pair in keep for t in pair]:
-        if t.device != dev:
-            raise ValueError(f"{name} must live on pos's device {dev}, got {t.device}")
-    if not pos.is_cuda:                                        # argument errors first, with or without a device
-        raise RuntimeError("topo4d_amd has no CPU path: the maps, the photographs and the depth must live on a HIP device")
+    pos, nrm, cov, held, g = _on_device(dev, pos, nrm, coverage, held + [("photos, depth and out", t) for t in out or ()], g)
     if out is None:
         count, sums = torch.zeros(V, V, dtype=torch.int64, device=dev), torch.zeros(V, V, 3, dtype=torch.int64, device=dev)
     elif not (count.is_contiguous() and sums.is_contiguous()):
         raise ValueError("out must be contiguous")
-    cov = (coverage.to(torch.uint8) if coverage.dtype == torch.bool else coverage).contiguous()
-    pos, nrm = pos.contiguous(), nrm.contiguous()
-    held = [(p.contiguous(), d.contiguous()) for p, d in keep[:len(groups)]]       # alive until the launch is queued on their stream
-    photo_ptrs = [p[k].data_ptr() for p, _ in held for k in range(p.shape[0])]
-    depth_ptrs = [d[k].data_ptr() for _, d in held for k in range(d.shape[0])]
+    # (held: the contiguous photographs and depth maps, alive until the launch is queued on their stream)
+    photo_ptrs = [p[k].data_ptr() for p in held[0:2 * len(groups):2] for k in range(p.shape[0])]
+    depth_ptrs = [d[k].data_ptr() for d in held[1:2 * len(groups):2] for k in range(d.shape[0])]
     tables = torch.tensor([photo_ptrs, depth_ptrs], dtype=torch.int64).to(dev)
     sizes_t = torch.tensor(sizes, dtype=torch.int32).to(dev)
     views = torch.cat(records).contiguous()
-    g = None if g is None else torch.from_numpy(g).to(dev)
     _lib.call("t4d_projtex_pair_stats", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, ptr(sizes_t), ptr(tables[0]), ptr(tables[1]),
-              int(power), float(cos_min), float(fade_px), float(depth_tol), float(stat_cos_min), float(stat_lo), float(stat_hi), ptr(g),
-              ptr(count), ptr(sums), _lib.stream(dev))
+              *_rule(o), float(stat["stat_cos_min"]), float(stat["stat_lo"]), float(stat["stat_hi"]), ptr(g), ptr(count), ptr(sums),
+              _lib.stream(dev))
     return count, sums
 
 
-def _solve(count, sums, prior: float, min_overlap: int):
-    check_solve_options(prior, min_overlap)
+def _solve(count, sums, prior=None, min_overlap=None):
+    prior, min_overlap = check_solve_options(prior, min_overlap).values()
     count = np.asarray(count.detach().cpu() if isinstance(count, torch.Tensor) else count)
     sums = np.asarray(sums.detach().cpu() if isinstance(sums, torch.Tensor) else sums)
     if count.ndim != 2 or count.shape[0] != count.shape[1] or count.shape[0] < 1 or sums.shape != (*count.shape, 3):
@@ -351,14 +338,14 @@ def _solve(count, sums, prior: float, min_overlap: int):
     return gains, report
 
 
-def solve_gains(count, sums, *, prior: float = 0.01, min_overlap: int = 64) -> np.ndarray:
+def solve_gains(count, sums, *, prior=None, min_overlap=None) -> np.ndarray:
     """float64 [V,3]: the gain of every camera and channel that makes the pairs of pair_stats agree, on the host in numpy float64.
     Per channel c, in the log domain: N_ij = count[i][j] for i != j, 0 where it is below min_overlap or where sums[i][j][c] or
     sums[j][i][c] is not positive; d_ij = log(sums[i][j][c]) - log(sums[j][i][c]), the log ratio of the two cameras' means over the
     texels they share; l minimises E(l) = sum_{i<j} N_ij (l_i - l_j + d_ij)^2 + prior sum_i n_i l_i^2 with n_i = sum_j N_ij, that
     is A l = b with A_ii = (1 + prior) n_i, A_ij = -N_ij, b_i = -sum_j N_ij d_ij; a camera with n_i = 0 keeps l_i = 0.  The gain is
-    exp(l).  The prior only fixes the common factor every connected group of cameras is free in, at about 1.  prior = 0.01 and
-    min_overlap = 64 are conventional choices, not tuned on a capture."""
+    exp(l).  The prior only fixes the common factor every connected group of cameras is free in, at about 1.  SOLVE_DEFAULTS (None)
+    are conventional choices, not tuned on a capture."""
     return _solve(count, sums, prior, min_overlap)[0]
 
 
@@ -459,60 +446,6 @@ def island_labels(face_obj, h: int, w: int, device=None) -> torch.Tensor:
     return torch.where(texfinish.coverage_from_obj(face_obj, h, w, device=dev) != 0, labels, torch.zeros_like(labels))
 
 
-def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0,
-                  depth_tol: float = 0.002, mode: str = "weighted", gains=None, device=None, band_radius: int = 8):
-    """(texture [h,w,3] uint8, weight [h,w] float32, count [h,w] uint8) of one frame: `dataset` holds ingest.get_dataset's entries
-    ("cam", "im"), vertices [N,3] the mesh in the training world frame.  The mesh is rendered once for the depth maps
-    (meshrender.MeshRenderer over a 1x1 dummy texture), surface_maps gives the texel maps, project gathers, texfinish.quantize
-    rounds as the PNG encoder does.  Views of one size go in one launch; a rig with several sizes (turned cameras) is merged
-    per size: weighted sums add up, "best" keeps the larger weight, the earlier size on ties.  gains [len(dataset),3] (None: none):
-    one row per entry of `dataset`, in its order.  mode "twoband": per size low_band (band_radius) and project_bands; the low bands
-    merge as "weighted" does, the detail by the larger best weight (the earlier size on ties), and the texture is their sum, one
-    float32 addition, clamped to [0, 1] (where the views disagree the sum overshoots, and the quantisation wraps)."""
-    from . import meshrender, texfinish
-    check_options(power, cos_min, fade_px, depth_tol, mode)
-    check_band_options(band_radius)
-    if not dataset:
-        raise ValueError("project_frame: no views")
-    gains = _gains(gains, len(dataset))
-    faces, uv_faces = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
-    dev = meshrender._device(device if device is not None else (vertices.device if vertices.is_cuda else None))
-    renderer = meshrender.MeshRenderer(faces, uv_faces, face_obj.uvs, np.zeros((1, 1, 3), np.uint8), device=dev)
-    pos, nrm, cov = surface_maps(face_obj, vertices, res, device=dev)
-    total, detail = None, None
-    for ks in _size_groups(dataset).values():
-        cams = [dataset[k]["cam"] for k in ks]
-        _, depth, _ = renderer.render(vertices, cams)
-        photos = torch.stack([dataset[k]["im"] for k in ks]).to(torch.float32)
-        if mode == "twoband":
-            color, weight, count, high, best = project_bands(pos, nrm, cov, cams, photos, low_band(photos, depth, band_radius), depth,
-                                                             power=power, cos_min=cos_min, fade_px=fade_px, depth_tol=depth_tol,
-                                                             gains=None if gains is None else gains[ks])
-            if detail is None:
-                detail = [high, best]
-            else:
-                take = best > detail[1]
-                detail = [torch.where(take[..., None], high, detail[0]), torch.where(take, best, detail[1])]
-        else:
-            color, weight, count = project(pos, nrm, cov, cams, photos, depth, power=power, cos_min=cos_min, fade_px=fade_px,
-                                           depth_tol=depth_tol, mode=mode, gains=None if gains is None else gains[ks])
-        if total is None:
-            total = [color, weight, count]
-            continue
-        c0, w0, n0 = total
-        if mode == "best":
-            take = weight > w0
-            total = [torch.where(take[..., None], color, c0), torch.where(take, weight, w0), n0 + count]
-        else:
-            ws = w0 + weight
-            mixed = (c0 * w0[..., None] + color * weight[..., None]) / ws.clamp_min(torch.finfo(torch.float32).tiny)[..., None]
-            total = [torch.where((ws > 0)[..., None], mixed, torch.zeros_like(mixed)), ws, n0 + count]
-    color, weight, count = total
-    if detail is not None:                                     # the sum of two bands can leave [0, 1], and quantize wraps as numpy's cast does
-        color = (color + detail[0]).clamp_(0.0, 1.0)
-    return texfinish.quantize(color), weight, count
-
-
 def _size_groups(dataset) -> dict:
     groups = {}
     for k, e in enumerate(dataset):
@@ -520,33 +453,88 @@ def _size_groups(dataset) -> dict:
     return groups
 
 
-def frame_stats(face_obj, vertices: torch.Tensor, dataset, res, *, out=None, stat_cos_min: float = 0.5, stat_lo: float = 0.02,
-                stat_hi: float = 0.98, power: int = 2, cos_min: float = 0.1, fade_px: float = 16.0, depth_tol: float = 0.002,
-                mode: str = "weighted", device=None, band_radius: int = 8):
-    """pair_stats of one frame, its views numbered as in `dataset`: the maps of surface_maps, the depth renders of project_frame.
-    out: the statistics of earlier frames of the same cameras, added to.  (mode and band_radius are accepted and ignored, so that
-    one dictionary of projection options serves project_frame and this.)"""
+def _frame_inputs(face_obj, vertices: torch.Tensor, dataset, res, device):
+    """(pos, nrm, coverage, groups) of one frame: surface_maps' texel maps and, one image size after the other, (the entries' indices
+    in `dataset`, their cams, their photographs [v,3,H,W] float32, their depth maps): the mesh is rendered once per size for the
+    depth (meshrender.MeshRenderer over a 1x1 dummy texture)."""
     from . import meshrender
-    check_options(power, cos_min, fade_px, depth_tol, mode)
+    faces, uv_faces = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
+    dev = meshrender._device(device if device is not None else (vertices.device if vertices.is_cuda else None))
+    renderer = meshrender.MeshRenderer(faces, uv_faces, face_obj.uvs, np.zeros((1, 1, 3), np.uint8), device=dev)
+
+    def groups():
+        for ks in _size_groups(dataset).values():
+            cams = [dataset[k]["cam"] for k in ks]
+            yield ks, cams, torch.stack([dataset[k]["im"] for k in ks]).to(torch.float32), renderer.render(vertices, cams)[1]
+
+    return (*surface_maps(face_obj, vertices, res, device=dev), groups())
+
+
+def _blend(a, b):
+    """(color, weight) of two weighted blends as one: the weighted sums add up"""
+    ws = a[1] + b[1]
+    mixed = (a[0] * a[1][..., None] + b[0] * b[1][..., None]) / ws.clamp_min(torch.finfo(torch.float32).tiny)[..., None]
+    return torch.where((ws > 0)[..., None], mixed, torch.zeros_like(mixed)), ws
+
+
+def _keep_larger(a, b):
+    """(value, weight) per texel of the one with the larger weight: a, the earlier size, on ties"""
+    take = b[1] > a[1]
+    return torch.where(take[..., None], b[0], a[0]), torch.where(take, b[1], a[1])
+
+
+def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power=None, cos_min=None, fade_px=None, depth_tol=None, mode=None,
+                  gains=None, device=None, band_radius: int = 8):
+    """(texture [h,w,3] uint8, weight [h,w] float32, count [h,w] uint8) of one frame: `dataset` holds ingest.get_dataset's entries
+    ("cam", "im"), vertices [N,3] the mesh in the training world frame.  _frame_inputs gives the texel maps and the depth maps,
+    project gathers, texfinish.quantize rounds as the PNG encoder does.  Views of one size go in one launch; a rig with several
+    sizes (turned cameras) is merged per size: weighted sums add up, "best" keeps the larger weight, the earlier size on ties.
+    gains [len(dataset),3] (None: none): one row per entry of `dataset`, in its order.  mode "twoband": per size low_band
+    (band_radius) and project_bands; the low bands merge as "weighted" does, the detail by the larger best weight (the earlier size
+    on ties), and the texture is their sum, one float32 addition, clamped to [0, 1] (where the views disagree the sum overshoots,
+    and the quantisation wraps)."""
+    from . import texfinish
+    o = check_options(power, cos_min, fade_px, depth_tol, mode)
+    mode, rule = o["mode"], {k: v for k, v in o.items() if k != "mode"}
     check_band_options(band_radius)
-    check_stat_options(stat_cos_min, stat_lo, stat_hi)
+    if not dataset:
+        raise ValueError("project_frame: no views")
+    gains = _gains(gains, len(dataset))
+    pos, nrm, cov, groups = _frame_inputs(face_obj, vertices, dataset, res, device)
+    total = detail = count = None
+    for ks, cams, photos, depth in groups:
+        g = None if gains is None else gains[ks]
+        if mode == "twoband":
+            color, weight, n, high, best = project_bands(pos, nrm, cov, cams, photos, low_band(photos, depth, band_radius), depth, gains=g, **rule)
+            detail = (high, best) if detail is None else _keep_larger(detail, (high, best))
+        else:
+            color, weight, n = project(pos, nrm, cov, cams, photos, depth, mode=mode, gains=g, **rule)
+        if total is None:
+            total, count = (color, weight), n
+        else:
+            total, count = (_keep_larger if mode == "best" else _blend)(total, (color, weight)), count + n
+    color, weight = total
+    if detail is not None:                                     # the sum of two bands can leave [0, 1], and quantize wraps as numpy's cast does
+        color = (color + detail[0]).clamp_(0.0, 1.0)
+    return texfinish.quantize(color), weight, count
+
+
+def frame_stats(face_obj, vertices: torch.Tensor, dataset, res, *, out=None, device=None, **options):
+    """pair_stats of one frame, its views numbered as in `dataset`, over _frame_inputs' maps and depth renders.  out: the statistics
+    of earlier frames of the same cameras, added to.  options: pair_stats' (stat_cos_min, stat_lo, stat_hi, power, cos_min, fade_px,
+    depth_tol)."""
+    check_options(**{k: v for k, v in options.items() if k not in STAT_DEFAULTS})
+    check_stat_options(**{k: v for k, v in options.items() if k in STAT_DEFAULTS})
     if not dataset:
         raise ValueError("frame_stats: no views")
     if len(dataset) > MAX_STAT_VIEWS:
         raise ValueError(f"at most {MAX_STAT_VIEWS} views can be equalised, got {len(dataset)}")
-    faces, uv_faces = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
-    dev = meshrender._device(device if device is not None else (vertices.device if vertices.is_cuda else None))
-    renderer = meshrender.MeshRenderer(faces, uv_faces, face_obj.uvs, np.zeros((1, 1, 3), np.uint8), device=dev)
-    pos, nrm, cov = surface_maps(face_obj, vertices, res, device=dev)
-    groups, order = [], []
-    for ks in _size_groups(dataset).values():
-        cams = [dataset[k]["cam"] for k in ks]
-        groups.append((cams, torch.stack([dataset[k]["im"] for k in ks]).to(torch.float32), renderer.render(vertices, cams)[1]))
-        order += ks
-    count, sums = pair_stats(pos, nrm, cov, groups, stat_cos_min=stat_cos_min, stat_lo=stat_lo, stat_hi=stat_hi, power=power,
-                             cos_min=cos_min, fade_px=fade_px, depth_tol=depth_tol)
+    pos, nrm, cov, groups = _frame_inputs(face_obj, vertices, dataset, res, device)
+    groups = list(groups)
+    order = [k for ks, *_ in groups for k in ks]
+    count, sums = pair_stats(pos, nrm, cov, [g[1:] for g in groups], **options)
     if order != sorted(order):                                 # several sizes: back from group order to dataset order
-        back = torch.tensor(np.argsort(order), device=dev)
+        back = torch.tensor(np.argsort(order), device=pos.device)
         count, sums = count[back][:, back], sums[back][:, back]
     if out is not None:
         out[0].add_(count)
@@ -555,7 +543,7 @@ def frame_stats(face_obj, vertices: torch.Tensor, dataset, res, *, out=None, sta
     return count.contiguous(), sums.contiguous()
 
 
-def estimate_gains(face_obj, vertices: torch.Tensor, dataset, res, *, prior: float = 0.01, min_overlap: int = 64, device=None, **options):
+def estimate_gains(face_obj, vertices: torch.Tensor, dataset, res, *, prior=None, min_overlap=None, device=None, **options):
     """(gains float64 [len(dataset),3], report) of one frame: frame_stats, then solve_gains.  options: frame_stats's.  report:
     per channel the number of camera pairs used ("pairs"), the count-weighted rms of the pairs' log ratios d_ij as the cameras come
     ("rms_before") and of l_i - l_j + d_ij with the gains applied ("rms_after")."""
@@ -632,55 +620,57 @@ def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: 
 
 
 # ---- command line ----------------------------------------------------------------------------------------------------------
+def _add_flags(p: argparse.ArgumentParser, suppress: bool, defaults: dict, helps, prefix: str = "", **more) -> None:
+    """One flag --<prefix><key> per entry of `defaults`, of the default's type, with its help text; `more`: further add_argument
+    arguments per key.  suppress (train's parser): absent from the parse unless given."""
+    for (k, v), text in zip(defaults.items(), helps):
+        p.add_argument(f"--{prefix}{k}", type=type(v), default=argparse.SUPPRESS if suppress else v, help=text, **more.get(k, {}))
+
+
+def _flags_of(args, defaults: dict, prefix: str = "") -> dict:
+    return {k: getattr(args, prefix + k, v) for k, v in defaults.items()}
+
+
 def add_options(p: argparse.ArgumentParser, suppress: bool = False) -> None:
-    """--mode and the four parameters, on the parser of this module and (suppress=True: absent unless given) of train."""
-    d = (lambda v: argparse.SUPPRESS) if suppress else (lambda v: v)
-    p.add_argument("--mode", choices=MODES, default=d(DEFAULTS["mode"]),
-                   help="Projection: blend the views that see a texel by their weights, keep the best one, or blend the photographs' "
-                        "low band and take the detail from the best view (default weighted).")
-    p.add_argument("--power", type=int, default=d(DEFAULTS["power"]), help=f"Projection: weight = cos^power, 0..{MAX_POWER} (default 2).")
-    p.add_argument("--cos_min", type=float, default=d(DEFAULTS["cos_min"]),
-                   help="Projection: drop a view whose viewing direction makes a cosine below this with the normal (default 0.1).")
-    p.add_argument("--fade_px", type=float, default=d(DEFAULTS["fade_px"]),
-                   help="Projection: fade a view's weight over this many pixels towards the image edge; 0: no fade (default 16).")
-    p.add_argument("--depth_tol", type=float, default=d(DEFAULTS["depth_tol"]),
-                   help="Projection: relative slack of the occlusion test against the mesh's depth map (default 0.002).")
+    """The four parameters and --mode, on the parser of this module and (suppress=True) of train."""
+    _add_flags(p, suppress, DEFAULTS, (
+        f"Projection: weight = cos^power, 0..{MAX_POWER} (default 2).",
+        "Projection: drop a view whose viewing direction makes a cosine below this with the normal (default 0.1).",
+        "Projection: fade a view's weight over this many pixels towards the image edge; 0: no fade (default 16).",
+        "Projection: relative slack of the occlusion test against the mesh's depth map (default 0.002).",
+        "Projection: blend the views that see a texel by their weights, keep the best one, or blend the photographs' "
+        "low band and take the detail from the best view (default weighted)."), mode=dict(choices=MODES))
 
 
 def options_of(args) -> dict:
-    return {k: getattr(args, k, v) for k, v in DEFAULTS.items()}
+    return _flags_of(args, DEFAULTS)
 
 
 def add_band_options(p: argparse.ArgumentParser, suppress: bool = False) -> None:
     """The parameter of --mode twoband, beside add_options' on both parsers."""
-    d = (lambda v: argparse.SUPPRESS) if suppress else (lambda v: v)
-    p.add_argument("--band_radius", type=int, default=d(BAND_DEFAULTS["band_radius"]), metavar="R",
-                   help=f"With --mode twoband: the low band is the photograph's mean over a box of 2R+1 pixels, 0..{MAX_BAND_RADIUS} (default 8).")
+    _add_flags(p, suppress, BAND_DEFAULTS, (
+        f"With --mode twoband: the low band is the photograph's mean over a box of 2R+1 pixels, 0..{MAX_BAND_RADIUS} (default 8).",),
+        band_radius=dict(metavar="R"))
 
 
 def band_options_of(args) -> dict:
-    return {k: getattr(args, k, v) for k, v in BAND_DEFAULTS.items()}
+    return _flags_of(args, BAND_DEFAULTS)
 
 
 def add_eq_options(p: argparse.ArgumentParser, suppress: bool = False) -> None:
     """The parameters of the equalisation, beside add_options' on both parsers."""
-    d = (lambda v: argparse.SUPPRESS) if suppress else (lambda v: v)
-    p.add_argument("--stat_cos_min", type=float, default=d(STAT_DEFAULTS["stat_cos_min"]),
-                   help="Equalisation: a view's texel counts when the cosine between normal and viewing direction is at least this (default 0.5).")
-    p.add_argument("--stat_lo", type=float, default=d(STAT_DEFAULTS["stat_lo"]),
-                   help="Equalisation: leave out samples with a channel below this: black follows no gain (default 0.02).")
-    p.add_argument("--stat_hi", type=float, default=d(STAT_DEFAULTS["stat_hi"]),
-                   help="Equalisation: leave out samples with a channel above this: clipped (default 0.98).")
-    p.add_argument("--eq_prior", type=float, default=d(SOLVE_DEFAULTS["prior"]),
-                   help="Equalisation: weight of the pull of every gain towards 1, which fixes the common factor (default 0.01).")
-    p.add_argument("--eq_min_overlap", type=int, default=d(SOLVE_DEFAULTS["min_overlap"]),
-                   help="Equalisation: ignore a pair of cameras that shares fewer texels than this (default 64).")
+    _add_flags(p, suppress, STAT_DEFAULTS, (
+        "Equalisation: a view's texel counts when the cosine between normal and viewing direction is at least this (default 0.5).",
+        "Equalisation: leave out samples with a channel below this: black follows no gain (default 0.02).",
+        "Equalisation: leave out samples with a channel above this: clipped (default 0.98)."))
+    _add_flags(p, suppress, SOLVE_DEFAULTS, (
+        "Equalisation: weight of the pull of every gain towards 1, which fixes the common factor (default 0.01).",
+        "Equalisation: ignore a pair of cameras that shares fewer texels than this (default 64)."), prefix="eq_")
 
 
 def eq_options_of(args) -> Tuple[dict, dict]:
     """(the stat_* options of pair_stats, the options of solve_gains) of a parse, checked"""
-    stat = {k: getattr(args, k, v) for k, v in STAT_DEFAULTS.items()}
-    solve = dict(prior=getattr(args, "eq_prior", SOLVE_DEFAULTS["prior"]), min_overlap=getattr(args, "eq_min_overlap", SOLVE_DEFAULTS["min_overlap"]))
+    stat, solve = _flags_of(args, STAT_DEFAULTS), _flags_of(args, SOLVE_DEFAULTS, "eq_")
     try:
         check_stat_options(**stat)
         check_solve_options(**solve)
@@ -705,7 +695,8 @@ class GainEstimator:
         elif self.names != _names(dataset):
             raise ValueError(f"the frames to equalise over hold different cameras: {self.names} and {_names(dataset)}")
         verts = torch.from_numpy(training_vertices(face_obj.vertices, trans_g)).to(dev)
-        self.out = frame_stats(face_obj, verts, dataset, self.res, out=self.out, device=dev, **self.options, **self.stat)
+        rule = {k: v for k, v in self.options.items() if k in DEFAULTS and k != "mode"}     # (mode and band_radius are project_frame's)
+        self.out = frame_stats(face_obj, verts, dataset, self.res, out=self.out, device=dev, **rule, **self.stat)
         self.frames += 1
 
     def finish(self, path: str) -> dict:
@@ -760,16 +751,14 @@ def build_parser() -> argparse.ArgumentParser:
 
 def _check_args(args, res: int) -> dict:
     from . import texfinish
-    opts = options_of(args)
-    if opts["mode"] == "twoband":                              # (only then: the options are recorded in proj_gains.json)
-        opts.update(band_options_of(args))
+    opts, band = options_of(args), band_options_of(args)
     try:
-        check_options(**{k: opts[k] for k in DEFAULTS})
-        check_band_options(**band_options_of(args))
+        check_options(**opts)
+        check_band_options(**band)
         texfinish.check_options(getattr(args, "tex_pad", 0), 0, getattr(args, "tex_sizes", ()), res)
     except ValueError as e:
         raise SystemExit(f"projection options: {e}") from None
-    return opts
+    return {**opts, **band} if opts["mode"] == "twoband" else opts      # (only then: the options are recorded in proj_gains.json)
 
 
 def _read_obj(frame_dir: str):
