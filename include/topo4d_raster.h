@@ -727,6 +727,44 @@ int t4d_project_texture_bands(const float *pos, const float *nrm, const uint8_t 
                               const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
                               double depth_tol, float *low_color, float *weight, uint8_t *count, float *high, float *best_weight,
                               void *hip_stream);
+/* Photo-consistency (projtex.consistency; project / project_bands / project_frame take its mask): a specular highlight, a leak of
+ * the occlusion test (hair, lashes, a nose rim the mesh does not model) and transient content in one camera are no gain per
+ * camera and no registration error; one view disagrees with a consensus of the others (Waechter et al., "Let There Be Color!").
+ * t4d_projtex_consistency: the maps, the views with sizes, the tables photos / depth, the rule's four parameters and gains as
+ * t4d_projtex_pair_stats takes them (1 <= n_views <= 32, numbered alike); 0 <= reject_tol <= 4, -1 <= vote_cos_min <= 1,
+ * 2 <= min_votes <= 32.  Outputs (device): skip [tex_h,tex_w] uint32, 0 at every texel that is not covered with a non-zero normal,
+ * and votes [tex_h,tex_w] uint8.  The rule is in integers, so no order of evaluation changes a bit (tests/projtex_consist_ref.py
+ * reproduces both outputs).  Per covered texel with a non-zero normal:
+ *   A.1. each view is taken through t4d_project_texture's steps as they stand, the sample times gains[v] when given
+ *   A.2. for every accepted view, with s' = s >= 0 ? (s <= 4 ? s : 4) : 0 (a NaN becomes 0): q[c] = llrint(s'[c] 65536)
+ *   A.3. a voter is an accepted view with cos >= vote_cos_min; votes = n, their number; if n < min_votes nothing is rejected here
+ *   A.4. per channel m[c] = the lower median of the voters' q[c]: the value of the voter of rank (n - 1) / 2 (integer division) in
+ *        the order by (q[c], view index) ascending
+ *   A.5. an accepted view, voter or not, is an outlier when max_c |q[c] - m[c]| > qt, qt = llrint(reject_tol 65536)
+ *   A.6. if every accepted view is an outlier there is no consensus and nothing is rejected; otherwise bit v of skip is set for
+ *        every outlier v: at least one accepted view is always kept
+ * Known limits: with fewer than min_votes facing views nothing is rejected (the rim of the coverage keeps its highlights); a
+ * defect most voters share survives; the threshold is absolute, so it is looser in the shadows than a relative one would be.
+ * t4d_project_texture_skip / t4d_project_texture_bands_skip: t4d_project_texture_gains / t4d_project_texture_bands with the mask
+ * skip [tex_h,tex_w] uint32 (device; NULL: none, and every output bit is theirs: they forward here): view v of the launch is left
+ * out at a texel, exactly as a view that failed the weight test (it adds to no sum, is no candidate for the best view and does
+ * not count), when bit skip_base + v of skip[texel] is set; with skip, skip_base >= 0 and skip_base + n_views <= 32.  count is
+ * the number of contributing views; under a mask of t4d_projtex_consistency over the same views it never drops to 0 where it was
+ * above 0.  No call synchronises the stream. */
+int t4d_projtex_consistency(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                            const float *views, int32_t n_views, const int32_t *sizes, const float *const *photos,
+                            const float *const *depth, int32_t power, double cos_min, double fade_px, double depth_tol,
+                            const double *gains, double reject_tol, double vote_cos_min, int32_t min_votes, uint32_t *skip,
+                            uint8_t *votes, void *hip_stream);
+int t4d_project_texture_skip(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                             const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos, const float *depth,
+                             const double *gains, int32_t power, double cos_min, double fade_px, double depth_tol, int32_t mode,
+                             float *color, float *weight, uint8_t *count, const uint32_t *skip, int32_t skip_base, void *hip_stream);
+int t4d_project_texture_bands_skip(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                   const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos, const float *low,
+                                   const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
+                                   double depth_tol, float *low_color, float *weight, uint8_t *count, float *high,
+                                   float *best_weight, const uint32_t *skip, int32_t skip_base, void *hip_stream);
 
 /* Exact closest point on a triangle soup, or on a bare point cloud, for many query points (csrc/t4d_closest.hip): what
  * topo4d_amd/scanscore.py scores a frame's face.obj against its multi-view-stereo scan with.  It stands in for

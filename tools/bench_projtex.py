@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Projection of the capture photographs into the UV texture (topo4d_amd/projtex.py, csrc/t4d_projtex.hip).  Prints one JSON line.
-    python tools/bench_projtex.py [--res 8192] [--n 513] [--views 24] [--height 3008] [--width 4096] [--equalize | --twoband [--radius 8]]
+    python tools/bench_projtex.py [--res 8192] [--n 513] [--views 24] [--height 3008] [--width 4096] [--equalize | --twoband [--radius 8] | --reject]
 The scene: scaffold.scene.uv_mesh(n) as the UV layout, its vertices lifted onto the front of the scaffold's head-sized ellipsoid,
 seen by scaffold.scene.camera_rig (24 views at 4096 x 3008) with random photographs.  kernel_ms: t4d_project_texture alone between
 HIP events on preallocated buffers (min of 6), for both modes.  frame_ms: what one frame costs from the mesh and the photographs
@@ -15,7 +15,13 @@ The photographs are random, so the solved gains say nothing; pair_counts describ
 --twoband times mode "twoband" instead of the frame, in the same run as kernel_ms: low_band_ms is t4d_projtex_low_band over all
 views and project_bands_ms t4d_project_texture_bands, both between HIP events (min of 6); twoband_frame_ms is the frame as above
 with the low bands, the two-band projection and the sum of the bands in the place of the projection, and frame_ms the weighted
-frame of the same run (min of 3 each)."""
+frame of the same run (min of 3 each).
+--reject times the photo-consistency check instead of the frame, in the same run as kernel_ms: consistency_ms is
+t4d_projtex_consistency over all views, project_skip_ms t4d_project_texture_skip (weighted) and project_bands_skip_ms
+t4d_project_texture_bands_skip under its mask, and project_bands_ms the two-band projection without a mask, all between HIP events
+(min of 6); the yardstick is the unmasked projection of the same run.  Random photographs over the whole range never agree, so
+with --reject they are drawn from [0.35, 0.65]: most views agree within the default tolerance and some do not; `rejected` describes
+the mask."""
 import argparse
 import ctypes as C
 import json
@@ -38,6 +44,7 @@ ap.add_argument("--height", type=int, default=3008)
 ap.add_argument("--width", type=int, default=4096)
 ap.add_argument("--equalize", action="store_true")
 ap.add_argument("--twoband", action="store_true")
+ap.add_argument("--reject", action="store_true")
 ap.add_argument("--radius", type=int, default=projtex.BAND_DEFAULTS["band_radius"])
 a = ap.parse_args()
 dev = torch.device("cuda", torch.cuda.current_device())
@@ -79,6 +86,8 @@ verts = torch.from_numpy((unit * np.array(SEMI_AXES)).astype(np.float32)).to(dev
 normals = torch.from_numpy((unit / np.array(SEMI_AXES)).astype(np.float32)).to(dev)
 cams = camera_rig(H, W, V, device=dev)
 photos = torch.rand(V, 3, H, W, device=dev)
+if a.reject:
+    photos.mul_(0.3).add_(0.35)
 uvs = np.stack([u, v], 1)
 renderer = meshrender.MeshRenderer(tris, tris, uvs, np.zeros((1, 1, 3), np.uint8), device=dev)
 
@@ -156,6 +165,54 @@ if a.equalize:
     off = pair_count.cpu().numpy()[~np.eye(V, dtype=bool)]
     result["pair_counts"] = {"pairs_with_overlap": int((off > 0).sum() // 2), "max": int(off.max()), "diagonal_mean": int(pair_count.diagonal().float().mean())}
     result["pair_stats_over_kernel"] = round(result["pair_stats_ms"] / result["kernel_ms"]["weighted"], 2)
+    print(json.dumps(result))
+    sys.exit(0)
+if a.reject:
+    if V > projtex.MAX_STAT_VIEWS:
+        sys.exit(f"--reject: at most {projtex.MAX_STAT_VIEWS} views")
+    skip = torch.zeros(res, res, dtype=torch.int32, device=dev)
+    votes = torch.zeros(res, res, dtype=torch.uint8, device=dev)
+    sizes = torch.tensor([[H, W]] * V, dtype=torch.int32, device=dev)
+    tables = torch.tensor([[photos[k].data_ptr() for k in range(V)], [depth[k].data_ptr() for k in range(V)]], dtype=torch.int64, device=dev)
+    low = torch.empty_like(photos)
+    high = torch.empty_like(color)
+    best_weight = torch.empty_like(weight)
+    c = projtex.CONSIST_DEFAULTS
+
+    def consist(s):
+        rc = lib.t4d_projtex_consistency(P(pos), P(nrm), P(cov), res, res, P(views), V, P(sizes), P(tables[0]), P(tables[1]), 2, 0.1, 16.0,
+                                         0.002, None, c["reject_tol"], c["vote_cos_min"], c["min_votes"], P(skip), P(votes), s)
+        assert rc == 0, _lib.last_error()
+
+    def masked(mask):
+        def launch(s):
+            rc = lib.t4d_project_texture_skip(P(pos), P(nrm), P(cov), res, res, P(views), V, H, W, P(photos), P(depth), None, 2, 0.1, 16.0,
+                                              0.002, 0, P(color), P(weight), P(count), mask, 0, s)
+            assert rc == 0, _lib.last_error()
+        return launch
+
+    def bands(mask):
+        def launch(s):
+            rc = lib.t4d_project_texture_bands_skip(P(pos), P(nrm), P(cov), res, res, P(views), V, H, W, P(photos), P(low), P(depth), None, 2,
+                                                    0.1, 16.0, 0.002, P(color), P(weight), P(count), P(high), P(best_weight), mask, 0, s)
+            assert rc == 0, _lib.last_error()
+        return launch
+
+    rc = lib.t4d_projtex_low_band(P(photos), P(depth), V, H, W, a.radius, P(low), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0, _lib.last_error()
+    result["consistency_ms"] = events_ms(consist)
+    result["project_skip_ms"] = events_ms(masked(P(skip)))
+    result["kernel_ms_again"] = events_ms(kernel(0))             # the plain kernel once more, after the others: the run's own spread
+    result["project_bands_ms"] = events_ms(bands(None))
+    result["project_bands_skip_ms"] = events_ms(bands(P(skip)))
+    live = votes > 0
+    n = projtex.rejected_count(skip)
+    result["rejected"] = {"texels_with_min_votes": round(float((votes >= c["min_votes"]).sum() / live.sum()), 4),
+                          "texels_with_a_rejected_view": round(float((n > 0).sum() / live.sum()), 4),
+                          "mean_rejected_views_there": round(float(n[n > 0].float().mean()), 2) if bool((n > 0).any()) else 0.0}
+    result["consistency_over_kernel"] = round(result["consistency_ms"] / result["kernel_ms"]["weighted"], 2)
+    result["skip_over_kernel"] = round(result["project_skip_ms"] / result["kernel_ms"]["weighted"], 2)
+    result["bands_skip_over_bands"] = round(result["project_bands_skip_ms"] / result["project_bands_ms"], 2)
     print(json.dumps(result))
     sys.exit(0)
 if a.twoband:

@@ -45,6 +45,31 @@
 //       ties stay with the lower view)
 // and at the end low_color = float32(sl / sw), weight = float32(sw), high = float32(hb), best_weight = float32(bw), count as
 // above; every other texel gets zeros.  The caller adds the bands: color = low_color + high.
+//
+// Photo-consistency (t4d_projtex_consistency; the rule is restated in tests/projtex_consist_ref.py): a specular highlight, a
+// leak of the occlusion test (hair, lashes, a nose rim the mesh does not model) and transient content in one camera are no gain per
+// camera and no registration error; what they share is that one view disagrees with a consensus of the others (Waechter et al.,
+// "Let There Be Color!").  The rule is in integers, so no order of evaluation changes a bit.  Per covered texel with a non-zero
+// normal, over all V <= 32 views of the call, of mixed image sizes, numbered as t4d_projtex_pair_stats numbers them:
+//   A.1. each view is taken through steps 1..6 as they stand, the sample times gains[v] when given
+//   A.2. for every accepted view, with s' = s >= 0 ? (s <= 4 ? s : 4) : 0 (a NaN becomes 0): q[c] = llrint(s'[c] 65536)
+//   A.3. a voter is an accepted view with cos >= vote_cos_min; n = the number of voters; if n < min_votes nothing is rejected here
+//   A.4. per channel m[c] = the lower median of the voters' q[c]: the value of the voter of rank (n - 1) / 2 (integer division)
+//        in the order by (q[c], view index) ascending
+//   A.5. an accepted view, voter or not, is an outlier when max_c |q[c] - m[c]| > qt, qt = llrint(reject_tol 65536)
+//   A.6. if every accepted view is an outlier there is no consensus and nothing is rejected; otherwise bit v of the texel's skip
+//        word is set for every outlier v, so at least one accepted view is always kept
+// skip [h,w] uint32 is 0 for every texel that is not live; votes [h,w] uint8 holds n.  The blends take the mask (kSkip below): view
+// v of a launch is left out at a texel, exactly as a view that failed step 5, when bit skip_base + v of skip[texel] is set.
+// k_projtex_consist: one lane per texel, one wave per workgroup, a tile of 16 x 4 texels (a wave's four rows of the 16 x 16 tile
+// of the other texel kernels, so neighbouring lanes still gather neighbouring pixels).  The view loop runs once; the accepted and
+// the voter mask stay in registers, and the packed q of every accepted view (three fields of 21 bits: q <= 2^18) goes to LDS as
+// one 64-bit word at [v][lane], V x 512 bytes per wave, sized by the call's V: 16 KiB at V = 32, so 10 waves per CU of the 160
+// KiB, 13 at the 24 views of a capture rig.  A 256-lane workgroup would take 64 KiB at V = 32 and leave 2 workgroups = 8 waves per
+// CU, with 32 KiB idle; the single wave keeps every 16 KiB in use, needs no barrier (a lane reads only its own column) and lets the
+// waves of an empty tile retire at once.  The median is found by rank counting over the voters, O(n^2) compares of words the lane
+// reads back from its column (consecutive lanes, consecutive 64-bit words: no bank conflict), all three channels per pair.  No
+// global scratch, no atomics: every texel is a pure function of its inputs.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -79,9 +104,11 @@ struct PTP {
     int H, W, mode;
     float *color, *weight;
     uint8_t *count;
+    const uint32_t *skip;                    // [th,tw] the consistency mask or NULL; view v is bit skip_base + v
+    int skip_base;
 };
 
-// The lane's texel of the 16x16 tile (tile_x, tile_y): whether it lies inside the texture, and there `at`; whether it is live (inside,
+// The texel (tx, ty), and through texel_load the lane's texel of the 16x16 tile (tile_x, tile_y): whether it lies inside the texture, and there `at`; whether it is live (inside,
 // covered, with a non-zero normal), and then its point and its normalised normal.  A texel outside the coverage costs one byte read.
 struct Texel {
     bool inside, live;
@@ -89,11 +116,10 @@ struct Texel {
     double X, Y, Z, nhx, nhy, nhz;
 };
 
-__device__ __forceinline__ Texel texel_load(const Tex &T, int tile_x, int tile_y)
+__device__ __forceinline__ Texel texel_at(const Tex &T, int tx, int ty)
 {
 #pragma clang fp contract(off)
     Texel t = {};
-    const int tx = tile_x * kTile + (int)(threadIdx.x % kTile), ty = tile_y * kTile + (int)(threadIdx.x / kTile);
     t.inside = tx < T.tw && ty < T.th;
     t.at = (size_t)ty * (size_t)T.tw + (size_t)tx;
     if (!t.inside || T.coverage[t.at] == 0) return t;
@@ -103,6 +129,11 @@ __device__ __forceinline__ Texel texel_load(const Tex &T, int tile_x, int tile_y
     t.X = (double)T.pos[3 * t.at]; t.Y = (double)T.pos[3 * t.at + 1]; t.Z = (double)T.pos[3 * t.at + 2];
     t.nhx = nx / nl; t.nhy = ny / nl; t.nhz = nz / nl;
     return t;
+}
+
+__device__ __forceinline__ Texel texel_load(const Tex &T, int tile_x, int tile_y)
+{
+    return texel_at(T, tile_x * kTile + (int)(threadIdx.x % kTile), tile_y * kTile + (int)(threadIdx.x / kTile));
 }
 
 struct View {                                 // one view of size H x W: its record (vm, then pm) and its depth [H,W]
@@ -180,7 +211,8 @@ __device__ __forceinline__ void view_sample(const float *img, const View &v, con
     }
 }
 
-template <bool kGains>                       // (two instances, so that the kernel without gains is the one it was before they existed)
+// (an instance per flag, so that the kernel without gains and without a mask is the one it was before they existed)
+template <bool kGains, bool kSkip>
 __global__ __launch_bounds__(kTile * kTile) void k_projtex(const PTP P)
 {
 #pragma clang fp contract(off)
@@ -192,7 +224,9 @@ __global__ __launch_bounds__(kTile * kTile) void k_projtex(const PTP P)
     if (t.live) {                                                           // (else, most of a face's UV layout: one byte read, zeros out)
         const size_t plane = (size_t)P.H * (size_t)P.W;
         const bool best = P.mode == T4D_PROJTEX_BEST;
+        const uint32_t skip = kSkip ? P.skip[at] >> P.skip_base : 0u;       // (skip_base + V <= 32: the entry point checks)
         for (int v = 0; v < P.T.V; ++v) {
+            if (kSkip && ((skip >> v) & 1u)) continue;                      // a rejected view: as one that failed step 5
             const View view = {P.T.views + (size_t)v * T4D_VIEW_FLOATS, P.depth + (size_t)v * plane, P.H, P.W};
             Hit h;
             if (!view_accept(view, P.T.rule, t, h)) continue;
@@ -331,6 +365,92 @@ __global__ __launch_bounds__(kTile * kTile) void k_pair_stats(const PSP P)
     }
 }
 
+// ---- photo-consistency: the views that disagree with the median of the facing ones (rule A.1..A.6 at the top) -------------------
+constexpr int kConsW = kTile, kConsH = 4;    // texels per workgroup of k_projtex_consist: one wave
+constexpr int kConsLanes = kConsW * kConsH;
+constexpr int kConsBits = 21;                // a field of the packed q: q <= 4 * 65536 = 2^18
+constexpr double kConsMax = 4.0;             // samples are clamped to [0, kConsMax] before they are rounded; reject_tol at most this
+
+struct PCP {
+    Tex T;
+    const int32_t *sizes;                    // [V,2] (h, w)
+    const float *const *photos, *const *depth;
+    double vote_cos_min;
+    int qt, min_votes;
+    uint32_t *skip;
+    uint8_t *votes;
+};
+
+__device__ __forceinline__ int cons_field(unsigned long long word, int c)
+{
+    return (int)((word >> (c * kConsBits)) & ((1ull << kConsBits) - 1));
+}
+
+__global__ __launch_bounds__(kConsLanes) void k_projtex_consist(const PCP P)
+{
+#pragma clang fp contract(off)
+    extern __shared__ unsigned long long cons_q[];                          // [V][64]: the packed q of the lane's accepted views
+    const int lane = (int)threadIdx.x, V = P.T.V;
+    const Texel t = texel_at(P.T, (int)blockIdx.x * kConsW + lane % kConsW, (int)blockIdx.y * kConsH + lane / kConsW);
+    if (!t.inside) return;
+    uint32_t accepted = 0, voters = 0, out = 0;
+    if (t.live) {
+        for (int v = 0; v < V; ++v) {
+            const View view = {P.T.views + (size_t)v * T4D_VIEW_FLOATS, P.depth[v], P.sizes[2 * v], P.sizes[2 * v + 1]};
+            if (view.H < 1 || view.W < 1 || view.H > kMaxDim || view.W > kMaxDim) continue;
+            Hit h;
+            if (!view_accept(view, P.T.rule, t, h)) continue;
+            double s[3];
+            view_sample(P.photos[v], view, h, P.T.gains ? P.T.gains + 3 * v : nullptr, s);
+            unsigned long long word = 0;
+            for (int c = 0; c < 3; ++c) {
+                const double sc = s[c] >= 0.0 ? (s[c] <= kConsMax ? s[c] : kConsMax) : 0.0;         // (a NaN fails the first comparison)
+                word |= (unsigned long long)llrint(sc * kStatScale) << (c * kConsBits);
+            }
+            cons_q[v * kConsLanes + lane] = word;
+            accepted |= 1u << v;
+            if (h.cs >= P.vote_cos_min) voters |= 1u << v;
+        }
+    }
+    const int n = __popc(voters);
+    if (n >= P.min_votes) {                                                 // (min_votes >= 2: never with n = 0)
+        // A.4: the voter that exactly (n - 1) / 2 voters precede in the order by (q[c], view index) holds the median of channel c
+        const int want = (n - 1) / 2;
+        int m[3] = {0, 0, 0};
+        int found = 0;
+        for (uint32_t bi = voters; bi && found < 3; bi &= bi - 1) {
+            const int i = __builtin_ctz(bi);
+            const unsigned long long wi = cons_q[i * kConsLanes + lane];
+            int rank[3] = {0, 0, 0};
+            for (uint32_t bj = voters; bj; bj &= bj - 1) {
+                const int j = __builtin_ctz(bj);
+                const unsigned long long wj = cons_q[j * kConsLanes + lane];
+                for (int c = 0; c < 3; ++c) {
+                    const int qi = cons_field(wi, c), qj = cons_field(wj, c);
+                    rank[c] += (qj < qi || (qj == qi && j < i)) ? 1 : 0;
+                }
+            }
+            for (int c = 0; c < 3; ++c)
+                if (rank[c] == want) { m[c] = cons_field(wi, c); ++found; }
+        }
+        // A.5, A.6
+        for (uint32_t b = accepted; b; b &= b - 1) {
+            const int v = __builtin_ctz(b);
+            const unsigned long long w = cons_q[v * kConsLanes + lane];
+            int worst = 0;
+            for (int c = 0; c < 3; ++c) {
+                const int d = cons_field(w, c) - m[c];
+                const int ad = d < 0 ? -d : d;
+                if (ad > worst) worst = ad;
+            }
+            if (worst > P.qt) out |= 1u << v;
+        }
+        if (out == accepted) out = 0;                                       // no consensus: every accepted view is kept
+    }
+    P.skip[t.at] = out;
+    P.votes[t.at] = (uint8_t)n;
+}
+
 // ---- two bands: the low band of the photographs, and the projection that blends it and keeps the best view's detail -----------
 constexpr int kLowW = 64, kLowH = 32;        // pixels per workgroup of k_low_band: a wave per row, 256 lanes
 constexpr int kLowStep = 4;                  // rows of A formed per step, one per wave
@@ -418,9 +538,11 @@ struct PBP {
     int H, W;
     float *low_color, *weight, *high, *best_weight;
     uint8_t *count;
+    const uint32_t *skip;                    // as PTP's
+    int skip_base;
 };
 
-template <bool kGains>
+template <bool kGains, bool kSkip>
 __global__ __launch_bounds__(kTile * kTile) void k_projtex_bands(const PBP P)
 {
 #pragma clang fp contract(off)
@@ -431,7 +553,9 @@ __global__ __launch_bounds__(kTile * kTile) void k_projtex_bands(const PBP P)
     int cnt = 0;
     if (t.live) {
         const size_t plane = (size_t)P.H * (size_t)P.W;
+        const uint32_t skip = kSkip ? P.skip[at] >> P.skip_base : 0u;
         for (int v = 0; v < P.T.V; ++v) {
+            if (kSkip && ((skip >> v) & 1u)) continue;
             const View view = {P.T.views + (size_t)v * T4D_VIEW_FLOATS, P.depth + (size_t)v * plane, P.H, P.W};
             const double *gain = kGains ? P.T.gains + 3 * v : nullptr;
             Hit h;
@@ -493,10 +617,20 @@ static dim3 tile_grid(int32_t tex_h, int32_t tex_w)
     return dim3((unsigned)((tex_w + kTile - 1) / kTile), (unsigned)((tex_h + kTile - 1) / kTile));
 }
 
-T4D_EXPORT int t4d_project_texture_gains(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
-                                         const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
-                                         const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
-                                         double depth_tol, int32_t mode, float *color, float *weight, uint8_t *count, void *hip_stream)
+// the mask of a blend: with skip given, its bits skip_base .. skip_base + n_views - 1 are the launch's views
+static int skip_check(const char *name, const uint32_t *skip, int32_t skip_base, int32_t n_views)
+{
+    if (skip && (skip_base < 0 || skip_base > kStatViews || skip_base + n_views > kStatViews))
+        return t4d_fail(T4D_ERR_ARG, "%s: with skip, need skip_base >= 0 and skip_base + n_views <= %d, got %d + %d", name, kStatViews,
+                        skip_base, n_views);
+    return T4D_OK;
+}
+
+T4D_EXPORT int t4d_project_texture_skip(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                        const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
+                                        const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
+                                        double depth_tol, int32_t mode, float *color, float *weight, uint8_t *count,
+                                        const uint32_t *skip, int32_t skip_base, void *hip_stream)
 {
     const char *name = "t4d_project_texture";
     if (const int rc = views_check(name, pos && nrm && coverage && views && photos && depth && color && weight && count, n_views, kMaxViews, h, w))
@@ -504,10 +638,21 @@ T4D_EXPORT int t4d_project_texture_gains(const float *pos, const float *nrm, con
     if (mode != T4D_PROJTEX_WEIGHTED && mode != T4D_PROJTEX_BEST)
         return t4d_fail(T4D_ERR_ARG, "%s: mode must be T4D_PROJTEX_WEIGHTED or T4D_PROJTEX_BEST, got %d", name, mode);
     if (const int rc = projtex_check(name, tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
+    if (const int rc = skip_check(name, skip, skip_base, n_views)) return rc;
     const PTP P = {tex_block(pos, nrm, coverage, tex_h, tex_w, views, n_views, gains, power, cos_min, fade_px, depth_tol),
-                   photos, depth, h, w, mode, color, weight, count};
-    hipLaunchKernelGGL(gains ? k_projtex<true> : k_projtex<false>, tile_grid(tex_h, tex_w), dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
+                   photos, depth, h, w, mode, color, weight, count, skip, skip_base};
+    const auto kernel = skip ? (gains ? k_projtex<true, true> : k_projtex<false, true>) : (gains ? k_projtex<true, false> : k_projtex<false, false>);
+    hipLaunchKernelGGL(kernel, tile_grid(tex_h, tex_w), dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
     return t4d_launch_status(name);
+}
+
+T4D_EXPORT int t4d_project_texture_gains(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                         const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
+                                         const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
+                                         double depth_tol, int32_t mode, float *color, float *weight, uint8_t *count, void *hip_stream)
+{
+    return t4d_project_texture_skip(pos, nrm, coverage, tex_h, tex_w, views, n_views, h, w, photos, depth, gains, power, cos_min,
+                                    fade_px, depth_tol, mode, color, weight, count, nullptr, 0, hip_stream);
 }
 
 T4D_EXPORT int t4d_project_texture(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
@@ -540,6 +685,26 @@ T4D_EXPORT int t4d_projtex_pair_stats(const float *pos, const float *nrm, const 
     return t4d_launch_status(name);
 }
 
+T4D_EXPORT int t4d_projtex_consistency(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                       const float *views, int32_t n_views, const int32_t *sizes, const float *const *photos,
+                                       const float *const *depth, int32_t power, double cos_min, double fade_px, double depth_tol,
+                                       const double *gains, double reject_tol, double vote_cos_min, int32_t min_votes, uint32_t *skip,
+                                       uint8_t *votes, void *hip_stream)
+{
+    const char *name = "t4d_projtex_consistency";            // (the image sides are per view, in `sizes` on the device: the kernel looks at them)
+    if (const int rc = views_check(name, pos && nrm && coverage && views && sizes && photos && depth && skip && votes, n_views, kStatViews, 1, 1))
+        return rc;
+    if (const int rc = projtex_check(name, tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
+    if (!(reject_tol >= 0.0 && reject_tol <= kConsMax) || !(vote_cos_min >= -1.0 && vote_cos_min <= 1.0) || min_votes < 2 || min_votes > kStatViews)
+        return t4d_fail(T4D_ERR_ARG, "%s: need reject_tol in [0, %g], vote_cos_min in [-1, 1] and min_votes in [2, %d]", name, kConsMax, kStatViews);
+    const PCP P = {tex_block(pos, nrm, coverage, tex_h, tex_w, views, n_views, gains, power, cos_min, fade_px, depth_tol),
+                   sizes, photos, depth, vote_cos_min, (int)llrint(reject_tol * kStatScale), min_votes, skip, votes};
+    const dim3 grid((unsigned)((tex_w + kConsW - 1) / kConsW), (unsigned)((tex_h + kConsH - 1) / kConsH));
+    hipLaunchKernelGGL(k_projtex_consist, grid, dim3(kConsLanes), (size_t)n_views * kConsLanes * sizeof(unsigned long long),
+                       (hipStream_t)hip_stream, P);
+    return t4d_launch_status(name);
+}
+
 T4D_EXPORT int t4d_projtex_low_band(const float *photos, const float *depth, int32_t n_views, int32_t h, int32_t w, int32_t radius,
                                     float *low, void *hip_stream)
 {
@@ -554,20 +719,32 @@ T4D_EXPORT int t4d_projtex_low_band(const float *photos, const float *depth, int
     return t4d_launch_status(name);
 }
 
-T4D_EXPORT int t4d_project_texture_bands(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
-                                         const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
-                                         const float *low, const float *depth, const double *gains, int32_t power, double cos_min,
-                                         double fade_px, double depth_tol, float *low_color, float *weight, uint8_t *count,
-                                         float *high, float *best_weight, void *hip_stream)
+T4D_EXPORT int t4d_project_texture_bands_skip(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                              const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
+                                              const float *low, const float *depth, const double *gains, int32_t power, double cos_min,
+                                              double fade_px, double depth_tol, float *low_color, float *weight, uint8_t *count,
+                                              float *high, float *best_weight, const uint32_t *skip, int32_t skip_base, void *hip_stream)
 {
     const char *name = "t4d_project_texture_bands";
     if (const int rc = views_check(name, pos && nrm && coverage && views && photos && low && depth && low_color && weight && count && high && best_weight,
                                    n_views, kMaxViews, h, w))
         return rc;
     if (const int rc = projtex_check(name, tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
+    if (const int rc = skip_check(name, skip, skip_base, n_views)) return rc;
     const PBP P = {tex_block(pos, nrm, coverage, tex_h, tex_w, views, n_views, gains, power, cos_min, fade_px, depth_tol),
-                   photos, low, depth, h, w, low_color, weight, high, best_weight, count};
-    hipLaunchKernelGGL(gains ? k_projtex_bands<true> : k_projtex_bands<false>, tile_grid(tex_h, tex_w), dim3(kTile * kTile), 0,
-                       (hipStream_t)hip_stream, P);
+                   photos, low, depth, h, w, low_color, weight, high, best_weight, count, skip, skip_base};
+    const auto kernel = skip ? (gains ? k_projtex_bands<true, true> : k_projtex_bands<false, true>)
+                             : (gains ? k_projtex_bands<true, false> : k_projtex_bands<false, false>);
+    hipLaunchKernelGGL(kernel, tile_grid(tex_h, tex_w), dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
     return t4d_launch_status(name);
+}
+
+T4D_EXPORT int t4d_project_texture_bands(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                         const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
+                                         const float *low, const float *depth, const double *gains, int32_t power, double cos_min,
+                                         double fade_px, double depth_tol, float *low_color, float *weight, uint8_t *count,
+                                         float *high, float *best_weight, void *hip_stream)
+{
+    return t4d_project_texture_bands_skip(pos, nrm, coverage, tex_h, tex_w, views, n_views, h, w, photos, low, depth, gains, power,
+                                          cos_min, fade_px, depth_tol, low_color, weight, count, high, best_weight, nullptr, 0, hip_stream);
 }

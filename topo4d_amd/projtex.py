@@ -10,6 +10,8 @@ states the per-texel rule; tests/projtex_ref.py restates it in numpy bit for bit
     pair_stats(pos, nrm, coverage, groups, ...)             -> (count [V,V], sums [V,V,3]) int64: what the cameras share, per pair
     solve_gains(count, sums, ...)                           -> float64 [V,3]: one gain per camera and channel, on the host
     estimate_gains(face_obj, vertices, dataset, res, ...)   -> (gains, report) of one frame; write_gains / read_gains: proj_gains.json
+    consistency(pos, nrm, coverage, groups, ...)            -> (skip int32 [h,w], votes uint8 [h,w]): the views to leave out, per texel
+    frame_consistency(face_obj, vertices, dataset, res, ...) -> (skip, votes) of one frame, the bits in dataset order; rejected_count(skip)
     uv_islands(face_obj)                                    -> int [n_uv]: the UV island of every UV vertex, numbered from 1 (host)
     island_labels(face_obj, h, w, device)                   -> uint8 [h,w]: the island of every texel, 0 outside the coverage
 
@@ -36,10 +38,23 @@ samples there (integers, so the result is the same bits in any order); solve_gai
 makes the pairs agree in the least-squares sense (the gain compensation of panorama stitchers, in the log domain), and project /
 project_frame take these gains.  Exposure belongs to the rig, not to a frame: one set of gains serves a whole run.
 
+Specular highlights (skin, eyes and lips are glossy, and a highlight sits elsewhere in every camera), leaks of the occlusion test
+(hair, lashes, a nose rim the tracked mesh does not model) and transient content in one camera (a blink) are no gain per camera
+and no registration error: one view disagrees with a consensus of the others.  consistency is the per-texel photo-consistency check
+of MVS texturing (Waechter et al., "Let There Be Color!"): at a texel the views that face it (cos >= vote_cos_min) vote, the lower
+median of their samples per channel is the consensus, and a view further than reject_tol from it in some channel is rejected: its
+bit is set in skip, which project, project_bands and project_frame(reject=...) take.  With fewer than min_votes voters, or when
+every view would go, nothing is rejected, so a texel never loses its last view.  The samples are integers of 2^-16, so the mask is
+the same bits in any order.  The stages run in the order equalise, reject, blend, fill.  The defaults (0.1, 0.5, 3) are conventional
+choices, not tuned on a capture.  Known limits: with fewer than min_votes facing views nothing is rejected, so the rim of the
+coverage keeps its highlights; a defect most voters share survives; the threshold is absolute, so it is looser in the shadows than
+a relative one would be.  --reject (train: --tex_reject) switches it on; --save_rejected also writes face_proj_rejected.png, the
+number of rejected views per texel.
+
 `python -m topo4d_amd.projtex -e EXP -s SEQ [-id ... -did ... -od ... -dr N] [--frames 1-10] [--views A,B] [--set low|dense]
 [--undistort] [--tex_res R] [--mode weighted|best|twoband [--band_radius R]] [--power P --cos_min C --fade_px F --depth_tol T] [--tex_pad R]
 [--tex_sizes 2048,1024] [--save_weight] [--tex_fill] [--equalize [--equalize_frames 1-10] | --gains FILE] [--stat_cos_min C --stat_lo L
---stat_hi H --eq_prior P --eq_min_overlap N]` works on an output tree that already exists (the reference's too): it writes
+--stat_hi H --eq_prior P --eq_min_overlap N] [--reject [--reject_tol T --vote_cos_min C --min_votes N] [--save_rejected]]` works on an output tree that already exists (the reference's too): it writes
 %06d/face_proj.png (and face_proj_<size>.png) beside every frame's face.obj, with --save_weight also face_proj_weight.png (the
 8-bit count of contributing views).  By default it projects the full-size photographs of the cameras training uses.
 --equalize gathers the pair statistics over --equalize_frames (default: the first frame projected), solves once, writes
@@ -78,6 +93,9 @@ MAX_STAT_VIEWS, MAX_STAT = 32, 1024.0                          # pair_stats: a 3
 STAT_DEFAULTS = dict(stat_cos_min=0.5, stat_lo=0.02, stat_hi=0.98)
 SOLVE_DEFAULTS = dict(prior=0.01, min_overlap=64)
 GAINS_NAME = "proj_gains.json"
+MAX_REJECT_TOL = 4.0                                           # consistency: samples are clamped to [0, 4] before they are rounded
+CONSIST_DEFAULTS = dict(reject_tol=0.1, vote_cos_min=0.5, min_votes=3)
+REJECTED_NAME = "face_proj_rejected.png"
 
 
 def _filled(defaults: dict, **given) -> dict:
@@ -117,6 +135,19 @@ def check_stat_options(stat_cos_min=None, stat_lo=None, stat_hi=None) -> dict:
         raise ValueError(f"stat_cos_min must be in [-1, 1], got {o['stat_cos_min']!r}")
     if not -MAX_STAT <= float(o["stat_lo"]) <= float(o["stat_hi"]) <= MAX_STAT:
         raise ValueError(f"need -{MAX_STAT:g} <= stat_lo <= stat_hi <= {MAX_STAT:g}, got {o['stat_lo']!r} and {o['stat_hi']!r}")
+    return o
+
+
+def check_consist_options(reject_tol=None, vote_cos_min=None, min_votes=None) -> dict:
+    """ValueError for a parameter consistency would refuse (callable without a device); the three options, None: CONSIST_DEFAULTS'."""
+    o = _filled(CONSIST_DEFAULTS, reject_tol=reject_tol, vote_cos_min=vote_cos_min, min_votes=min_votes)
+    for k, lo, hi in (("reject_tol", 0.0, MAX_REJECT_TOL), ("vote_cos_min", -1.0, 1.0)):
+        if isinstance(o[k], bool) or not isinstance(o[k], (int, float, np.integer, np.floating)) or not lo <= float(o[k]) <= hi:
+            raise ValueError(f"{k} must be in [{lo:g}, {hi:g}], got {o[k]!r}")
+    n = o["min_votes"]
+    if isinstance(n, bool) or not isinstance(n, (int, float, np.integer, np.floating)) or not np.isfinite(n) or int(n) != n \
+            or not 2 <= int(n) <= MAX_STAT_VIEWS:
+        raise ValueError(f"min_votes must be an integer in [2, {MAX_STAT_VIEWS}], got {n!r}")
     return o
 
 
@@ -175,6 +206,22 @@ def _view_group(dev, cams, depth, **images) -> tuple:
     return views, V, H, W
 
 
+def _skip(skip, skip_base, h: int, w: int, V: int) -> list:
+    """[] for no mask, or [("skip", skip)] for _on_device: skip an int32 [h,w] tensor (consistency's), skip_base an integer with
+    skip_base >= 0 and skip_base + V <= 32; ValueError for anything else"""
+    if isinstance(skip_base, bool) or not isinstance(skip_base, (int, np.integer)):
+        raise ValueError(f"skip_base must be an integer, got {skip_base!r}")
+    if skip is None:
+        if skip_base != 0:
+            raise ValueError(f"skip_base {skip_base} without skip")
+        return []
+    _map(skip, "skip", (h, w), torch.int32)
+    if skip_base < 0 or skip_base + V > MAX_STAT_VIEWS:
+        raise ValueError(f"skip holds {MAX_STAT_VIEWS} views: need skip_base >= 0 and skip_base + {V} views <= {MAX_STAT_VIEWS}, got "
+                         f"skip_base {skip_base}")
+    return [("skip", skip)]
+
+
 def _on_device(dev, pos, nrm, coverage, others, g) -> tuple:
     """The last step before a launch, after every argument error: the named tensors `others` live where pos does (ValueError), and
     that is a HIP device (RuntimeError).  (pos, nrm, coverage as uint8, others' tensors), all contiguous, and the gains uploaded."""
@@ -188,25 +235,31 @@ def _on_device(dev, pos, nrm, coverage, others, g) -> tuple:
 
 
 def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, photos: torch.Tensor, depth: torch.Tensor, *,
-            power=None, cos_min=None, fade_px=None, depth_tol=None, mode=None, gains=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+            power=None, cos_min=None, fade_px=None, depth_tol=None, mode=None, gains=None, skip=None,
+            skip_base=0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8).  pos / nrm [h,w,3] float32: each texel's point in the
     training world frame and its normal (any length; a zero normal switches the texel off); coverage [h,w] uint8 or bool;
     cams: a sequence of GaussianRasterizationSettings of one size, or (packed view records, H, W), as MeshRenderer.render takes
     them; photos [V,3,H,W] float32; depth [V,1,H,W] float32, MeshRenderer.render's (0: empty).  Everything on one HIP device.
     power, cos_min, fade_px, depth_tol, mode: None is DEFAULTS'.  gains [V,3] (None: none): view v's sample is multiplied by
-    gains[v] in the kernel, in float64; no scaled copy of the photographs is made."""
+    gains[v] in the kernel, in float64; no scaled copy of the photographs is made.  skip (None: no mask): consistency's int32
+    [h,w] mask on the same device; view v of this call is left out at a texel, exactly as a view the rule does not accept there,
+    when bit skip_base + v of skip is set (skip_base an integer, skip_base + V <= 32): it enters no blend, cannot be the best
+    view and does not count."""
     o = check_options(power, cos_min, fade_px, depth_tol, mode)
     if o["mode"] not in _MODES:
         raise ValueError(f"mode {o['mode']!r} has five outputs and takes the low bands: it is project_bands'")
     h, w, dev = _texel_maps(pos, nrm, coverage)
     views, V, H, W = _view_group(dev, cams, depth, photos=photos)
     g = _gains(gains, V)
-    pos, nrm, cov, (photos, depth), g = _on_device(dev, pos, nrm, coverage, [("photos", photos), ("depth", depth)], g)
+    mask = _skip(skip, skip_base, h, w, V)
+    pos, nrm, cov, (photos, depth, *mask), g = _on_device(dev, pos, nrm, coverage, [("photos", photos), ("depth", depth), *mask], g)
     color = torch.empty(h, w, 3, dtype=torch.float32, device=dev)
     weight = torch.empty(h, w, dtype=torch.float32, device=dev)
     count = torch.empty(h, w, dtype=torch.uint8, device=dev)
-    _lib.call("t4d_project_texture_gains", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(depth), ptr(g),
-              *_rule(o), _MODES[o["mode"]], ptr(color), ptr(weight), ptr(count), _lib.stream(dev))
+    _lib.call("t4d_project_texture_skip", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(depth), ptr(g),
+              *_rule(o), _MODES[o["mode"]], ptr(color), ptr(weight), ptr(count), ptr(mask[0]) if mask else None, int(skip_base),
+              _lib.stream(dev))
     return color, weight, count
 
 
@@ -236,24 +289,56 @@ def low_band(photos: torch.Tensor, depth: torch.Tensor, radius: int = 8) -> torc
 
 
 def project_bands(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, photos: torch.Tensor, low: torch.Tensor,
-                  depth: torch.Tensor, *, power=None, cos_min=None, fade_px=None, depth_tol=None,
-                  gains=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                  depth: torch.Tensor, *, power=None, cos_min=None, fade_px=None, depth_tol=None, gains=None, skip=None,
+                  skip_base=0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """(low_color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8, high [h,w,3] float32, best_weight [h,w] float32): the
     two bands of mode "twoband".  The arguments of project and low [V,3,H,W] float32, low_band's.  Every view that project would
     accept at a texel gives its sample s and, by the same bilinear mix over the same taps of low, its low band l (both times
     gains[v] when given).  low_color, weight, count: the blend of the l as mode "weighted" blends the s.  high = s - l and
-    best_weight = the weight of the view mode "best" would keep.  The texture is low_color + high; zeros where no view counts."""
+    best_weight = the weight of the view mode "best" would keep.  The texture is low_color + high; zeros where no view counts.
+    skip, skip_base: as project takes them; a masked view enters neither band."""
     o = check_options(power, cos_min, fade_px, depth_tol)
     h, w, dev = _texel_maps(pos, nrm, coverage)
     views, V, H, W = _view_group(dev, cams, depth, photos=photos, low=low)
     g = _gains(gains, V)
-    pos, nrm, cov, (photos, low, depth), g = _on_device(dev, pos, nrm, coverage, [("photos", photos), ("low", low), ("depth", depth)], g)
+    mask = _skip(skip, skip_base, h, w, V)
+    pos, nrm, cov, (photos, low, depth, *mask), g = _on_device(dev, pos, nrm, coverage,
+                                                              [("photos", photos), ("low", low), ("depth", depth), *mask], g)
     low_color, high = (torch.empty(h, w, 3, dtype=torch.float32, device=dev) for _ in range(2))
     weight, best_weight = (torch.empty(h, w, dtype=torch.float32, device=dev) for _ in range(2))
     count = torch.empty(h, w, dtype=torch.uint8, device=dev)
-    _lib.call("t4d_project_texture_bands", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(low), ptr(depth),
-              ptr(g), *_rule(o), ptr(low_color), ptr(weight), ptr(count), ptr(high), ptr(best_weight), _lib.stream(dev))
+    _lib.call("t4d_project_texture_bands_skip", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(low), ptr(depth),
+              ptr(g), *_rule(o), ptr(low_color), ptr(weight), ptr(count), ptr(high), ptr(best_weight), ptr(mask[0]) if mask else None,
+              int(skip_base), _lib.stream(dev))
     return low_color, weight, count, high, best_weight
+
+
+def _mixed_views(dev, groups: list, name: str, what: str) -> tuple:
+    """(packed records per group, (H, W) per view, [(what, photos), (what, depth)] per group for _on_device) of the groups pair_stats
+    and consistency take: (cams, photos, depth) per image size, at most 32 views in all; ValueError for anything else"""
+    if not groups:
+        raise ValueError(f"{name}: no views")
+    records, sizes, held = [], [], []
+    for cams, photos, depth in groups:
+        views, v, H, W = _view_group(dev, cams, depth, photos=photos)
+        if not 1 <= H <= 65536 or not 1 <= W <= 65536:
+            raise ValueError(f"image sides must be in [1, 65536], got {H} x {W}")
+        records.append(views)
+        sizes += [(H, W)] * v
+        held += [(what, photos), (what, depth)]
+    if len(sizes) > MAX_STAT_VIEWS:
+        raise ValueError(f"at most {MAX_STAT_VIEWS} views per call, got {len(sizes)}")
+    return records, sizes, held
+
+
+def _view_tables(dev, records, sizes, held) -> tuple:
+    """(views [V,40], sizes [V,2] int32, tables [2,V] int64: the views' photograph and depth pointers) on the device.  held: the
+    contiguous photographs and depth maps of _on_device, group after group; the caller keeps them alive until the launch is queued
+    on their stream."""
+    photo_ptrs = [p[k].data_ptr() for p in held[0::2] for k in range(p.shape[0])]
+    depth_ptrs = [d[k].data_ptr() for d in held[1::2] for k in range(d.shape[0])]
+    tables = torch.tensor([photo_ptrs, depth_ptrs], dtype=torch.int64).to(dev)
+    return torch.cat(records).contiguous(), torch.tensor(sizes, dtype=torch.int32).to(dev), tables
 
 
 def pair_stats(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, groups, *, gains=None, out=None, stat_cos_min=None,
@@ -270,19 +355,8 @@ def pair_stats(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, gro
     stat = check_stat_options(stat_cos_min, stat_lo, stat_hi)
     h, w, dev = _texel_maps(pos, nrm, coverage)
     groups = list(groups)
-    if not groups:
-        raise ValueError("pair_stats: no views")
-    records, sizes, held = [], [], []
-    for cams, photos, depth in groups:
-        views, v, H, W = _view_group(dev, cams, depth, photos=photos)
-        if not 1 <= H <= 65536 or not 1 <= W <= 65536:
-            raise ValueError(f"image sides must be in [1, 65536], got {H} x {W}")
-        records.append(views)
-        sizes += [(H, W)] * v
-        held += [("photos, depth and out", photos), ("photos, depth and out", depth)]
+    records, sizes, held = _mixed_views(dev, groups, "pair_stats", "photos, depth and out")
     V = len(sizes)
-    if V > MAX_STAT_VIEWS:
-        raise ValueError(f"at most {MAX_STAT_VIEWS} views per call, got {V}")
     g = _gains(gains, V)
     if out is not None:
         count, sums = out
@@ -293,16 +367,42 @@ def pair_stats(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, gro
         count, sums = torch.zeros(V, V, dtype=torch.int64, device=dev), torch.zeros(V, V, 3, dtype=torch.int64, device=dev)
     elif not (count.is_contiguous() and sums.is_contiguous()):
         raise ValueError("out must be contiguous")
-    # (held: the contiguous photographs and depth maps, alive until the launch is queued on their stream)
-    photo_ptrs = [p[k].data_ptr() for p in held[0:2 * len(groups):2] for k in range(p.shape[0])]
-    depth_ptrs = [d[k].data_ptr() for d in held[1:2 * len(groups):2] for k in range(d.shape[0])]
-    tables = torch.tensor([photo_ptrs, depth_ptrs], dtype=torch.int64).to(dev)
-    sizes_t = torch.tensor(sizes, dtype=torch.int32).to(dev)
-    views = torch.cat(records).contiguous()
+    views, sizes_t, tables = _view_tables(dev, records, sizes, held[:2 * len(groups)])
     _lib.call("t4d_projtex_pair_stats", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, ptr(sizes_t), ptr(tables[0]), ptr(tables[1]),
               *_rule(o), float(stat["stat_cos_min"]), float(stat["stat_lo"]), float(stat["stat_hi"]), ptr(g), ptr(count), ptr(sums),
               _lib.stream(dev))
     return count, sums
+
+
+def consistency(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, groups, *, gains=None, reject_tol=None, vote_cos_min=None,
+                min_votes=None, power=None, cos_min=None, fade_px=None, depth_tol=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(skip int32 [h,w], votes uint8 [h,w]) on the device: the per-texel photo-consistency check (Waechter et al., "Let There Be
+    Color!").  pos, nrm, coverage, groups and gains as pair_stats takes them: V <= 32 views of any mix of sizes, numbered in the
+    order given.  At a texel the views project would accept (power, cos_min, fade_px, depth_tol) give their samples (times gains[v]),
+    clamped to [0, 4] and rounded to integers of 2^-16; those with a cosine >= vote_cos_min are the voters, votes their number.
+    With at least min_votes voters, a view (voter or not) whose sample is further than reject_tol from the voters' lower median in
+    some channel is an outlier, and bit v of skip (bit 31: the sign) is set for every outlier v, unless every accepted view is one:
+    then, as with fewer voters, nothing is rejected, so a texel never loses its last view.  Integers throughout: the result is the
+    same bits in any order (include/topo4d_raster.h states the rule, tests/projtex_consist_ref.py restates it).  project and
+    project_bands take skip.  The three defaults (None: CONSIST_DEFAULTS': a tenth of the range, a facing limit of 60 degrees, three
+    voters) are conventional choices, not tuned on a capture.  Known limits: where fewer than min_votes views face a texel (the
+    rim of the coverage) nothing is rejected; a defect most voters share survives; the threshold is absolute, so it is looser in the
+    shadows than a relative one would be."""
+    o = check_options(power, cos_min, fade_px, depth_tol)
+    c = check_consist_options(reject_tol, vote_cos_min, min_votes)
+    h, w, dev = _texel_maps(pos, nrm, coverage)
+    groups = list(groups)
+    records, sizes, held = _mixed_views(dev, groups, "consistency", "photos and depth")
+    V = len(sizes)
+    g = _gains(gains, V)
+    pos, nrm, cov, held, g = _on_device(dev, pos, nrm, coverage, held, g)
+    views, sizes_t, tables = _view_tables(dev, records, sizes, held)
+    skip = torch.empty(h, w, dtype=torch.int32, device=dev)
+    votes = torch.empty(h, w, dtype=torch.uint8, device=dev)
+    _lib.call("t4d_projtex_consistency", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, ptr(sizes_t), ptr(tables[0]), ptr(tables[1]),
+              *_rule(o), ptr(g), float(c["reject_tol"]), float(c["vote_cos_min"]), int(c["min_votes"]), ptr(skip), ptr(votes),
+              _lib.stream(dev))
+    return skip, votes
 
 
 def _solve(count, sums, prior=None, min_overlap=None):
@@ -483,8 +583,50 @@ def _keep_larger(a, b):
     return torch.where(take[..., None], b[0], a[0]), torch.where(take, b[1], a[1])
 
 
+def _reject_options(reject, n_views: int):
+    """None, or the checked consist options of project_frame's `reject`; ValueError for anything else"""
+    if reject is None:
+        return None
+    if not isinstance(reject, dict) or set(reject) - set(CONSIST_DEFAULTS):
+        raise ValueError(f"reject must be a dict of {', '.join(CONSIST_DEFAULTS)}, got {reject!r}")
+    if n_views > MAX_STAT_VIEWS:
+        raise ValueError(f"at most {MAX_STAT_VIEWS} views can be checked for consistency, got {n_views}")
+    return check_consist_options(**reject)
+
+
+def rejected_count(skip: torch.Tensor) -> torch.Tensor:
+    """uint8 [h,w]: the number of views consistency rejects at each texel, the set bits of skip"""
+    bits = skip.to(torch.int64) & 0xFFFFFFFF
+    n = torch.zeros_like(skip, dtype=torch.uint8)
+    for i in range(MAX_STAT_VIEWS):
+        n += ((bits >> i) & 1).to(torch.uint8)
+    return n
+
+
+def frame_consistency(face_obj, vertices: torch.Tensor, dataset, res, *, gains=None, device=None, **options):
+    """consistency of one frame over _frame_inputs' maps and depth renders: (skip, votes), bit v of skip for entry v of `dataset`
+    whatever the image sizes are (the views go in size group after size group, and the bits are put back).  gains
+    [len(dataset),3] in the order of `dataset`.  options: consistency's (reject_tol, vote_cos_min, min_votes, power, cos_min,
+    fade_px, depth_tol)."""
+    check_options(**{k: v for k, v in options.items() if k not in CONSIST_DEFAULTS})
+    _reject_options({k: v for k, v in options.items() if k in CONSIST_DEFAULTS}, len(dataset))
+    if not dataset:
+        raise ValueError("frame_consistency: no views")
+    gains = _gains(gains, len(dataset))
+    pos, nrm, cov, groups = _frame_inputs(face_obj, vertices, dataset, res, device)
+    groups = list(groups)
+    order = [k for ks, *_ in groups for k in ks]
+    skip, votes = consistency(pos, nrm, cov, [g[1:] for g in groups], gains=None if gains is None else gains[order], **options)
+    if order != sorted(order):                                 # several sizes: back from group order to dataset order
+        bits, back = skip.to(torch.int64) & 0xFFFFFFFF, torch.zeros_like(skip, dtype=torch.int64)
+        for i, k in enumerate(order):
+            back |= ((bits >> i) & 1) << k
+        skip = torch.where(back >= 2 ** 31, back - 2 ** 32, back).to(torch.int32)
+    return skip, votes
+
+
 def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power=None, cos_min=None, fade_px=None, depth_tol=None, mode=None,
-                  gains=None, device=None, band_radius: int = 8):
+                  gains=None, device=None, band_radius: int = 8, reject=None):
     """(texture [h,w,3] uint8, weight [h,w] float32, count [h,w] uint8) of one frame: `dataset` holds ingest.get_dataset's entries
     ("cam", "im"), vertices [N,3] the mesh in the training world frame.  _frame_inputs gives the texel maps and the depth maps,
     project gathers, texfinish.quantize rounds as the PNG encoder does.  Views of one size go in one launch; a rig with several
@@ -492,23 +634,42 @@ def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power=None,
     gains [len(dataset),3] (None: none): one row per entry of `dataset`, in its order.  mode "twoband": per size low_band
     (band_radius) and project_bands; the low bands merge as "weighted" does, the detail by the larger best weight (the earlier size
     on ties), and the texture is their sum, one float32 addition, clamped to [0, 1] (where the views disagree the sum overshoots,
-    and the quantisation wraps)."""
+    and the quantisation wraps).  reject (None: no check): a dict of consistency's options (reject_tol, vote_cos_min, min_votes; {}
+    for CONSIST_DEFAULTS), at most 32 views: consistency runs first over all sizes at once, with the gains, and every size's
+    projection takes its part of the mask, in every mode.  The order is equalise, reject, blend, fill.  With "twoband" the low bands
+    are still made from every photograph; the mask decides which views enter the two blends and which may be the best view.
+    count is then the number of views that contributed."""
+    return _project_frame(face_obj, vertices, dataset, res, dict(power=power, cos_min=cos_min, fade_px=fade_px, depth_tol=depth_tol, mode=mode),
+                          gains, device, band_radius, reject)[:3]
+
+
+def _project_frame(face_obj, vertices, dataset, res, options: dict, gains, device, band_radius, reject) -> tuple:
+    """project_frame, and as a fourth result the mask of consistency (group order; None without `reject`)"""
     from . import texfinish
-    o = check_options(power, cos_min, fade_px, depth_tol, mode)
+    o = check_options(**options)
     mode, rule = o["mode"], {k: v for k, v in o.items() if k != "mode"}
     check_band_options(band_radius)
     if not dataset:
         raise ValueError("project_frame: no views")
     gains = _gains(gains, len(dataset))
+    reject = _reject_options(reject, len(dataset))
     pos, nrm, cov, groups = _frame_inputs(face_obj, vertices, dataset, res, device)
+    skip, base = None, 0
+    if reject is not None:                                     # every size at once: a texel's voters come from all of them
+        groups = list(groups)
+        order = [k for ks, *_ in groups for k in ks]
+        skip, _ = consistency(pos, nrm, cov, [g[1:] for g in groups], gains=None if gains is None else gains[order], **reject, **rule)
     total = detail = count = None
     for ks, cams, photos, depth in groups:
         g = None if gains is None else gains[ks]
+        mask = {} if skip is None else dict(skip=skip, skip_base=base)      # the group's views are bits base .. base + len(ks) - 1
+        base += len(ks)
         if mode == "twoband":
-            color, weight, n, high, best = project_bands(pos, nrm, cov, cams, photos, low_band(photos, depth, band_radius), depth, gains=g, **rule)
+            color, weight, n, high, best = project_bands(pos, nrm, cov, cams, photos, low_band(photos, depth, band_radius), depth, gains=g,
+                                                         **mask, **rule)
             detail = (high, best) if detail is None else _keep_larger(detail, (high, best))
         else:
-            color, weight, n = project(pos, nrm, cov, cams, photos, depth, mode=mode, gains=g, **rule)
+            color, weight, n = project(pos, nrm, cov, cams, photos, depth, mode=mode, gains=g, **mask, **rule)
         if total is None:
             total, count = (color, weight), n
         else:
@@ -516,7 +677,7 @@ def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power=None,
     color, weight = total
     if detail is not None:                                     # the sum of two bands can leave [0, 1], and quantize wraps as numpy's cast does
         color = (color + detail[0]).clamp_(0.0, 1.0)
-    return texfinish.quantize(color), weight, count
+    return texfinish.quantize(color), weight, count, skip
 
 
 def frame_stats(face_obj, vertices: torch.Tensor, dataset, res, *, out=None, device=None, **options):
@@ -588,16 +749,23 @@ def _names(dataset) -> list:
 
 
 def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: int = 0, sizes=(), save_weight: bool = False,
-                device=None, gains=None, fill: bool = False) -> list:
+                device=None, gains=None, fill: bool = False, save_rejected: bool = False) -> list:
     """One frame's face_proj.png (and face_proj_<size>.png, face_proj_weight.png) in `frame_dir`, from the face.obj read there:
     what the command line and train --tex_project both call.  Returns the files written.  The gutter of `pad` texels is filled
     from the texels some view contributed to (count > 0), through texfinish.finish.  gains: None, or
     {camera name: [r, g, b]} holding every camera of `dataset`.  fill: the texels of an island that no view contributed to take the
     push-pull interpolation of that island's projected texels (texfinish.fill_islands over island_labels) and count as projected
-    for the gutter and the smaller levels; face_proj_weight.png is unchanged, so its zeros inside an island mark what was filled."""
+    for the gutter and the smaller levels; face_proj_weight.png is unchanged, so its zeros inside an island mark what was filled.
+    Consistency options among `options` (reject_tol, vote_cos_min, min_votes: what _check_args merges under --reject) switch the
+    photo-consistency check on (project_frame's reject); save_rejected then also writes face_proj_rejected.png, the 8-bit number
+    of rejected views per texel."""
     from . import texfinish
     from .evaluate import training_vertices
     from .png import write_png
+    reject = {k: v for k, v in options.items() if k in CONSIST_DEFAULTS} or None
+    options = {k: v for k, v in options.items() if k not in CONSIST_DEFAULTS}
+    if save_rejected and reject is None:
+        raise ValueError("save_rejected needs the consistency options: nothing is rejected without them")
     dev = torch.device(device if device is not None else "cuda")
     verts = torch.from_numpy(training_vertices(face_obj.vertices, trans_g)).to(dev)
     if gains is not None:
@@ -605,7 +773,8 @@ def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: 
         if missing:
             raise ValueError(f"no gains for camera(s) {', '.join(missing)}")
         gains = np.asarray([gains[n] for n in _names(dataset)], dtype=np.float64)
-    tex, _, count = project_frame(face_obj, verts, dataset, res, device=dev, gains=gains, **options)
+    band_radius = options.pop("band_radius", BAND_DEFAULTS["band_radius"])
+    tex, _, count, skip = _project_frame(face_obj, verts, dataset, res, options, gains, dev, band_radius, reject)
     seen = (count > 0).to(torch.uint8)
     if fill:
         tex, filled = texfinish.fill_islands(tex, seen, island_labels(face_obj, tex.shape[0], tex.shape[1], device=dev))
@@ -615,6 +784,10 @@ def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: 
     if save_weight:
         path = os.path.join(frame_dir, WEIGHT_NAME)
         write_png(path, count)
+        written.append(path)
+    if save_rejected:
+        path = os.path.join(frame_dir, REJECTED_NAME)
+        write_png(path, rejected_count(skip))
         written.append(path)
     return written
 
@@ -677,6 +850,26 @@ def eq_options_of(args) -> Tuple[dict, dict]:
     except ValueError as e:
         raise SystemExit(f"equalisation options: {e}") from None
     return stat, solve
+
+
+def add_consist_options(p: argparse.ArgumentParser, suppress: bool = False) -> None:
+    """The parameters of the photo-consistency check (--reject here, --tex_reject on train's parser), beside add_options' on both."""
+    _add_flags(p, suppress, CONSIST_DEFAULTS, (
+        f"Consistency: reject a view whose sample differs from the median of the facing views by more than this in some channel, "
+        f"0..{MAX_REJECT_TOL:g} in colour units (default 0.1, a conventional choice).",
+        "Consistency: a view votes for the median when the cosine between normal and viewing direction is at least this (default 0.5).",
+        f"Consistency: reject nothing at a texel with fewer voters than this, 2..{MAX_STAT_VIEWS} (default 3)."),
+        reject_tol=dict(metavar="T"), vote_cos_min=dict(metavar="C"), min_votes=dict(metavar="N"))
+
+
+def consist_options_of(args) -> dict:
+    return _flags_of(args, CONSIST_DEFAULTS)
+
+
+def check_frame_views(dataset, options: dict) -> None:
+    """SystemExit when `options` (of _check_args) ask for the consistency check and the frame holds more views than its mask"""
+    if any(k in options for k in CONSIST_DEFAULTS) and len(dataset) > MAX_STAT_VIEWS:
+        raise SystemExit(f"consistency: at most {MAX_STAT_VIEWS} views can be checked, the frame has {len(dataset)}")
 
 
 class GainEstimator:
@@ -746,19 +939,30 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--tex_fill", action="store_true",
                    help="Fill the texels of every UV island that no view sees by push-pull from the island's projected texels "
                         "(texfinish.fill_islands); the gutter and the smaller levels are then built from the filled texture.")
+    p.add_argument("--reject", action="store_true",
+                   help="Leave a view out of a texel where it disagrees with the median of the views that face it: specular "
+                        "highlights, occlusion leaks, content only one camera holds (at most 32 views; after the equalisation, before the blend).")
+    add_consist_options(p)
+    p.add_argument("--save_rejected", action="store_true",
+                   help="With --reject: also write %%06d/face_proj_rejected.png, the number of rejected views per texel.")
     return p
 
 
 def _check_args(args, res: int) -> dict:
     from . import texfinish
-    opts, band = options_of(args), band_options_of(args)
+    opts, band, consist = options_of(args), band_options_of(args), consist_options_of(args)
+    reject = getattr(args, "reject", False) or getattr(args, "tex_reject", False)     # (this module's flag, train's flag)
     try:
         check_options(**opts)
         check_band_options(**band)
+        if reject:
+            check_consist_options(**consist)
         texfinish.check_options(getattr(args, "tex_pad", 0), 0, getattr(args, "tex_sizes", ()), res)
     except ValueError as e:
         raise SystemExit(f"projection options: {e}") from None
-    return {**opts, **band} if opts["mode"] == "twoband" else opts      # (only then: the options are recorded in proj_gains.json)
+    # (the band radius and the consistency options only when they act: the options are recorded in proj_gains.json, and
+    # write_frame takes the presence of the latter for the switch)
+    return {**opts, **(band if opts["mode"] == "twoband" else {}), **(consist if reject else {})}
 
 
 def _read_obj(frame_dir: str):
@@ -775,6 +979,9 @@ def project_tree(args, device=None) -> list:
     if not os.path.isdir(run_dir):
         raise SystemExit(f"no run at {run_dir}")
     opts = _check_args(args, args.tex_res)
+    save_rejected = getattr(args, "save_rejected", False)
+    if save_rejected and not getattr(args, "reject", False):
+        raise SystemExit("--save_rejected writes what the consistency check rejects: it needs --reject")
     equalize, gains_file = getattr(args, "equalize", False), getattr(args, "gains", None)
     if equalize and gains_file:
         raise SystemExit("--equalize estimates the gains and --gains reads them: give one of the two")
@@ -831,9 +1038,10 @@ def project_tree(args, device=None) -> list:
                     continue
                 if gains is not None and any(n not in gains for n in _names(dataset)):
                     raise SystemExit(f"equalisation: no gains for camera(s) {', '.join(n for n in _names(dataset) if n not in gains)}")
+                check_frame_views(dataset, opts)
                 written += write_frame(os.path.join(run_dir, "%06d" % t), obj, trans_g, dataset, args.tex_res, opts,
                                        pad=args.tex_pad, sizes=args.tex_sizes, save_weight=args.save_weight, device=dev, gains=gains,
-                                       fill=getattr(args, "tex_fill", False))
+                                       fill=getattr(args, "tex_fill", False), save_rejected=save_rejected)
         finally:
             pool.shutdown(wait=True)
             pf.close()

@@ -25,7 +25,8 @@ face_proj.png beside every face.obj, the frame's full-size photographs projected
 --gen_tex; --mode, --band_radius, --power, --cos_min, --fade_px and --depth_tol as python -m topo4d_amd.projtex takes them; --tex_equalize
 estimates one gain per camera and channel on the first frame written, stores proj_gains.json in the run directory and projects
 every frame with it; --tex_fill fills the texels of every UV island that no view sees by push-pull from the island's projected
-texels, texfinish.fill_islands).  Without them nothing changes.
+texels, texfinish.fill_islands; --tex_reject leaves a view out of a texel where it disagrees with the median of the views that
+face it, projtex.consistency, with --reject_tol, --vote_cos_min and --min_votes).  Without them nothing changes.
 
 The region "freezes" of train.py:676-700 are FusedAdamPins pins, written by the step kernel itself; the pin set changes at
 most twice per frame (the dynamic-eye pins end at iteration int(0.7 n) of frame 0) and the learning rates once (the colour
@@ -324,6 +325,8 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
     tex_fill = getattr(args, "tex_fill", False)
     if tex_fill and not tex_project:
         raise SystemExit("--tex_fill fills the holes of the projected texture: it needs --tex_project")
+    if getattr(args, "tex_reject", False) and not tex_project:
+        raise SystemExit("--tex_reject rejects inconsistent views of the projected texture: it needs --tex_project")
     dev = coarse._device(device)
     clock = _Clock(timings, dev)
     with torch.cuda.device(dev), clock("setup"):
@@ -453,6 +456,7 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
                                 est = projtex.GainEstimator(args.tex_res, proj_opts, eq_stat, eq_solve, device=dev)
                                 est.add(face_obj, trans_g, dense)
                                 proj_gains = est.finish(os.path.join(out_dir, projtex.GAINS_NAME))
+                            projtex.check_frame_views(dense, proj_opts)
                             projtex.write_frame(frame_dir, face_obj, trans_g, dense, args.tex_res, proj_opts, pad=tex_pad,
                                                 sizes=tex_sizes, device=dev, gains=proj_gains, fill=tex_fill)
                 state["frames"] = t + 1
@@ -530,10 +534,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--tex_fill', action='store_true', default=argparse.SUPPRESS,
                    help="With --tex_project: fill the texels of every UV island that no view sees by push-pull from the island's "
                         "projected texels (topo4d_amd.projtex --tex_fill).")
-    from .projtex import add_band_options, add_eq_options, add_options
+    p.add_argument('--tex_reject', action='store_true', default=argparse.SUPPRESS,
+                   help="With --tex_project: leave a view out of a texel where it disagrees with the median of the views that face "
+                        "it (topo4d_amd.projtex --reject; --reject_tol, --vote_cos_min and --min_votes as it takes them).")
+    from .projtex import add_band_options, add_consist_options, add_eq_options, add_options
     add_options(p, suppress=True)
     add_band_options(p, suppress=True)
     add_eq_options(p, suppress=True)
+    add_consist_options(p, suppress=True)
     return p
 
 
