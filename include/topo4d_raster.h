@@ -784,8 +784,28 @@ int t4d_project_texture_bands_skip(const float *pos, const float *nrm, const uin
  * results; kept for measurement).  Uses a work area inside `index`: one query at a time per index.  The result equals a
  * float64 brute force over all primitives with the arithmetic of tests/scanscore_ref.py, bit for bit.
  * t4d_closest_signed: signed_dist[i] = sqrt(d2[i]) with the sign of (p - closest) . ((b - a) x (c - a)) of the chosen
- * triangle; 0 where that is 0, for point primitives and for unmatched queries. */
+ * triangle; 0 where that is 0, for point primitives and for unmatched queries.
+ * t4d_closest_raycast: per ray (origins, dirs: float64 [n_rays,3]) the triangle of a triangle index (a point index is
+ * T4D_ERR_ARG) that the line o + t d meets at the smallest |t| within [t_lo, t_hi] (host; finite, with a finite difference):
+ * out_t (float64), out_prim (int32) and out_uv (float64 [n_rays,2], the hit is a + u (b - a) + v (c - a)).  scratch as for
+ * t4d_closest_query; flags: T4D_CLOSEST_INPUT_ORDER as there, T4D_RAY_SAME_SIDE counts only triangles whose normal
+ * (b - a) x (c - a) points along d.  The hit rule, in float64 without contraction and with dot3(u,v) = (u0 v0 + u1 v1) + u2 v2,
+ * for ray (o, d) and triangle (a, b, c), in this order:
+ *   1. e1 = b - a, e2 = c - a, pv = d x e2, det = dot3(e1, pv); det == 0 is a miss.
+ *   2. With T4D_RAY_SAME_SIDE, det >= 0 is a miss.
+ *   3. tv = o - a, u = dot3(tv, pv) / det; a miss unless u >= 0 && u <= 1.
+ *   4. qv = tv x e1, v = dot3(d, qv) / det; a miss unless v >= 0 && u + v <= 1.
+ *   5. t = dot3(e2, qv) / det; a miss unless t >= t_lo && t <= t_hi.
+ *   6. Box condition: on every axis k the computed point p_k = o_k + t d_k satisfies p_k >= min(a_k, b_k, c_k) - margin and
+ *      p_k <= max(a_k, b_k, c_k) + margin, margin being the grid's (2^-40 of the coordinates' magnitude), else a miss.
+ * Quotients, not a reciprocal; a NaN fails every comparison.  Among the hits the smallest |t| wins, then t >= 0 over t < 0,
+ * then the lowest triangle index.  A miss writes t = 0, prim = -1, uv = 0; a ray with a non-finite origin or direction, with
+ * an all-zero direction, or with t_lo > t_hi misses every triangle.  The box condition is what makes a walk over the grid
+ * cells along the ray equal an all-pairs search however ill-conditioned a grazing ray is: a hit's computed point lies in
+ * cells that list its triangle.  Equals tests/scanray_ref.py bit for bit.  The interval is cut into at most 1024 pieces of at
+ * most a cell each: a reach of more than 1024 cells is walked in pieces that cover many cells at once, correctly but slowly. */
 #define T4D_CLOSEST_INPUT_ORDER 1
+#define T4D_RAY_SAME_SIDE 2
 size_t t4d_closest_index_bytes(int64_t n_vert, int64_t n_faces, const double *bbox, double mean_extent, int64_t entry_capacity);
 int t4d_closest_build(const double *vertices, int64_t n_vert, const int32_t *faces, int64_t n_faces, const double *bbox,
                       double mean_extent, void *index, size_t index_bytes, int64_t entry_capacity, int64_t *entries_needed,
@@ -795,6 +815,9 @@ int t4d_closest_query(void *index, size_t index_bytes, const double *points, int
                       double *d2, int32_t *prim_index, double *closest, void *scratch, size_t scratch_bytes, void *hip_stream);
 int t4d_closest_signed(const void *index, size_t index_bytes, const double *points, int64_t n_queries, const double *d2,
                        const int32_t *prim_index, const double *closest, double *signed_dist, void *hip_stream);
+int t4d_closest_raycast(void *index, size_t index_bytes, const double *origins, const double *dirs, int64_t n_rays, double t_lo,
+                        double t_hi, int32_t flags, double *out_t, int32_t *out_prim, double *out_uv, void *scratch,
+                        size_t scratch_bytes, void *hip_stream);
 
 /* Optional per-kernel timing with HIP events recorded on the stream the kernels are launched on.  Between
  * t4d_profile_begin() and t4d_profile_end() every kernel launch of this library is bracketed by two events;

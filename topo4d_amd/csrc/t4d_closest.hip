@@ -20,6 +20,10 @@
 // u2 v2; Ericson's region walk (Real-Time Collision Detection, 5.1.5) with quotients instead of a reciprocal; a triangle whose
 // unnormalised normal is exactly zero, or whose interior weights do not come out >= 0 with a positive sum, is the nearest of its
 // edges ab, bc, ca (the first wins a tie); an edge of zero length is its first end.  Equal d2: the lowest primitive index wins.
+//
+// Ray query (t4d_closest_raycast, what topo4d_amd/scanbake.py bakes a displacement map with): on a triangle index, per ray the
+// triangle met at the smallest |t| within [t_lo, t_hi], by the hit rule of include/topo4d_raster.h; tests/scanray_ref.py applies
+// it to every (ray, triangle) pair and the walk of k_closest_raycast equals that bit for bit.
 #include <stdint.h>
 #include <math.h>
 #include <string.h>
@@ -518,6 +522,115 @@ __global__ __launch_bounds__(kBlock) void k_closest_signed(const CGrid *gp, cons
     out[i] = r;
 }
 
+// ---- ray cast ---------------------------------------------------------------------------------------------------------------
+// The hit rule of include/topo4d_raster.h (t4d_closest_raycast), which tests/scanray_ref.py applies to every (ray, triangle)
+// pair: a hit's computed point lies in the triangle's box grown by the margin, hence in cells that list the triangle, and that
+// is what lets a walk over the cells along the ray equal the all-pairs search bit for bit.
+struct Hit {
+    double t, u, v;
+    int32_t prim;
+};
+
+__device__ __forceinline__ void ray_consider(const double *rec, int32_t prim, const double *o, const double *d, double t_lo, double t_hi,
+                                             int same_side, double margin, Hit &best)
+{
+#pragma clang fp contract(off)
+    const double *a = rec + 9 * (int64_t)prim, *b = a + 3, *c = a + 6;
+    const double e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+    const double e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+    const double pv[3] = {d[1] * e2[2] - d[2] * e2[1], d[2] * e2[0] - d[0] * e2[2], d[0] * e2[1] - d[1] * e2[0]};
+    const double det = dot3(e1, pv);
+    if (det == 0.0 || (same_side && det >= 0.0)) return;
+    const double tv[3] = {o[0] - a[0], o[1] - a[1], o[2] - a[2]};
+    const double u = dot3(tv, pv) / det;
+    if (!(u >= 0.0 && u <= 1.0)) return;
+    const double qv[3] = {tv[1] * e1[2] - tv[2] * e1[1], tv[2] * e1[0] - tv[0] * e1[2], tv[0] * e1[1] - tv[1] * e1[0]};
+    const double v = dot3(d, qv) / det;
+    if (!(v >= 0.0 && u + v <= 1.0)) return;
+    const double t = dot3(e2, qv) / det;
+    if (!(t >= t_lo && t <= t_hi)) return;
+    for (int k = 0; k < 3; k++) {                                   // the box condition
+        const double p = o[k] + t * d[k];
+        const double mn = fmin(a[k], fmin(b[k], c[k])), mx = fmax(a[k], fmax(b[k], c[k]));
+        if (!(p >= mn - margin && p <= mx + margin)) return;
+    }
+    const double at = fabs(t), bt = fabs(best.t);
+    const bool fwd = t >= 0.0, best_fwd = best.t >= 0.0;
+    if (best.prim < 0 || at < bt || (at == bt && ((fwd && !best_fwd) || (fwd == best_fwd && prim < best.prim)))) {
+        best.t = t; best.u = u; best.v = v; best.prim = prim;
+    }
+}
+
+// one lane per ray (order != NULL: grouped by the cell of the origin).  [t_lo, t_hi] is cut into pieces of at most one cell
+// along the ray's longest axis (1024 at the most); o + t d is monotone in t under rounding, so a piece's computed points lie in
+// the box of its two ends, and the cells of that box grown by twice the margin (once for the box condition, once for the
+// rounding of the sums that undo it) list every triangle the piece can hit.  The pieces are walked outward from the one next to
+// t = 0 until every piece left begins beyond the best |t|; a piece outside the grid is passed over.
+__global__ __launch_bounds__(kBlock) void k_closest_raycast(const CGrid *gp, const double *rec, const int32_t *start, const int32_t *entries,
+                                                            const double *org, const double *dir, int64_t n_rays, const int32_t *order,
+                                                            double t_lo, double t_hi, int same_side, double *out_t, int32_t *out_prim,
+                                                            double *out_uv)
+{
+#pragma clang fp contract(off)
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= n_rays) return;
+    const int64_t ri = order ? order[s] : s;
+    const CGrid g = *gp;
+    const double o[3] = {org[3 * ri], org[3 * ri + 1], org[3 * ri + 2]};
+    const double d[3] = {dir[3 * ri], dir[3 * ri + 1], dir[3 * ri + 2]};
+    Hit best;
+    best.t = best.u = best.v = 0.0; best.prim = -1;
+    bool ok = t_lo <= t_hi && (d[0] != 0.0 || d[1] != 0.0 || d[2] != 0.0);
+    for (int a = 0; a < 3; a++) ok = ok && isfinite(o[a]) && isfinite(d[a]);
+    if (ok) {
+        const double span = t_hi - t_lo;
+        const double want = ceil(span * fmax(fabs(d[0]), fmax(fabs(d[1]), fabs(d[2]))) / g.cell);
+        const int np = !(want >= 1.0) ? 1 : want >= 1024.0 ? 1024 : (int)want;
+        const double h = span / (double)np;
+        auto cut = [&](int i) { return i >= np ? t_hi : t_lo + (double)i * h; };
+        auto nearest = [&](int k) {                                 // min |t| over piece k
+            const double lo = cut(k), hi = cut(k + 1);
+            return lo > 0.0 ? lo : hi < 0.0 ? -hi : 0.0;
+        };
+        int k = 0;
+        if (t_hi <= 0.0) k = np - 1;
+        else if (t_lo < 0.0) {
+            const double f = floor(-t_lo / h);
+            k = !(f > 0.0) ? 0 : f >= (double)np ? np - 1 : (int)f;
+        }
+        int down = k - 1, up = k + 1;
+        for (;;) {
+            const double lo = cut(k), hi = cut(k + 1);
+            int32_t c0[3], c1[3];
+            bool inside = true;
+            for (int a = 0; a < 3; a++) {
+                const double pa = o[a] + lo * d[a], pb = o[a] + hi * d[a];
+                const double mn = fmin(pa, pb) - 2.0 * g.margin, mx = fmax(pa, pb) + 2.0 * g.margin;
+                inside = inside && !(mx < g.lo[a]) && !(mn > g.lo[a] + (double)g.dim[a] * g.cell);
+                c0[a] = cell_coord(mn, g.lo[a], g.cell, g.dim[a]);
+                c1[a] = cell_coord(mx, g.lo[a], g.cell, g.dim[a]);
+            }
+            if (inside)
+                for (int32_t z = c0[2]; z <= c1[2]; z++)
+                    for (int32_t y = c0[1]; y <= c1[1]; y++)
+                        for (int32_t x = c0[0]; x <= c1[0]; x++) {
+                            const int64_t id = cell_id(g, x, y, z);
+                            const int32_t b = start[id], e = start[id + 1];
+                            for (int32_t j = b; j < e; j++) ray_consider(rec, entries[j], o, d, t_lo, t_hi, same_side, g.margin, best);
+                        }
+            const double nd = down >= 0 ? nearest(down) : INFINITY, nu = up < np ? nearest(up) : INFINITY;
+            if (down < 0 && up >= np) break;
+            if (best.prim >= 0 && fmin(nd, nu) > fabs(best.t)) break;
+            if (nd <= nu) k = down--;
+            else k = up++;
+        }
+    }
+    out_t[ri] = best.t;
+    out_prim[ri] = best.prim;
+    out_uv[2 * ri] = best.u;
+    out_uv[2 * ri + 1] = best.v;
+}
+
 bool build_args_ok(int64_t n_vert, int64_t n_faces, const double *bbox, double mean_extent, int64_t entry_capacity)
 {
     const int64_t n = n_faces > 0 ? n_faces : n_vert;
@@ -648,4 +761,38 @@ T4D_EXPORT int t4d_closest_signed(const void *index, size_t index_bytes, const d
     hipLaunchKernelGGL(k_closest_signed, dim3(blocks(n_queries, kBlock)), dim3(kBlock), 0, stream, (const CGrid *)(b + L.head),
                        (const double *)(b + L.rec), points, n_queries, d2, prim_index, closest, signed_dist);
     return t4d_launch_status("t4d_closest_signed");
+}
+
+T4D_EXPORT int t4d_closest_raycast(void *index, size_t index_bytes, const double *origins, const double *dirs, int64_t n_rays, double t_lo,
+                                   double t_hi, int32_t flags, double *out_t, int32_t *out_prim, double *out_uv, void *scratch,
+                                   size_t scratch_bytes, void *hip_stream)
+{
+    if (!index || !origins || !dirs || !out_t || !out_prim || !out_uv || !scratch || n_rays < 1 || n_rays > INT32_MAX / 2 ||
+        index_bytes < 256 || (flags & ~(T4D_CLOSEST_INPUT_ORDER | T4D_RAY_SAME_SIDE)) || !isfinite(t_lo) || !isfinite(t_hi) ||
+        !isfinite(t_hi - t_lo))
+        return t4d_fail(T4D_ERR_ARG, "t4d_closest_raycast: bad arguments (NULL buffer, no rays, unknown flag, or limits that are not finite with a finite difference)");
+    const QLayout Q = query_layout(n_rays);
+    if (scratch_bytes < Q.total) return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_closest_raycast: scratch too small (%zu < %zu)", scratch_bytes, Q.total);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    CGrid g;
+    CLayout L;
+    const int rc = read_index("t4d_closest_raycast", index, index_bytes, stream, &g, &L);
+    if (rc != T4D_OK) return rc;
+    if (!g.is_tri) return t4d_fail(T4D_ERR_ARG, "t4d_closest_raycast: the index holds points, and a ray meets only triangles");
+    char *b = (char *)index, *s = (char *)scratch;
+    const CGrid *gd = (const CGrid *)(b + L.head);
+    const double *rec = (const double *)(b + L.rec);
+    const int32_t *start = (const int32_t *)(b + L.start), *entries = (const int32_t *)(b + L.entries);
+    int32_t *work = (int32_t *)(b + L.work), *bsum = (int32_t *)(b + L.bsum);
+    int32_t *order = (int32_t *)(s + Q.order), *qcell = (int32_t *)(s + Q.qcell);
+    const bool sorted = !(flags & T4D_CLOSEST_INPUT_ORDER);
+    if (sorted) {                                                   // the rays grouped by the cell of their origin
+        T4D_HIP_CHECK(hipMemsetAsync(work, 0, sizeof(int32_t) * (size_t)(g.n_cells + 1), stream));
+        hipLaunchKernelGGL(k_closest_query_cells, dim3(blocks(n_rays, kBlock)), dim3(kBlock), 0, stream, gd, origins, n_rays, qcell, work);
+        exclusive_scan(work, nullptr, bsum, g.n_cells + 1, L.nscan, stream);
+        hipLaunchKernelGGL(k_closest_query_order, dim3(blocks(n_rays, kBlock)), dim3(kBlock), 0, stream, qcell, n_rays, work, order);
+    }
+    hipLaunchKernelGGL(k_closest_raycast, dim3(blocks(n_rays, kBlock)), dim3(kBlock), 0, stream, gd, rec, start, entries, origins, dirs, n_rays,
+                       sorted ? order : (const int32_t *)nullptr, t_lo, t_hi, (flags & T4D_RAY_SAME_SIDE) ? 1 : 0, out_t, out_prim, out_uv);
+    return t4d_launch_status("t4d_closest_raycast");
 }

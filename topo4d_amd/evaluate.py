@@ -1,7 +1,8 @@
 """
 Score a finished run: `python -m topo4d_amd.evaluate -e EXP -s SEQ [-id ... -did ... -od ...] [--frames 1-10] [--views A,B]
 [--set low|dense|both|none] [--save_renders] [--scans DIR [--scan_max_dist X] [--scan_unit S] [--scan_thresholds a,b,c]
-[--scan_transform FILE] [--save_scan_errors]] [--tex_pad R [--tex_erode E]] [--texture NAME]`.
+[--scan_transform FILE] [--save_scan_errors] [--bake_disp DIST [--bake_res N] [--bake_both_sides]]] [--tex_pad R [--tex_erode E]]
+[--texture NAME]`.
 
 For every frame of <od>/<exp>/<seq>: read %06d/face.obj (save_mesh's vertices: the training frame mapped by the trans_g of
 cameras.get_cameras, whose inverse maps them back, in float64) and %06d/face.png (PIL, on the host; frame t+1's files are read on a thread
@@ -14,6 +15,13 @@ reference's train.py as well: the layout and save_mesh's formats are the same.
 With --scans DIR every frame's face.obj is also measured against that frame's 3D scan, DIR/%06d.ply or else DIR/%06d.obj
 (scanscore.score_scan: scan -> mesh and mesh -> scan distances).  face.obj is compared as written: save_mesh writes world
 coordinates, the frame Metashape exports its scans in.  eval.json gains the key "scan"; --set none scores scans alone.
+
+With --bake_disp DIST (scan file units) every scored frame's scan detail is also baked into the UV layout of its face.obj
+(scanbake.bake_displacement: per texel a ray along the surface normal, both ways, within DIST; --scan_transform applies first):
+%06d/face_disp.npy (float32 [N,N], scan file units, positive outward, N = --bake_res) and %06d/face_disp_hit.png (255 where the
+ray met the scan).  The frame's "scan" row gains "displacement" (scanbake.displacement_stats, in --scan_unit) and
+"mesh_to_scan_normal" (every mesh vertex shot along its normal within DIST: the normal-shooting distance), the summary their
+means.  --bake_both_sides also counts scan triangles that face away from the texel's normal.
 
 With --tex_pad R every face.png is padded in memory before it is sampled (texfinish.finish: a gutter of R texels round the UV
 islands of face.obj, whose coverage is first eroded --tex_erode rounds, 1 by default), so that the bilinear taps on the UV seams
@@ -237,6 +245,12 @@ def _read_scan_files(run_dir: str, scan_dir: str, t: int, transform):
     return obj, scan
 
 
+def texfinish_coverage(obj, res: int, device) -> torch.Tensor:
+    """The coverage the displacement bake walked: projtex.surface_maps' (texfinish.coverage_from_obj), uint8 [res,res]."""
+    from . import texfinish
+    return texfinish.coverage_from_obj(obj, int(res), int(res), device=device)
+
+
 def _scan_summary(frames: dict) -> dict:
     scored = {f: fr for f, fr in frames.items() if "scan_to_mesh" in fr}
     out = {"frames": len(scored)}
@@ -246,6 +260,17 @@ def _scan_summary(frames: dict) -> dict:
         keys = list(rows[0]["within"]) if rows else []
         part["within"] = {k: float(np.mean([r["within"][k] for r in rows])) for k in keys}
         out[d] = part
+    shot = [fr["mesh_to_scan_normal"] for fr in scored.values() if fr.get("mesh_to_scan_normal", {}).get("count")]
+    if any("mesh_to_scan_normal" in fr for fr in scored.values()):
+        part = {n: float(np.mean([r[n] for r in shot])) if shot else None for n in ("mean", "rms")}
+        part["within"] = {k: float(np.mean([r["within"][k] for r in shot])) for k in (list(shot[0]["within"]) if shot else [])}
+        out["mesh_to_scan_normal"] = part
+    baked = [fr["displacement"] for fr in scored.values() if "hit_fraction" in fr.get("displacement", {})]
+    if any("displacement" in fr for fr in scored.values()):
+        out["displacement"] = {"hit_fraction": float(np.mean([r["hit_fraction"] for r in baked])) if baked else None}
+        for n in ("mean", "rms"):
+            xs = [r[n] for r in baked if r.get(n) is not None]
+            out["displacement"][n] = float(np.mean(xs)) if xs else None
     worst = [(f, fr["scan_to_mesh"]["mean"]) for f, fr in scored.items() if fr["scan_to_mesh"].get("count")]
     out["worst_frame"] = max(worst, key=lambda w: w[1])[0] if worst else None
     return out
@@ -262,6 +287,7 @@ def score_scans(args, device) -> dict:
         if transform.shape != (4, 4) or not np.isfinite(transform).all():
             raise SystemExit(f"--scan_transform: {args.scan_transform} does not hold a finite 4x4 matrix")
     result = {}
+    bake_disp = getattr(args, "bake_disp", None)
     pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="t4d-eval-scan")
     try:
         pending = {}
@@ -283,8 +309,19 @@ def score_scans(args, device) -> dict:
                 result[key] = {"skipped": "no scan"}
                 continue
             faces, _ = meshrender.triangulate(obj.faces_ori, obj.uv_faces_ori)
+            bake = bake_disp is not None and scan.faces is not None
             score = scanscore.score_scan(obj.vertices, faces, scan, max_dist=args.scan_max_dist, thresholds=args.scan_thresholds,
-                                         unit=args.scan_unit, device=device, per_element=args.save_scan_errors)
+                                         unit=args.scan_unit, device=device, per_element=args.save_scan_errors,
+                                         **({"shoot": bake_disp} if bake else {}))
+            if bake:
+                from . import scanbake
+                disp, hit, _ = scanbake.bake_displacement(obj, obj.vertices, scan, args.bake_res, bake_disp,
+                                                          same_side=not args.bake_both_sides, device=device)
+                scanbake.write_frame(os.path.join(run_dir, key), disp, hit)
+                score["displacement"] = scanbake.displacement_stats(disp, hit, texfinish_coverage(obj, args.bake_res, device),
+                                                                    unit=args.scan_unit)
+            elif bake_disp is not None:
+                score["displacement"] = {"skipped": "scan has no faces"}
             arrays = score.pop("arrays", None)
             if arrays is not None:
                 np.savez(os.path.join(run_dir, key, "scan_score.npz"), **arrays)
@@ -294,7 +331,10 @@ def score_scans(args, device) -> dict:
             result[key] = row
     finally:
         pool.shutdown(wait=True)
-    return {"unit": args.scan_unit, "max_dist": args.scan_max_dist, "frames": result, "summary": _scan_summary(result)}
+    out = {"unit": args.scan_unit, "max_dist": args.scan_max_dist, "frames": result, "summary": _scan_summary(result)}
+    if bake_disp is not None:
+        out["bake"] = {"dist": bake_disp, "res": args.bake_res, "same_side": not args.bake_both_sides}
+    return out
 
 
 def _floats(spec: str) -> List[float]:
@@ -339,6 +379,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--scan_transform", default=None, metavar="FILE", help="Scan scoring: a 4x4 text matrix applied to every scan.")
     p.add_argument("--save_scan_errors", action="store_true",
                    help="Scan scoring: also write %%06d/scan_score.npz (face_count, face_mean, vertex_dist).")
+    p.add_argument("--bake_disp", type=float, default=None, metavar="DIST",
+                   help="With --scans: bake each frame's scan into %%06d/face_disp.npy and face_disp_hit.png, a displacement map in the "
+                        "UV layout of face.obj, with rays of reach DIST (scan file units) along the surface normal, both ways.")
+    p.add_argument("--bake_res", type=int, default=4096, metavar="N",
+                   help="--bake_disp: the side of the displacement map (default 4096; evaluate has no texture size of its own).")
+    p.add_argument("--bake_both_sides", action="store_true",
+                   help="--bake_disp: also count scan triangles whose normal points against the texel's normal.")
     return p
 
 
@@ -353,6 +400,12 @@ def evaluate(args, device=None) -> dict:
         raise SystemExit(f"--scans: no directory {scans}")
     if not sets and scans is None:
         raise SystemExit("--set none scores nothing without --scans")
+    bake_disp = getattr(args, "bake_disp", None)
+    if bake_disp is not None:
+        if scans is None:
+            raise SystemExit("--bake_disp needs --scans")
+        if not (math.isfinite(bake_disp) and bake_disp >= 0.0) or not 1 <= args.bake_res <= 16384:
+            raise SystemExit("--bake_disp needs a finite DIST >= 0 and --bake_res in 1..16384")
     tex_pad = getattr(args, "tex_pad", None)
     if tex_pad is not None:
         from . import texfinish

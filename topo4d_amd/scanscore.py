@@ -3,11 +3,13 @@ A frame's exported mesh scored against that frame's 3D scan (the multi-view-ster
 project exports), on the GPU.
 
     read_scan(path)                               PLY (ascii / binary_little_endian) or OBJ -> Scan(vertices, faces | None)
-    ClosestPointIndex(vertices, faces=None)       grid index on the device; .query(points, max_dist) -> (d2, index, closest)
+    ClosestPointIndex(vertices, faces=None)       grid index on the device; .query(points, max_dist) -> (d2, index, closest),
+                                                  .raycast(origins, dirs, t_lo, t_hi) -> (t, prim, uv)
     score_scan(mesh_vertices, mesh_faces, scan)   scan -> mesh (accuracy) and mesh -> scan (completeness) statistics
 
-over `t4d_closest_build` / `t4d_closest_query` / `t4d_closest_signed` (include/topo4d_raster.h, csrc/t4d_closest.hip).  The
-query's rules are fixed there so that tests/scanscore_ref.py (numpy, float64) reproduces every output bit.  The statistics are
+over `t4d_closest_build` / `t4d_closest_query` / `t4d_closest_signed` / `t4d_closest_raycast` (include/topo4d_raster.h,
+csrc/t4d_closest.hip).  The rules of the query and of the ray cast are fixed there so that tests/scanscore_ref.py and
+tests/scanray_ref.py (numpy, float64) reproduce every output bit.  The statistics are
 torch reductions over the per-query output (a full-size direction is 2 million doubles: a sort and five sums, about as fast as a
 kernel of our own would be, and torch's sum uses no atomics, so two runs agree to the bit).  There is no CPU path.
 """
@@ -25,6 +27,7 @@ from . import _lib
 from ._lib import T4D_ERR_PAIR_OVERFLOW, T4D_OK, ptr
 
 T4D_CLOSEST_INPUT_ORDER = 1
+T4D_RAY_SAME_SIDE = 2
 DEFAULT_THRESHOLDS = (0.5, 1.0, 2.0)
 
 
@@ -293,6 +296,7 @@ class ClosestPointIndex:
                 corners = v[f.long()]                                 # [F,3,3]
                 extent = float((corners.amax(1) - corners.amin(1)).amax(1).mean())
             bb = (C.c_double * 6)(*bbox.tolist())
+            self.mean_extent = extent                                 # (what fixed the grid, with the vertices' box)
             capacity = 16 * self.n_prims + 1024
             lib = _lib.load()
             for _ in range(3):
@@ -341,6 +345,32 @@ class ClosestPointIndex:
                       ptr(d2), ptr(idx), ptr(closest), ptr(s), s.numel(), _lib.stream(self.dev))
         return d2, idx, closest
 
+    def raycast(self, origins, dirs, t_lo: float, t_hi: float, same_side: bool = False, input_order: bool = False):
+        """(t float64 [R], prim int32 [R], uv float64 [R,2]) on the device: per ray o + t d the triangle met at the smallest |t|
+        within [t_lo, t_hi] (then t >= 0 before t < 0, then the lowest index), by the hit rule of include/topo4d_raster.h; the hit
+        is a + u (b - a) + v (c - a).  A miss is t = 0, prim = -1, uv = 0; a ray with a non-finite origin or direction, an all-zero
+        direction, or t_lo > t_hi misses everything.  same_side: only triangles whose normal points along d count.  input_order
+        as in query.  ValueError for an index built without faces, wrong shapes or dtypes, and limits that are not finite."""
+        if not self.is_tri:
+            raise ValueError("raycast needs an index built with faces: a ray meets only triangles")
+        o = _points(origins, "origins", self.dev)
+        d = _points(dirs, "dirs", self.dev)
+        if o.shape != d.shape:
+            raise ValueError(f"origins and dirs must have one shape, got {tuple(o.shape)} and {tuple(d.shape)}")
+        t_lo, t_hi = float(t_lo), float(t_hi)
+        if not (math.isfinite(t_lo) and math.isfinite(t_hi) and math.isfinite(t_hi - t_lo)):
+            raise ValueError(f"t_lo and t_hi must be finite with a finite difference, got {t_lo} and {t_hi}")
+        r = int(o.shape[0])
+        t = torch.empty(r, dtype=torch.float64, device=self.dev)
+        prim = torch.empty(r, dtype=torch.int32, device=self.dev)
+        uv = torch.empty((r, 2), dtype=torch.float64, device=self.dev)
+        with torch.cuda.device(self.dev):
+            s = self._query_scratch(r)
+            _lib.call("t4d_closest_raycast", ptr(self._index), self._index.numel(), ptr(o), ptr(d), r, t_lo, t_hi,
+                      (T4D_RAY_SAME_SIDE if same_side else 0) | (T4D_CLOSEST_INPUT_ORDER if input_order else 0),
+                      ptr(t), ptr(prim), ptr(uv), ptr(s), s.numel(), _lib.stream(self.dev))
+        return t, prim, uv
+
     def signed_distance(self, points, d2, index, closest) -> torch.Tensor:
         """float64 [Q]: sqrt(d2) with the sign of (p - closest) . n of the chosen triangle; 0 for points and unmatched queries."""
         p = _points(points, "points", self.dev)
@@ -376,15 +406,29 @@ def direction_stats(d2: torch.Tensor, index: torch.Tensor, signed: torch.Tensor,
     return out
 
 
+def shoot_normals(target: ClosestPointIndex, mesh_vertices: torch.Tensor, mesh_faces, dist: float):
+    """raycast of `target` from every mesh vertex (float64 [N,3], on the device) along its objexport.vertex_normals normal, within
+    -dist .. +dist: (t, prim, uv).  The normals are of unit length up to rounding, so t is a distance in file units."""
+    from . import objexport
+    return target.raycast(mesh_vertices, objexport.vertex_normals(mesh_vertices, mesh_faces), -dist, dist)
+
+
 def score_scan(mesh_vertices, mesh_faces, scan: Scan, max_dist: Optional[float] = None,
-               thresholds: Sequence[float] = DEFAULT_THRESHOLDS, unit: float = 1.0, device=None, per_element: bool = False) -> dict:
+               thresholds: Sequence[float] = DEFAULT_THRESHOLDS, unit: float = 1.0, device=None, per_element: bool = False,
+               shoot: Optional[float] = None) -> dict:
     """{"scan_to_mesh": {...}, "mesh_to_scan": {...}}: every scan vertex against the mesh triangles (accuracy), every mesh vertex
     against the scan's triangles, or its points when it has no faces (completeness).  max_dist in file units; thresholds and every
     reported distance in unit x file units.  per_element adds "arrays": face_count int64 [F] and face_mean float64 [F] (scan
     points that landed on each mesh face and their mean distance, NaN where none) and vertex_dist float64 [N] (mesh_to_scan per
-    mesh vertex, +inf where unmatched), numpy."""
+    mesh vertex, +inf where unmatched), numpy.  shoot (file units, needs a scan with faces) adds "mesh_to_scan_normal": every mesh
+    vertex shot along its objexport.vertex_normals normal, both ways, within shoot; the statistics are direction_stats over |t|
+    with the sign of t, and "unmatched" counts the vertices whose ray met nothing."""
     if len(thresholds) > 8:
         raise ValueError("at most 8 thresholds")
+    if shoot is not None and not (math.isfinite(float(shoot)) and float(shoot) >= 0.0):
+        raise ValueError(f"shoot must be a finite distance >= 0 or None, got {shoot}")
+    if shoot is not None and (scan.faces is None or len(scan.faces) == 0):
+        raise ValueError("shoot needs a scan with faces: a ray meets only triangles")
     dev = _device(device)
     mv = _points(torch.as_tensor(np.asarray(mesh_vertices, np.float64)) if not isinstance(mesh_vertices, torch.Tensor) else mesh_vertices,
                  "mesh_vertices", dev)
@@ -398,6 +442,9 @@ def score_scan(mesh_vertices, mesh_faces, scan: Scan, max_dist: Optional[float] 
     out["scan_to_mesh"] = direction_stats(d2, idx, mesh.signed_distance(sv, d2, idx, cl), thresholds, unit)
     e2, jdx, cm = target.query(mv, max_dist)
     out["mesh_to_scan"] = direction_stats(e2, jdx, target.signed_distance(mv, e2, jdx, cm), thresholds, unit)
+    if shoot is not None:
+        t, prim, _ = shoot_normals(target, mv, mesh_faces, float(shoot))
+        out["mesh_to_scan_normal"] = direction_stats(t * t, prim, t, thresholds, unit)
     if per_element:
         m = idx >= 0
         hit = idx[m].long()
