@@ -324,8 +324,12 @@ def rasterize(view: View, means3D, means2D, opacities, shs=None, colors_precomp=
 
 def rasterize_with_grads(view: View, means3D, opacities, scales, rotations, colors_precomp=None,
                          shs=None, cov3D_precomp=None, dL_dcolor=None, dL_ddepth=None, dL_dalpha=None,
-                         dtype=torch.float64):
-    """Convenience: forward + backward against given output cotangents.  Returns (outputs, grads)."""
+                         dtype=torch.float64, extra_cotangents=None):
+    """Convenience: forward + backward against given output cotangents.  Returns (outputs, grads).
+
+    extra_cotangents (optional): a sequence of further (dL_dcolor, dL_ddepth, dL_dalpha) triples (None = absent).  Each is run
+    backward over the SAME forward graph - the forward is the expensive half - and the return value becomes
+    (outputs, grads, [grads of each triple]); every entry is what a separate call with that triple returns."""
     def leaf(t):
         return None if t is None else t.detach().to(dtype).clone().requires_grad_(True)
     m3, op, sc, ro, cp, sh, cv = map(leaf, (means3D, opacities, scales, rotations, colors_precomp, shs,
@@ -333,23 +337,32 @@ def rasterize_with_grads(view: View, means3D, opacities, scales, rotations, colo
     m2 = torch.zeros(m3.shape[0], 3, dtype=dtype, requires_grad=True)
     color, radii, depth, alpha, aux = rasterize(view, m3, m2, op, sh, cp, sc, ro, cv, dtype=dtype,
                                                 return_aux=True)
-    loss = 0.0
-    if dL_dcolor is not None:
-        loss = loss + (color * dL_dcolor.to(dtype)).sum()
-    if dL_ddepth is not None:
-        loss = loss + (depth * dL_ddepth.to(dtype)).sum()
-    if dL_dalpha is not None:
-        loss = loss + (alpha * dL_dalpha.to(dtype)).sum()
     names = ["means3D", "means2D", "opacities", "scales", "rotations", "colors_precomp", "shs", "cov3D_precomp"]
     leaves = [m3, m2, op, sc, ro, cp, sh, cv]
     have = [(n, l) for n, l in zip(names, leaves) if l is not None]
-    if torch.is_tensor(loss) and loss.requires_grad:
-        gs = torch.autograd.grad(loss, [l for _, l in have], allow_unused=True)
-    else:
-        # no Gaussian reaches a pixel (all culled): the outputs are constants - background, zero depth and alpha - and every
-        # gradient is zero, as oracle/raster_oracle.c returns for such a view
-        gs = [None] * len(have)
-    grads = {n: (g if g is not None else torch.zeros_like(l)) for (n, l), g in zip(have, gs)}
+
+    def backward(dc, dd, da, retain_graph):
+        loss = 0.0
+        if dc is not None:
+            loss = loss + (color * dc.to(dtype)).sum()
+        if dd is not None:
+            loss = loss + (depth * dd.to(dtype)).sum()
+        if da is not None:
+            loss = loss + (alpha * da.to(dtype)).sum()
+        if torch.is_tensor(loss) and loss.requires_grad:
+            gs = torch.autograd.grad(loss, [l for _, l in have], allow_unused=True, retain_graph=retain_graph)
+        else:
+            # no Gaussian reaches a pixel (all culled): the outputs are constants - background, zero depth and alpha - and every
+            # gradient is zero, as oracle/raster_oracle.c returns for such a view
+            gs = [None] * len(have)
+        return {n: (g if g is not None else torch.zeros_like(l)) for (n, l), g in zip(have, gs)}
+
+    grads = backward(dL_dcolor, dL_ddepth, dL_dalpha, retain_graph=bool(extra_cotangents))
+    extra = None
+    if extra_cotangents is not None:
+        extra = [backward(*cot, retain_graph=j + 1 < len(extra_cotangents)) for j, cot in enumerate(extra_cotangents)]
     outs = dict(color=color.detach(), radii=radii, depth=depth.detach(), alpha=alpha.detach(),
                 final_T=aux["final_T"], n_contrib=aux["n_contrib"], aux=aux)
+    if extra is not None:
+        return outs, grads, extra
     return outs, grads

@@ -78,13 +78,14 @@ def c_oracle_render_many(cams, rv, dcs=None, dds=None, das=None, threads=None):
             yield f.result()
 
 
-def torch_oracle_render(cam, rv, dc=None, dd=None, da=None, dtype=torch.float64):
+def torch_oracle_render(cam, rv, dc=None, dd=None, da=None, dtype=torch.float64, extra_cotangents=None):
+    """(outs, grads) of the float64 oracle; with `extra_cotangents` - further (dc, dd, da) triples run backward over the same
+    forward - (outs, grads, [grads per triple])."""
     view = TO.View(*cam)
-    outs, grads = TO.rasterize_with_grads(view, rv["means3D"], rv["opacities"], rv.get("scales"), rv.get("rotations"),
-                                          colors_precomp=rv.get("colors_precomp"), shs=rv.get("shs"),
-                                          cov3D_precomp=rv.get("cov3D_precomp"), dL_dcolor=dc, dL_ddepth=dd,
-                                          dL_dalpha=da, dtype=dtype)
-    return outs, grads
+    return TO.rasterize_with_grads(view, rv["means3D"], rv["opacities"], rv.get("scales"), rv.get("rotations"),
+                                   colors_precomp=rv.get("colors_precomp"), shs=rv.get("shs"),
+                                   cov3D_precomp=rv.get("cov3D_precomp"), dL_dcolor=dc, dL_ddepth=dd,
+                                   dL_dalpha=da, dtype=dtype, extra_cotangents=extra_cotangents)
 
 
 def decode_state(batch):
