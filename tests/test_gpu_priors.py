@@ -1,6 +1,9 @@
 """GPU: the fused topology priors (t4d_priors_eval, topo4d_amd.priors) against G12 - the reference's own get_loss on the real
 facial-region topology - and against the plain-torch evaluation; determinism, accumulation, the cos_init cache, the autograd
-wrapper, and the geometry loop with priors= (eager, explicit, graphed)."""
+wrapper, and the geometry loop with priors= (eager, explicit, graphed).
+
+The gradient checks here hold the SUM of all terms to 1e-4 of each tensor's largest entry; tests/test_gpu_priors_rows.py holds
+every term alone, and every vertex, to 1e-4 of its own scale (tests/priors_rows.py)."""
 import numpy as np
 import pytest
 import torch
@@ -141,7 +144,11 @@ def test_autograd_function_equals_the_explicit_path():
 
 
 # ---- a triangulated lat-lon head (scaffold.scene.make_gaussians' vertex order) with its own topology ------------------------
-def grid_priors(n_lat, n_lon, means3D, seed=0, device="cuda"):
+def grid_priors(n_lat, n_lon, means3D, seed=0, device="cuda", n_edges=None, no_regions=(), drop_slot_every=0, weights=None):
+    """The topology of the lat-lon head.  The optional arguments (tests/priors_rows.py) change it after every random draw, so the
+    callers that leave them out see the same values: `n_edges` {edge term: its first n elements, 0 = absent}, `no_regions` the
+    absent region terms, `drop_slot_every` = m masks a middle slot of every m-th vertex (FlattenLoss_v2's mask, neighbor_num
+    one less), `weights` the loss weights."""
     from topo4d_amd import priors as T
     P = n_lat * n_lon
     vid = lambda i, j: i * n_lon + (j % n_lon)
@@ -168,13 +175,23 @@ def grid_priors(n_lat, n_lon, means3D, seed=0, device="cuda"):
         pick = [inter[i] for i in sorted(rng.choice(len(inter), size=len(inter) // 2, replace=False))]
         edges[k] = tuple(np.array(col) for col in zip(*[(e[0], e[1], o[0], o[1]) for e, o in pick]))
     regions = {k: rng.choice(P, size=P // 5, replace=False) for k in T.REGION_TERMS}
+    for k, n in (n_edges or {}).items():
+        edges[k] = tuple(col[:n] for col in edges[k])
+    for k in no_regions:
+        del regions[k]
+    mask = None
+    if drop_slot_every:
+        mask = (np.arange(K)[None, :] < nnum[:, None]).astype(np.float32)
+        rows = np.arange(0, P, drop_slot_every)
+        mask[rows, nnum[rows] // 2] = 0.0
+        nnum[rows] -= 1
     x = means3D.detach().cpu().numpy().astype(np.float64)
     dist = np.sqrt(((x[nbr] - x[:, None]) ** 2).sum(-1))
     w = np.exp(-2000 * dist ** 2)
     w[nbr == np.arange(P)[:, None]] = 0.0
     init_scale = rng.uniform(0.002, 0.01, P)
     return T.TopologyPriors(nbr, dist, w * rng.uniform(0, 1, w.shape), w * rng.uniform(0, 2, w.shape), w, init_scale, nnum, edges,
-                            regions, device=device)
+                            regions, nbr_mask=mask, weights=weights, device=device)
 
 
 def _moved(p, scale, seed):

@@ -6,8 +6,9 @@
 //    element's weighted loss and writes its local gradient contributions, each to a record of its own (no atomics), and one loss
 //    partial per block and term.
 //  * k_priors_vertices (phase B): one thread per vertex gathers the records that name it - its own K neighbour slots, the slots of
-//    other Gaussians that name it (transposed neighbour list), and the flatten records (CSR) - in a fixed order, then applies the
-//    chain rule through quat_mult, normalize and exp and writes (or adds) the three raw gradients.  Block 0 also reduces the loss
+//    other Gaussians that name it (transposed neighbour list), and the flatten records (CSR) - in a fixed order, every term into a
+//    sum of its own and the terms' sums added last, then applies the chain rule through quat_mult, normalize and exp (per term
+//    for the quaternion) and writes (or adds) the three raw gradients.  Block 0 also reduces the loss
 //    partials, term by term in block order.
 //
 // Fixed summation orders everywhere: the result is bit-identical from run to run.  The arithmetic restates the reference's
@@ -42,7 +43,7 @@ struct Segs {
 
 struct Ptr {
     const float *x, *q, *ls;
-    float4 *posG, *posN, *rotG, *rotN, *rec, *scale_g;
+    float4 *posR, *posI, *rotR, *rotQ, *rec, *scale_g;   // rigid / iso offset gradients, rigid / rot rel_rot gradients per (g, k)
     float *partial;
 };
 
@@ -174,7 +175,7 @@ __global__ __launch_bounds__(kBlock) void k_priors_elements(const T4DPriors pr, 
             const float s1 = sqrtf(dot3(d, d) * wr + 1e-20f);
             v[0] = s1 * S.coef_nbr[0];
             const float3 gv = mul3(d, S.coef_nbr[0] * wr / s1);
-            float3 goff = make_float3(R[0][0] * gv.x + R[0][1] * gv.y + R[0][2] * gv.z, R[1][0] * gv.x + R[1][1] * gv.y + R[1][2] * gv.z,
+            const float3 goff = make_float3(R[0][0] * gv.x + R[0][1] * gv.y + R[0][2] * gv.z, R[1][0] * gv.x + R[1][1] * gv.y + R[1][2] * gv.z,
                                       R[2][0] * gv.x + R[2][1] * gv.y + R[2][2] * gv.z);
             // dL/dR[j][i] = gv_i off_j, then through the matrix entries to (r, x, y, z)
             const float o[3] = {off.x, off.y, off.z}, gvv[3] = {gv.x, gv.y, gv.z};
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(kBlock) void k_priors_elements(const T4DPriors pr, 
             const float gz_ = 2.f * (-2.f * z * G[0][0] - r * G[0][1] + x * G[0][2] + r * G[1][0] - 2.f * z * G[1][1] + y * G[1][2] +
                                      x * G[2][0] + y * G[2][1]);
             const float pd = r * gr_ + x * gx_ + y * gy_ + z * gz_;
-            float4 grg = make_float4((gr_ - r * pd) / nq, (gx_ - x * pd) / nq, (gy_ - y * pd) / nq, (gz_ - z * pd) / nq);
+            const float4 grg = make_float4((gr_ - r * pd) / nq, (gx_ - x * pd) / nq, (gy_ - y * pd) / nq, (gz_ - z * pd) / nq);
             // rot: || rel_rot[nbr] - rel_rot ||, weighted_l2_loss_v2
             const float4 dq = make_float4(rn.x - rg.x, rn.y - rg.y, rn.z - rg.z, rn.w - rg.w);
             const float wq = pr.rot_w[e];
@@ -199,18 +200,18 @@ __global__ __launch_bounds__(kBlock) void k_priors_elements(const T4DPriors pr, 
             v[1] = s2 * S.coef_nbr[1];
             const float c2 = S.coef_nbr[1] * wq / s2;
             const float4 grn = make_float4(dq.x * c2, dq.y * c2, dq.z * c2, dq.w * c2);
-            grg = make_float4(grg.x - grn.x, grg.y - grn.y, grg.z - grn.z, grg.w - grn.w);
             // iso: | sqrt(|off|^2 + 1e-20) - neighbor_dist |, weighted_l2_loss_v1 (helpers.py:126-127)
             const float mag = sqrtf(dot3(off, off) + 1e-20f);
             const float rd = mag - pr.nbr_dist[e];
             const float wi = pr.iso_w[e];
             const float s3 = sqrtf(rd * rd * wi + 1e-20f);
             v[2] = s3 * S.coef_nbr[2];
-            goff = add3(goff, mul3(off, S.coef_nbr[2] * wi * rd / s3 / mag));
-            p.posG[e] = make_float4(-goff.x, -goff.y, -goff.z, 0.f);
-            p.posN[e] = make_float4(goff.x, goff.y, goff.z, 0.f);
-            p.rotG[e] = grg;
-            p.rotN[e] = grn;
+            const float3 giso = mul3(off, S.coef_nbr[2] * wi * rd / s3 / mag);
+            // one record per term: the neighbour receives it, the Gaussian its negative (rot: rel_rot[nbr] - rel_rot likewise)
+            p.posR[e] = make_float4(goff.x, goff.y, goff.z, 0.f);
+            p.posI[e] = make_float4(giso.x, giso.y, giso.z, 0.f);
+            p.rotR[e] = grg;
+            p.rotQ[e] = grn;
         } else if (sg.kind == SEG_SCALE) {
             // scale = sum_g min_c exp(ls), scale_max = sum_g relu(max_c exp(ls) - 1.5 init_scale) (train.py:360-363).
             // Tie rule: torch.min / torch.max over dim 1 return the FIRST index of the extreme value (the CPU golden shows the
@@ -298,34 +299,59 @@ __global__ __launch_bounds__(kBlock) void k_priors_vertices(const T4DPriors pr, 
     const int v = blockIdx.x * kBlock + threadIdx.x;
     const float up = upstream ? *upstream : 1.f;
     if (v < pr.P) {
+        // Every term is summed on its own, in the order a one-term evaluation sums it, and the terms are added last: the gradient
+        // of all terms is the rounded sum of the gradients of the terms alone, whatever cancels inside a term.
         float3 gx = make_float3(0.f, 0.f, 0.f);
-        float4 grr = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 qr = make_float4(0.f, 0.f, 0.f, 0.f), qo = qr;     // d rigid / d rel_rot, d rot / d rel_rot
         if (!is_initial) {
+            float3 xr = make_float3(0.f, 0.f, 0.f), xi = xr;
             for (int k = 0; k < pr.K; k++) {
-                const float4 a = p.posG[v * pr.K + k], b = p.rotG[v * pr.K + k];
-                gx = add3(gx, make_float3(a.x, a.y, a.z));
-                grr = make_float4(grr.x + b.x, grr.y + b.y, grr.z + b.z, grr.w + b.w);
+                const int e = v * pr.K + k;
+                const float4 a = p.posR[e], c = p.posI[e], b = p.rotR[e], d = p.rotQ[e];
+                xr = sub3(xr, make_float3(a.x, a.y, a.z));
+                xi = sub3(xi, make_float3(c.x, c.y, c.z));
+                qr = make_float4(qr.x + b.x, qr.y + b.y, qr.z + b.z, qr.w + b.w);
+                qo = make_float4(qo.x - d.x, qo.y - d.y, qo.z - d.z, qo.w - d.w);
             }
             for (int j = pr.nbr_t_off[v]; j < pr.nbr_t_off[v + 1]; j++) {
                 const int e = pr.nbr_t_idx[j];
-                const float4 a = p.posN[e], b = p.rotN[e];
-                gx = add3(gx, make_float3(a.x, a.y, a.z));
-                grr = make_float4(grr.x + b.x, grr.y + b.y, grr.z + b.z, grr.w + b.w);
+                const float4 a = p.posR[e], c = p.posI[e], d = p.rotQ[e];
+                xr = add3(xr, make_float3(a.x, a.y, a.z));
+                xi = add3(xi, make_float3(c.x, c.y, c.z));
+                qo = make_float4(qo.x + d.x, qo.y + d.y, qo.z + d.z, qo.w + d.w);
             }
+            gx = add3(xr, xi);
         }
+        // the flatten records of a vertex ascend, so they come term by term: a term's sum joins the total where the next one begins
         const int f = is_initial ? 0 : 1;
+        int si = 0;
+        while (si < S.n && S.s[si].kind != SEG_EDGE && S.s[si].kind != SEG_REGION) si++;
+        float3 acc = make_float3(0.f, 0.f, 0.f);
         for (int j = pr.rec_off[f][v]; j < pr.rec_off[f][v + 1]; j++) {
-            const float4 a = p.rec[pr.rec_idx[f][j]];
-            gx = add3(gx, make_float3(a.x, a.y, a.z));
+            const int rid = pr.rec_idx[f][j];
+            while (si + 1 < S.n && (int64_t)rid >= S.s[si + 1].rec_base) {
+                gx = add3(gx, acc);
+                acc = make_float3(0.f, 0.f, 0.f);
+                si++;
+            }
+            const float4 a = p.rec[rid];
+            acc = add3(acc, make_float3(a.x, a.y, a.z));
         }
-        // rel_rot = quat_mult(normalize(q), prev_inv_rot): back through the product and the normalisation
+        gx = add3(gx, acc);
+        // rel_rot = quat_mult(normalize(q), prev_inv_rot): back through the product and the normalisation, term by term
         float4 gq = make_float4(0.f, 0.f, 0.f, 0.f);
         if (!is_initial) {
             float den;
             const float4 rn = normalize4(ld4(p.q, v), den);
-            const float4 gn = quat_mult_bwd_a(ld4(pr.prev_inv_rot, v), grr);
-            const float pd = rn.x * gn.x + rn.y * gn.y + rn.z * gn.z + rn.w * gn.w;
-            gq = make_float4((gn.x - rn.x * pd) / den, (gn.y - rn.y * pd) / den, (gn.z - rn.z * pd) / den, (gn.w - rn.w * pd) / den);
+            const float4 pinv = ld4(pr.prev_inv_rot, v);
+            const float4 grr[2] = {qr, qo};
+#pragma unroll
+            for (int t = 0; t < 2; t++) {
+                const float4 gn = quat_mult_bwd_a(pinv, grr[t]);
+                const float pd = rn.x * gn.x + rn.y * gn.y + rn.z * gn.z + rn.w * gn.w;
+                gq = make_float4(gq.x + (gn.x - rn.x * pd) / den, gq.y + (gn.y - rn.y * pd) / den, gq.z + (gn.z - rn.z * pd) / den,
+                                 gq.w + (gn.w - rn.w * pd) / den);
+            }
         }
         float3 gs = make_float3(0.f, 0.f, 0.f);
         if (is_initial) {
@@ -422,7 +448,7 @@ Segs make_segs(const T4DPriors *pr, int is_initial)
 }
 
 struct Layout {
-    size_t posG, posN, rotG, rotN, rec, scale_g, partial, total;
+    size_t posR, posI, rotR, rotQ, rec, scale_g, partial, total;
 };
 
 Layout scratch_layout(const T4DPriors *pr)
@@ -433,10 +459,10 @@ Layout scratch_layout(const T4DPriors *pr)
     const size_t blocks = (size_t)(a.blocks > b.blocks ? a.blocks : b.blocks);
     Layout L;
     size_t o = 0;
-    L.posG = o; o = al(o + 16 * PK);
-    L.posN = o; o = al(o + 16 * PK);
-    L.rotG = o; o = al(o + 16 * PK);
-    L.rotN = o; o = al(o + 16 * PK);
+    L.posR = o; o = al(o + 16 * PK);
+    L.posI = o; o = al(o + 16 * PK);
+    L.rotR = o; o = al(o + 16 * PK);
+    L.rotQ = o; o = al(o + 16 * PK);
     L.rec = o; o = al(o + 16 * (size_t)record_layout(pr, nullptr));
     L.scale_g = o; o = al(o + 16 * (size_t)pr->P);
     L.partial = o; o = al(o + sizeof(float) * kNbrTerms * blocks);
@@ -493,8 +519,8 @@ T4D_EXPORT int t4d_priors_eval(const T4DPriors *pr, int32_t is_initial, const fl
     char *base = (char *)scratch;
     Ptr p;
     p.x = means3D; p.q = unnorm_rotations; p.ls = log_scales;
-    p.posG = (float4 *)(base + L.posG); p.posN = (float4 *)(base + L.posN);
-    p.rotG = (float4 *)(base + L.rotG); p.rotN = (float4 *)(base + L.rotN);
+    p.posR = (float4 *)(base + L.posR); p.posI = (float4 *)(base + L.posI);
+    p.rotR = (float4 *)(base + L.rotR); p.rotQ = (float4 *)(base + L.rotQ);
     p.rec = (float4 *)(base + L.rec); p.scale_g = (float4 *)(base + L.scale_g);
     p.partial = (float *)(base + L.partial);
     hipStream_t stream = (hipStream_t)hip_stream;

@@ -293,7 +293,7 @@ class TopologyPriors:
             for k in REGION_TERMS:
                 r = self.regions[k].long()
                 ave = (x[nbr] * self.nbr_mask[..., None]).sum(1) / self.neighbor_num[:, None]
-                L[k] = ((ave[r] - x[r]) ** 2).mean()
+                L[k] = ((ave[r] - x[r]) ** 2).mean() if r.numel() else x.new_zeros(())    # a missing term contributes nothing
             for k in SOFT_TERMS:
                 cos = self._edge_cos(x, k)
                 L[k] = (1 - torch.cos(torch.abs(torch.arccos(cos) - torch.arccos(self.cos_init[k])))).sum()
