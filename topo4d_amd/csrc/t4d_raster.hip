@@ -48,6 +48,7 @@
 #include "../../include/t4d_config.h"
 #include "../../include/topo4d_raster.h"
 #include "t4d_activations.h"
+#include "t4d_tile_div.h"
 
 #define T4D_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -246,11 +247,33 @@ struct KP {
     uint32_t *live;                  // seg_mode 2: slot-table indices of the live segments, status->live_segments of them (order: as the item builders got to them)
     uint32_t slots_by_offset;        // seg_mode 2: a long tile's first slot is off / kSeg + off / kSegLongMin (seg_slot0), not off / kSeg + tile
     uint32_t views_per_set;          // T4DProblem.views_per_param_set: view v reads the per-Gaussian inputs of parameter set v / views_per_set (0: one set for all views)
+    // Divisions of a wave-uniform index by a launch constant in the render kernels, as a scalar multiply-high and shift
+    // (t4d_tile_div.h; mul == 0: the divisor is 1)
+    T4DDiv div_gx;                   // tile / gx                 (tile < T)
+    T4DDiv div_gy;                   // fill workgroup / gy       (k_render_fwd: row of tiles -> view; index < V gy)
+    T4DDiv div_spans;                // spare workgroup / spans   (k_render_bwd: empty tiles' share of cotangent_dot; index < V spans)
+    T4DDiv div_blocks;               // k_render_fwd: (workgroup * fill_blocks) / (tile_blocks + fill_blocks), which spreads the fill workgroups
+    uint32_t div_blocks_ok;          // ... 0: the products exceed 32 bits (or no multiplier): the kernel keeps its 64-bit divisions
+    uint32_t div_ok;                 // host only: every divider above is exact over its range (else the call fails before any launch)
 };
 
 // ---------------------------------------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------------------------------------
+// The kernel parameter block as it lies in the kernarg segment, behind a pointer the compiler cannot see through.  A per-tile
+// kernel uses some twenty pointers of KP once per tile; read through the by-value argument they are all loaded at kernel entry and
+// stay live across the tile loop - more wave-uniform state than the scalar registers hold beside the walk's, so the compiler
+// parks them in lanes of a vector register (v_writelane at entry, v_readlane per tile: vector instructions, in every wave).
+// Read through THIS pointer, taken anew per tile, each is a scalar load from the constant cache where it is used and lives no
+// longer than its tile's prologue.  (KP is the kernels' only argument: offset 0 of the segment.)
+typedef const __attribute__((address_space(4))) KP *kp_kernarg_p;
+__device__ __forceinline__ kp_kernarg_p kernarg_kp()
+{
+    kp_kernarg_p p = (kp_kernarg_p)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
 __device__ __forceinline__ float ndc2pix(float v, int S)
 {
 #pragma clang fp contract(off)      // (v + 1) * S - 1 must not become an fma: S is not a power of two for 512x375 / 4096x3008 images
@@ -631,6 +654,10 @@ void fill_common(KP &kp, const T4DProblem &p, const Layout &L, char *st)
     // seg_mode 2: the caller's word that no list is long (T4D_FLAG_NO_LONG_BINS) keeps every tile whole
     kp.seg_min_pairs = seg_mode(p) == 2 ? ((p.flags & T4D_FLAG_NO_LONG_BINS) ? 0xffffffffu : (uint32_t)kSegLongMin) : 0u;
     static_assert(kSegOne == 64 && kSeg == 128, "seg_shift assumes segment lengths of 64 and 128");
+    // (check_problem keeps every index below 2^30, so a multiplier always exists: see t4d_tile_div.h)
+    kp.div_ok = (t4d_div_make((uint32_t)kp.gx, (uint64_t)kp.T, kp.div_gx) &&
+                 t4d_div_make((uint32_t)kp.gy, (uint64_t)kp.V * (uint64_t)kp.gy, kp.div_gy) &&
+                 t4d_div_make(empty_spans(kp.T), (uint64_t)kp.V * empty_spans(kp.T), kp.div_spans)) ? 1u : 0u;
 }
 
 }  // namespace
@@ -718,6 +745,7 @@ T4D_EXPORT int t4d_rasterize_forward(const T4DProblem *prob, const T4DForwardIO 
     KP kp;
     memset(&kp, 0, sizeof(kp));
     fill_common(kp, p, L, st);
+    if (!kp.div_ok) return fail(T4D_ERR_ARG, "no exact multiplier for this tile grid");
     kp.views = io->views; kp.means3D = io->means3D; kp.opacities = io->opacities; kp.scales = io->scales;
     kp.rotations = io->rotations; kp.cov3D_precomp = io->cov3D_precomp; kp.colors_precomp = io->colors_precomp;
     kp.shs = io->shs;
@@ -811,6 +839,10 @@ T4D_EXPORT int t4d_rasterize_forward(const T4DProblem *prob, const T4DForwardIO 
     kp.fill_vec = (p.W % 4 == 0 && (((uintptr_t)io->out_color | (uintptr_t)io->out_depth | (uintptr_t)io->out_alpha) & 15u) == 0) ? 1u : 0u;
     if (getenv("T4D_FILL_SCALAR")) kp.fill_vec = 0u;       // tests: the 4-byte path on images that would take the 16-byte one
     const dim3 fgrid(kp.tile_blocks + kp.fill_blocks);
+    {
+        const uint64_t top = (uint64_t)fgrid.x * kp.fill_blocks;              // the largest numerator: (last workgroup + 1) * fill_blocks
+        kp.div_blocks_ok = (top < (1ull << 32) && t4d_div_make(fgrid.x, top + 1u, kp.div_blocks)) ? 1u : 0u;
+    }
     // small launch, or a big one-view launch that may hold long lists: snapshots for the segmented backward (kSeg)
     const bool seg = kp.slots_per_view != 0u && kp.seg_min_pairs != 0xffffffffu;
     const bool seg_one = seg && seg_positions(p) == kSegOne;
@@ -878,6 +910,7 @@ T4D_EXPORT int t4d_rasterize_backward(const T4DProblem *prob, const T4DBackwardI
     KP kp;
     memset(&kp, 0, sizeof(kp));
     fill_common(kp, p, L, st);
+    if (!kp.div_ok) return fail(T4D_ERR_ARG, "no exact multiplier for this tile grid");
     kp.views = io->views; kp.means3D = io->means3D; kp.opacities = io->opacities; kp.scales = io->scales;
     kp.rotations = io->rotations; kp.cov3D_precomp = io->cov3D_precomp; kp.colors_precomp = io->colors_precomp;
     kp.shs = io->shs;

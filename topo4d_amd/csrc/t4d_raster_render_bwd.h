@@ -118,7 +118,7 @@ __device__ __forceinline__ float reduce_moments_row(const float e, const float e
 }
 
 // which of the ten sums (slab entry / record order) lane i of a row holds after reduce_moments_row; -1 = none (or a duplicate)
-__device__ __forceinline__ int row10_index(const int lane)
+constexpr int row10_index(const int lane)
 {
     const int b0 = lane & 1, b1 = (lane >> 1) & 1, bank = (lane >> 2) & 3;
     if (!b0) {
@@ -129,6 +129,19 @@ __device__ __forceinline__ int row10_index(const int lane)
     }
     if (!b1) return bank == 0 ? 3 : (bank == 1 ? 7 : (bank == 2 ? 6 : 8));      // M20, sum w dL/dC1, C0, C2
     return bank == 0 ? 9 : -1;                                                  // sum w dL/dD (with a depth cotangent only)
+}
+
+// row10_index of the sixteen lanes of a row as a table of 4-bit entries (index + 1; 0 = none): what a lane reads at kernel entry.
+// Evaluated there as nested conditions it was forty vector instructions under exec masks, once per workgroup.
+template <bool NINE>          // NINE: as reduce_moments_row - the lane that would hold sum 9 holds nothing
+constexpr unsigned long long row10_table()
+{
+    unsigned long long t = 0ull;
+    for (int i = 0; i < 16; i++) {
+        const int s = row10_index(i);
+        t |= (unsigned long long)((NINE && s == 9) ? 0 : s + 1) << (4 * i);
+    }
+    return t;
 }
 
 // A slab entry's raw moments about the origin o become the record's sums about the splat centre; p = centre - o.
@@ -188,6 +201,7 @@ __device__ __forceinline__ uint32_t row_max_u32(uint32_t v)      // every lane g
 #define T4D_BWD_ATTR __attribute__((amdgpu_waves_per_eu(LAT ? 1 : T4D_BWD_NW, T4D_BWD_NW)))
 constexpr int kAcc = 10;                 // sums per (wave, staged splat) slab entry
 constexpr int kEmptySpan = 64;           // tiles per spare workgroup of the empty-tile share of cotangent_dot
+__host__ __device__ inline uint32_t empty_spans(const int T) { return (uint32_t)(T + kEmptySpan - 1) / kEmptySpan; }      // spare workgroups per view
 // LAT: the latency build (see k_render_fwd): one slab per DPP ROW instead of one per wave (82 KB of LDS: one workgroup per CU
 // is all such a launch has anyway), so two rows holding the same splat in the same step never meet and the conflict
 // detection and its branches disappear; the gradient arithmetic is predicated with selects instead of an exec-masked region,
@@ -201,6 +215,7 @@ constexpr int kEmptySpan = 64;           // tiles per spare workgroup of the emp
 template <bool DA, bool LAT, int SEGN, bool LONG = false>
 __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
 {
+    // T4D_REGION entry
     constexpr bool SEG = SEGN != 0;
     // a segment is ONE staged batch: the segmented build stages SEGN splats per round (128, or 64 for a one-view launch), the
     // whole-tile builds kBwdBatch (these shadow the globals inside the kernel)
@@ -237,11 +252,20 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
     auto &s_list = sh.list;
     constexpr int kNull = kBwdBatch;
 
+    // Whole tiles: the items are ordered by length, so a tile workgroup whose FIRST item is empty has nothing to do at all (a
+    // quarter of a config-2 launch, two thirds of config 4's): it leaves here, before the slab clear and before the kernel's
+    // wave-uniform state is set up.  The item is kept for the first round of the tile loop.
+    uint4 it = make_uint4(0u, 0u, 0u, 0u);
+    if (!SEG && blockIdx.x < kp.tile_blocks) {           // (tile_blocks <= V T: tile_grid)
+        it = kp.items[blockIdx.x];
+        if (it.z == 0u) return;
+    }
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, row = lane >> 4;      // wave: a scalar
     // without a depth cotangent the seventh value is not reduced (reduce_moments_row<true>): the lane that would hold sum 9 holds a
     // second copy of sum 3 and must stay out
-    const int my_slot = (!DA && row10_index(lane & 15) == 9) ? -1 : row10_index(lane & 15);
+    constexpr unsigned long long kSlotTable = row10_table<!DA>();
+    const int my_slot = (int)((uint32_t)(kSlotTable >> (4 * (lane & 15))) & 15u) - 1;
     const RowWeights rw = row_weights(lane);
     if (tid == 0) {
 #pragma unroll
@@ -251,9 +275,9 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
         // Spare workgroups behind the tile workgroups, launched only when the caller asked for <outputs, cotangents>: the EMPTY
         // tiles' share.  An empty tile shows the background at T = 1, so on black (Topo4D: helpers.py setup_camera, bg = 0)
         // there is nothing to add and the workgroup leaves at once; otherwise it sums bg . dL/dC over its kEmptySpan tiles.
-        const uint32_t spans = (uint32_t)(kp.T + kEmptySpan - 1) / kEmptySpan;
+        const uint32_t spans = empty_spans(kp.T);
         const uint32_t j = blockIdx.x - kp.tile_blocks;
-        const int v = (int)(j / spans), t0 = (int)(j % spans) * kEmptySpan;
+        const int v = (int)t4d_div(j, kp.div_spans), t0 = (int)(j - (uint32_t)v * spans) * kEmptySpan;
         const float *vb = kp.views + (size_t)v * T4D_VIEW_FLOATS + 35;
         const float b0 = vb[0], b1 = vb[1], b2 = vb[2];
         if (b0 == 0.f && b1 == 0.f && b2 == 0.f) return;
@@ -261,7 +285,7 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
         const float *dc = kp.dL_dcolor + (size_t)v * 3 * HWe;
         for (int t = t0; t < min(t0 + kEmptySpan, kp.T); t++) {
             if (kp.tile_count[(size_t)v * kp.T + t] != 0u) continue;           // workgroup-uniform
-            const int ty = t / kp.gx, tx = t - ty * kp.gx;
+            const int ty = (int)t4d_div((uint32_t)t, kp.div_gx), tx = t - ty * kp.gx;
             int ex, ey;
             tile_pixel(tid, tx, ty, ex, ey);
             float d = 0.f;
@@ -274,53 +298,63 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
         }
         return;
     }
-    uint4 it;
     if (SEG && !LONG) {
         it = kp.slot_tab[blockIdx.x];                // one slot per workgroup; most slots hold no segment
         if (it.w == 0u) return;
     }
-    for (int i = tid; i < kSlabs * (kBwdBatch + 1) * kAcc; i += kBlock) (&s_acc[0][0][0])[i] = 0.f;   // slabs are all-zero between batches
+    {
+        // slabs are all-zero between batches.  8 bytes per store at compile-time offsets: the counted loop over single floats was
+        // 20 stores and 60 vector instructions of index arithmetic per thread, once per workgroup - which is once per tile
+        constexpr int kPairs = kSlabs * (kBwdBatch + 1) * kAcc / 2;
+        static_assert(kAcc % 2 == 0, "slab entries are cleared as float2");
+        float2 *a2 = reinterpret_cast<float2 *>(&s_acc[0][0][0]);
+#pragma unroll
+        for (int i = 0; i < kPairs / kBlock; i++) a2[i * kBlock + tid] = make_float2(0.f, 0.f);
+        if (tid < kPairs % kBlock) a2[(kPairs / kBlock) * kBlock + tid] = make_float2(0.f, 0.f);
+    }
     // work items: the length-ordered tile list (whole tiles), ONE slot of the slot table (segments of a small launch), or a strided
     // walk over the mostly empty table of a big one-view launch (LONG)
     // (LONG segments: entries k, k + grid, ... of the compact list of live segments - the table itself is mostly empty, and a
     // strided walk over it, even with one gather per 64 slots, cost 20-40 us and dealt the segments out unevenly)
+    // T4D_REGION tile prologue
     for (uint32_t item = blockIdx.x; item < (SEG ? (LONG ? kp.status->live_segments : blockIdx.x + 1u) : (uint32_t)(kp.V * kp.T)); item += kp.tile_blocks) {
     if (SEG && LONG) it = kp.slot_tab[kp.live[item]];
-    if (!SEG) it = kp.items[item];
+    if (!SEG && item != blockIdx.x) it = kp.items[item];
     const int seg_j = SEG ? (int)(it.w & 0x7fffffffu) : 0;           // this item's segment: list positions [seg_j kSeg, (seg_j + 1) kSeg)
     const int v = (int)(it.x >> 20), t_ = (int)(it.x & 0xfffffu);
-    const int ty = t_ / kp.gx, tx = t_ - ty * kp.gx;
+    const int ty = (int)t4d_div((uint32_t)t_, kp.div_gx), tx = t_ - ty * kp.gx;
     const uint32_t off = it.y, n = it.z;
     if (n == 0) break;                                             // ordered by length: only empty tiles remain
     // a big one-view launch: the tiles the forward cut into segments (it wrote their slot-table entries with their snapshots) are
     // the segmented launch's
     if (!SEG && LONG && n >= kp.seg_min_pairs &&
         kp.slot_tab[(size_t)v * kp.slots_per_view + seg_slot0(kp, off, (uint32_t)t_)].w != 0u) continue;
-    const unsigned long long *keys = kp.keys + (size_t)v * kp.cap + off;
-    const float *r2_in = kp.cut_r2 + (size_t)v * kp.cap + off;
-    const float2 *xy = kp.xy + (size_t)v * kp.P;
-    const float4 *co = kp.conic_opacity + (size_t)v * kp.P;
-    const float *rgb = kp.shs ? kp.rgb + (size_t)v * kp.P * 3 : kp.colors_precomp + 3 * param_row0(kp, v);
-    const int32_t *radii = kp.radii + (size_t)v * kp.P;
-    const uint32_t *pair_off = kp.pair_off + (size_t)v * kp.P;
-    float2 *grad_pair = reinterpret_cast<float2 *>(kp.grad_pair) + (size_t)v * kp.cap * (kGP / 2);
-    const float *vr = kp.views + (size_t)v * T4D_VIEW_FLOATS;
+    const kp_kernarg_p kt = kernarg_kp();          // this tile's reads of the parameter block: scalar loads here, nothing kept across tiles
+    const unsigned long long *keys = kt->keys + (size_t)v * kt->cap + off;
+    const float *r2_in = kt->cut_r2 + (size_t)v * kt->cap + off;
+    const float2 *xy = kt->xy + (size_t)v * kt->P;
+    const float4 *co = kt->conic_opacity + (size_t)v * kt->P;
+    const float *rgb = kt->shs ? kt->rgb + (size_t)v * kt->P * 3 : kt->colors_precomp + 3 * param_row0(kp, v);
+    const int32_t *radii = kt->radii + (size_t)v * kt->P;
+    const uint32_t *pair_off = kt->pair_off + (size_t)v * kt->P;
+    float2 *grad_pair = reinterpret_cast<float2 *>(kt->grad_pair) + (size_t)v * kt->cap * (kGP / 2);
+    const float *vr = kt->views + (size_t)v * T4D_VIEW_FLOATS;
 
     int px, py;
     tile_pixel_bwd(tid, tx, ty, px, py);
-    const bool inside = px < kp.W && py < kp.H;
+    const bool inside = px < kt->W && py < kt->H;
     const v2f pix_f = { (float)px, (float)py };
-    const size_t HW = (size_t)kp.H * kp.W, pix = (size_t)py * kp.W + px;
+    const size_t HW = (size_t)kt->H * kt->W, pix = (size_t)py * kt->W + px;
 
     float T_final = 0.f, dp0 = 0.f, dp1 = 0.f, dp2 = 0.f, ddep = 0.f, dalp = 0.f;
     uint32_t last_contributor = 0;
     if (inside) {
-        T_final = kp.final_T[(size_t)v * HW + pix];
-        last_contributor = kp.n_contrib[(size_t)v * HW + pix];
-        const float *dc = kp.dL_dcolor + (size_t)v * 3 * HW;
+        T_final = kt->final_T[(size_t)v * HW + pix];
+        last_contributor = kt->n_contrib[(size_t)v * HW + pix];
+        const float *dc = kt->dL_dcolor + (size_t)v * 3 * HW;
         dp0 = dc[pix]; dp1 = dc[HW + pix]; dp2 = dc[2 * HW + pix];
-        if (DA && kp.dL_ddepth) ddep = kp.dL_ddepth[(size_t)v * HW + pix];
-        if (DA && kp.dL_dalpha) dalp = kp.dL_dalpha[(size_t)v * HW + pix];
+        if (DA && kt->dL_ddepth) ddep = kt->dL_ddepth[(size_t)v * HW + pix];
+        if (DA && kt->dL_dalpha) dalp = kt->dL_dalpha[(size_t)v * HW + pix];
     }
     const v2f dp01 = { dp0, dp1 };
     float T = T_final;
@@ -366,6 +400,7 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
         const uint32_t lo = (uint32_t)bi * kBwdBatch;
         const int cnt = (int)min((uint32_t)kBwdBatch, n - lo);
         const bool live = lo < tile_max;      // workgroup-uniform
+        // T4D_REGION staging
         // ---- stage ----
         if (tid < cnt) s_pair[tid] = 0xffffffffu;
         if (tid < kChunks * 64) {
@@ -407,6 +442,7 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
         }
         __syncthreads();
         if (live) {
+            // T4D_REGION masks + lists
             // which of the staged splats can touch which of this wave's four sub-blocks: the forward's test, on the forward's numbers
             unsigned long long mt[4][kChunks];
 #pragma unroll
@@ -468,6 +504,7 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
             // NEXT group are fetched while this group is processed, the colour records are fetched together with the
             // geometry records, and a step's slab value is read BEFORE its arithmetic and written back after it
             // (same wave, program order: the previous step's write is already ahead of the read in the LDS queue).
+            // T4D_REGION walk
             uint2 pk = *reinterpret_cast<const uint2 *>(list);
             for (int k = 0; k < nsteps; k += 4) {
                 const uint32_t ee[4] = { pk.x & 0xffffu, pk.x >> 16, pk.y & 0xffffu, pk.y >> 16 };
@@ -551,6 +588,7 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
             }
         }
         __syncthreads();
+        // T4D_REGION write-out
         // ---- write one record per pair (zeros when no wave touched it); fixed wave order => deterministic ----
         if (tid < cnt) {
             float a[10];
@@ -588,12 +626,14 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
         }
         __syncthreads();
     }
-    if (kp.tile_dot && seg_j == 0) {
+    // T4D_REGION tile epilogue
+    const kp_kernarg_p ke = kernarg_kp();
+    if (ke->tile_dot && seg_j == 0) {
         // The suffix recursion has reached the eye: acc = sum_i T_i alpha_i q_i + T_final bg . dL/dC = <colour, dL/dC> (+ <depth, dL/dD> +
         // <alpha, dL/dA>), this pixel's <outputs, cotangents> - the per-view sum costs one reduction per tile.
         // One float per wave, no barrier: a workgroup's lifetime is what this launch is made of.
         const float d = wave_sum_to_lane63(acc);
-        if (lane == 63) kp.tile_dot[((size_t)v * kp.T + t_) * 4 + wave] = d;
+        if (lane == 63) ke->tile_dot[((size_t)v * ke->T + t_) * 4 + wave] = d;
     }
     }
 }

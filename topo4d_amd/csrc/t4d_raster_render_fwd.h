@@ -137,7 +137,7 @@ __device__ __forceinline__ void pad_visit_list(unsigned short *list, const int c
 __device__ __forceinline__ void fill_empty_tile_row(const KP &kp, const uint32_t j)
 {
     const int tid = threadIdx.x;
-    const int v = (int)(j / (uint32_t)kp.gy), ty = (int)(j - (uint32_t)v * (uint32_t)kp.gy);
+    const int v = (int)t4d_div(j, kp.div_gy), ty = (int)(j - (uint32_t)v * (uint32_t)kp.gy);
     const uint32_t *tc = kp.tile_count + (size_t)v * kp.T + (size_t)ty * kp.gx;
     const float *vr = kp.views + (size_t)v * T4D_VIEW_FLOATS;
     const float b0 = vr[35], b1 = vr[36], b2 = vr[37];
@@ -202,6 +202,7 @@ __device__ __forceinline__ void fill_empty_tile_row(const KP &kp, const uint32_t
 template <bool LAT, int FB, int SEGN, bool PRUNE, bool LONG = false>
 __global__ __launch_bounds__(kBlock) T4D_FWD_ATTR void k_render_fwd(const KP kp)
 {
+    // T4D_REGION entry
     constexpr bool SEG = SEGN != 0;
     constexpr int kSeg = SEG ? SEGN : 128;           // (shadows the global default: this launch's segment length)
     constexpr int kU = LAT ? 8 : 4;                  // steps per group
@@ -243,9 +244,18 @@ __global__ __launch_bounds__(kBlock) T4D_FWD_ATTR void k_render_fwd(const KP kp)
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63, row = lane >> 4;
     // fill workgroups are spread evenly over the launch: workgroup b is one iff floor(b F / total) steps up at b
+    // (two quotients per workgroup: by the launch's multiplier where the products fit 32 bits - the host says so - else by the
+    // 64-bit divisions this always was)
     const uint32_t total_blocks = kp.tile_blocks + kp.fill_blocks;
-    const uint32_t fills_before = (uint32_t)(((unsigned long long)blockIdx.x * kp.fill_blocks) / total_blocks);
-    if ((uint32_t)(((unsigned long long)(blockIdx.x + 1u) * kp.fill_blocks) / total_blocks) != fills_before) {
+    uint32_t fills_before, fills_through;
+    if (kp.div_blocks_ok) {
+        fills_before = t4d_div(blockIdx.x * kp.fill_blocks, kp.div_blocks);
+        fills_through = t4d_div((blockIdx.x + 1u) * kp.fill_blocks, kp.div_blocks);
+    } else {
+        fills_before = (uint32_t)(((unsigned long long)blockIdx.x * kp.fill_blocks) / total_blocks);
+        fills_through = (uint32_t)(((unsigned long long)(blockIdx.x + 1u) * kp.fill_blocks) / total_blocks);
+    }
+    if (fills_through != fills_before) {
         fill_empty_tile_row(kp, fills_before);
         return;
     }
@@ -267,32 +277,34 @@ __global__ __launch_bounds__(kBlock) T4D_FWD_ATTR void k_render_fwd(const KP kp)
         }
     }
     if (tid < kRec / 4) reinterpret_cast<float *>(s_rec + kNull * kRec)[tid] = 0.f;
+    // T4D_REGION tile prologue
     for (uint32_t item = blockIdx.x - fills_before; item < (uint32_t)(kp.V * kp.T); item += kp.tile_blocks) {
     const uint4 it = kp.items[item];
     if (it.w == 0u) break;                           // ordered by length: only empty tiles remain, and those are not ours
     const int v = (int)(it.x >> 20), t_ = (int)(it.x & 0xfffffu);
-    const int ty = t_ / kp.gx, tx = t_ - ty * kp.gx;
+    const int ty = (int)t4d_div((uint32_t)t_, kp.div_gx), tx = t_ - ty * kp.gx;
     const uint32_t off = it.y, n = it.z;
     if (LONG && n >= kp.seg_min_pairs) continue;     // workgroup-uniform, before anything of this tile is touched
-    const unsigned long long *keys = kp.keys + (size_t)v * kp.cap + off;
-    float *r2_out = kp.cut_r2 + (size_t)v * kp.cap + off;
-    const float2 *xy = kp.xy + (size_t)v * kp.P;
-    const float4 *co = kp.conic_opacity + (size_t)v * kp.P;
-    const float *rgb = kp.shs ? kp.rgb + (size_t)v * kp.P * 3 : kp.colors_precomp + 3 * param_row0(kp, v);
+    const kp_kernarg_p kt = kernarg_kp();          // this tile's reads of the parameter block: scalar loads here, nothing kept across tiles
+    const unsigned long long *keys = kt->keys + (size_t)v * kt->cap + off;
+    float *r2_out = kt->cut_r2 + (size_t)v * kt->cap + off;
+    const float2 *xy = kt->xy + (size_t)v * kt->P;
+    const float4 *co = kt->conic_opacity + (size_t)v * kt->P;
+    const float *rgb = kt->shs ? kt->rgb + (size_t)v * kt->P * 3 : kt->colors_precomp + 3 * param_row0(kp, v);
     // segmented backward: this tile's snapshot slots (a tile of one segment keeps none: its replay starts at the list's end)
     float *snap = nullptr;
-    if (SEG && n > (uint32_t)kSeg && n >= kp.seg_min_pairs)
-        snap = kp.snap + ((size_t)v * kp.slots_per_view + seg_slot0(kp, off, (uint32_t)t_)) * (kSnapFloats * kBlock) + tid;
+    if (SEG && n > (uint32_t)kSeg && n >= kt->seg_min_pairs)
+        snap = kt->snap + ((size_t)v * kt->slots_per_view + seg_slot0(kp, off, (uint32_t)t_)) * (kSnapFloats * kBlock) + tid;
 
     int px, py;
     tile_pixel(tid, tx, ty, px, py);
-    const bool inside = px < kp.W && py < kp.H;
+    const bool inside = px < kt->W && py < kt->H;
     const v2f pix_f = { (float)px, (float)py };
     // The background colour is fetched HERE, into scalar registers.  Fetched where it is used - between the output stores - each
     // of its three loads was followed by a wait for ALL outstanding memory operations (gfx9 counts loads and stores in one
     // counter): store, wait for it, load, wait, store ... three dependent round trips at the end of every tile (config 4:
     // 1,143 -> 1,111 us).
-    const float *vr = kp.views + (size_t)v * T4D_VIEW_FLOATS;
+    const float *vr = kt->views + (size_t)v * T4D_VIEW_FLOATS;
     const float bg0 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(vr[35])));
     const float bg1 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(vr[36])));
     const float bg2 = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(vr[37])));
@@ -328,6 +340,7 @@ __global__ __launch_bounds__(kBlock) T4D_FWD_ATTR void k_render_fwd(const KP kp)
     }
 
     for (uint32_t b = 0; b < n; b += kFB) {
+        // T4D_REGION staging
         if (b != 0) {                                // a further batch: needed only while some pixel of the tile is unfinished
             if (lane == 0) s_wave_done[wave] = done_m == ~0ull ? 1u : 0u;
             __syncthreads();                         // (also: everyone has left the previous batch's records)
@@ -380,6 +393,7 @@ __global__ __launch_bounds__(kBlock) T4D_FWD_ATTR void k_render_fwd(const KP kp)
                 pre_r0 = rgb[3 * (size_t)g1]; pre_r1 = rgb[3 * (size_t)g1 + 1]; pre_r2 = rgb[3 * (size_t)g1 + 2];
             }
         }
+        // T4D_REGION masks + lists
         if (done_m == ~0ull) continue;               // wave-uniform; still takes part in the barriers above
         uint32_t last_e = 0xffffffffu;               // entry of the last splat blended in this batch
 #pragma clang loop unroll(disable)
@@ -420,6 +434,7 @@ __global__ __launch_bounds__(kBlock) T4D_FWD_ATTR void k_render_fwd(const KP kp)
 #pragma unroll
         for (int r = 0; r < 4; r++) pad_visit_list<kU>(s_list[wave][r], cnts[r], nsteps, lane, (unsigned short)(kNull * kRec));
         __builtin_amdgcn_wave_barrier();
+        // T4D_REGION walk
         const unsigned short *list = s_list[wave][row];
         for (int k = 0; k < nsteps; k += kU) {
             uint32_t e[kU];
@@ -488,6 +503,7 @@ __global__ __launch_bounds__(kBlock) T4D_FWD_ATTR void k_render_fwd(const KP kp)
             }
             if (done_m == ~0ull) break;
         }
+        // T4D_REGION tile epilogue
         if (SEG) {
             // the blend state in front of list position sub_lo + kSeg, for the backward segment that ends there.  A pixel that is
             // finished keeps its final state, which the backward takes from the final snapshot: a finished WAVE writes nothing.
@@ -504,20 +520,21 @@ __global__ __launch_bounds__(kBlock) T4D_FWD_ATTR void k_render_fwd(const KP kp)
         float *sp = snap + (size_t)((n - 1u) / kSeg) * (kSnapFloats * kBlock);
         sp[0] = T; sp[kBlock] = C0; sp[2 * kBlock] = C1; sp[3 * kBlock] = C2; sp[4 * kBlock] = D;
     }
+    const kp_kernarg_p ke = kernarg_kp();          // (again: what the output stores need was not kept across the walk)
     if (inside) {
-        const size_t HW = (size_t)kp.H * kp.W, pix = (size_t)py * kp.W + px;
+        const size_t HW = (size_t)ke->H * ke->W, pix = (size_t)py * ke->W + px;
         if (n != 0) {                                 // the backward never visits an empty tile: no replay state for it
-            kp.final_T[(size_t)v * HW + pix] = T;
-            kp.n_contrib[(size_t)v * HW + pix] = last_contributor;
+            ke->final_T[(size_t)v * HW + pix] = T;
+            ke->n_contrib[(size_t)v * HW + pix] = last_contributor;
         }
-        float *oc = kp.out_color + (size_t)v * 3 * HW;
+        float *oc = ke->out_color + (size_t)v * 3 * HW;
         oc[pix] = C0 + T * bg0;
         oc[HW + pix] = C1 + T * bg1;
         oc[2 * HW + pix] = C2 + T * bg2;
-        kp.out_depth[(size_t)v * HW + pix] = D;
+        ke->out_depth[(size_t)v * HW + pix] = D;
         // alpha = sum of the blend weights w_i = T_i - T_(i+1): the sum telescopes to 1 - T_final, which is at hand (upstream adds
         // the weights up one by one; one add per step less here, and one rounding instead of one per splat)
-        kp.out_alpha[(size_t)v * HW + pix] = 1.f - T;
+        ke->out_alpha[(size_t)v * HW + pix] = 1.f - T;
     }
     __syncthreads();                                 // staging buffers are reused by the next tile
     }
