@@ -16,6 +16,16 @@ four steps (89 = 4 x 22.25); the backward's four steps are separate blocks (a sa
 
     python tools/isa_fixed_work.py 'k_render_bwdILb0ELb0ELi0ELb0E' 'k_render_fwdILb0ELi192ELi0ELb0ELb0E' [--root DIR] [--json OUT]
     python tools/isa_fixed_work.py ... --before OLD.json        # before / after table (markdown)
+
+--dynamic LANES.jsonl adds, per kernel, a DYNAMIC estimate for the regions that run once per staged batch (staging, masks + lists,
+write-out): every basic block's vector count x the block's trip count per launch, trip counts from the counted launch of
+tools/count_lanes.py (profiles/r06_lanes.jsonl; --config / --opacity pick the record):
+  masks + lists   a block runs once per live wave-batch (`wave_batches`); a block that branches to itself (the padding loops: 64
+                  entries a trip) once as well;
+  staging,        once per wave that holds a staged splat: sum over tiles of ceil(n / 64) ~ pairs / 64 + nonempty_tiles / 2;
+  write-out       a block that branches to itself (the loop over the four waves' slabs) four times that.
+An UPPER estimate: both arms of every wave-uniform branch and every tail-duplicated copy of a block are counted as if each ran;
+what it is for is the DIFFERENCE between two trees, set against the difference SQ_INSTS_VALU measures.
 """
 import argparse, json, os, re, subprocess, sys, tempfile
 
@@ -58,14 +68,15 @@ def classify(op):
     return c
 
 
-def census(asm_lines, want, root, dump=None):
+def census(asm_lines, want, root, dump=None, lanes=None):
     start = next(i for i, l in enumerate(asm_lines) if re.match(r"^_Z\w*" + re.escape(want) + r"\w*:", l))
     end = next(i for i in range(start, len(asm_lines)) if asm_lines[i].startswith(".Lfunc_end"))
     name = asm_lines[start].split(":")[0]
     markers, order = {}, []          # file -> markers
     region = "entry"
     counts = {}
-    block, blocks = {"region": None, "vector": 0}, []
+    new_block = lambda label: {"region": None, "vector": 0, "label": label, "by_region": {}, "loops": False}
+    block, blocks = new_block(None), []
     for l in asm_lines[start + 1:end]:
         t = l.strip()
         if t.startswith(".loc"):
@@ -84,11 +95,13 @@ def census(asm_lines, want, root, dump=None):
             if dump:
                 print(t.split(";")[0].strip())
             blocks.append(block)
-            block = {"region": None, "vector": 0}
+            block = new_block(t.split(":")[0])
             continue
         if not t or t[0] in ";.":
             continue
         op = t.split()[0]
+        if op.startswith("s_cbranch") and t.split()[1:2] == [block["label"]]:
+            block["loops"] = True
         cl = classify(op)
         if not cl:
             continue
@@ -102,14 +115,56 @@ def census(asm_lines, want, root, dump=None):
         if "vector" in cl:
             block["vector"] += 1
             block["region"] = block["region"] or region
+            block["by_region"][region] = block["by_region"].get(region, 0) + 1
     blocks.append(block)
     body = max([b["vector"] for b in blocks if b["region"] == "walk"] or [0])
     res = {"kernel": name, "regions": {r: counts[r] for r in order}, "walk_block": body}
+    if lanes:
+        res["dynamic"] = dynamic_estimate(name, blocks, lanes)
     for l in asm_lines[end:end + 80]:                               # the resource summary behind the function
         m = re.match(r";\s*(NumVgprs|NumSgprs|ScratchSize|Occupancy|LDSByteSize):\s*(\d+)", l.strip())
         if m:
             res[m.group(1)] = int(m.group(2))
     return res
+
+
+PER_BATCH = ("staging", "masks + lists", "write-out")
+
+
+def dynamic_estimate(name, blocks, lanes):
+    """{region: {"blocks", "static", "trips", "vector_M"}} for the per-batch regions (see the module docstring)."""
+    side = lanes["bwd" if "k_render_bwd" in name else "fwd"]
+    staging_waves = lanes["pairs"] / 64.0 + side["nonempty_tiles"] / 2.0
+    out = {}
+    for r in PER_BATCH:
+        base = side["wave_batches"] if r == "masks + lists" else staging_waves
+        n = static = dyn = 0
+        for b in blocks:
+            v = b["by_region"].get(r, 0)
+            if v:
+                n += 1
+                static += v
+                dyn += v * base * (4 if b["loops"] and r == "write-out" else 1)
+        if n:
+            out[r] = {"blocks": n, "static": static, "trips": int(round(base)), "vector_M": round(dyn / 1e6, 2)}
+    return out
+
+
+def show_dynamic(res, before=None):
+    print("| region (per staged batch) | blocks | static vector | trips per launch | dynamic vector, M per launch |")
+    print("|---|---|---|---|---|")
+    tot = totb = 0.0
+    zero = {"blocks": 0, "static": 0, "trips": 0, "vector_M": 0.0}
+    for r in PER_BATCH:
+        a, b = res["dynamic"].get(r), ((before or {}).get("dynamic") or {}).get(r)
+        if a is None and b is None:
+            continue
+        a, b = a or zero, b or a or zero
+        cell = lambda k, f="%s": (f % a[k]) if a[k] == b[k] else (f + " -> " + f) % (b[k], a[k])
+        tot += a["vector_M"]; totb += b["vector_M"]
+        print("| " + r + " | " + cell("blocks") + " | " + cell("static") + " | " + cell("trips") + " | " + cell("vector_M", "%.2f") + " |")
+    print("| **per-batch regions** | | | | " + ("%.2f" % tot if tot == totb else "%.2f -> %.2f (%+.2f)" % (totb, tot, tot - totb)) + " |")
+    print()
 
 
 def show(res, before=None):
@@ -136,6 +191,8 @@ def show(res, before=None):
     print(", ".join("%s %s" % (k, (("%s -> %s" % (before.get(k), res[k])) if before and before.get(k) != res.get(k) else res[k]))
                     for k in extra if k in res))
     print()
+    if "dynamic" in res:
+        show_dynamic(res, before)
 
 
 def main():
@@ -147,6 +204,9 @@ def main():
     ap.add_argument("--dump", metavar="REGION", help="also list the instructions of this region (with every block label)")
     ap.add_argument("--json", help="write the counts here")
     ap.add_argument("--before", help="counts of an earlier tree (--json): print before -> after")
+    ap.add_argument("--dynamic", metavar="LANES.jsonl", help="also estimate the per-batch regions' dynamic vector count from this counted launch")
+    ap.add_argument("--config", default="C2", help="--dynamic: the record's config (default C2)")
+    ap.add_argument("--opacity", default="A", help="--dynamic: the record's opacity scenario (default A)")
     a = ap.parse_args()
     root = os.path.abspath(a.root)
     if a.asm:
@@ -163,7 +223,11 @@ def main():
             lines = open(out).read().split("\n")
             if a.keep_asm:
                 open(a.keep_asm, "w").write("\n".join(lines))
-    results = [census(lines, k, root, a.dump) for k in a.kernels]
+    lanes = None
+    if a.dynamic:
+        recs = [json.loads(l) for l in open(a.dynamic) if l.strip()]
+        lanes = next(r for r in recs if r["config"] == a.config and r["opacity"] == a.opacity)
+    results = [census(lines, k, root, a.dump, lanes) for k in a.kernels]
     before = {r["kernel"]: r for r in json.load(open(a.before))} if a.before else {}
     for r in results:
         show(r, before.get(r["kernel"]))

@@ -15,12 +15,16 @@ else
   B="python $ROOT/bench.py --no-cpu-baseline --no-extras --frames-in-flight 1"     # kernels alone on the chip: per-kernel figures
   LONG="--steps 20 --warmup 3"; SHORT="--steps 2 --warmup 1"
 fi
-( cd $ROOT && $B $LONG "$@" ) > /dev/null 2>&1      # (first run outside the profiler: pages the image in)
-rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/trace -o t -- $B $LONG "$@" > $OUT/bench_trace.log 2>&1
-rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU --output-format csv -d $RAW/pmc1 -o p -- $B $SHORT "$@" > $OUT/bench_pmc1.log 2>&1
-rocprofv3 --kernel-trace --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE --output-format csv -d $RAW/pmc2 -o p -- $B $SHORT "$@" > $OUT/bench_pmc2.log 2>&1
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $RAW/pmc3 -o p -- $B $SHORT "$@" > $OUT/bench_pmc3.log 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $RAW/pmc4 -o p -- $B $SHORT "$@" > $OUT/bench_pmc4.log 2>&1
+# Every pass runs under its own time limit and only if the one before it ended well: after a fault or a hang nothing more is started.
+# The counters are collected in passes of their own, without any tracing; kernel times come from the trace pass.
+T="timeout -k 10 ${PROF_PASS_LIMIT:-300}"
+PMC="rocprofv3 --output-format csv"
+( cd $ROOT && $T $B $LONG "$@" ) > /dev/null 2>&1 &&      # (first run outside the profiler: pages the image in)
+$T rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/trace -o t -- $B $LONG "$@" > $OUT/bench_trace.log 2>&1 &&
+$T $PMC --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU -d $RAW/pmc1 -o p -- $B $SHORT "$@" > $OUT/bench_pmc1.log 2>&1 &&
+$T $PMC --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE -d $RAW/pmc2 -o p -- $B $SHORT "$@" > $OUT/bench_pmc2.log 2>&1 &&
+$T $PMC --pmc FETCH_SIZE -d $RAW/pmc3 -o p -- $B $SHORT "$@" > $OUT/bench_pmc3.log 2>&1 &&
+$T $PMC --pmc WRITE_SIZE -d $RAW/pmc4 -o p -- $B $SHORT "$@" > $OUT/bench_pmc4.log 2>&1 || { echo "prof.sh: a pass failed (status $?), see $OUT/*.log"; exit 1; }
 python $ROOT/tools/summarize_prof.py $RAW $OUT > /dev/null
 python - <<PY
 import json, sys

@@ -49,6 +49,7 @@
 #include "../../include/topo4d_raster.h"
 #include "t4d_activations.h"
 #include "t4d_tile_div.h"
+#include "t4d_raster_visit_pad.h"
 
 #define T4D_EXPORT extern "C" __attribute__((visibility("default")))
 

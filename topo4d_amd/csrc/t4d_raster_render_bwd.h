@@ -454,7 +454,11 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
 #pragma unroll
                 for (int r = 0; r < 4; r++) mt[r][c2] = mc[r];
             }
-            int nsteps = 0, cnts[4];
+            // every row walks as many steps as the wave's longest list, four at a time (and the walk fetches one group ahead): the
+            // lists are null wherever no entry is written.  The block sits 8 bytes off a 16-byte boundary: 8-byte stores.
+            static_assert(offsetof(Shared, list) % 8 == 0 && (sizeof(unsigned short) * 4 * kListStride) % 8 == 0, "8-byte stores");
+            prefill_visit_lists<4 * kListStride * 2, uint2>(&s_list[wave][0][0], lane, (unsigned short)(kNull * kEnt));
+            int nsteps = 0;
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 unsigned long long m[kChunks];
@@ -466,11 +470,9 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
                     if (row_max[r] <= base) m[c2] = 0;
                     else if (row_max[r] - base < 64u) m[c2] &= (1ull << (row_max[r] - base)) - 1ull;
                 }
-                cnts[r] = build_visit_list<kChunks, true, kEnt>(m, s_list[wave][r], lane);   // back to front
-                nsteps = max(nsteps, cnts[r]);
+                build_visit_list<kChunks, true, kEnt>(m, s_list[wave][r], lane);   // back to front
+                nsteps = uniform_max(nsteps, visit_count(m));
             }
-#pragma unroll
-            for (int r = 0; r < 4; r++) pad_visit_list(s_list[wave][r], cnts[r], nsteps, lane, (unsigned short)(kNull * kEnt));
             __builtin_amdgcn_wave_barrier();
             // Steps in which two rows of this wave hold the SAME splat (about one in five) must not do their slab updates in
             // one instruction; they are found here, 64 steps per pass, so that the replay only tests a scalar bit.
@@ -600,16 +602,18 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
             for (int w = 0; w < 4; w++) {
                 // the wave's raw moments (the latency build: of its four rows' slabs), then their shift from the centre of the
                 // wave's 8x8 block to the splat centre; both differences below are exact
+                // (the first slab is taken as it is, not added to zero: 0 + x is an instruction the compiler must keep for x = -0,
+                // ten per wave and trip.  A slab starts at +0 and only ever has sums added to it, so it never holds -0; and a
+                // zero's sign could not reach a record anyway: everything below is added to a[], which starts at +0)
                 float m[10];
-#pragma unroll
-                for (int k = 0; k < 10; k++) m[k] = 0.f;
 #pragma unroll
                 for (int s = 0; s < kSlabs / 4; s++) {
                     float2 *src = reinterpret_cast<float2 *>(&s_acc[w * (kSlabs / 4) + s][tid][0]);
 #pragma unroll
                     for (int k = 0; k < 5; k++) {
                         const float2 b2 = src[k];
-                        m[2 * k] += b2.x; m[2 * k + 1] += b2.y;
+                        if (s == 0) { m[2 * k] = b2.x; m[2 * k + 1] = b2.y; }
+                        else { m[2 * k] += b2.x; m[2 * k + 1] += b2.y; }
                         src[k] = make_float2(0.f, 0.f);              // leave the slab zeroed for the next batch
                     }
                 }

@@ -128,6 +128,45 @@ __device__ __forceinline__ void pad_visit_list(unsigned short *list, const int c
     for (int p2 = cnt + lane; p2 < nsteps + GROUP - 1; p2 += 64) list[p2] = null_entry;
 }
 
+// The render kernels pad BEFORE they build: a wave's four row lists are one contiguous block of BYTES bytes, and it is filled with
+// the null entry by a few wide stores (VEC = 16 or 8 bytes per lane, whatever the block's alignment allows; where they go:
+// t4d_raster_visit_pad.h) ahead of build_visit_list, whose entries then overwrite the front of every row.  A wave's LDS
+// operations execute in program order, so the lists read back as pad_visit_list left them - and null beyond - for 3-4 vector
+// instructions per wave and batch instead of four loops of six to seven, and the rows' lengths are no longer needed per lane.
+template <int BYTES, typename VEC>
+__device__ __forceinline__ void prefill_visit_lists(unsigned short *lists, const int lane, const unsigned short null_entry)
+{
+    static_assert(sizeof(VEC) % 4 == 0, "filled as 32-bit words");
+    VEC val;
+#pragma unroll
+    for (int k = 0; k < (int)sizeof(VEC) / 4; k++) reinterpret_cast<uint32_t *>(&val)[k] = (uint32_t)null_entry * 0x10001u;
+#pragma unroll
+    for (int k = 0; k < visit_prefill_stores<BYTES, (int)sizeof(VEC)>(); k++) {
+        int offset = 0;
+        if (visit_prefill_store<BYTES, (int)sizeof(VEC)>(k, lane, offset))
+            *reinterpret_cast<VEC *>(reinterpret_cast<unsigned char *>(lists) + offset) = val;
+    }
+}
+
+// maximum of two wave-uniform counts ON THE SCALAR UNIT.  Written as max(max(a, b), c) the compiler selects v_max3_u32 for scalar
+// operands too, and the walk's trip count then lives in a vector register: a vector compare per group of steps.
+__device__ __forceinline__ int uniform_max(const int a, const int b)
+{
+    int r;
+    asm("s_max_u32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc");
+    return r;
+}
+
+// steps of a row's list: what build_visit_list returns, from the masks alone (scalar instructions)
+template <int NCHUNK>
+__device__ __forceinline__ int visit_count(const unsigned long long (&m)[NCHUNK])
+{
+    int cnt = 0;
+#pragma unroll
+    for (int c = 0; c < NCHUNK; c++) cnt += __builtin_popcountll(m[c]);
+    return cnt;
+}
+
 // The pixels of EMPTY tiles (config 4: two thirds of 2048^2): background colour, zero depth, zero alpha - 20 bytes per pixel that
 // no splat ever touches.  Written tile by tile (a tile's row is 64 bytes of a plane, a wave's store 32) they went to HBM at
 // 2.5 TB/s and made up a third of k_render_fwd at config 4 (803 us for an all-empty launch).  Here one workgroup takes a whole
@@ -236,7 +275,7 @@ __global__ __launch_bounds__(kBlock) T4D_FWD_ATTR void k_render_fwd(const KP kp)
         s_sort = reinterpret_cast<unsigned long long *>(s_raw);
     } else {
         __shared__ __attribute__((aligned(16))) unsigned char s_rec_[(kFB + 1) * kRec];
-        __shared__ __attribute__((aligned(8))) unsigned short s_list_[4][4][kListStride];
+        __shared__ __attribute__((aligned(16))) unsigned short s_list_[4][4][kListStride];      // (16: prefill_visit_lists)
         __shared__ unsigned long long s_sort_[LAT ? kSortLdsCap : 1];
         s_rec = s_rec_; s_list = s_list_; s_sort = s_sort_;
     }
@@ -425,14 +464,15 @@ __global__ __launch_bounds__(kBlock) T4D_FWD_ATTR void k_render_fwd(const KP kp)
 #pragma unroll
             for (int r = 0; r < 4; r++) m[r][c4] = mc[r];
         }
-        int nsteps = 0, cnts[4];
+        // every row walks as many steps as the wave's longest list, kU at a time: the lists are null wherever no entry is written
+        static_assert(kListStride >= kSub + kU - 1, "a full list and its padding fit a row");
+        prefill_visit_lists<4 * kListStride * 2, uint4>(&s_list[wave][0][0], lane, (unsigned short)(kNull * kRec));
+        int nsteps = 0;
 #pragma unroll
         for (int r = 0; r < 4; r++) {                // one visit list per sub-block
-            cnts[r] = build_visit_list<kSubChunks, false, kRec>(m[r], s_list[wave][r], lane, sub * kSubChunks);
-            nsteps = max(nsteps, cnts[r]);
+            build_visit_list<kSubChunks, false, kRec>(m[r], s_list[wave][r], lane, sub * kSubChunks);
+            nsteps = uniform_max(nsteps, visit_count(m[r]));
         }
-#pragma unroll
-        for (int r = 0; r < 4; r++) pad_visit_list<kU>(s_list[wave][r], cnts[r], nsteps, lane, (unsigned short)(kNull * kRec));
         __builtin_amdgcn_wave_barrier();
         // T4D_REGION walk
         const unsigned short *list = s_list[wave][row];
