@@ -451,6 +451,32 @@ size_t t4d_texture_fill_scratch_bytes(int32_t h, int32_t w, int32_t c);
 int t4d_texture_fill(const uint8_t *image, const uint8_t *valid, const uint8_t *domain, int32_t h, int32_t w, int32_t c,
                      uint8_t *out_image, uint8_t *out_filled, void *scratch, size_t scratch_bytes, void *hip_stream);
 
+/* Tracking drift between two frames' UV textures: a census block matcher (topo4d_amd/drift.py, csrc/t4d_drift.hip), under the
+ * conventions of the texture family above.  luma_a, luma_b uint8 [h,w] (drift.luma: (77 R + 150 G + 29 B + 128) >> 8); valid_a,
+ * valid_b uint8 [h,w], non-zero = the texel holds a photograph; labels uint8 [h,w], 0 = no island, one layout for both frames;
+ * block B even in 8..64, stride S in 1..B, radius R in 0..16, min_count in 1..B^2; out int32 [nby,nbx,16].  Everything is integer
+ * arithmetic, so the table is a pure function of the inputs; tests/drift_ref.py restates the rule in numpy.
+ * Census: for texel p the 48 neighbours p + (j, i), j (rows) and i (columns) in -3..3 in row-major order without the centre; the
+ * k-th sets bit k of the 64-bit word C(p) when L(neighbour) < L(p).  p is census-valid in a frame when all 49 texels lie inside the
+ * image and are valid in that frame and labels[p] != 0; otherwise C(p) is unused.
+ * Blocks: block (by, bx) covers rows by S .. by S + B - 1 and columns bx S .. bx S + B - 1; only blocks wholly inside the image
+ * exist: nby = (h - B) / S + 1 and nbx = (w - B) / S + 1 in integer division, none when h < B or w < B (T4D_OK, nothing launched).
+ * Cost: for each d = (dy, dx) in [-R, R]^2, n(d) counts the block's texels p with p census-valid in a, p + d inside the image and
+ * census-valid in b, and labels[p] == labels[p + d]; c(d) is the sum over them of popcount(Ca(p) ^ Cb(p + d)).  d is admissible
+ * when n(d) >= min_count.
+ * Order: d1 is better than d2 when c1 n2 < c2 n1 (64-bit integers: the smaller c / n); ties go to the smaller dy^2 + dx^2, then the
+ * smaller dy, then the smaller dx.  The best is the first admissible d of that order; the second is the first admissible d whose
+ * Chebyshev distance max(|dy - dy_best|, |dx - dx_best|) from the best exceeds 1.
+ * Output per block: dy, dx, then (c, n) of the best, of (dy - 1, dx), of (dy + 1, dx), of (dy, dx - 1), of (dy, dx + 1) and of the
+ * second, then two zeros.  (0, 0) stands for a neighbour outside [-R, R]^2 or inadmissible and for a second that does not exist;
+ * a block without an admissible d is all zeros.
+ * Scratch: t4d_drift_scratch_bytes(h, w, block, stride, radius) (0 and a message for a bad shape or option; the census words of
+ * both frames); T4D_ERR_STATE_SIZE when it is smaller.  The scratch must be aligned to 8 bytes. */
+size_t t4d_drift_scratch_bytes(int32_t h, int32_t w, int32_t block, int32_t stride, int32_t radius);
+int t4d_drift_match(const uint8_t *luma_a, const uint8_t *valid_a, const uint8_t *luma_b, const uint8_t *valid_b, const uint8_t *labels,
+                    int32_t h, int32_t w, int32_t block, int32_t stride, int32_t radius, int32_t min_count, int32_t *out, void *scratch,
+                    size_t scratch_bytes, void *hip_stream);
+
 /* Lossless PNG encoder for a device image (write_texture(..., encoder="gpu"): the last CPU step of save_mesh, helpers.py:953-960).
  * image [h,w,c] on the device, uint8 (is_float32 = 0) or float32 (is_float32 = 1, quantised exactly like numpy's
  * (x*255).astype(np.uint8) on x86-64: truncation toward zero to int32, low byte kept, NaN -> 0); c in {1, 3, 4} gives colour

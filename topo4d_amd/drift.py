@@ -1,0 +1,364 @@
+"""
+Tracking drift between two frames, measured by matching their UV textures on the GPU (csrc/t4d_drift.hip).
+
+    luma(image)                                               uint8 [h,w]: (77 R + 150 G + 29 B + 128) >> 8
+    match(image_a, valid_a, image_b, valid_b, labels, ...)    -> int32 [nby,nbx,16]: per block the best displacement and its costs
+    flow(table, radius, ratio)                                -> (d float64 [nby,nbx,2], kept bool [nby,nbx]): sub-texel (dy, dx)
+    metric(d, kept, pos, labels, block, stride)               -> (drift float64 [nby,nbx] in surface units, kept)
+    drift_stats(texels, units, kept, unit)                    blocks, kept, kept_fraction and mean, median, p90, max
+    frame_pair(obj_a, tex_a, valid_a, tex_b, valid_b, level)  the steps above for two frames' textures
+
+One topology is tracked through a sequence, so with perfect tracking a pore or a mole stays on the same texel of every frame's
+projected texture (projtex: face_proj.png).  The displacement between two frames' textures, taken through the surface's metric, is
+therefore how far the mesh slid along the skin: the number that neither the photometric score (each frame's own texture on its own
+mesh) nor the scan score (distances along the normal) can see.
+
+match compares census words (7 x 7, 48 bits: which neighbours are darker than the texel), so a change of exposure or shading
+between the frames does not matter; a texel takes part only if its whole census window is valid and inside a UV island, and a pair
+only if both texels carry one island label.  include/topo4d_raster.h states the rule and the layout of the table exactly; it is
+integer arithmetic, and tests/drift_ref.py restates it, flow and metric in numpy bit for bit.
+
+flow keeps a block when it has a best and a second candidate, the second's c > 0 (a flat block, whose costs are all zero, is
+never kept), q_best <= ratio q_second with q = c / n (the best stands out), and max(|dy|, |dx|) < radius (a best on the rim of
+the search range is a clipped match).  Per axis the sub-texel offset is (q- - q+) / (2 ((q- - 2 q0) + q+)), clamped to +-0.5,
+from the costs q-, q+ of the best's two neighbours on that axis; it applies when both are admissible and the denominator is
+positive, and is 0 otherwise.  All of it is float64 torch arithmetic in that order.
+
+metric takes the central differences Jx, Jy of surface_maps' pos over +-1 texel at the block's centre texel
+(y0 + B/2, x0 + B/2), in float64: the drift is |Jx dx + Jy dy|, with |v| = sqrt((v0 v0 + v1 v1) + v2 v2).  A block whose five
+texels do not share one non-zero label is dropped from kept.
+
+Known limits: an expression that stretches the skin changes the texture itself, not only its place; census tolerates shading
+changes but not wrinkles.  A drift beyond `radius` texels at the chosen level is dropped, not measured.  The defaults (block 32,
+stride 16, radius 8, ratio 0.8, level 2) are conventional, not tuned on a capture.  There is no CPU path.
+
+`python -m topo4d_amd.drift -e EXP -s SEQ -od DIR [--frames 1-10] [--texture face_proj.png] [--ref first|previous] [--level 2]
+[--block 32] [--stride S] [--radius 8] [--ratio 0.8] [--unit 1000] [--save_fields]` works over an output tree that exists (the
+reference's too) and writes <od>/<exp>/<seq>/drift.json: the options, per frame the pair and its statistics, and a summary.  A
+frame's validity is face_proj_weight.png > 0 where that file exists and texfinish.coverage_from_obj of its face.obj otherwise
+("valid_from").  --ref first measures the drift accumulated since the first selected frame, --ref previous the slip from frame to
+frame; --save_fields also writes %06d/face_drift.npz (table, d, kept, drift).  `evaluate --drift` puts the same dictionary under
+"drift" in eval.json.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+from typing import Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import ptr
+
+MIN_BLOCK, MAX_BLOCK, MAX_RADIUS = 8, 64, 16
+TABLE_WIDTH = 16
+TEXTURE_FILE = "face_proj.png"
+WEIGHT_FILE = "face_proj_weight.png"
+FIELDS_NAME = "face_drift.npz"
+DEFAULTS = dict(texture=TEXTURE_FILE, ref="first", level=2, block=32, stride=None, radius=8, ratio=0.8, unit=1000.0)
+
+
+def check_options(block=32, stride=None, radius=8, min_count=None) -> Tuple[int, int, int, int]:
+    """(block, stride, radius, min_count) with the defaults filled in (stride = block // 2, min_count = block^2 // 2); ValueError
+    for what t4d_drift_match would refuse (callable without a device)."""
+    block, radius = int(block), int(radius)
+    if not MIN_BLOCK <= block <= MAX_BLOCK or block % 2:
+        raise ValueError(f"block must be even and in [{MIN_BLOCK}, {MAX_BLOCK}], got {block}")
+    stride = block // 2 if stride is None else int(stride)
+    if not 1 <= stride <= block:
+        raise ValueError(f"stride must be in [1, block = {block}], got {stride}")
+    if not 0 <= radius <= MAX_RADIUS:
+        raise ValueError(f"radius must be in [0, {MAX_RADIUS}], got {radius}")
+    min_count = block * block // 2 if min_count is None else int(min_count)
+    if not 1 <= min_count <= block * block:
+        raise ValueError(f"min_count must be in [1, block^2 = {block * block}], got {min_count}")
+    return block, stride, radius, min_count
+
+
+def blocks(h: int, w: int, block: int, stride: int) -> Tuple[int, int]:
+    """(nby, nbx): the blocks that lie wholly inside an [h,w] image."""
+    return ((h - block) // stride + 1 if h >= block else 0), ((w - block) // stride + 1 if w >= block else 0)
+
+
+def _image(image, what: str) -> Tuple[int, int]:
+    if not isinstance(image, torch.Tensor) or image.dtype != torch.uint8 or image.dim() not in (2, 3):
+        raise ValueError(f"{what} must be a uint8 [h,w] or [h,w,c] tensor")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    c = 1 if image.dim() == 2 else int(image.shape[2])
+    if h < 1 or w < 1 or c not in (1, 3, 4):
+        raise ValueError(f"{what} must be [h,w] or [h,w,c] with h, w >= 1 and c in (1, 3, 4); got {tuple(image.shape)}")
+    return h, w
+
+
+def _mask(mask, what: str, h: int, w: int, dtypes=(torch.uint8, torch.bool)) -> None:
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in dtypes or tuple(mask.shape) != (h, w):
+        kinds = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise ValueError(f"{what} must be a {kinds} [{h},{w}] tensor, got {getattr(mask, 'dtype', type(mask))} "
+                         f"{list(getattr(mask, 'shape', ()))}")
+
+
+def _on_device(t: torch.Tensor, what: str, device=None) -> torch.Tensor:
+    if not t.is_cuda or (device is not None and t.device != device):
+        raise RuntimeError(f"topo4d_amd has no CPU path: {what} must live on {'a' if device is None else 'the same'} HIP device")
+    return (t.to(torch.uint8) if t.dtype == torch.bool else t).contiguous()
+
+
+def luma(image: torch.Tensor) -> torch.Tensor:
+    """uint8 [h,w]: (77 R + 150 G + 29 B + 128) >> 8 of a uint8 [h,w,3] image (RGBA: its first three channels), in integer torch
+    ops; a one-channel image is its own luma."""
+    h, w = _image(image, "image")
+    if image.dim() == 2 or image.shape[2] == 1:
+        return image.reshape(h, w).contiguous()
+    rgb = image[..., :3].to(torch.int32)
+    return ((77 * rgb[..., 0] + 150 * rgb[..., 1] + 29 * rgb[..., 2] + 128) >> 8).to(torch.uint8).contiguous()
+
+
+def match(image_a: torch.Tensor, valid_a: torch.Tensor, image_b: torch.Tensor, valid_b: torch.Tensor, labels: torch.Tensor,
+          block: int = 32, stride: int = None, radius: int = 8, min_count: int = None) -> torch.Tensor:
+    """int32 [nby,nbx,16] on the device: per block of `block`^2 texels of frame a, every `stride` texels, the displacement
+    (dy, dx) in [-radius, radius]^2 at which frame b's census words differ least, with the costs flow needs
+    (include/topo4d_raster.h states the rule and the table, tests/drift_ref.py restates it).  images uint8 [h,w] or [h,w,c];
+    valid_a, valid_b uint8 or bool [h,w], non-zero = the texel holds a photograph; labels uint8 [h,w] (projtex.island_labels;
+    0: no island).  A shape without a whole block gives an empty table."""
+    h, w = _image(image_a, "image_a")                          # argument errors first, with or without a device
+    if _image(image_b, "image_b") != (h, w):
+        raise ValueError(f"image_b {tuple(image_b.shape)} does not match image_a's [{h},{w}]")
+    _mask(valid_a, "valid_a", h, w)
+    _mask(valid_b, "valid_b", h, w)
+    _mask(labels, "labels", h, w, dtypes=(torch.uint8,))
+    block, stride, radius, min_count = check_options(block, stride, radius, min_count)
+    img_a = _on_device(image_a, "image_a")
+    dev = img_a.device
+    img_b, val_a, val_b = _on_device(image_b, "image_b", dev), _on_device(valid_a, "valid_a", dev), _on_device(valid_b, "valid_b", dev)
+    lab = _on_device(labels, "labels", dev)
+    nby, nbx = blocks(h, w, block, stride)
+    if nby == 0 or nbx == 0:
+        return torch.zeros(nby, nbx, TABLE_WIDTH, dtype=torch.int32, device=dev)
+    nbytes = int(_lib.load().t4d_drift_scratch_bytes(h, w, block, stride, radius))
+    if nbytes == 0:
+        raise _lib.error("t4d_drift_scratch_bytes", exc=ValueError)
+    with torch.cuda.device(dev):
+        la, lb = luma(img_a), luma(img_b)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(nby, nbx, TABLE_WIDTH, dtype=torch.int32, device=dev)
+        _lib.call("t4d_drift_match", ptr(la), ptr(val_a), ptr(lb), ptr(val_b), ptr(lab), h, w, block, stride, radius, min_count,
+                  ptr(out), ptr(scratch), nbytes, _lib.stream(dev))
+    return out
+
+
+def flow(table: torch.Tensor, radius: int, ratio: float = 0.8) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(d float64 [nby,nbx,2] = (dy, dx) with its sub-texel offset, kept bool [nby,nbx]) of match's table, by the module's rule:
+    float64 torch operations in the order the docstring states."""
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 3 or table.shape[2] != TABLE_WIDTH:
+        raise ValueError(f"table must be match's int32 [nby,nbx,{TABLE_WIDTH}] tensor")
+    radius, ratio = int(radius), float(ratio)
+    if not 0 <= radius <= MAX_RADIUS or not 0.0 < ratio <= 1.0:
+        raise ValueError(f"flow: radius must be in [0, {MAX_RADIUS}] and ratio in (0, 1], got {radius}, {ratio}")
+    t = table.to(torch.float64)
+    one = torch.ones((), dtype=torch.float64, device=table.device)
+    q = lambda k: t[..., k] / torch.maximum(t[..., k + 1], one)          # c / n, 0 where there is none
+    has = lambda k: table[..., k + 1] > 0
+    q0, q2 = q(2), q(12)
+    kept = has(2) & has(12) & (table[..., 12] > 0) & (q0 <= ratio * q2)
+    kept &= torch.maximum(table[..., 0].abs(), table[..., 1].abs()) < radius
+    d = []
+    for axis, k in ((0, 4), (1, 8)):
+        qm, qp = q(k), q(k + 2)
+        den = (qm - 2.0 * q0) + qp
+        ok = has(2) & has(k) & has(k + 2) & (den > 0.0)
+        off = ((qm - qp) / (2.0 * torch.where(ok, den, one))).clamp(-0.5, 0.5)
+        d.append(t[..., axis] + torch.where(ok, off, torch.zeros_like(off)))
+    return torch.stack(d, dim=-1), kept
+
+
+def length(d: torch.Tensor) -> torch.Tensor:
+    """float64 [nby,nbx]: sqrt(dy dy + dx dx) of flow's d, the drift in texels."""
+    return torch.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1])
+
+
+def metric(d: torch.Tensor, kept: torch.Tensor, pos: torch.Tensor, labels: torch.Tensor, block: int, stride: int = None):
+    """(drift float64 [nby,nbx], kept bool [nby,nbx]): flow's displacement in the units of pos (projtex.surface_maps' map of the
+    same size as the matched textures) by the module's rule; a block whose centre texel and its four neighbours do not share one
+    non-zero label is dropped from kept."""
+    block, stride, _, _ = check_options(block, stride)
+    if not isinstance(pos, torch.Tensor) or pos.dim() != 3 or pos.shape[2] != 3 or not pos.is_floating_point():
+        raise ValueError("pos must be a float [h,w,3] tensor")
+    h, w = int(pos.shape[0]), int(pos.shape[1])
+    _mask(labels, "labels", h, w, dtypes=(torch.uint8,))
+    nby, nbx = blocks(h, w, block, stride)
+    if not isinstance(d, torch.Tensor) or tuple(d.shape) != (nby, nbx, 2) or tuple(kept.shape) != (nby, nbx):
+        raise ValueError(f"d and kept must be flow's [{nby},{nbx},2] and [{nby},{nbx}] for this size, block and stride")
+    dev = d.device
+    cy = (torch.arange(nby, device=dev) * stride + block // 2)[:, None].expand(nby, nbx)
+    cx = (torch.arange(nbx, device=dev) * stride + block // 2)[None, :].expand(nby, nbx)
+    p = pos.to(torch.float64)
+    jx = (p[cy, cx + 1] - p[cy, cx - 1]) * 0.5
+    jy = (p[cy + 1, cx] - p[cy - 1, cx]) * 0.5
+    v = jx * d[..., 1:2] + jy * d[..., 0:1]
+    drift = torch.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2])
+    lab = labels[cy, cx]
+    same = (lab != 0) & (labels[cy, cx + 1] == lab) & (labels[cy, cx - 1] == lab) & (labels[cy + 1, cx] == lab) & (labels[cy - 1, cx] == lab)
+    return drift, kept & same
+
+
+def drift_stats(texels: torch.Tensor, units: torch.Tensor, kept: torch.Tensor, unit: float = 1.0) -> dict:
+    """blocks, kept, kept_fraction and, over the kept blocks, mean, median (the lower one), p90 and max of `units` x unit and, as
+    *_texels, of `texels`; a field without a kept block has the first three only (scanbake.displacement_stats' conventions)."""
+    m = kept.reshape(-1)
+    total, n = int(m.numel()), int(m.sum())
+    out = {"blocks": total, "kept": n, "kept_fraction": n / total if total else 0.0}
+    if n == 0:
+        return out
+    for values, suffix in ((units.reshape(-1)[m].to(torch.float64) * unit, ""), (texels.reshape(-1)[m].to(torch.float64), "_texels")):
+        srt = torch.sort(values).values
+        picks = torch.stack([srt[(n - 1) // 2], srt[min(n - 1, -(-9 * n // 10) - 1)], srt[-1], values.sum()]).cpu().tolist()
+        out["mean" + suffix] = picks[3] / n
+        out["median" + suffix], out["p90" + suffix], out["max" + suffix] = picks[0], picks[1], picks[2]
+    return out
+
+
+def frame_pair(obj_a, tex_a: torch.Tensor, valid_a: torch.Tensor, tex_b: torch.Tensor, valid_b: torch.Tensor, level: int = 2,
+               block: int = 32, stride: int = None, radius: int = 8, min_count: int = None, ratio: float = 0.8, device=None) -> dict:
+    """table, d, kept, texels (the drift in texels of the level) and drift (in the units of obj_a's vertices) for two frames'
+    textures of one size on the device.  Textures and validities are halved `level` times (texfinish.halve: means over the valid
+    texels alone); island_labels and surface_maps of that size come from frame a's face.obj (meshrender.FaceObj)."""
+    from . import projtex, texfinish
+    level = int(level)
+    h, w = _image(tex_a, "tex_a")
+    block, stride, radius, min_count = check_options(block, stride, radius, min_count)
+    if not 0 <= level <= 8 or h % (1 << level) or w % (1 << level):
+        raise ValueError(f"level must be in [0, 8] with {h} x {w} divisible by 2^level, got {level}")
+    dev = tex_a.device if device is None else torch.device(device)
+    with torch.cuda.device(dev):
+        a, va, b, vb = tex_a, valid_a, tex_b, valid_b
+        for _ in range(level):
+            a, va = texfinish.halve(a, va)
+            b, vb = texfinish.halve(b, vb)
+        h, w = h >> level, w >> level
+        labels = projtex.island_labels(obj_a, h, w, device=dev)
+        verts = torch.from_numpy(np.ascontiguousarray(obj_a.vertices, np.float64)).to(dev)
+        pos = projtex.surface_maps(obj_a, verts, (h, w), device=dev)[0]
+        table = match(a, va, b, vb, labels, block, stride, radius, min_count)
+        d, kept = flow(table, radius, ratio)
+        drift, kept = metric(d, kept, pos, labels, block, stride)
+    return {"table": table, "d": d, "kept": kept, "texels": length(d), "drift": drift}
+
+
+# ---- command line ----------------------------------------------------------------------------------------------------------
+def add_options(p: argparse.ArgumentParser, prefix: str = "") -> None:
+    """The matcher's flags, as `python -m topo4d_amd.drift` has them (prefix "": --level ...) and evaluate (prefix "drift_")."""
+    flag = lambda name: f"--{prefix}{name}"
+    p.add_argument(flag("texture"), default=DEFAULTS["texture"], metavar="NAME",
+                   help="Drift: the file of every frame directory that is matched (default face_proj.png).")
+    p.add_argument(flag("ref"), choices=("first", "previous"), default=DEFAULTS["ref"],
+                   help="Drift: match every frame against the first selected frame (accumulated drift) or the one before (slip).")
+    p.add_argument(flag("level"), type=int, default=DEFAULTS["level"], metavar="K", help="Drift: halve the textures K times first (default 2).")
+    p.add_argument(flag("block"), type=int, default=DEFAULTS["block"], metavar="B", help="Drift: block side in texels, even, 8..64 (default 32).")
+    p.add_argument(flag("stride"), type=int, default=DEFAULTS["stride"], metavar="S", help="Drift: block spacing, 1..B (default B / 2).")
+    p.add_argument(flag("radius"), type=int, default=DEFAULTS["radius"], metavar="R", help="Drift: search radius in texels, 0..16 (default 8).")
+    p.add_argument(flag("ratio"), type=float, default=DEFAULTS["ratio"],
+                   help="Drift: keep a block whose best cost is at most this fraction of its second's (default 0.8).")
+    p.add_argument(flag("unit"), type=float, default=DEFAULTS["unit"],
+                   help="Drift: reported unit per face.obj unit (default 1000: metres -> mm).")
+
+
+def options_of(args, prefix: str = "") -> dict:
+    return {k: getattr(args, prefix + k, v) for k, v in DEFAULTS.items()}
+
+
+def build_parser() -> argparse.ArgumentParser:
+    from .evaluate import _frames
+    from .train import build_parser as train_parser
+    p = argparse.ArgumentParser(prog="python -m topo4d_amd.drift",
+                                description="Measure tracking drift between the frames of a run by matching their UV textures.")
+    for a in train_parser()._actions:                         # -e/-s/-od exactly as topo4d_amd.train has them
+        if a.dest in ("exp", "seq", "output_dir"):
+            p.add_argument(*a.option_strings, type=a.type, default=a.default, help=a.help)
+    p.add_argument("--frames", type=_frames, default=None, help="Frames to measure: '1-10', '1,5,9' (default: every frame directory).")
+    add_options(p)
+    p.add_argument("--save_fields", action="store_true", help=f"Also write %%06d/{FIELDS_NAME} (table, d, kept, drift).")
+    return p
+
+
+def _read_frame(frame_dir: str, texture: str, dev):
+    """(FaceObj, texture uint8 [h,w,3], valid uint8 [h,w], "weight" | "obj") of one frame directory; None without its files."""
+    from PIL import Image
+    from . import meshrender, texfinish
+    obj_path, png_path = os.path.join(frame_dir, "face.obj"), os.path.join(frame_dir, texture)
+    if not (os.path.exists(obj_path) and os.path.exists(png_path)):
+        return None
+    obj = meshrender.read_face_obj(obj_path)
+    tex = torch.from_numpy(np.ascontiguousarray(np.array(Image.open(png_path).convert("RGB")))).to(dev)
+    weight_path = os.path.join(frame_dir, WEIGHT_FILE)
+    if os.path.exists(weight_path):
+        weight = np.array(Image.open(weight_path))
+        if weight.shape[:2] != tuple(tex.shape[:2]):
+            raise SystemExit(f"{weight_path}: {weight.shape[:2]} does not match {texture}'s {tuple(tex.shape[:2])}")
+        valid = torch.from_numpy(np.ascontiguousarray((weight.reshape(weight.shape[0], weight.shape[1], -1) > 0).any(-1))).to(dev)
+        return obj, tex, valid.to(torch.uint8), "weight"
+    return obj, tex, texfinish.coverage_from_obj(obj, int(tex.shape[0]), int(tex.shape[1]), device=dev), "obj"
+
+
+def drift_tree(args, device=None, options: dict = None) -> dict:
+    """The dictionary of drift.json for the run <od>/<exp>/<seq>: the options, per measured frame its pair and drift_stats, and a
+    summary.  options: options_of(args) by default.  Frames without face.obj or the texture are left out."""
+    o = dict(options if options is not None else options_of(args))
+    try:
+        block, stride, radius, min_count = check_options(o["block"], o["stride"], o["radius"])
+        if not 0.0 < float(o["ratio"]) <= 1.0 or not 0 <= int(o["level"]) <= 8:
+            raise ValueError(f"ratio must be in (0, 1] and level in [0, 8], got {o['ratio']}, {o['level']}")
+    except ValueError as e:
+        raise SystemExit(f"drift: {e}") from None
+    o["stride"] = stride
+    dev = torch.device(device if device is not None else "cuda")
+    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
+    if not os.path.isdir(run_dir):
+        raise SystemExit(f"no run at {run_dir}")
+    frames = getattr(args, "frames", None) or sorted(int(d) for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
+    out = {"options": {**o, "min_count": min_count}, "frames": {}}
+    ref = None                                                # (key, files) of the frame matched against
+    with torch.cuda.device(dev):
+        for t in frames:
+            key = "%06d" % t
+            cur = _read_frame(os.path.join(run_dir, key), o["texture"], dev)
+            if cur is None:
+                continue
+            if ref is not None:
+                (ref_key, (obj_a, tex_a, val_a, from_a)), (_, tex_b, val_b, from_b) = ref, cur
+                if tex_a.shape != tex_b.shape:
+                    raise SystemExit(f"{key}/{o['texture']}: {tuple(tex_b.shape)} does not match frame {ref_key}'s {tuple(tex_a.shape)}")
+                try:
+                    r = frame_pair(obj_a, tex_a, val_a, tex_b, val_b, o["level"], block, stride, radius, min_count, o["ratio"], device=dev)
+                except ValueError as e:
+                    raise SystemExit(f"{key}/{o['texture']}: {e}") from None
+                row = {"pair": [ref_key, key], "valid_from": {ref_key: from_a, key: from_b}}
+                row.update(drift_stats(r["texels"], r["drift"], r["kept"], unit=float(o["unit"])))
+                out["frames"][key] = row
+                if getattr(args, "save_fields", False):
+                    np.savez(os.path.join(run_dir, key, FIELDS_NAME), **{k: r[k].cpu().numpy() for k in ("table", "d", "kept", "drift")})
+            if ref is None or o["ref"] == "previous":
+                ref = (key, cur)
+    rows = out["frames"]
+    scored = {k: r for k, r in rows.items() if "mean" in r}
+    summary = {"frames": len(rows), "kept_fraction": sum(r["kept_fraction"] for r in rows.values()) / len(rows) if rows else 0.0}
+    if scored:
+        summary["mean"] = sum(r["mean"] for r in scored.values()) / len(scored)
+        worst = max(sorted(scored), key=lambda k: scored[k]["mean"])
+        summary["worst_frame"], summary["worst_mean"] = worst, scored[worst]["mean"]
+    out["summary"] = summary
+    return out
+
+
+def main(argv=None) -> None:
+    args = build_parser().parse_args(argv)
+    out = drift_tree(args)
+    with open(os.path.join(args.output_dir, args.exp, args.seq, "drift.json"), "w") as f:
+        json.dump(out, f, indent=1)
+    print("drift", json.dumps(out["summary"]))
+
+
+if __name__ == "__main__":
+    main()

@@ -2,7 +2,8 @@
 Score a finished run: `python -m topo4d_amd.evaluate -e EXP -s SEQ [-id ... -did ... -od ...] [--frames 1-10] [--views A,B]
 [--set low|dense|both|none] [--save_renders] [--scans DIR [--scan_max_dist X] [--scan_unit S] [--scan_thresholds a,b,c]
 [--scan_transform FILE] [--save_scan_errors] [--bake_disp DIST [--bake_res N] [--bake_both_sides]]] [--tex_pad R [--tex_erode E]]
-[--texture NAME]`.
+[--texture NAME] [--drift [--drift_texture NAME] [--drift_ref first|previous] [--drift_level K] [--drift_block B] [--drift_stride S]
+[--drift_radius R] [--drift_ratio Q] [--drift_unit U]]`.
 
 For every frame of <od>/<exp>/<seq>: read %06d/face.obj (save_mesh's vertices: the training frame mapped by the trans_g of
 cameras.get_cameras, whose inverse maps them back, in float64) and %06d/face.png (PIL, on the host; frame t+1's files are read on a thread
@@ -29,6 +30,10 @@ no longer mix in the file's black background.  The files stay as they are; eval.
 
 With --texture NAME that file of every frame directory is sampled instead of face.png, e.g. face_proj.png (projtex); eval.json
 gains "texture_file".
+
+With --drift the tracking drift between the frames' UV textures is measured too (topo4d_amd.drift.drift_tree, the --drift_* flags
+being that module's flags): eval.json gains "drift", the dictionary `python -m topo4d_amd.drift` writes to drift.json.  --set none
+with --drift measures the drift alone.
 """
 from __future__ import annotations
 
@@ -386,6 +391,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--bake_disp: the side of the displacement map (default 4096; evaluate has no texture size of its own).")
     p.add_argument("--bake_both_sides", action="store_true",
                    help="--bake_disp: also count scan triangles whose normal points against the texel's normal.")
+    p.add_argument("--drift", action="store_true",
+                   help="Also measure the tracking drift between the frames' UV textures (topo4d_amd.drift); eval.json gains \"drift\".")
+    from . import drift
+    drift.add_options(p, prefix="drift_")
     return p
 
 
@@ -398,8 +407,9 @@ def evaluate(args, device=None) -> dict:
     scans = getattr(args, "scans", None)
     if scans is not None and not os.path.isdir(scans):
         raise SystemExit(f"--scans: no directory {scans}")
-    if not sets and scans is None:
-        raise SystemExit("--set none scores nothing without --scans")
+    with_drift = bool(getattr(args, "drift", False))
+    if not sets and scans is None and not with_drift:
+        raise SystemExit("--set none scores nothing without --scans or --drift")
     bake_disp = getattr(args, "bake_disp", None)
     if bake_disp is not None:
         if scans is None:
@@ -423,6 +433,9 @@ def evaluate(args, device=None) -> dict:
             out[which] = score_set(args, which, dev)
         if scans is not None:
             out["scan"] = score_scans(args, dev)
+        if with_drift:
+            from . import drift
+            out["drift"] = drift.drift_tree(args, dev, options=drift.options_of(args, "drift_"))
     with open(os.path.join(run_dir, "eval.json"), "w") as f:
         json.dump(out, f, indent=1)
     return out
@@ -436,6 +449,8 @@ def main(argv=None) -> None:
             print(which, json.dumps(out[which]["summary"]))
     if "scan" in out:
         print("scan", json.dumps(out["scan"]["summary"]))
+    if "drift" in out:
+        print("drift", json.dumps(out["drift"]["summary"]))
 
 
 if __name__ == "__main__":
