@@ -450,6 +450,14 @@ int t4d_texture_halve(const uint8_t *image, const uint8_t *coverage, int32_t h, 
 size_t t4d_texture_fill_scratch_bytes(int32_t h, int32_t w, int32_t c);
 int t4d_texture_fill(const uint8_t *image, const uint8_t *valid, const uint8_t *domain, int32_t h, int32_t w, int32_t c,
                      uint8_t *out_image, uint8_t *out_filled, void *scratch, size_t scratch_bytes, void *hip_stream);
+/* The same fill for 16-bit samples (texfinish.fill16: a quantised displacement map).  image and out_image are int32 [h,w,c]; a
+ * sample is the low 16 bits of its word, 0..65535, and every output word holds 0..65535.  The rule is t4d_texture_fill's word for
+ * word: C0 = 256 image, the same pull, push and output expressions.  The push sum reaches 16 * 65535 * 256 + 8, which is above 2^31
+ * and below 2^32: it is taken in unsigned 32-bit arithmetic.  Scratch: t4d_texture_fill16_scratch_bytes(h, w, c), aligned to 4
+ * bytes; errors as t4d_texture_fill. */
+size_t t4d_texture_fill16_scratch_bytes(int32_t h, int32_t w, int32_t c);
+int t4d_texture_fill16(const int32_t *image, const uint8_t *valid, const uint8_t *domain, int32_t h, int32_t w, int32_t c,
+                       int32_t *out_image, uint8_t *out_filled, void *scratch, size_t scratch_bytes, void *hip_stream);
 
 /* Tracking drift between two frames' UV textures: a census block matcher (topo4d_amd/drift.py, csrc/t4d_drift.hip), under the
  * conventions of the texture family above.  luma_a, luma_b uint8 [h,w] (drift.luma: (77 R + 150 G + 29 B + 128) >> 8); valid_a,
@@ -498,6 +506,50 @@ int t4d_png_encode(const void *image, int32_t is_float32, int32_t h, int32_t w, 
  * synchronise the stream. */
 int t4d_png_encode_chw(const float *image, int32_t h, int32_t w, uint8_t *out, size_t out_capacity, int64_t *out_bytes /* device */,
                        void *scratch, size_t scratch_bytes, void *hip_stream);
+/* The same encoder for 16-bit samples (png.encode_png16: a displacement map, its normal map).  image int32 [h,w,c] on the device,
+ * c in {1, 3, 4}; a sample is the low 16 bits of its word.  IHDR carries bit depth 16 and colour type 0 / 2 / 6; a sample is
+ * written high byte first, so a filtered row is 1 + 2 w c bytes, and the five filters run at a byte distance of bpp = 2 c.  The
+ * filter choice (least sum |int8 residual|, the lowest filter number on a tie), the 16 KiB segments, the per-segment Huffman block,
+ * CRC-32 and Adler-32 are t4d_png_encode's.  out_capacity >= t4d_png_max_bytes16(h, w, c), scratch >=
+ * t4d_png_scratch_bytes16(h, w, c); error codes as t4d_png_encode.  Does not synchronise the stream. */
+size_t t4d_png_max_bytes16(int32_t h, int32_t w, int32_t c);
+size_t t4d_png_scratch_bytes16(int32_t h, int32_t w, int32_t c);
+int t4d_png_encode16(const int32_t *image, int32_t h, int32_t w, int32_t c, uint8_t *out, size_t out_capacity,
+                     int64_t *out_bytes /* device */, void *scratch, size_t scratch_bytes, void *hip_stream);
+
+/* Finishing a baked displacement map (topo4d_amd/dispmap.py, csrc/t4d_dispmap.hip), under the conventions of the texture family
+ * above: 1 <= h, w <= 65536, device pointers, arguments checked before anything touches a device, no synchronisation.  A code map is
+ * int32 [h,w] whose low 16 bits count; every output word holds 0..65535.  has uint8 [h,w], non-zero = the texel has a value;
+ * labels uint8 [h,w], the texel's UV island, 0 = none.  Float64 arithmetic is done in the order written, without contraction, with
+ * dot3(u, v) = (u0 v0 + u1 v1) + u2 v2 and rint rounding half to even; tests/dispmap_ref.py restates every rule in numpy.
+ *
+ * t4d_disp_quantize: disp float32 [h,w] (scanbake's map, scan units), hit uint8 [h,w], dist finite and > 0 (the bake's reach).
+ * Where hit != 0 and disp is finite: code = 32768 + clamp(rint((double(disp) / dist) * 32767.0), -32767, 32767) and has = 1;
+ * elsewhere code = 32768 and has = 0.  So 32768 is zero displacement and one code step is unit = dist / 32767 scan units.
+ *
+ * t4d_disp_smooth: `rounds` (0..8) rounds of a 5x5 binomial filter that stays inside an island; each round reads the output of the
+ * round before.  With w = (1, 4, 6, 4, 1), a texel with has != 0 and label L != 0 takes S = sum w_j w_i code[y+j][x+i] and
+ * Wt = sum w_j w_i over the taps (j, i in -2..2) that lie inside the image, have has != 0 and carry label L, and becomes
+ * (2 S + Wt) / (2 Wt) in integer division; the centre always counts, so Wt >= 36.  Every other texel is copied through; has and
+ * labels do not change; 0 rounds is a copy.  out must not be code.  Scratch: t4d_disp_smooth_scratch_bytes(h, w) (one more code
+ * map for the rounds to alternate on), aligned to 4 bytes; T4D_ERR_STATE_SIZE when it is smaller.
+ *
+ * t4d_disp_normals: the tangent-space normal map of the displaced surface, normal int32 [h,w,3].  pos float32 [h,w,3] is the point
+ * of the undisplaced surface per texel (projtex.surface_maps), unit finite and > 0 the scan units per code step.  For a texel with
+ * has != 0 and label L != 0: xp = x + 1 if that texel is inside the image, has a value and carries label L, else x; xm, yp, ym
+ * likewise.  If xp == xm, sx = 0; otherwise Tx = double(pos[y][xp]) - double(pos[y][xm]) per component, a = sqrt(dot3(Tx, Tx)),
+ * sx = (double(code[y][xp] - code[y][xm]) * unit) / a, and sx = 0 when a == 0.  sy likewise along y.  Image y runs against v
+ * (texture.process_uv flips it), so with +u right and +v up (the OpenGL convention) n = (-sx, +sy, 1), len = sqrt((sx sx + sy sy) +
+ * 1.0), and each component is stored as clamp(rint(((n_i / len) * 0.5 + 0.5) * 65535.0), 0, 65535) (a NaN gives 0).  A texel
+ * without a value or label gets the same on (0, 0, 1): (32768, 32768, 65535).  Known limit: the slopes are taken along u and v
+ * separately through the surface's own texel lengths; the shear between dp/du and dp/dv and the curvature terms are ignored. */
+int t4d_disp_quantize(const float *disp, const uint8_t *hit, int32_t h, int32_t w, double dist, int32_t *code, uint8_t *has,
+                      void *hip_stream);
+size_t t4d_disp_smooth_scratch_bytes(int32_t h, int32_t w);
+int t4d_disp_smooth(const int32_t *code, const uint8_t *has, const uint8_t *labels, int32_t h, int32_t w, int32_t rounds, int32_t *out,
+                    void *scratch, size_t scratch_bytes, void *hip_stream);
+int t4d_disp_normals(const int32_t *code, const uint8_t *has, const uint8_t *labels, const float *pos, int32_t h, int32_t w,
+                     double unit, int32_t *normal, void *hip_stream);
 
 /* face.obj of helpers.save_mesh (helpers.py:963-990) on the device (topo4d_amd/objexport.py, csrc/t4d_obj.hip).  Every pointer
  * but `transform` is device memory; none of these synchronises the stream.

@@ -170,12 +170,21 @@ SIGNATURES = {
     "t4d_texture_halve": (_INT, [_VP, _VP] + [_I32] * 3 + [_VP] * 3),
     "t4d_texture_fill_scratch_bytes": (_SZ, [_I32] * 3),
     "t4d_texture_fill": (_INT, [_VP] * 3 + [_I32] * 3 + [_VP] * 3 + [_SZ, _VP]),
+    "t4d_texture_fill16_scratch_bytes": (_SZ, [_I32] * 3),
+    "t4d_texture_fill16": (_INT, [_VP] * 3 + [_I32] * 3 + [_VP] * 3 + [_SZ, _VP]),
     "t4d_drift_scratch_bytes": (_SZ, [_I32] * 5),
     "t4d_drift_match": (_INT, [_VP] * 5 + [_I32] * 6 + [_VP, _VP, _SZ, _VP]),
     "t4d_png_max_bytes": (_SZ, [_I32] * 3),
     "t4d_png_scratch_bytes": (_SZ, [_I32] * 3),
     "t4d_png_encode": (_INT, [_VP] + [_I32] * 4 + [_VP, _SZ, _VP, _VP, _SZ, _VP]),
     "t4d_png_encode_chw": (_INT, [_VP] + [_I32] * 2 + [_VP, _SZ, _VP, _VP, _SZ, _VP]),
+    "t4d_png_max_bytes16": (_SZ, [_I32] * 3),
+    "t4d_png_scratch_bytes16": (_SZ, [_I32] * 3),
+    "t4d_png_encode16": (_INT, [_VP] + [_I32] * 3 + [_VP, _SZ, _VP, _VP, _SZ, _VP]),
+    "t4d_disp_quantize": (_INT, [_VP, _VP, _I32, _I32, C.c_double, _VP, _VP, _VP]),
+    "t4d_disp_smooth_scratch_bytes": (_SZ, [_I32] * 2),
+    "t4d_disp_smooth": (_INT, [_VP] * 3 + [_I32] * 3 + [_VP, _VP, _SZ, _VP]),
+    "t4d_disp_normals": (_INT, [_VP] * 4 + [_I32, _I32, C.c_double, _VP, _VP]),
     "t4d_obj_csr_scratch_bytes": (_SZ, [_I32]),
     "t4d_obj_vertex_faces": (_INT, [_VP, _I64, _I32] + [_VP] * 4 + [_SZ, _VP]),
     "t4d_obj_normals_scratch_bytes": (_SZ, [_I64]),

@@ -1,16 +1,17 @@
 // t4d_png.hip — lossless PNG encoder for baked UV textures (write_texture(..., encoder="gpu")) and progress renders
 // (progress.save_image), on the device.
 //
-// The file is a plain PNG: signature, IHDR (8-bit, no interlace, colour type 0 / 2 / 6 for C = 1 / 3 / 4), a 2-byte IDAT with
-// the zlib header, one IDAT per segment, a 4-byte IDAT with the Adler-32 trailer, IEND.  The IDAT payloads joined are one zlib
-// stream.  Compression model ("PNG encoder"): every row is filtered with the PNG filter of least sum |int8 residual|,
+// The file is a plain PNG: signature, IHDR (8-bit, or 16-bit from t4d_png_encode16; no interlace, colour type 0 / 2 / 6 for
+// C = 1 / 3 / 4), a 2-byte IDAT with the zlib header, one IDAT per segment, a 4-byte IDAT with the Adler-32 trailer, IEND.  The
+// IDAT payloads joined are one zlib stream.  Compression model ("PNG encoder"): every row is filtered with the PNG filter of least sum |int8 residual|,
 // the filtered byte stream is cut into independent segments of kSeg bytes, and each segment is one dynamic-Huffman deflate block
 // of literals and distance-1 runs (or one stored block where that is smaller), closed by an empty stored block so the next segment
 // starts byte-aligned.  Four launches:
 //
 //  * k_png_filter   one workgroup per row: quantise (float32 [h,w,c] exactly as numpy's (x*255).astype(uint8) on x86-64, or a
-//                   float32 [3,h,w] render exactly as torchvision's save_image), score the five filters, write filter byte +
-//                   filtered row to scratch.
+//                   float32 [3,h,w] render exactly as torchvision's save_image; or the low 16 bits of an int32 [h,w,c] image as
+//                   two bytes, high byte first), score the five filters at a byte distance of bytes per pixel, write filter
+//                   byte + filtered row to scratch.  The later launches see filtered bytes only.
 //  * k_png_encode   one workgroup per segment: segment into LDS; the parse into literals and distance-1 runs is fixed by the
 //                   maximal equal-byte runs (every thread walks its own slice, with run bounds carried in by block scans);
 //                   histograms by LDS integer atomics; length-limited Huffman codes (15 / 7 bits); bits OR'ed into LDS words at
@@ -54,16 +55,17 @@ struct SegInfo {
 
 struct Shape {
     int32_t h, w, c;
-    int64_t row;                                 // filtered bytes per row: 1 + w * c
+    int32_t bps;                                 // bytes per sample: 1, or 2 (16-bit, big-endian)
+    int64_t row;                                 // filtered bytes per row: 1 + w * c * bps
     int64_t n;                                   // filtered bytes in all: h * row
     int64_t segs;
 };
 
-__host__ __device__ inline Shape make_shape(int32_t h, int32_t w, int32_t c)
+__host__ __device__ inline Shape make_shape(int32_t h, int32_t w, int32_t c, int32_t bps = 1)
 {
     Shape s;
-    s.h = h; s.w = w; s.c = c;
-    s.row = 1 + (int64_t)w * c;
+    s.h = h; s.w = w; s.c = c; s.bps = bps;
+    s.row = 1 + (int64_t)w * c * bps;
     s.n = (int64_t)h * s.row;
     s.segs = (s.n + kSeg - 1) / kSeg;
     return s;
@@ -90,10 +92,10 @@ PngLayout png_layout(const Shape &s)
     return L;
 }
 
-bool shape_ok(int32_t h, int32_t w, int32_t c)
+bool shape_ok(int32_t h, int32_t w, int32_t c, int32_t bps = 1)
 {
     if (h < 1 || w < 1 || !(c == 1 || c == 3 || c == 4)) return false;
-    return make_shape(h, w, c).n <= kMaxFiltered;
+    return make_shape(h, w, c, bps).n <= kMaxFiltered;
 }
 
 // deflate length symbols 257..285 (RFC 1951 3.2.5)
@@ -138,16 +140,21 @@ __device__ __forceinline__ uint32_t quant_tv(float x)
 }
 
 // input forms of k_png_filter
-enum PixMode { kU8 = 0, kF32 = 1, kF32Chw = 2 };
+enum PixMode { kU8 = 0, kF32 = 1, kF32Chw = 2, kU16 = 3 };
 
-// byte x of row r of the [h, w*c] image: [h,w,c] uint8 or float32 (numpy's cast), or a contiguous [3,h,w] float32 (torchvision's
-// rounding), whose byte x is plane x % 3, column x / 3
+// byte x of row r of the [h, w*c*bps] image: [h,w,c] uint8 or float32 (numpy's cast), a contiguous [3,h,w] float32 (torchvision's
+// rounding), whose byte x is plane x % 3, column x / 3, or [h,w,c] int32 whose sample x / 2 gives its bits 15..8 for even x and its
+// bits 7..0 for odd x
 template <int MODE>
 __device__ __forceinline__ uint32_t pix(const void *img, const Shape &s, int64_t r, int64_t x)
 {
     if (MODE == kF32Chw) {
         const int64_t col = x / 3, plane = x - 3 * col;
         return quant_tv(((const float *)img)[(plane * s.h + r) * s.w + col]);
+    }
+    if (MODE == kU16) {
+        const uint32_t v = (uint32_t)((const int32_t *)img)[r * ((int64_t)s.w * s.c) + (x >> 1)];
+        return ((x & 1) ? v : v >> 8) & 0xFFu;
     }
     const int64_t i = r * ((int64_t)s.w * s.c) + x;
     if (MODE == kF32) return t4d_quant_u8(((const float *)img)[i]);
@@ -172,8 +179,8 @@ __global__ __launch_bounds__(kBlock) void k_png_filter(const void *img, Shape s,
 {
     __shared__ unsigned long long red[5][kBlock];
     const int64_t r = blockIdx.x;
-    const int64_t wc = (int64_t)s.w * s.c;
-    const int c = s.c;
+    const int64_t wc = (int64_t)s.w * s.c * s.bps;               // bytes in the row
+    const int c = s.c * s.bps;                                    // bytes per pixel: the filters' byte distance
     unsigned long long sum[5] = {0, 0, 0, 0, 0};
     for (int64_t x = threadIdx.x; x < wc; x += kBlock) {
         const uint32_t v = pix<MODE>(img, s, r, x);
@@ -681,7 +688,7 @@ __global__ __launch_bounds__(kBlock) void k_png_finalize(Shape s, const SegInfo 
     uint8_t *p = out + 8;
     put_be32(p + 8, (uint32_t)s.w);
     put_be32(p + 12, (uint32_t)s.h);
-    p[16] = 8;                                                        // bit depth
+    p[16] = (uint8_t)(8 * s.bps);                                     // bit depth
     p[17] = s.c == 1 ? 0 : s.c == 3 ? 2 : 6;                          // grey, RGB, RGBA
     p[18] = 0; p[19] = 0; p[20] = 0;                                  // deflate, adaptive filtering, no interlace
     close_chunk(p, "IHDR", 13);
@@ -781,4 +788,39 @@ T4D_EXPORT int t4d_png_encode_chw(const float *image, int32_t h, int32_t w, uint
                        (uint8_t *)((char *)scratch + L.filt));
     launch_deflate(s, L, scratch, out, out_capacity, out_bytes, stream);
     return t4d_launch_status("t4d_png_encode_chw");
+}
+
+T4D_EXPORT size_t t4d_png_max_bytes16(int32_t h, int32_t w, int32_t c)
+{
+    if (!shape_ok(h, w, c, 2)) {
+        t4d_fail(T4D_ERR_ARG, "t4d_png_max_bytes16: need h, w >= 1, c in {1, 3, 4} and h*(1+2*w*c) <= 2^38");
+        return 0;
+    }
+    return (size_t)max_bytes(make_shape(h, w, c, 2));
+}
+
+T4D_EXPORT size_t t4d_png_scratch_bytes16(int32_t h, int32_t w, int32_t c)
+{
+    if (!shape_ok(h, w, c, 2)) {
+        t4d_fail(T4D_ERR_ARG, "t4d_png_scratch_bytes16: need h, w >= 1, c in {1, 3, 4} and h*(1+2*w*c) <= 2^38");
+        return 0;
+    }
+    return png_layout(make_shape(h, w, c, 2)).total;
+}
+
+T4D_EXPORT int t4d_png_encode16(const int32_t *image, int32_t h, int32_t w, int32_t c, uint8_t *out, size_t out_capacity,
+                                int64_t *out_bytes, void *scratch, size_t scratch_bytes, void *hip_stream)
+{
+    if (!image || !out || !out_bytes || !scratch || !shape_ok(h, w, c, 2))
+        return t4d_fail(T4D_ERR_ARG, "t4d_png_encode16: bad arguments (NULL buffer, or h, w < 1, c not in {1, 3, 4} or h*(1+2*w*c) > 2^38)");
+    const Shape s = make_shape(h, w, c, 2);
+    if (out_capacity < (size_t)max_bytes(s))
+        return t4d_fail(T4D_ERR_ARG, "t4d_png_encode16: out_capacity below t4d_png_max_bytes16");
+    const PngLayout L = png_layout(s);
+    if (scratch_bytes < L.total) return t4d_fail(T4D_ERR_STATE_SIZE, "t4d_png_encode16: scratch below t4d_png_scratch_bytes16");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(k_png_filter<kU16>, dim3((unsigned)h), dim3(kBlock), 0, stream, (const void *)image, s,
+                       (uint8_t *)((char *)scratch + L.filt));
+    launch_deflate(s, L, scratch, out, out_capacity, out_bytes, stream);
+    return t4d_launch_status("t4d_png_encode16");
 }

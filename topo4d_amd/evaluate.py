@@ -1,7 +1,8 @@
 """
 Score a finished run: `python -m topo4d_amd.evaluate -e EXP -s SEQ [-id ... -did ... -od ...] [--frames 1-10] [--views A,B]
 [--set low|dense|both|none] [--save_renders] [--scans DIR [--scan_max_dist X] [--scan_unit S] [--scan_thresholds a,b,c]
-[--scan_transform FILE] [--save_scan_errors] [--bake_disp DIST [--bake_res N] [--bake_both_sides]]] [--tex_pad R [--tex_erode E]]
+[--scan_transform FILE] [--save_scan_errors] [--bake_disp DIST [--bake_res N] [--bake_both_sides] [--disp_png] [--disp_fill]
+[--disp_smooth K] [--disp_normals]]] [--tex_pad R [--tex_erode E]]
 [--texture NAME] [--drift [--drift_texture NAME] [--drift_ref first|previous] [--drift_level K] [--drift_block B] [--drift_stride S]
 [--drift_radius R] [--drift_ratio Q] [--drift_unit U]]`.
 
@@ -23,6 +24,12 @@ With --bake_disp DIST (scan file units) every scored frame's scan detail is also
 ray met the scan).  The frame's "scan" row gains "displacement" (scanbake.displacement_stats, in --scan_unit) and
 "mesh_to_scan_normal" (every mesh vertex shot along its normal within DIST: the normal-shooting distance), the summary their
 means.  --bake_both_sides also counts scan triangles that face away from the texel's normal.
+
+With --disp_png the map is also finished into %06d/face_disp.png, a 16-bit grey PNG a renderer loads (dispmap.finish: code 32768 is
+no displacement, one step is DIST / 32767 scan file units); --disp_fill fills the texels whose ray missed from their UV island
+(push-pull), --disp_smooth K smooths K rounds (0..8) within the islands, --disp_normals also writes %06d/face_disp_normal.png, the
+16-bit tangent-space normal map; each of the three implies --disp_png, and all need --bake_disp with DIST > 0.  eval.json's "bake"
+gains "png" (zero, unit and the steps taken) and each frame's "displacement" gains "filled", the texels filled.
 
 With --tex_pad R every face.png is padded in memory before it is sampled (texfinish.finish: a gutter of R texels round the UV
 islands of face.obj, whose coverage is first eroded --tex_erode rounds, 1 by default), so that the bilinear taps on the UV seams
@@ -293,6 +300,7 @@ def score_scans(args, device) -> dict:
             raise SystemExit(f"--scan_transform: {args.scan_transform} does not hold a finite 4x4 matrix")
     result = {}
     bake_disp = getattr(args, "bake_disp", None)
+    disp_png = disp_png_options(args)
     pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="t4d-eval-scan")
     try:
         pending = {}
@@ -325,6 +333,12 @@ def score_scans(args, device) -> dict:
                 scanbake.write_frame(os.path.join(run_dir, key), disp, hit)
                 score["displacement"] = scanbake.displacement_stats(disp, hit, texfinish_coverage(obj, args.bake_res, device),
                                                                     unit=args.scan_unit)
+                if disp_png is not None:
+                    from . import dispmap
+                    finished = dispmap.finish(obj, obj.vertices, disp, hit, bake_disp, fill=disp_png["fill"], smooth=disp_png["smooth"],
+                                              normals=disp_png["normals"], device=device)
+                    dispmap.write_frame(os.path.join(run_dir, key), finished)
+                    score["displacement"]["filled"] = int(finished["filled"].sum())
             elif bake_disp is not None:
                 score["displacement"] = {"skipped": "scan has no faces"}
             arrays = score.pop("arrays", None)
@@ -339,7 +353,19 @@ def score_scans(args, device) -> dict:
     out = {"unit": args.scan_unit, "max_dist": args.scan_max_dist, "frames": result, "summary": _scan_summary(result)}
     if bake_disp is not None:
         out["bake"] = {"dist": bake_disp, "res": args.bake_res, "same_side": not args.bake_both_sides}
+        if disp_png is not None:
+            out["bake"]["png"] = disp_png
     return out
+
+
+def disp_png_options(args) -> Optional[dict]:
+    """dispmap.png_info for --disp_png / --disp_fill / --disp_smooth / --disp_normals (the last three imply the first); None
+    without any of them."""
+    fill, rounds, normals = (getattr(args, n, d) for n, d in (("disp_fill", False), ("disp_smooth", 0), ("disp_normals", False)))
+    if not (getattr(args, "disp_png", False) or fill or rounds or normals) or getattr(args, "bake_disp", None) is None:
+        return None
+    from . import dispmap
+    return dispmap.png_info(args.bake_disp, fill, rounds, normals)
 
 
 def _floats(spec: str) -> List[float]:
@@ -391,6 +417,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--bake_disp: the side of the displacement map (default 4096; evaluate has no texture size of its own).")
     p.add_argument("--bake_both_sides", action="store_true",
                    help="--bake_disp: also count scan triangles whose normal points against the texel's normal.")
+    p.add_argument("--disp_png", action="store_true",
+                   help="--bake_disp: also write %%06d/face_disp.png, the map as a 16-bit grey PNG (32768 = none, step DIST / 32767).")
+    p.add_argument("--disp_fill", action="store_true",
+                   help="--bake_disp: fill the texels whose ray missed from their UV island before writing the PNG (implies --disp_png).")
+    p.add_argument("--disp_smooth", type=int, default=0, metavar="K",
+                   help="--bake_disp: smooth the map K rounds (0..8) within the UV islands (K > 0 implies --disp_png).")
+    p.add_argument("--disp_normals", action="store_true",
+                   help="--bake_disp: also write %%06d/face_disp_normal.png, the 16-bit tangent-space normal map (implies --disp_png).")
     p.add_argument("--drift", action="store_true",
                    help="Also measure the tracking drift between the frames' UV textures (topo4d_amd.drift); eval.json gains \"drift\".")
     from . import drift
@@ -416,6 +450,14 @@ def evaluate(args, device=None) -> dict:
             raise SystemExit("--bake_disp needs --scans")
         if not (math.isfinite(bake_disp) and bake_disp >= 0.0) or not 1 <= args.bake_res <= 16384:
             raise SystemExit("--bake_disp needs a finite DIST >= 0 and --bake_res in 1..16384")
+    if any(getattr(args, n, 0) for n in ("disp_png", "disp_fill", "disp_smooth", "disp_normals")):
+        if bake_disp is None or not bake_disp > 0.0:
+            raise SystemExit("--disp_png, --disp_fill, --disp_smooth and --disp_normals need --bake_disp with DIST > 0")
+        from . import dispmap
+        try:
+            dispmap.check_options(bake_disp, args.disp_smooth)
+        except ValueError as e:
+            raise SystemExit(f"--disp_smooth: {e}") from None
     tex_pad = getattr(args, "tex_pad", None)
     if tex_pad is not None:
         from . import texfinish

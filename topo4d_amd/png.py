@@ -1,11 +1,14 @@
 """
-Lossless PNG encoding of a device image on the GPU, over `t4d_png_encode` and `t4d_png_encode_chw` (include/topo4d_raster.h,
-csrc/t4d_png.hip).
+Lossless PNG encoding of a device image on the GPU, over `t4d_png_encode`, `t4d_png_encode_chw` and `t4d_png_encode16`
+(include/topo4d_raster.h, csrc/t4d_png.hip).
 
     encode_png(image) -> bytes        uint8 or float32 [H,W] / [H,W,C], C in {1, 3, 4}, on a HIP device
     encode_png(image, chw=True)       float32 [3,H,W] (a render), quantised as torchvision's save_image (t4d_png_encode_chw)
     write_png(path, image, chw=False)
     max_encoded_bytes(h, w, c)        the output bound the encoder allocates (a function of the shape alone)
+    encode_png16(image_i32) -> bytes  int32 [H,W] / [H,W,C] holding 0..65535: a 16-bit PNG (grey, RGB or RGBA), big-endian samples
+    write_png16(path, image_i32)
+    max_encoded_bytes16(h, w, c)
 
 float32 [H,W,C] is quantised exactly as numpy's `(x * 255).astype(np.uint8)` on x86-64, so `encode_png(render_colors(...))`
 decodes to the array `texture.bake_texture` returns.  float32 [3,H,W] with chw=True is quantised exactly as torchvision's
@@ -67,6 +70,32 @@ def _check_chw(image) -> tuple:
     return h, w, 3
 
 
+def max_encoded_bytes16(h: int, w: int, c: int) -> int:
+    """max_encoded_bytes for the 16-bit file of an [h,w,c] image."""
+    _shape(int(h), int(w), int(c))
+    n = _lib.load().t4d_png_max_bytes16(int(h), int(w), int(c))
+    if n == 0:
+        raise _lib.error("t4d_png_max_bytes16", exc=ValueError)
+    return int(n)
+
+
+def _check16(image) -> tuple:
+    if not isinstance(image, torch.Tensor):
+        raise ValueError("encode_png16 expects a torch tensor")
+    if image.dtype != torch.int32:
+        raise ValueError(f"encode_png16 expects int32 holding 0..65535, got {image.dtype}")
+    if image.dim() == 2:
+        h, w, c = int(image.shape[0]), int(image.shape[1]), 1
+    elif image.dim() == 3:
+        h, w, c = (int(d) for d in image.shape)
+    else:
+        raise ValueError(f"encode_png16 expects [H,W] or [H,W,C], got shape {tuple(image.shape)}")
+    _shape(h, w, c)
+    if not image.is_cuda:
+        raise RuntimeError("topo4d_amd has no CPU path: encode_png16 needs the image on a HIP device")
+    return h, w, c
+
+
 def _pinned(nbytes: int) -> torch.Tensor:
     buf = _PINNED.get("host")
     if buf is None or buf.numel() < nbytes:
@@ -101,6 +130,34 @@ def encode_png(image: torch.Tensor, chw: bool = False) -> bytes:
     host = _pinned(n)
     host[:n].copy_(out[:n])
     return host[:n].numpy().tobytes()
+
+
+def encode_png16(image: torch.Tensor) -> bytes:
+    """The 16-bit PNG file of an int32 image (the low 16 bits of every word; see the module docstring).  Runs and synchronises as
+    encode_png does."""
+    h, w, c = _check16(image)
+    lib = _lib.load()
+    dev = image.device
+    img = image.contiguous()
+    cap = max_encoded_bytes16(h, w, c)
+    nscratch = int(lib.t4d_png_scratch_bytes16(h, w, c))
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+    length = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.call("t4d_png_encode16", ptr(img), h, w, c, ptr(out), cap, ptr(length), ptr(scratch), nscratch, _lib.stream(dev))
+    n = int(length.item())                                        # the one synchronisation
+    if n <= 0 or n > cap:
+        raise RuntimeError(f"t4d_png_encode16: bad output length {n} (capacity {cap})")
+    host = _pinned(n)
+    host[:n].copy_(out[:n])
+    return host[:n].numpy().tobytes()
+
+
+def write_png16(path, image: torch.Tensor) -> None:
+    """encode_png16(image) written to `path`."""
+    data = encode_png16(image)
+    with open(path, "wb") as f:
+        f.write(data)
 
 
 def write_png(path, image: torch.Tensor, chw: bool = False) -> None:

@@ -12,7 +12,8 @@ units.  There is no CPU path.
 
 Known limits: a ray along the interpolated normal can leave through a crease of the scan and miss; same_side (the default,
 which keeps a ray from landing on the back of a fold) drops surfaces that face the other way, such as the inside of the
-nostrils; the map is neither hole-filled nor smoothed; and a .npy is not the 16-bit PNG or EXR a renderer loads.
+nostrils.  The map this module writes is the raw bake, with holes where a ray missed and the scan's noise, as a .npy:
+topo4d_amd.dispmap finishes it (hole fill per UV island, smoothing, a 16-bit PNG and the tangent-space normal map; no EXR).
 """
 from __future__ import annotations
 

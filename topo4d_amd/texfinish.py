@@ -12,6 +12,8 @@ Finishing a baked UV texture on the GPU, over csrc/t4d_texfinish.hip (include/to
     fill(image, valid, domain=None)            -> (image, filled): every texel of `domain` that is not valid takes a smooth
                                                interpolation of the valid texels: push-pull over a pyramid, csrc/t4d_texfill.hip
     fill_islands(image, valid, labels)         -> (image, filled): fill per UV island, from that island's valid texels alone
+    fill16(image_i32, valid, domain=None)      fill for 16-bit samples held in int32 (0..65535): a quantised displacement map
+    fill16_islands(image_i32, valid, labels)   fill_islands for them, by the same per-island rule
 
 pad is right for a gutter and wrong for a hole: the nearest texel makes blocky streaks with a crease where two fronts meet.  fill is
 for the holes of a projected texture (projtex: the texels no camera sees): the valid texels are averaged down a pyramid over valid
@@ -141,6 +143,18 @@ def halve(image: torch.Tensor, coverage: torch.Tensor) -> Tuple[torch.Tensor, to
     return out, out_cov
 
 
+def _image16(image, what: str, need_device: bool = True) -> Tuple[torch.Tensor, int, int, int]:
+    if not isinstance(image, torch.Tensor) or image.dtype != torch.int32 or image.dim() not in (2, 3):
+        raise ValueError(f"{what} must be an int32 [h,w] or [h,w,c] tensor holding 0..65535")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    c = 1 if image.dim() == 2 else int(image.shape[2])
+    if h < 1 or w < 1 or c not in (1, 3, 4):
+        raise ValueError(f"{what} must be [h,w] or [h,w,c] with h, w >= 1 and c in (1, 3, 4); got {tuple(image.shape)}")
+    if need_device and not image.is_cuda:
+        raise RuntimeError(f"topo4d_amd has no CPU path: {what} must live on a HIP device")
+    return image.contiguous(), h, w, c
+
+
 def _mask(mask, what: str, h: int, w: int) -> None:
     if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (h, w):
         raise ValueError(f"{what} must be a uint8 or bool [{h},{w}] tensor, got {getattr(mask, 'dtype', type(mask))} "
@@ -153,26 +167,35 @@ def _on_device(mask: torch.Tensor, what: str, device) -> torch.Tensor:
     return (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
 
 
+def _fill(image, valid, domain, check, entry: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    _, h, w, c = check(image, "image", need_device=False)      # argument errors first, with or without a device
+    _mask(valid, "valid", h, w)
+    if domain is not None:
+        _mask(domain, "domain", h, w)
+    img = check(image, "image")[0]
+    val = _on_device(valid, "valid", img.device)
+    dom = None if domain is None else _on_device(domain, "domain", img.device)
+    nbytes = int(getattr(_lib.load(), entry + "_scratch_bytes")(h, w, c))
+    if nbytes == 0:
+        raise _lib.error(entry + "_scratch_bytes", exc=ValueError)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+    out = torch.empty_like(img)
+    filled = torch.empty(h, w, dtype=torch.uint8, device=img.device)
+    _lib.call(entry, ptr(img), ptr(val), ptr(dom), h, w, c, ptr(out), ptr(filled), ptr(scratch), nbytes, _lib.stream(img.device))
+    return out, filled
+
+
 def fill(image: torch.Tensor, valid: torch.Tensor, domain: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """(image, filled uint8 [h,w]): every texel of `domain` (None: every texel) that is not `valid` takes the push-pull
     interpolation of the valid texels (include/topo4d_raster.h states the rule, tests/texfill_ref.py restates it); every other
     texel is copied through.  filled is 1 at the texels written.  Without any valid texel the image comes back as it is."""
-    _, h, w, c = _image(image, "image", need_device=False)     # argument errors first, with or without a device
-    _mask(valid, "valid", h, w)
-    if domain is not None:
-        _mask(domain, "domain", h, w)
-    img = _image(image, "image")[0]
-    val = _on_device(valid, "valid", img.device)
-    dom = None if domain is None else _on_device(domain, "domain", img.device)
-    nbytes = int(_lib.load().t4d_texture_fill_scratch_bytes(h, w, c))
-    if nbytes == 0:
-        raise _lib.error("t4d_texture_fill_scratch_bytes", exc=ValueError)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
-    out = torch.empty_like(img)
-    filled = torch.empty(h, w, dtype=torch.uint8, device=img.device)
-    _lib.call("t4d_texture_fill", ptr(img), ptr(val), ptr(dom), h, w, c, ptr(out), ptr(filled), ptr(scratch), nbytes,
-              _lib.stream(img.device))
-    return out, filled
+    return _fill(image, valid, domain, _image, "t4d_texture_fill")
+
+
+def fill16(image_i32: torch.Tensor, valid: torch.Tensor, domain: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fill for an int32 image of 16-bit samples (0..65535; the low 16 bits of every word count), over t4d_texture_fill16: the
+    same rule in units of 1/256 of a 16-bit step (tests/dispmap_ref.py restates it)."""
+    return _fill(image_i32, valid, domain, _image16, "t4d_texture_fill16")
 
 
 def fill_islands(image: torch.Tensor, valid: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -181,12 +204,21 @@ def fill_islands(image: torch.Tensor, valid: torch.Tensor, labels: torch.Tensor)
     island's colours never enter another island's holes, and an island without any valid texel stays as it is.  Every pass runs on
     the whole image (a crop would shift the pyramid and change the bits).  The labels that need a pass are found by one read of
     two flags per label from the device."""
-    _, h, w, _ = _image(image, "image", need_device=False)
+    return _fill_islands(image, valid, labels, _image, fill)
+
+
+def fill16_islands(image_i32: torch.Tensor, valid: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fill_islands for an int32 image of 16-bit samples: exactly its per-island rule, with fill16 for every pass."""
+    return _fill_islands(image_i32, valid, labels, _image16, fill16)
+
+
+def _fill_islands(image, valid, labels, check, fill) -> Tuple[torch.Tensor, torch.Tensor]:
+    _, h, w, _ = check(image, "image", need_device=False)
     _mask(valid, "valid", h, w)
     if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or tuple(labels.shape) != (h, w):
         raise ValueError(f"labels must be a uint8 [{h},{w}] tensor, got {getattr(labels, 'dtype', type(labels))} "
                          f"{list(getattr(labels, 'shape', ()))}")
-    img = _image(image, "image")[0]
+    img = check(image, "image")[0]
     val = _on_device(valid, "valid", img.device) != 0
     lab = _on_device(labels, "labels", img.device)
     flat = lab.reshape(-1).to(torch.int64)
