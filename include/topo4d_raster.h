@@ -551,6 +551,51 @@ int t4d_disp_smooth(const int32_t *code, const uint8_t *has, const uint8_t *labe
 int t4d_disp_normals(const int32_t *code, const uint8_t *has, const uint8_t *labels, const float *pos, int32_t h, int32_t w,
                      double unit, int32_t *normal, void *hip_stream);
 
+/* Applying a finished displacement map: the flat level-N tessellation of a triangle mesh and its displacement by the code map
+ * (topo4d_amd/tessellate.py, csrc/t4d_tessellate.hip).  Device pointers, arguments checked before anything touches a device, no
+ * synchronisation; float64 in the order written, without contraction, dot3 as above; tests/tessellate_ref.py restates every rule in
+ * numpy.  level N is the number of segments per edge, 1 <= N <= 64, and N^2 n_tri < 2^31.
+ *
+ * Topology.  tri int32 [n_tri,3] holds the corners (a, b, c) of every triangle, a, b, c distinct and in [0, n_corner); the n_edges
+ * undirected edges are the sorted pairs (lo < hi) in lexicographic order; tri_edge int32 [n_tri,3] names the edge of (a, b), (b, c)
+ * and (c, a); edges int32 [n_edges,3] holds (lo, hi, owner): the owner is the lowest triangle that has the edge.  With
+ * I = (N - 1)(N - 2) / 2 the fine vertices are, in id order: the n_corner corners; per edge e the vertices s = 1..N-1 counted from lo,
+ * at n_corner + e (N - 1) + (s - 1); per triangle t the lattice points (i, j, k), i + j + k = N, all >= 1, numbered by
+ * `for j in 1..N-2: for k in 1..N-1-j`, at n_corner + n_edges (N - 1) + t I + index.  n_fine = n_corner + n_edges (N - 1) + n_tri I
+ * must be below 2^31.  A lattice point with a zero coordinate lies on an edge and is that edge's vertex: on a -> b (k = 0), j steps
+ * from a, s = j if a < b, else N - j; on b -> c (i = 0), k steps from b; on c -> a (j = 0), i steps from c.
+ *
+ * t4d_tess_faces: out int32 [N^2 n_tri,3].  Triangle t writes rows t N^2 ..: for r = 0..N-1 and s = 0..r, with (i, j, k) =
+ * (N - r, r - s, s), the triangle [(i,j,k), (i-1,j+1,k), (i-1,j,k+1)] and, if s < r, [(i,j,k), (i-1,j,k+1), (i,j-1,k+1)] after it.
+ * One thread per fine triangle, integer arithmetic only.
+ *
+ * t4d_tess_points: out float64 [n_fine,dim], dim in {2, 3}, the flat tessellation of values float64 [n_corner,dim]: a corner is
+ * copied; an edge vertex is ((N - s) V_lo + s V_hi) / N per component; an interior one ((i A + j B) + k C) / N, (A, B, C) the values
+ * at (a, b, c).  The integers are converted to float64 first; the two products are rounded before their sum.
+ *
+ * t4d_tess_displace: out float64 [n_fine,3] and sampled uint8 [n_fine].  vertices and normals float64 [n_vert,3] (n_vert takes
+ * n_corner's place above), uvs float64 [n_uv,2], uv_tri int32 [n_tri,3] the UV corners standing at tri's corners, tri_island int32
+ * [n_tri] the label of the triangle's UV island, corner_owner int32 [n_vert] the first corner 3 t + c that names the vertex in
+ * row-major order of tri, or -1 for a vertex in no triangle: that vertex is copied through with sampled = 0.  A corner is owned by
+ * the triangle of its corner_owner, an edge vertex by the edge's owner, an interior vertex by its own triangle.  Position P and
+ * normal n follow t4d_tess_points' rules; so does the UV (u, v), over the owner's UV corners that stand at the same mesh corners (at
+ * lo and hi for an edge vertex); L is the owner's tri_island.  len = sqrt(dot3(n, n)); if len is zero or P, n, u, v or len is not
+ * finite, out = P and sampled = 0.  Otherwise the code map (code int32 [h,w], low 16 bits; has, labels uint8 [h,w]; 1 <= h, w <=
+ * 65536) is sampled at x = u (w - 1), y = (h - v (h - 1)) - 1: x0 = clamp(floor(x), 0, max(w - 2, 0)), x1 = min(x0 + 1, w - 1),
+ * fx = clamp(x - x0, 0, 1), and y alike; the taps are (y0,x0), (y0,x1), (y1,x0), (y1,x1) with the weights (1 - fx)(1 - fy),
+ * fx (1 - fy), (1 - fx) fy, fx fy; a tap counts where has != 0 and labels == L.  In tap order, S = sum of weight * double(code - 32768)
+ * and W = sum of weight, a tap that does not count adding 0.0 to both.  If W > 0, d = (S / W) unit; else if a tap counts, d =
+ * (double(sum of code - 32768 over the counting taps) / double(their number)) unit; else d = 0 and sampled = 0.  out_c = P_c +
+ * d (n_c / len); sampled = 1 where a tap counted.  unit finite (scan units per code step).  One thread per fine vertex. */
+int t4d_tess_faces(const int32_t *tri, const int32_t *tri_edge, int32_t n_tri, int32_t n_corner, int32_t n_edges, int32_t level,
+                   int32_t *out, void *hip_stream);
+int t4d_tess_points(const double *values, int32_t dim, int32_t n_corner, const int32_t *edges, int32_t n_edges, const int32_t *tri,
+                    int32_t n_tri, int32_t level, double *out, void *hip_stream);
+int t4d_tess_displace(const double *vertices, const double *normals, const double *uvs, const int32_t *corner_owner,
+                      const int32_t *edges, const int32_t *tri, const int32_t *uv_tri, const int32_t *tri_island, int32_t n_vert,
+                      int32_t n_uv, int32_t n_edges, int32_t n_tri, int32_t level, const int32_t *code, const uint8_t *has,
+                      const uint8_t *labels, int32_t h, int32_t w, double unit, double *out, uint8_t *sampled, void *hip_stream);
+
 /* face.obj of helpers.save_mesh (helpers.py:963-990) on the device (topo4d_amd/objexport.py, csrc/t4d_obj.hip).  Every pointer
  * but `transform` is device memory; none of these synchronises the stream.
  *

@@ -185,6 +185,9 @@ SIGNATURES = {
     "t4d_disp_smooth_scratch_bytes": (_SZ, [_I32] * 2),
     "t4d_disp_smooth": (_INT, [_VP] * 3 + [_I32] * 3 + [_VP, _VP, _SZ, _VP]),
     "t4d_disp_normals": (_INT, [_VP] * 4 + [_I32, _I32, C.c_double, _VP, _VP]),
+    "t4d_tess_faces": (_INT, [_VP, _VP] + [_I32] * 4 + [_VP, _VP]),
+    "t4d_tess_points": (_INT, [_VP, _I32, _I32, _VP, _I32, _VP, _I32, _I32, _VP, _VP]),
+    "t4d_tess_displace": (_INT, [_VP] * 8 + [_I32] * 5 + [_VP] * 3 + [_I32, _I32, C.c_double, _VP, _VP, _VP]),
     "t4d_obj_csr_scratch_bytes": (_SZ, [_I32]),
     "t4d_obj_vertex_faces": (_INT, [_VP, _I64, _I32] + [_VP] * 4 + [_SZ, _VP]),
     "t4d_obj_normals_scratch_bytes": (_SZ, [_I64]),

@@ -2,7 +2,7 @@
 Score a finished run: `python -m topo4d_amd.evaluate -e EXP -s SEQ [-id ... -did ... -od ...] [--frames 1-10] [--views A,B]
 [--set low|dense|both|none] [--save_renders] [--scans DIR [--scan_max_dist X] [--scan_unit S] [--scan_thresholds a,b,c]
 [--scan_transform FILE] [--save_scan_errors] [--bake_disp DIST [--bake_res N] [--bake_both_sides] [--disp_png] [--disp_fill]
-[--disp_smooth K] [--disp_normals]]] [--tex_pad R [--tex_erode E]]
+[--disp_smooth K] [--disp_normals] [--disp_apply N [--disp_save_obj]]]] [--tex_pad R [--tex_erode E]]
 [--texture NAME] [--drift [--drift_texture NAME] [--drift_ref first|previous] [--drift_level K] [--drift_block B] [--drift_stride S]
 [--drift_radius R] [--drift_ratio Q] [--drift_unit U]]`.
 
@@ -30,6 +30,13 @@ no displacement, one step is DIST / 32767 scan file units); --disp_fill fills th
 (push-pull), --disp_smooth K smooths K rounds (0..8) within the islands, --disp_normals also writes %06d/face_disp_normal.png, the
 16-bit tangent-space normal map; each of the three implies --disp_png, and all need --bake_disp with DIST > 0.  eval.json's "bake"
 gains "png" (zero, unit and the steps taken) and each frame's "displacement" gains "filled", the texels filled.
+
+With --disp_apply N (1..64, implies --disp_png) the finished map is also applied: the frame's mesh is tessellated into N segments per
+edge, every fine vertex is pushed along its interpolated normal by the map sampled at its UV (tessellate.Tessellation.displace), and
+the displaced mesh is scored against the scan under the frame's own options.  The frame's row gains "scan_displaced" (scan_to_mesh
+and mesh_to_scan, to be read next to the tracked mesh's) and "tessellation" (level, vertices, faces, unsampled: the fine vertices no
+texel of their island gave a value), "bake" gains "apply", the summary the mean of scan_displaced.scan_to_mesh.mean.
+--disp_save_obj also writes %06d/face_hi.obj, the displaced mesh in the tracked topology's UV layout.
 
 With --tex_pad R every face.png is padded in memory before it is sampled (texfinish.finish: a gutter of R texels round the UV
 islands of face.obj, whose coverage is first eroded --tex_erode rounds, 1 by default), so that the bilinear taps on the UV seams
@@ -277,6 +284,10 @@ def _scan_summary(frames: dict) -> dict:
         part = {n: float(np.mean([r[n] for r in shot])) if shot else None for n in ("mean", "rms")}
         part["within"] = {k: float(np.mean([r["within"][k] for r in shot])) for k in (list(shot[0]["within"]) if shot else [])}
         out["mesh_to_scan_normal"] = part
+    if any("scan_displaced" in fr for fr in scored.values()):
+        xs = [fr["scan_displaced"]["scan_to_mesh"]["mean"] for fr in scored.values()
+              if fr.get("scan_displaced", {}).get("scan_to_mesh", {}).get("count")]
+        out["scan_displaced"] = {"scan_to_mesh": {"mean": float(np.mean(xs)) if xs else None}}
     baked = [fr["displacement"] for fr in scored.values() if "hit_fraction" in fr.get("displacement", {})]
     if any("displacement" in fr for fr in scored.values()):
         out["displacement"] = {"hit_fraction": float(np.mean([r["hit_fraction"] for r in baked])) if baked else None}
@@ -301,6 +312,8 @@ def score_scans(args, device) -> dict:
     result = {}
     bake_disp = getattr(args, "bake_disp", None)
     disp_png = disp_png_options(args)
+    disp_apply = getattr(args, "disp_apply", None) if disp_png is not None else None
+    tess = None
     pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="t4d-eval-scan")
     try:
         pending = {}
@@ -339,6 +352,20 @@ def score_scans(args, device) -> dict:
                                               normals=disp_png["normals"], device=device)
                     dispmap.write_frame(os.path.join(run_dir, key), finished)
                     score["displacement"]["filled"] = int(finished["filled"].sum())
+                    if disp_apply is not None:
+                        from . import projtex, tessellate
+                        if tess is None or not tess.matches(obj):
+                            tess = tessellate.Tessellation(obj, disp_apply, device=device)
+                        labels = projtex.island_labels(obj, args.bake_res, args.bake_res, device=device)
+                        fine, sampled = tess.displace(obj.vertices, finished["code"], finished["has"], labels, disp_png["unit"])
+                        hi = scanscore.score_scan(fine, tess.faces, scan, max_dist=args.scan_max_dist, thresholds=args.scan_thresholds,
+                                                  unit=args.scan_unit, device=device)
+                        score["scan_displaced"] = {d: {n: (_finite(v) if isinstance(v, float) else v) for n, v in hi[d].items()}
+                                                   for d in ("scan_to_mesh", "mesh_to_scan")}
+                        score["tessellation"] = {"level": tess.level, "vertices": tess.n_vertices, "faces": tess.n_faces,
+                                                 "unsampled": tess.n_vertices - int(sampled.sum())}
+                        if getattr(args, "disp_save_obj", False):
+                            tessellate.write_frame(os.path.join(run_dir, key), tess, fine)
             elif bake_disp is not None:
                 score["displacement"] = {"skipped": "scan has no faces"}
             arrays = score.pop("arrays", None)
@@ -355,14 +382,17 @@ def score_scans(args, device) -> dict:
         out["bake"] = {"dist": bake_disp, "res": args.bake_res, "same_side": not args.bake_both_sides}
         if disp_png is not None:
             out["bake"]["png"] = disp_png
+            if disp_apply is not None:
+                out["bake"]["apply"] = int(disp_apply)
     return out
 
 
 def disp_png_options(args) -> Optional[dict]:
-    """dispmap.png_info for --disp_png / --disp_fill / --disp_smooth / --disp_normals (the last three imply the first); None
-    without any of them."""
+    """dispmap.png_info for --disp_png / --disp_fill / --disp_smooth / --disp_normals / --disp_apply (the last four imply the
+    first); None without any of them."""
     fill, rounds, normals = (getattr(args, n, d) for n, d in (("disp_fill", False), ("disp_smooth", 0), ("disp_normals", False)))
-    if not (getattr(args, "disp_png", False) or fill or rounds or normals) or getattr(args, "bake_disp", None) is None:
+    apply = getattr(args, "disp_apply", None) is not None
+    if not (getattr(args, "disp_png", False) or fill or rounds or normals or apply) or getattr(args, "bake_disp", None) is None:
         return None
     from . import dispmap
     return dispmap.png_info(args.bake_disp, fill, rounds, normals)
@@ -425,6 +455,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--bake_disp: smooth the map K rounds (0..8) within the UV islands (K > 0 implies --disp_png).")
     p.add_argument("--disp_normals", action="store_true",
                    help="--bake_disp: also write %%06d/face_disp_normal.png, the 16-bit tangent-space normal map (implies --disp_png).")
+    p.add_argument("--disp_apply", type=int, default=None, metavar="N",
+                   help="--bake_disp: tessellate each frame's mesh into N segments per edge (1..64), displace it by the finished map and "
+                        "score it against the scan too (implies --disp_png).")
+    p.add_argument("--disp_save_obj", action="store_true", help="--disp_apply: also write %%06d/face_hi.obj, the displaced mesh.")
     p.add_argument("--drift", action="store_true",
                    help="Also measure the tracking drift between the frames' UV textures (topo4d_amd.drift); eval.json gains \"drift\".")
     from . import drift
@@ -450,9 +484,18 @@ def evaluate(args, device=None) -> dict:
             raise SystemExit("--bake_disp needs --scans")
         if not (math.isfinite(bake_disp) and bake_disp >= 0.0) or not 1 <= args.bake_res <= 16384:
             raise SystemExit("--bake_disp needs a finite DIST >= 0 and --bake_res in 1..16384")
-    if any(getattr(args, n, 0) for n in ("disp_png", "disp_fill", "disp_smooth", "disp_normals")):
+    disp_apply = getattr(args, "disp_apply", None)
+    if getattr(args, "disp_save_obj", False) and disp_apply is None:
+        raise SystemExit("--disp_save_obj needs --disp_apply")
+    if any(getattr(args, n, 0) for n in ("disp_png", "disp_fill", "disp_smooth", "disp_normals")) or disp_apply is not None:
         if bake_disp is None or not bake_disp > 0.0:
-            raise SystemExit("--disp_png, --disp_fill, --disp_smooth and --disp_normals need --bake_disp with DIST > 0")
+            raise SystemExit("--disp_png, --disp_fill, --disp_smooth, --disp_normals and --disp_apply need --bake_disp with DIST > 0")
+        if disp_apply is not None:
+            from . import tessellate
+            try:
+                tessellate.check_level(disp_apply)
+            except ValueError as e:
+                raise SystemExit(f"--disp_apply: {e}") from None
         from . import dispmap
         try:
             dispmap.check_options(bake_disp, args.disp_smooth)
