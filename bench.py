@@ -3,8 +3,8 @@
 bench.py — rasterizer forward+backward views/sec on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C4] [--opacity A|B] [--scaling weak|strong]
-                    [--shard frames|views] [--allreduce-grads] [--frames-in-flight F] [--no-cpu-baseline] [--no-extras]
-                    [--dump-outputs DIR]
+                    [--shard frames|views] [--allreduce-grads] [--frames-in-flight F] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extras]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -14,20 +14,25 @@ all inputs already resident in HBM and seeded dL/dcolor supplied.  One "view" = 
 (Settings, params) -> colour/depth/alpha -> per-view dL/dparams round trip.
 Frames are independent units, so F = 3 of them (config 4: 2) are in flight on as many HIP streams (own state buffers each): the latency-bound
 binning kernels of one frame run beside the issue-bound render kernels of the other.  Every step is still executed in full, K
-steps are timed; `sequential` in the JSON line is the same run with F = 1, and the per-kernel figures of `roofline` are taken
-with F = 1 (a kernel alone on the chip).
+steps are timed.
+
+A plain run does what the headline figure needs and nothing else: set-up, the checked warm-up that learns the pair-arena capacity,
+W warm-up steps, the K timed steps, --dump-outputs, the JSON line (`metric`, `value`, `unit`, `ms_per_step`, `repeats`, `config`;
+every object of a measurement that did not run is null, and `full` is false).  --full adds every other measurement and check to
+the same line - the rest of this text describes them: `sequential` is the same run with F = 1, and the per-kernel figures of
+`roofline` are taken with F = 1 (a kernel alone on the chip).  --no-cpu-baseline and --no-extras leave parts of --full out.
 
 Multi-GPU (BASELINE config 3): the 64-frame sequence is sharded by frame — rank r renders frames r, r+N, ...
   --scaling weak   (default; what the driver runs): every rank times K steps, per-GPU work is fixed (24 views per step);
   --scaling strong : the job is fixed — K frame-steps in total (default 64 = config 3's sequence), K/N per rank.
   --shard views    : the split Topo4D's REAL loop could use (frames are sequential there, train.py:646: frame t starts from
                      frame t-1): every rank steps through ALL frames and renders views r::N of each (24/8 = 3 views per rank);
-                     --allreduce-grads adds the data-parallel gradient all_reduce.  The default command carries this figure too
+                     --allreduce-grads adds the data-parallel gradient all_reduce.  The --full line carries this figure too
                      (`view_sharded`), next to the frame-sharded `value` / `strong`.
 The only collective is an RCCL all_gather of the per-view scalar losses (24 floats per rank per step), overlapped with the
 next step.
 
-The JSON line carries `roofline` (dominant kernel by HIP-event time, algorithmic bytes per launch, HBM traffic and the
+The --full JSON line carries `roofline` (dominant kernel by HIP-event time, algorithmic bytes per launch, HBM traffic and the
 vector-ALU counters of the committed rocprofv3 passes), `cpu_baseline` (oracle/raster_oracle.c, OpenMP, bounded sample,
 min of 5), `repeats` (`value`, `sequential` and `scenario_b` each time ONE region of exactly --steps steps; the other side figures
 are medians of several regions of their own), `scenario_b` (unsaturated opacities), `single_view` (the reference's own call shape: one
@@ -585,7 +590,7 @@ def forecast_probe(dev, in_flight):
 
 
 def c4_probe(dev, steps=6):
-    """BASELINE config 4 (24 x 2048^2, P = 120,000, SH degree 3: 'the 1-MI355X HBM-roofline run') in the default command."""
+    """BASELINE config 4 (24 x 2048^2, P = 120,000, SH degree 3: 'the 1-MI355X HBM-roofline run') in the --full line."""
     wl = Workload("C4", "A", dev, in_flight=2, resident=2)
     wl.learn_capacity()
     dt, _, st = timed_run(wl, steps, 2, 0.1, lambda: torch.cuda.synchronize(dev), lambda x: x, regions=5, min_region_s=0.0)
@@ -948,8 +953,12 @@ def main():
                          "one-GPU run's, --frames-in-flight of them in flight.  1: one frame at a time on one stream - the schedule of "
                          "Topo4D's real loop, whose frames are sequential (train.py:646)")
     ap.add_argument("--allreduce-grads", action="store_true", help="--shard views: sum the view-summed parameter gradients over the ranks")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the scenario-B and single-view side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure and check everything else too: `sequential`, the other scaling mode, the per-kernel "
+                         "HIP-event pass and `roofline`, `view_sharded`, the one-GPU side measurements and `cpu_baseline` (minutes).  Without "
+                         "it a run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip `view_sharded` and the one-GPU side measurements")
     ap.add_argument("--cpu-sample-views", type=int, default=0)
     ap.add_argument("--frames-in-flight", dest="in_flight", type=int, default=int(os.environ.get("T4D_BENCH_IN_FLIGHT", "0")),
                     help="independent frames in flight on as many HIP streams (1 = one frame after the other on one stream; "
@@ -1050,7 +1059,7 @@ def main():
             dumped = {"dir": args.dump_outputs, "step": my_steps - 1, "arrays": dump_outputs(wl.last_outputs, args.dump_outputs)}
         wl.last_outputs = None
     sequential = None
-    if wl.F > 1:                     # the same steps, one frame after the other on one stream: what the overlap is worth
+    if args.full and wl.F > 1:       # the same steps, one frame after the other on one stream: what the overlap is worth
         wl.sequential = True
         dts, _, sts_seq = timed_run(wl, my_steps, args.warmup, 0.05, barrier, all_reduce_max)
         wl.sequential = False
@@ -1060,7 +1069,7 @@ def main():
     # The OTHER scaling mode in the same line: the driver's one command per N must yield both the weak figure (`value`) and the
     # number north_star asks for - the fixed 64-frame job of BASELINE config 3 split over the ranks (strong scaling).
     other = None
-    if args.config == "C2" and not by_views:
+    if args.full and args.config == "C2" and not by_views:
         o_steps = 20 if args.scaling == "strong" else max(1, min(strong_steps_per_rank, 512))
         dto, _, sto = timed_run(wl, o_steps, min(args.warmup, 2), 0.05, barrier, all_reduce_max, regions=3,
                                 min_region_s=(0.0 if args.scaling == "weak" else MIN_REGION_S))
@@ -1093,44 +1102,45 @@ def main():
     # ---- per-kernel durations with HIP events (same steps again; keeps `value` free of event overhead) ----
     # Every rank replays the steps (a step contains the loss all_gather when N > 1, so all ranks must take part);
     # only rank 0 records events.
-    prof, tp = kernel_profile(wl, my_steps)
     roofline = None
-    sh_bytes = 0 if cfg["sh_degree"] is None else 3 * (cfg["sh_degree"] + 1) ** 2 * 4
-    VL = V * G                       # views per launch set
-    R_view = total_pairs_all / VL
-    per_kernel, total_bytes = algorithmic_bytes(P, R_view, H * W, sh_bytes)
-    if rank == 0:
-        kernels = {}
-        for name, (ms, n) in prof.items():
-            if n:
-                kernels[name] = {"avg_us": round(1e3 * ms / n, 2), "launches": n,
-                                 "alg_GBs": round(per_kernel[name] * VL / (1e-3 * ms / n) / 1e9, 1)}
-        dom = max(kernels, key=lambda k: kernels[k]["avg_us"])
-        ach = per_kernel[dom] * VL / (kernels[dom]["avg_us"] * 1e-6) / 1e9
-        traffic = load_profile_json("traffic.json", args.config, dom)
-        # vector-ALU counters of the committed rocprofv3 --pmc passes (tools/prof.sh -> profiles/valu.json): what actually limits
-        # the render kernels (HISTORY.md section 5).  busy = SQ_ACTIVE_INST_VALU (quad-cycles) * 4 / (SIMDs * kernel cycles).
-        valu = load_profile_json("valu.json", args.config, dom)
-        # What bounds the dominant kernel, FROM THE COUNTERS: the vector ALUs are "busy" SQ_ACTIVE_INST_VALU x 4 / (SIMDs x kernel
-        # cycles) of the time; above 0.6 the kernel is issue-bound and the HBM fraction is low by construction.  `achieved`/`peak`/
-        # `frac` stay the HBM figures the contract asks for; `issue` and `useful_lane_fraction` sit next to them.
-        busy = valu.get("valu_busy") if valu else None
-        lanes_key = args.config + ("" if args.opacity == "A" else "_" + args.opacity)
-        lanes = load_profile_json("lanes.json", lanes_key, "bwd" if dom == "k_render_bwd" else "fwd")
-        issue = None
-        if valu:
-            issue = {"valu_busy": busy, "achieved_inst_per_cycle_per_simd": round(valu["SQ_INSTS_VALU"] / (1024.0 * valu["kernel_cycles"]), 4),
-                     "peak_inst_per_cycle_per_simd": 0.45, "note": "peak = measured v_fma_f32 rate (tools/micro/valu_issue.hip); DPP adds run at 0.23"}
-        roofline = {"bound": ("valu" if busy is not None and busy > 0.6 else "hbm"), "kernel": dom, "achieved": round(ach, 1),
-                    "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                    "frac": round(ach / PEAK_HBM_GBS, 4), "traffic": traffic,
-                    "alg_bytes_per_launch": int(per_kernel[dom] * VL), "avg_us": kernels[dom]["avg_us"],
-                    "pairs_per_view": int(R_view), "ms_per_step_profiled": round(1e3 * tp / my_steps, 4),
-                    "pipeline_alg_bytes_per_view": int(total_bytes), "kernels": kernels,
-                    "valu": valu, "issue": issue,
-                    "useful_lane_fraction": (lanes or {}).get("useful_lane_fraction"), "row_balance": (lanes or {}).get("row_balance"),
-                    "counters": counters_provenance(args.config, lanes_key),
-                    "measured_limiter": ("vector-ALU issue" if busy is not None and busy > 0.6 else None)}
+    if args.full:
+        prof, tp = kernel_profile(wl, my_steps)
+        sh_bytes = 0 if cfg["sh_degree"] is None else 3 * (cfg["sh_degree"] + 1) ** 2 * 4
+        VL = V * G                       # views per launch set
+        R_view = total_pairs_all / VL
+        per_kernel, total_bytes = algorithmic_bytes(P, R_view, H * W, sh_bytes)
+        if rank == 0:
+            kernels = {}
+            for name, (ms, n) in prof.items():
+                if n:
+                    kernels[name] = {"avg_us": round(1e3 * ms / n, 2), "launches": n,
+                                     "alg_GBs": round(per_kernel[name] * VL / (1e-3 * ms / n) / 1e9, 1)}
+            dom = max(kernels, key=lambda k: kernels[k]["avg_us"])
+            ach = per_kernel[dom] * VL / (kernels[dom]["avg_us"] * 1e-6) / 1e9
+            traffic = load_profile_json("traffic.json", args.config, dom)
+            # vector-ALU counters of the committed rocprofv3 --pmc passes (tools/prof.sh -> profiles/valu.json): what actually limits
+            # the render kernels (HISTORY.md section 5).  busy = SQ_ACTIVE_INST_VALU (quad-cycles) * 4 / (SIMDs * kernel cycles).
+            valu = load_profile_json("valu.json", args.config, dom)
+            # What bounds the dominant kernel, FROM THE COUNTERS: the vector ALUs are "busy" SQ_ACTIVE_INST_VALU x 4 / (SIMDs x kernel
+            # cycles) of the time; above 0.6 the kernel is issue-bound and the HBM fraction is low by construction.  `achieved`/`peak`/
+            # `frac` stay the HBM figures the contract asks for; `issue` and `useful_lane_fraction` sit next to them.
+            busy = valu.get("valu_busy") if valu else None
+            lanes_key = args.config + ("" if args.opacity == "A" else "_" + args.opacity)
+            lanes = load_profile_json("lanes.json", lanes_key, "bwd" if dom == "k_render_bwd" else "fwd")
+            issue = None
+            if valu:
+                issue = {"valu_busy": busy, "achieved_inst_per_cycle_per_simd": round(valu["SQ_INSTS_VALU"] / (1024.0 * valu["kernel_cycles"]), 4),
+                         "peak_inst_per_cycle_per_simd": 0.45, "note": "peak = measured v_fma_f32 rate (tools/micro/valu_issue.hip); DPP adds run at 0.23"}
+            roofline = {"bound": ("valu" if busy is not None and busy > 0.6 else "hbm"), "kernel": dom, "achieved": round(ach, 1),
+                        "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                        "frac": round(ach / PEAK_HBM_GBS, 4), "traffic": traffic,
+                        "alg_bytes_per_launch": int(per_kernel[dom] * VL), "avg_us": kernels[dom]["avg_us"],
+                        "pairs_per_view": int(R_view), "ms_per_step_profiled": round(1e3 * tp / my_steps, 4),
+                        "pipeline_alg_bytes_per_view": int(total_bytes), "kernels": kernels,
+                        "valu": valu, "issue": issue,
+                        "useful_lane_fraction": (lanes or {}).get("useful_lane_fraction"), "row_balance": (lanes or {}).get("row_balance"),
+                        "counters": counters_provenance(args.config, lanes_key),
+                        "measured_limiter": ("vector-ALU issue" if busy is not None and busy > 0.6 else None)}
     if dist is not None:
         barrier()
 
@@ -1138,7 +1148,7 @@ def main():
     # `value`: the 64 independent frames of config 3, N of them per launch set (24 views per set at every N) and --frames-in-flight
     # sets in flight; `sequential_frames`: one frame at a time on one stream, the schedule Topo4D's real loop allows (train.py:646).
     view_sharded = None
-    if not by_views and not args.no_extras and args.config == "C2":
+    if args.full and not by_views and not args.no_extras and args.config == "C2":
         def run_view_sharded(frames_per_launch, in_flight):
             wv = Workload(args.config, args.opacity, dev, rank, world, in_flight, gather=dist is not None, view_shard=(rank, world),
                           resident=4, frames_per_launch=frames_per_launch)
@@ -1169,7 +1179,7 @@ def main():
 
     # ---- side measurements on one GPU ----
     scenario_b = single_view = drop_in = small_v = forecast = c4 = dense_1m = full_iteration = loss_k = bake = None
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         def guarded(fn, *a):
             try:                        # side measurements must never take the headline number down with them
                 return fn(*a)
@@ -1213,7 +1223,7 @@ def main():
             roofline["pipeline_frac_of_peak"] = round(value / world * total_bytes / 1e9 / PEAK_HBM_GBS, 4)
             roofline["pipeline_frac_of_achievable"] = round(value / world * total_bytes / 1e9 / ACHIEVABLE_HBM_GBS, 4)
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             n_s = args.cpu_sample_views or (24 if args.config == "C2" else 4)
             try:
                 cpu = cpu_baseline(cfg, n_s, reps=5)
@@ -1223,7 +1233,7 @@ def main():
             "metric": "rasterizer fwd+bwd views/sec", "value": round(value, 2), "unit": "views/s",
             "n_gpus": world, "steps": (my_steps * G if by_views else (my_steps * world if args.scaling == "strong" else args.steps)), "warmup": args.warmup,
             "ms_per_step": round(1e3 * dt / (my_steps * G), 4), "higher_is_better": True, "scaling": args.scaling, "repeats": repeats,
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": f"{args.config}: {V} views x {H}x{W}, P={P} vertex-bound Gaussians, "
                                    f"{'SH degree %d' % cfg['sh_degree'] if cfg['sh_degree'] is not None else 'precomputed RGB'}, "
                                    f"opacity scenario {args.opacity}, forward+backward, per-view gradients",

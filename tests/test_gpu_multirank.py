@@ -43,7 +43,7 @@ def _run(cmd, env):
 @pytest.mark.parametrize("scaling,steps", [("weak", 3), ("strong", 6)])
 def test_two_rank_dry_run_matches_single_rank_frame_by_frame(scaling, steps):
     env = dict(os.environ, T4D_BENCH_SHARE_GPU="1", T4D_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = ["--warmup", "1", "--prewarm-s", "0", "--no-cpu-baseline", "--no-extras"]
+    common = ["--warmup", "1", "--prewarm-s", "0", "--full", "--no-cpu-baseline", "--no-extras"]      # --full: `roofline`
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", str(steps), "--scaling", scaling] + common,
                dict(env, T4D_BENCH_DUMP_LOSSES="2"))
@@ -71,28 +71,29 @@ def test_rccl_branch_with_a_process_group_of_one_rank():
     """The driver's launch line with ONE rank and the real backend ("nccl" = RCCL): init_process_group(device_id=...), the
     asynchronous all_gather_into_tensor of the per-view losses on the step's stream, barrier(device_ids=...), the MAX
     all_reduce of the timing and destroy_process_group all execute once on the test box's GPU.  The gathered losses equal the
-    single-process ones bit for bit, and the line carries both scaling modes."""
+    single-process ones bit for bit, and the --full line carries both scaling modes."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", T4D_DIST_BACKEND="nccl", T4D_BENCH_DUMP_LOSSES="2",
                T4D_FORCE_COLLECTIVES="1")       # a one-rank group takes the no-collective fast path otherwise (dist._group_active)
-    common = ["--warmup", "1", "--prewarm-s", "0", "--no-cpu-baseline", "--no-extras"]
+    common = ["--warmup", "1", "--prewarm-s", "0", "--full", "--no-cpu-baseline", "--no-extras"]       # --full: `strong`
     one = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                 "--master-port", str(_free_port()), "bench.py", "--gpus", "1", "--steps", "3"] + common, env)
     plain = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3"] + common,
                  dict(os.environ, T4D_BENCH_DUMP_LOSSES="2"))
     assert one["dist_backend"] == "nccl" and plain["dist_backend"] is None
     assert one["n_gpus"] == 1 and one["scaling"] == "weak" and one["value"] > 0
-    for line in (one, plain):                       # the fixed 64-frame job of config 3 rides along in every line
+    for line in (one, plain):                       # the fixed 64-frame job of config 3 rides along in every --full line
+        assert line["full"] is True
         assert line["strong"]["scaling"] == "strong" and line["strong"]["job_frame_steps"] == 64 and line["strong"]["value"] > 0
     np.testing.assert_array_equal(np.asarray(one["gathered_losses_first_steps"], np.float32),
                                   np.asarray(plain["gathered_losses_first_steps"], np.float32))
 
 
 def test_the_drivers_two_gpu_command_carries_every_multi_rank_object():
-    """The command the driver launches for N = 2 (no --no-extras): `value` (weak, frame-sharded), `strong` (the 64-frame job) AND
+    """The command the driver launches for N = 2 with --full (no --no-extras): `value` (weak, frame-sharded), `strong` (the 64-frame job) AND
     `view_sharded` (12 views per rank and frame) all come out of one line; the one-GPU-only probes stay out of it."""
     env = dict(os.environ, T4D_BENCH_SHARE_GPU="1", T4D_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--prewarm-s", "0"], env)
+                "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--prewarm-s", "0", "--full"], env)
     assert two["n_gpus"] == 2 and two["scaling"] == "weak" and two["value"] > 0
     assert two["repeats"]["regions"] == 1 and two["repeats"]["steps_per_region"] == 2          # --steps 2: exactly two timed steps
     assert two["strong"]["job_frame_steps"] == 64 and two["strong"]["value"] > 0
@@ -108,7 +109,7 @@ def test_view_sharded_two_rank_dry_run_equals_the_24_view_launch():
     share its launch, so the gathered per-view losses of the two ranks' launch sets (12 cameras x 2 consecutive frames each: the
     default --frames-per-launch is the number of ranks) equal those of the one-GPU run's 24-view launches bit for bit, and so do
     rank 0's per-view gradient checksums (views 0, 2, 4, ...).  The same command with ONE RCCL rank runs too."""
-    common = ["--steps", "2", "--warmup", "1", "--prewarm-s", "0", "--no-cpu-baseline", "--no-extras", "--shard", "views"]
+    common = ["--steps", "2", "--warmup", "1", "--prewarm-s", "0", "--shard", "views"]
     env = dict(os.environ, T4D_BENCH_SHARE_GPU="1", T4D_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", T4D_BENCH_DUMP_LOSSES="2")
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + common, env)
@@ -145,7 +146,7 @@ def test_strong_scaling_rounds_the_job_up_to_whole_steps_per_rank():
     env = dict(os.environ, T4D_BENCH_SHARE_GPU="1", T4D_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                 "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", "7", "--scaling", "strong",
-                "--warmup", "1", "--prewarm-s", "0", "--no-cpu-baseline", "--no-extras"], env)
+                "--warmup", "1", "--prewarm-s", "0", "--full", "--no-cpu-baseline", "--no-extras"], env)
     assert two["config"]["steps_per_rank"] == 4 and two["steps"] == 8 and two["scaling"] == "strong"
     assert two["weak"]["scaling"] == "weak" and two["weak"]["value"] > 0
 
@@ -160,7 +161,7 @@ def test_view_sharded_four_rank_dry_run_equals_the_24_view_launch():
     (HISTORY.md section 5), whose replay starts from the forward's snapshots: its sums - and the per-view scalar <colour, dL/dcolour>
     the ranks gather, a by-product of that replay - agree with the whole-tile replay of the 24-view launch to summation-order
     rounding.  What IS exact there: every view lands in its slot of the gathered vector."""
-    common = ["--steps", "2", "--warmup", "1", "--prewarm-s", "0", "--no-cpu-baseline", "--no-extras", "--shard", "views"]
+    common = ["--steps", "2", "--warmup", "1", "--prewarm-s", "0", "--shard", "views"]
     env = dict(os.environ, T4D_BENCH_SHARE_GPU="1", T4D_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", T4D_BENCH_DUMP_LOSSES="1")
     batched = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
                     "--master-port", str(_free_port()), "bench.py", "--gpus", "4"] + common, env)
@@ -195,17 +196,17 @@ def test_view_sharded_four_rank_dry_run_equals_the_24_view_launch():
 
 
 def test_frame_sharded_four_rank_dry_run_of_the_drivers_default_line():
-    """`bench.py --gpus 4` as the driver launches it (default flags: weak frame sharding as `value`, the fixed 64-frame job as
+    """`bench.py --gpus 4 --full` as the driver launches it (otherwise default flags: weak frame sharding as `value`, the fixed 64-frame job as
     `strong`, the view-sharded split as `view_sharded`), four ranks sharing the test GPU: every multi-rank object comes out of ONE
     line and frame f's gathered losses equal the one-rank run's."""
     env = dict(os.environ, T4D_BENCH_SHARE_GPU="1", T4D_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", T4D_BENCH_DUMP_LOSSES="1")
     four = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-                 "--master-port", str(_free_port()), "bench.py", "--gpus", "4", "--steps", "2", "--warmup", "1", "--prewarm-s", "0"], env)
+                 "--master-port", str(_free_port()), "bench.py", "--gpus", "4", "--steps", "2", "--warmup", "1", "--prewarm-s", "0", "--full"], env)
     assert four["n_gpus"] == 4 and four["scaling"] == "weak" and four["value"] > 0
     assert four["config"]["parallelism"] == "frame-sharded x4"
     assert four["strong"]["job_frame_steps"] == 64 and four["strong"]["value"] > 0
     assert four["view_sharded"]["views_per_rank"] == 6 and four["view_sharded"]["value"] > 0
-    one = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--prewarm-s", "0", "--no-cpu-baseline", "--no-extras"],
+    one = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--prewarm-s", "0"],
                dict(os.environ, T4D_BENCH_DUMP_LOSSES="4"))
     g4 = np.asarray(four["gathered_losses_first_steps"], np.float32)         # [1 step, 4 ranks x 24]: frames 0..3
     g1 = np.asarray(one["gathered_losses_first_steps"], np.float32)          # [4 steps, 24]

@@ -8,7 +8,7 @@ for rep in $(seq 1 ${REPS:-1}); do
 for tag in "$@"; do
   lib=$ROOT/topo4d_amd/csrc/variants/lib_$tag.so
   [ "$tag" = shipped ] && lib=$ROOT/topo4d_amd/csrc/libtopo4d_raster.so
-  T4D_LIB=$lib python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --frames-in-flight 1 ${BENCH_ARGS} 2>/dev/null | tail -1 | python -c "
+  T4D_LIB=$lib python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras --frames-in-flight 1 ${BENCH_ARGS} 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['kernels']
 print('%-10s step %.3f ms  ' % ('$tag', d['ms_per_step']) + '  '.join('%s %.1f' % (n[2:], v['avg_us']) for n, v in k.items()))"

@@ -12,7 +12,7 @@ cd /tmp
 if [ -n "$PROF_CMD" ]; then
   B="$PROF_CMD"; LONG=""; SHORT=""
 else
-  B="python $ROOT/bench.py --no-cpu-baseline --no-extras --frames-in-flight 1"     # kernels alone on the chip: per-kernel figures
+  B="python $ROOT/bench.py --frames-in-flight 1"     # kernels alone on the chip: per-kernel figures
   LONG="--steps 20 --warmup 3"; SHORT="--steps 2 --warmup 1"
 fi
 # Every pass runs under its own time limit and only if the one before it ended well: after a fault or a hang nothing more is started.

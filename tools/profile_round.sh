@@ -29,6 +29,8 @@ cp profiles/traffic.json profiles/valu.json profiles/lanes.json gpurun_out/ 2>/d
 tools/side_benches.sh ${R}_side > /dev/null 2>&1
 python tools/small_launch.py 2>&1 | grep -v amdgpu.ids > gpurun_out/${R}_small_launch.txt      # 1-8 views per call, every build switch
 tools/micro/sort_bin > gpurun_out/${R}_sort_bin_micro.txt 2>&1
-python bench.py > gpurun_out/${R}_bench_c2.json 2> gpurun_out/${R}_bench_c2.err
-python bench.py --config C4 --steps 20 > gpurun_out/${R}_bench_c4.json 2> gpurun_out/${R}_bench_c4.err
+# the two --full bench lines go beside the round's other artefacts: into the folder that holds the ${R}_c2 of tools/prof.sh above
+O=$(dirname "$(ls -d $ROOT/*/${R}_c2 | head -1)")
+python bench.py --full > $O/${R}_bench_c2.json 2> $O/${R}_bench_c2.err
+python bench.py --full --config C4 --steps 20 > $O/${R}_bench_c4.json 2> $O/${R}_bench_c4.err
 ls gpurun_out | grep ${R}_
