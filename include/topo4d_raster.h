@@ -485,6 +485,35 @@ int t4d_drift_match(const uint8_t *luma_a, const uint8_t *valid_a, const uint8_t
                     int32_t h, int32_t w, int32_t block, int32_t stride, int32_t radius, int32_t min_count, int32_t *out, void *scratch,
                     size_t scratch_bytes, void *hip_stream);
 
+/* What follows from the measured drift (drift.dense_flow, drift.warp, csrc/t4d_stabilise.hip): the flow of every texel of the
+ * full-resolution texture, and frame b's texture resampled through it, so that a feature sits on the texel it has in frame a.
+ * Integer arithmetic in a fixed order, so both are pure functions of their inputs; tests/stabilise_ref.py restates the rule in numpy.
+ * The matcher ran at level L: on maps of h x w texels, halved L times from the full resolution H x W with H = h 2^L and W = w 2^L
+ * (L in 0..8; both divisible by 2^L).  A displacement d = (dy, dx) of block (by, bx), in texels of level L, says that the feature
+ * at x in frame a lies at x + d in frame b.  labels uint8 [H,W] is the full-resolution island map, 0 = no island.
+ * Nodes: block (by, bx) of the nby x nbx blocks of t4d_drift_match on h x w (block B, stride S) is a node at the doubled
+ * full-resolution texel indices ny = 2^(L+1) (by S + B/2) - 1 and nx = 2^(L+1) (bx S + B/2) - 1: the block's centre, which falls
+ * between two texels (texel y has the doubled index 2 y).  Its value is q = rint(d 2^L 256) (round half to even), int32, in units of
+ * 1/256 of a full-resolution texel, with |q| <= 2^22; nodes is int32 [nby,nbx,2] = (q_y, q_x).  Its label is
+ * labels[2^L (by S + B/2)][2^L (bx S + B/2)].  It takes part when kept[by][bx] (uint8 [nby,nbx]) is non-zero and its label is not 0.
+ * t4d_drift_dense: with T = reach 2 S 2^L (reach in 1..4; T <= 46340, so that a weight fits 32 bits: T4D_ERR_ARG otherwise), a
+ * texel (y, x) of label l != 0 gives every participating node of label l the weight wy wx, wy = max(0, T - |2 y - ny|) and wx = max(0, T - |2 x - nx|): with reach 1 the bilinear weights between the four
+ * nodes round the texel, renormalised over those that take part.  num = sum of w q (per component) and den = sum of w in 64-bit
+ * integers, which the bounds above keep below 2^63.  flow int32 [H,W,2] = (f_y, f_x) = floor((2 num + den) / (2 den)) and support
+ * uint8 [H,W] = 1 where den > 0; a texel with l = 0 or den = 0 gets f = 0 and support = 0, and so does every texel of a shape
+ * without a block (nodes and kept may then be NULL).  flow must be aligned to 8 bytes.
+ * t4d_drift_warp: image uint8 [H,W,c], c in (1, 3, 4), valid uint8 [H,W] (non-zero = the texel holds a photograph) and labels are
+ * frame b's; flow as above.  For texel (y, x): Y = 256 y + f_y, X = 256 x + f_x, y0 = Y >> 8, ty = Y & 255 (arithmetic shift: the
+ * floor), x0 and tx likewise.  The taps (y0, x0), (y0, x0 + 1), (y0 + 1, x0), (y0 + 1, x0 + 1) weigh (256 - ty) (256 - tx),
+ * (256 - ty) tx, ty (256 - tx), ty tx.  A tap is admissible when it lies inside the image, valid is non-zero there, its label equals
+ * labels[y][x] and that label is not 0.  With Wt = the sum of the admissible weights, out_image = floor((2 sum of w v + Wt) / (2 Wt))
+ * per channel and out_valid = 1; where Wt = 0 both are 0.  A texel without support has f = 0 and is a copy.  The outputs must not
+ * be the inputs and must be aligned to 4 bytes. */
+int t4d_drift_dense(const int32_t *nodes, const uint8_t *kept, const uint8_t *labels, int32_t h, int32_t w, int32_t block, int32_t stride,
+                    int32_t level, int32_t reach, int32_t *flow, uint8_t *support, void *hip_stream);
+int t4d_drift_warp(const uint8_t *image, const uint8_t *valid, const uint8_t *labels, const int32_t *flow, int32_t h, int32_t w, int32_t c,
+                   uint8_t *out_image, uint8_t *out_valid, void *hip_stream);
+
 /* Lossless PNG encoder for a device image (write_texture(..., encoder="gpu"): the last CPU step of save_mesh, helpers.py:953-960).
  * image [h,w,c] on the device, uint8 (is_float32 = 0) or float32 (is_float32 = 1, quantised exactly like numpy's
  * (x*255).astype(np.uint8) on x86-64: truncation toward zero to int32, low byte kept, NaN -> 0); c in {1, 3, 4} gives colour
