@@ -251,6 +251,17 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
     auto &s_wmax = sh.wmax;
     auto &s_list = sh.list;
     constexpr int kNull = kBwdBatch;
+    // PF (the throughput build on whole tiles): a batch is staged by the waves that write no records - waves kStageWave0 and up
+    // request batch bi - 1 while the waves below them write batch bi out, and commit it to LDS behind the barrier that ends
+    // the write-out (which reads the centres and pair slots of batch bi).  Staged one after the other on the same two waves,
+    // the new batch's loads queued behind the record stores (one in-order counter for both), the other two waves idled
+    // through both phases, and all of the per-batch vector work sat on the SIMDs of waves 0 and 1.  The latency and the
+    // segmented builds stage one batch per item or have the chip's LDS to themselves: they stage where they always did.
+    constexpr bool PF = !LAT && !SEG;
+    constexpr int kStageWave0 = kBlock / 64 - kChunks;          // first staging wave of the PF build
+    static_assert(!PF || (kStageWave0 >= kChunks && kBwdBatch == kChunks * 64), "staging and write-out waves are disjoint, one lane per slot");
+    // what a staging lane holds of its splat between request and commit
+    struct Staged { unsigned long long key; float r2; float2 p; int rad; uint32_t po; float4 c; float c0, c1, c2; };
 
     // Whole tiles: the items are ordered by length, so a tile workgroup whose FIRST item is empty has nothing to do at all (a
     // quarter of a config-2 launch, two thirds of config 4's): it leaves here, before the slab clear and before the kernel's
@@ -340,6 +351,84 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
     float2 *grad_pair = reinterpret_cast<float2 *>(kt->grad_pair) + (size_t)v * kt->cap * (kGP / 2);
     const float *vr = kt->views + (size_t)v * T4D_VIEW_FLOATS;
 
+    // Staging in two halves.  stage_request_key + stage_request: lane t asks for everything slot t of the batch at list position
+    // lo needs - the key and the kept cut-off, and behind the key ONE level of dependent loads: everything a splat needs is
+    // requested before any of it is used (centre and radius, then the pair slot, then conic and colour were four dependent
+    // round trips per batch while the other waves waited at the barrier).  stage_commit: the same lane turns what arrived
+    // into the staged record, the cut-off and the pair slot in LDS.  `want` = the batch will be walked (or may be: the tile's
+    // first batch is requested before that is known); conic, colour and cut-off are loaded only then, and used only if the
+    // batch is live.
+    // stage_commit reads of a Staged exactly what stage_request loaded under the same conditions; nothing else is set.  A
+    // Staged starts out as stage_none leaves it: every member defined by an empty asm statement - no instruction, but a
+    // definition on every path.  Left uninitialised, a member keeps "whatever it held in the previous tile or batch" on the
+    // waves that request nothing, and those fourteen registers stay allocated across the walk (84 bytes of scratch).
+    auto stage_none = [](Staged &s) __attribute__((always_inline)) {
+        asm("" : "=v"(s.key), "=v"(s.r2), "=v"(s.p.x), "=v"(s.p.y), "=v"(s.rad), "=v"(s.po));
+        asm("" : "=v"(s.c.x), "=v"(s.c.y), "=v"(s.c.z), "=v"(s.c.w), "=v"(s.c0), "=v"(s.c1), "=v"(s.c2));
+    };
+    // (the array bases are read from the parameter block again, scalar loads on the requesting waves: held in scalar
+    // registers from the tile's prologue to the last request they pushed five other scalars out into vector lanes)
+    auto stage_request_key = [&](Staged &s, const int t, const uint32_t lo, const int cnt, const bool want) __attribute__((always_inline)) {
+        const kp_kernarg_p kq = kernarg_kp();
+        const size_t at = (size_t)v * kq->cap + off + lo;
+        if (t < cnt) {
+            s.key = kq->keys[at + t];
+            if (want) s.r2 = kq->cut_r2[at + t];                               // = cutoff_radius2(c), kept by the forward
+        }
+    };
+    auto stage_request = [&](Staged &s, const int t, const int cnt, const bool want) __attribute__((always_inline)) {
+        const kp_kernarg_p kq = kernarg_kp();
+        const size_t vP = (size_t)v * kq->P;
+        if (t < cnt) {
+            const uint32_t g = (uint32_t)s.key;
+            if (g < (uint32_t)kp.P) {                                          // stale entries after an overflow are skipped
+                s.p = kq->xy[vP + g];
+                s.rad = kq->radii[vP + g];
+                s.po = kq->pair_off[vP + g];
+                if (want) { s.c = kq->conic_opacity[vP + g]; s.c0 = rgb[3 * (size_t)g]; s.c1 = rgb[3 * (size_t)g + 1]; s.c2 = rgb[3 * (size_t)g + 2]; }
+            }
+        }
+    };
+    auto stage_commit = [&](const Staged &s, const int t, const int cnt, const bool live) __attribute__((always_inline)) {
+        if (t < cnt) s_pair[t] = 0xffffffffu;
+        float r2 = -1.f;                                 // a slot without a splat touches nothing ...
+        float2 p = make_float2(0.f, 0.f);                // ... and holds a finite centre
+        if (t < cnt && (uint32_t)s.key < (uint32_t)kp.P) {
+            p = s.p;
+            int x0, y0, x1, y1;
+            tile_rect(s.p.x, s.p.y, s.rad, kp.gx, kp.gy, x0, y0, x1, y1);
+            const int local = (ty - y0) * (x1 - x0) + (tx - x0);
+            s_pair[t] = (tx >= x0 && tx < x1 && ty >= y0 && ty < y1) ? s.po + (uint32_t)local : 0xffffffffu;
+            if (live) {
+                const float4 q4 = scale_conic(s.c);
+                float2 *rec = reinterpret_cast<float2 *>(s_rec + t * kEnt);
+                rec[0] = make_float2(q4.x, q4.y); rec[1] = make_float2(q4.z, q4.w);
+                rec[2] = make_float2(s.c0, s.c1);
+                rec[3] = make_float2(s.c2, __uint_as_float((uint32_t)(s.key >> 32)));
+                r2 = s.r2;
+            }
+        }
+        if (live) {
+            reinterpret_cast<float2 *>(s_rec + t * kEnt)[4] = p;
+            s_r2[t] = r2;
+        }
+    };
+    const int nb = (int)((n + kBwdBatch - 1) / kBwdBatch);
+    const int stage_t = tid - kStageWave0 * 64;          // PF: the slot a lane of the staging waves stages
+    Staged st_first;
+    if (PF) stage_none(st_first);
+    // T4D_REGION staging
+    if (PF && wave >= kStageWave0) {
+        // the tile's first batch (its last): the keys go out ahead of the pixel-state loads below, what hangs on the keys
+        // behind them, so that the gathers are in flight under the row maxima and the barrier that follow.  (The memory counter
+        // is in order, and as compiled the wait for the keys also takes in the pixel loads - they sit in a divergent branch,
+        // and the wait count at the join is the conservative one: keys and pixel state share one round trip, the gathers are
+        // the second.)  Whether the batch is live is known only behind that barrier.
+        const uint32_t lo0 = (uint32_t)(nb - 1) * kBwdBatch;
+        stage_request_key(st_first, stage_t, lo0, (int)(n - lo0), true);
+    }
+    // T4D_REGION tile prologue
+
     int px, py;
     tile_pixel_bwd(tid, tx, ty, px, py);
     const bool inside = px < kt->W && py < kt->H;
@@ -356,6 +445,9 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
         if (DA && kt->dL_ddepth) ddep = kt->dL_ddepth[(size_t)v * HW + pix];
         if (DA && kt->dL_dalpha) dalp = kt->dL_dalpha[(size_t)v * HW + pix];
     }
+    // T4D_REGION staging
+    if (PF && wave >= kStageWave0) stage_request(st_first, stage_t, (int)(n - (uint32_t)(nb - 1) * kBwdBatch), true);
+    // T4D_REGION tile prologue
     const v2f dp01 = { dp0, dp1 };
     float T = T_final;
     // Suffix state of the replay.  Upstream keeps one running "colour behind me" per channel (+ depth, + alpha) and dots
@@ -368,7 +460,6 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
     // and dL/dalpha_i = (q_i - acc') T_i hold exactly - one multiply and one fused multiply-add less per step, and for a black
     // background (Topo4D: helpers.py setup_camera, bg = 0) the same bits as before.
     float acc = vr[35] * dp0 + vr[36] * dp1 + vr[37] * dp2;
-    const int nb = (int)((n + kBwdBatch - 1) / kBwdBatch);
     if (SEG && seg_j + 1 < nb) {
         // A segment that does not end at the list's end starts from the forward's snapshot at position p = (seg_j + 1) kSeg:
         // T = the transmittance in front of p, acc = the colour behind p as the recursion would hold it there,
@@ -395,6 +486,11 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
     if (lane == 0) s_wmax[wave] = wave_max;
     __syncthreads();
     const uint32_t tile_max = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
+    // T4D_REGION staging
+    if (PF && wave >= kStageWave0) {
+        const uint32_t lo0 = (uint32_t)(nb - 1) * kBwdBatch;
+        stage_commit(st_first, stage_t, (int)(n - lo0), lo0 < tile_max);
+    }
 
     for (int bi = SEG ? seg_j : nb - 1; bi >= (SEG ? seg_j : 0); bi--) {
         const uint32_t lo = (uint32_t)bi * kBwdBatch;
@@ -402,8 +498,9 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
         const bool live = lo < tile_max;      // workgroup-uniform
         // T4D_REGION staging
         // ---- stage ----
-        if (tid < cnt) s_pair[tid] = 0xffffffffu;
-        if (tid < kChunks * 64) {
+        // (PF: this batch was staged behind the previous write-out, or in the tile's prologue)
+        if (!PF && tid < cnt) s_pair[tid] = 0xffffffffu;
+        if (!PF && tid < kChunks * 64) {
             float r2 = -1.f;                                 // a slot without a splat touches nothing ...
             float2 p = make_float2(0.f, 0.f);                // ... and holds a finite centre
             if (tid < cnt) {
@@ -590,6 +687,20 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
             }
         }
         __syncthreads();
+        // the next batch of the tile (always a full one; none behind the tile's first)
+        const uint32_t lo_n = lo - (uint32_t)(bi > 0 ? kBwdBatch : 0);
+        const int cnt_n = bi > 0 ? kBwdBatch : 0;
+        const bool live_n = lo_n < tile_max;
+        Staged st;
+        if (PF) stage_none(st);
+        // T4D_REGION staging
+        if (PF && wave >= kStageWave0) {
+            // while the other waves write this batch out, the waves that have no record to write request the next one.  Its
+            // loads stay in flight across the barrier below - the compiler waits for them where stage_commit uses them - and
+            // queue behind no record store: those are the other waves'.
+            stage_request_key(st, stage_t, lo_n, cnt_n, live_n);
+            stage_request(st, stage_t, cnt_n, live_n);
+        } else
         // T4D_REGION write-out
         // ---- write one record per pair (zeros when no wave touched it); fixed wave order => deterministic ----
         if (tid < cnt) {
@@ -629,6 +740,9 @@ __global__ __launch_bounds__(kBlock) T4D_BWD_ATTR void k_render_bwd(const KP kp)
             }
         }
         __syncthreads();
+        // T4D_REGION staging
+        // (behind the barrier: the write-out read the centres and pair slots of the batch these stores replace)
+        if (PF && wave >= kStageWave0 && bi > 0) stage_commit(st, stage_t, cnt_n, live_n);
     }
     // T4D_REGION tile epilogue
     const kp_kernarg_p ke = kernarg_kp();

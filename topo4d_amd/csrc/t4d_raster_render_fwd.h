@@ -420,8 +420,10 @@ __global__ __launch_bounds__(kBlock) T4D_FWD_ATTR void k_render_fwd(const KP kp)
         }
         __syncthreads();
         if (LAT) {
-            // the next batch's records and the keys of the one after it: in flight during this batch's walk.  Requested BEHIND the
-            // barrier (a barrier waits for every outstanding memory operation of the wave), by every thread, finished wave or not.
+            // the next batch's records and the keys of the one after it: in flight during this batch's walk, requested by every
+            // thread, finished wave or not.  (They sit behind the barrier because they overwrite the registers the staging above
+            // reads, not because of the barrier itself: the compiler emits a bare s_barrier here and a counted vmcnt wait only where
+            // a loaded value is used, so plain loads stay in flight across a barrier - the backward's staging relies on that.)
             k_cur = k_nxt;
             k_nxt = ~0ull;
             const uint32_t pos2 = b + 2u * kFB + (uint32_t)tid;
