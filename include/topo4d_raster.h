@@ -165,7 +165,11 @@ int t4d_rasterize_forward(const T4DProblem *prob, const T4DForwardIO *io, T4DSta
 
 /* Backward: per-tile back-to-front replay (atomic-free, deterministic) -> per-Gaussian gather + chain rule.
  * If the forward that produced `state` overflowed its pair arena (only possible without T4D_FLAG_CHECKED), every
- * gradient of this call is written as ZERO: a truncated pass never yields garbage. */
+ * gradient of this call is written as ZERO: a truncated pass never yields garbage.
+ * `prob` must be the T4DProblem of the forward that produced `state`, FLAGS INCLUDED: which kernels run (whole tiles or depth
+ * segments, one launch or two) is re-derived from it, not read from the state.  The mix that goes wrong: a forward with
+ * T4D_FLAG_NO_LONG_BINS on a one-view launch of more than 8,192 tiles keeps no slot table, and a backward of the same call without
+ * the flag leaves the long tiles out of its whole-tile launch, expecting segments that were never written. */
 int t4d_rasterize_backward(const T4DProblem *prob, const T4DBackwardIO *io, void *hip_stream);
 
 /* Copies the status block of a forward's state buffer to the host (synchronises the stream). */

@@ -17,9 +17,11 @@
 //     (Gaussian,tile) pair, and the per-Gaussian kernel gathers its pairs in fixed order.  Gradients are
 //     bit-reproducible run to run.
 //
-// One translation unit in six files: this one (constants, state layout, kernel parameter block, device helpers, host side and C ABI)
-// and, included below, t4d_raster_binning.h, t4d_raster_sort.h, t4d_raster_render_fwd.h, t4d_raster_render_bwd.h and
-// t4d_raster_gaussian_bwd.h.
+// One translation unit in ten files: this one (state layout, kernel parameter block, device helpers, host side and C ABI);
+// t4d_raster_plan.h (plain C++: the regime constants and the launch plan - which kernels and builds a call runs, decided in one
+// place for the forward and the backward); the plain-C++ helpers t4d_tile_div.h and t4d_raster_visit_pad.h; and the kernels,
+// included below: t4d_raster_binning.h, t4d_raster_sort.h, t4d_raster_render_fwd.h, t4d_raster_render_fwd_long.h,
+// t4d_raster_render_bwd.h and t4d_raster_gaussian_bwd.h.
 // Kernels (DESIGN.md has the bytes/roofline of each):
 //   k_preprocess      A.1  per (view,Gaussian): cull, project, cov3D, EWA cov2D, conic, radius, tile rect, SH colour;
 //                          + per-tile counts and pair ranks + pair-slot allocation (one returning atomic per workgroup)
@@ -38,15 +40,14 @@
 //   k_preprocess_bwd  A.5  per (view,Gaussian): gather pair records, conic/cov2D/projection/cov3D chain rule
 //   k_sh_bwd16, k_sh_bwd   SH colours: dL/dshs and the view-direction term of dL/dmeans3D (degree 3 / any degree)
 //   k_view_dot_*, k_mark_visible: small utilities of the ABI
+#include "t4d_raster_plan.h"
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 #include <vector>
 
-#include "../../include/t4d_config.h"
-#include "../../include/topo4d_raster.h"
 #include "t4d_activations.h"
 #include "t4d_tile_div.h"
 #include "t4d_raster_visit_pad.h"
@@ -55,55 +56,16 @@
 
 namespace {
 
-constexpr int kBlock = 256;          // threads per workgroup everywhere (4 wave64)
-#ifndef T4D_FWD_BATCH
-#define T4D_FWD_BATCH 192
-#endif
-constexpr int kFwdBatch = T4D_FWD_BATCH;   // splats staged in LDS per round of the forward blend (one per thread: <= 256; sweep of round 3 with 7 waves per SIMD, config 2 / config 4: 128: 106 / 1,197 us, 192: 101.5 / 1,113, 256: 102 / 1,134)
 #ifndef T4D_BWD_BATCH
 #define T4D_BWD_BATCH 128
 #endif
 constexpr int kBwdBatch = T4D_BWD_BATCH;   // splats staged per round of the backward replay (64 or 128)
-constexpr int kSortLdsCap = 2048;    // keys sorted in LDS by k_sort_tiles (16 KiB: 8 workgroups per CU); longer bins go to k_sort_long
-constexpr int kLongBlock = 1024;     // k_sort_long_chunks, k_merge_long (bins beyond kSortLdsCap keys) and small launches' k_sort_tiles: threads per workgroup
-constexpr int kScanChunk = 1024;     // tiles scanned per workgroup of k_scan_tiles
 constexpr int kRankSortMax = 512;    // bins up to this length: register-sorted runs of 64 + one ranking pass (one barrier)
 constexpr int kHist = 1024;          // per-workgroup LDS tile histogram (bounding box of the tiles a workgroup touches)
 constexpr int kBuckets = 24;         // tile-length classes (floor(log2 n), descending; last = empty) for launch ordering
 constexpr int kGP = T4D_GRAD_PAIR_FLOATS;
-// pair-slot cursors per view, at most (same-address returning atomics are serial: see k_preprocess).  A view gets one cursor per 16
-// workgroups of Gaussians up to this many: 8 at config 2 (118 workgroups per view), 32 at config 4, 64 for ONE view of 10^6 Gaussians -
-// 3,907 workgroups on 8 cursors were 488 serial atomics each: k_preprocess 60.4 -> 37.8 us there (round 5; 256 cursors: 33.5, but the
-// scan's walk over them costs what that saves)
-constexpr int kCursorSegs = 64;
-// Small launches (the reference's own call shape: ONE view per call, train.py:661-673; a view-sharded rank: three views) cannot
-// fill the chip with whole tiles: a kernel lasts as long as its LONGEST tile list is walked by one workgroup.  For launches of
-// at most kSegMaxTiles tiles the backward is therefore cut along DEPTH: a tile list of n pairs becomes ceil(n / kSeg)
-// independent work items.  What makes them independent is kept by the forward: the per-pixel blend state (T, C, D) at every
-// kSeg-th list position (a "snapshot", 20 bytes per pixel and boundary) - the backward's replay of positions [j kSeg, (j+1) kSeg)
-// starts from the transmittance in front of position (j+1) kSeg and from the suffix colour (C_final - C_prefix) / T, both taken
-// from the snapshots instead of from the replay of everything behind.  No running value of the replay feeds a discrete
-// decision, so the segments take the decisions of the whole-list replay; sums differ by rounding only.
-#ifndef T4D_SEG
-#define T4D_SEG 128
-#endif
-constexpr int kSeg = T4D_SEG;        // list positions per backward segment of a 2-8 view launch; a ONE-view launch takes kSegOne (seg_positions)
-constexpr int kSegOne = 64;          // round 4 measured it with a compile-time switch: one view of Topo4D's size 85.4 -> 81.3 us (half the walk per
-                                     // work item, twice the list rounds in the forward), three views of the config-2 scene 176 -> 183: hence per launch
-constexpr int kSegMaxTiles = 8192;   // launches of at most this many tiles (V * T) run the segmented backward
-// A ONE-view launch of more tiles than that (the texture pass: one 4096 x 3008 view = 48,128 tiles of 10^6 Gaussians) fills the chip
-// with whole tiles - until the short tiles run out and a few workgroups are still walking lists of thousands of pairs: the SAME
-// number of wave-steps (counting build) took the backward 343 us on a scene whose longest list held 1,459 pairs and 400 / 906 us
-// (two cameras) on one with lists of 9,000 - 12,000.  There the tiles of at least kSegLongMin pairs - and only those - are cut into
-// segments (kSeg positions each, their own launch behind the whole-tile one, which skips them): same box, whole tiles / threshold
-// 1,024 / 2,048 / 4,096: 400 / 406 / 403 / 382 us and 906 / 414 / 398 / 529 us.  (Segments for EVERY tile of such a launch, the
-// small launches' way: 488 / 506 us and 50 us more in the forward, which then keeps 40,000 snapshots.)
-#ifndef T4D_SEG_LONG_MIN
-#define T4D_SEG_LONG_MIN 2048
-#endif
-constexpr int kSegLongMin = T4D_SEG_LONG_MIN;
 constexpr int kSnapFloats = 6;       // T, C0, C1, C2, D per pixel and boundary (+ the last contributor so far: the depth-parallel forward of long tiles)
-static_assert((kSegLongMin & (kSegLongMin - 1)) == 0, "k_fwd_long_prefix stops at the first work item of a shorter length CLASS (powers of two)");
+// (the constants that decide a launch's regime - kBlock, kSeg, kSegMaxTiles, ... - are in t4d_raster_plan.h)
 
 thread_local char g_err[512] = "";
 
@@ -138,34 +100,11 @@ struct DevStatus {            // first bytes of the state buffer
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-// segmented backward (see kSeg): decided by the problem's dimensions alone, so that t4d_state_bytes, the forward and the
-// backward of a call agree without talking to each other
-// 0: whole tiles only; 1: every tile is segmented (small launch); 2: the long tiles of a big one-view launch are
-inline int seg_mode(const T4DProblem &p)
-{
-    const long long T = (long long)((p.W + T4D_TILE_X - 1) / T4D_TILE_X) * (long long)((p.H + T4D_TILE_Y - 1) / T4D_TILE_Y);
-    if ((long long)p.n_views * T <= kSegMaxTiles) return 1;
-    return p.n_views == 1 ? 2 : 0;
-}
-inline bool seg_capable(const T4DProblem &p) { return seg_mode(p) != 0; }
-// Segment slots of a view.  Tile t (arena offset off, n pairs) owns the slots floor(off / kSeg) + t ... + ceil(n / kSeg) - 1:
-// disjoint from tile to tile ((off + n) / kSeg - off / kSeg >= floor(n / kSeg)) without a prefix sum over the tiles.
-// seg_mode 2 (only the tiles of at least kSegLongMin pairs own slots): floor(off / kSeg) + floor(off / kSegLongMin) instead - the
-// second term grows by at least one from a long tile to the next ((off + n) / kSegLongMin - off / kSegLongMin >= 1 for n >=
-// kSegLongMin), which is all the "+ t" was for: cap / kSeg + cap / kSegLongMin slots instead of cap / kSeg + T (one
-// 4096 x 3008 view carried 48,128 x 6 KB = 290 MB of snapshot slots for tiles that can never own one).
-inline int seg_positions(const T4DProblem &p) { return (p.n_views == 1 && seg_mode(p) == 1) ? kSegOne : kSeg; }
-inline size_t seg_slots_per_view(const T4DProblem &p, size_t T)
-{
-    if (seg_mode(p) == 2) return (size_t)p.pair_capacity / (size_t)kSeg + (size_t)p.pair_capacity / (size_t)kSegLongMin + 2;
-    return (size_t)p.pair_capacity / (size_t)seg_positions(p) + T + 1;
-}
-
 Layout make_layout(const T4DProblem &p)
 {
     Layout L;
     const size_t V = (size_t)p.n_views, P = (size_t)p.P;
-    const size_t T = (size_t)((p.W + T4D_TILE_X - 1) / T4D_TILE_X) * (size_t)((p.H + T4D_TILE_Y - 1) / T4D_TILE_Y);
+    const size_t T = (size_t)tile_dims(p.W, p.H).T;
     const size_t HW = (size_t)p.H * p.W;
     const size_t cap = (size_t)p.pair_capacity;
     size_t o = 0;
@@ -174,7 +113,7 @@ Layout make_layout(const T4DProblem &p)
     L.view_cursor = o;   o = align_up(o + V * kCursorSegs * 4);
     L.tile_count = o;    o = align_up(o + V * T * 4);
     L.bucket_fill = o;   o = align_up(o + kBuckets * 4);
-    const size_t slots = seg_capable(p) ? V * seg_slots_per_view(p, T) : 0;
+    const size_t slots = seg_mode(p) != 0 ? V * seg_slots_per_view(p, T) : 0;
     L.slot_tab = o;      o = align_up(o + slots * 16);           // (zeroed with the counters: an all-zero entry is "no segment")
     L.zero_end = o;
     L.snap = o;          o = align_up(o + slots * kSnapFloats * kBlock * 4);
@@ -481,7 +420,7 @@ __device__ __forceinline__ bool block_and_view(const uint32_t b, const uint32_t 
     gb = grp * 8u + (rem & 7u);
     return gb < nblocks;
 }
-__host__ __device__ inline unsigned gaussian_grid(const int P, const int V) { return (unsigned)((((P + kBlock - 1) / kBlock + 7) / 8) * 8 * V); }
+// (the grid that goes with it: gaussian_grid, t4d_raster_plan.h)
 
 // ---------------------------------------------------------------------------------------------------------
 // the kernels, one file per stage of the path (all part of THIS translation unit and of its anonymous namespace)
@@ -526,66 +465,16 @@ struct ProfScope {
     }
 };
 
-#define T4D_LAUNCH_CHECK(name)                                                                 \
+// after a launch on `stream`: the launch error, and with `sync` (T4D_FLAG_DEBUG_SYNC) the kernel's own
+#define T4D_LAUNCH_CHECK(name, sync)                                                           \
     do {                                                                                       \
         hipError_t e_ = hipGetLastError();                                                     \
         if (e_ != hipSuccess) return fail(T4D_ERR_HIP, name " launch: %s", hipGetErrorString(e_)); \
-        if (debug) {                                                                           \
+        if (sync) {                                                                            \
             e_ = hipStreamSynchronize(stream);                                                 \
             if (e_ != hipSuccess) return fail(T4D_ERR_HIP, name " exec: %s", hipGetErrorString(e_)); \
         }                                                                                      \
     } while (0)
-
-int device_cus()
-{
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;                                             // MI355X
-        cus = n;
-    }
-    return cus;
-}
-
-// Grid of the per-tile kernels.  They are grid-stride loops over the length-ordered work items, so the grid size is a
-// free choice.  Measured on MI355X (config 2): a RESIDENT grid (CUs x 4-6 workgroups; the switch is gone) loses 1.3x to
-// the hardware dispatcher's dynamic balancing; one workgroup per tile pays ~25k workgroup launches of which two
-// thirds only find an empty tile; V*T / div workgroups, each taking items b, b+G, b+2G, ... (one from every length
-// class, heavy first), keeps the dynamic balancing and divides the launch overhead.  T4D_TILE_DIV overrides div.
-int tile_grid(int n_tiles, int per_cu, int div)
-{
-    static int env_div = -1;
-    if (env_div < 0) {
-        const char *d = getenv("T4D_TILE_DIV");
-        env_div = d ? atoi(d) : 0;
-    }
-    if (env_div > 0) return max(min(n_tiles, device_cus() * per_cu), (n_tiles + env_div - 1) / env_div);
-    // ... up to kMaxGridPerCu workgroups per CU: beyond that (config 4: 393k tiles per launch) more workgroups only add prologues -
-    // the best div measured there was 12-16 (24-33k workgroups: 5.13 -> 4.79 ms per step), at config 2 (24.6k tiles) it is 2
-    constexpr int kMaxGridPerCu = 96;
-    return max(min(n_tiles, device_cus() * per_cu), min((n_tiles + div - 1) / div, device_cus() * kMaxGridPerCu));
-}
-
-// A launch of at most this many tiles runs the LATENCY builds of the render kernels: with <= 4 workgroups per CU in total
-// nothing queues behind anything, and a kernel lasts as long as its longest tile (T4D_LATENCY_TILES overrides; 0 = never).
-bool latency_launch(int n_tiles)
-{
-    const char *e = getenv("T4D_LATENCY_TILES");        // read per call: the tests switch builds at run time
-    return n_tiles <= (e ? atoi(e) : 4 * device_cus());
-}
-// The FORWARD's latency build (registers for instruction-level parallelism, its own tile's bin sorted in the workgroup, records
-// of the next batch in flight during the walk) stays ahead of the throughput build for much larger launches than the
-// backward's did (which needs 82 KiB of LDS per workgroup): T4D_FWD_LATENCY_TILES overrides, T4D_LATENCY_TILES too (tests).
-bool latency_launch_fwd(int n_tiles, uint32_t flags)
-{
-    const char *e = getenv("T4D_FWD_LATENCY_TILES");
-    if (!e) e = getenv("T4D_LATENCY_TILES");
-    // Where the two builds cross depends on the scene: a launch that waits for one long list (the config-2 scene: 1,400 pairs in a
-    // tile) is better off in the latency build up to ~6 views (4 views: 67 against 82 us), a launch of many short lists (Topo4D's
-    // scene, longest 470) only up to 4 (5 views: 48 against 35 us).  The caller's T4D_FLAG_LONG_LISTS says which it is.
-    return n_tiles <= (e ? atoi(e) : ((flags & T4D_FLAG_LONG_LISTS) ? 24 : 12) * device_cus());
-}
 
 int check_problem(const T4DProblem *p)
 {
@@ -593,9 +482,9 @@ int check_problem(const T4DProblem *p)
     if (p->abi_version != T4D_ABI_VERSION) return fail(T4D_ERR_ARG, "abi_version mismatch");
     if (p->n_views < 1 || p->P < 1 || p->H < 1 || p->W < 1) return fail(T4D_ERR_ARG, "n_views, P, H, W must be >= 1");
     if (p->n_views > 4095) return fail(T4D_ERR_ARG, "n_views must be <= 4095");
-    if ((int64_t)((p->W + T4D_TILE_X - 1) / T4D_TILE_X) * ((p->H + T4D_TILE_Y - 1) / T4D_TILE_Y) > 0xfffff)
-        return fail(T4D_ERR_ARG, "image too large: more than 2^20 tiles");
-    if ((int64_t)p->n_views * ((p->W + T4D_TILE_X - 1) / T4D_TILE_X) * ((p->H + T4D_TILE_Y - 1) / T4D_TILE_Y) > (1LL << 30))
+    const int64_t T = tile_dims(p->W, p->H).T;
+    if (T > 0xfffff) return fail(T4D_ERR_ARG, "image too large: more than 2^20 tiles");
+    if ((int64_t)p->n_views * T > (1LL << 30))
         return fail(T4D_ERR_ARG, "n_views * tiles exceeds 2^30 work items: split the batch");
     if (p->pair_capacity < 1 || p->pair_capacity > 0x7fffffffLL) return fail(T4D_ERR_ARG, "pair_capacity out of range");
     if (p->views_per_param_set != 0u && (p->views_per_param_set > (uint32_t)p->n_views || (uint32_t)p->n_views % p->views_per_param_set != 0u))
@@ -606,23 +495,38 @@ int check_problem(const T4DProblem *p)
     return T4D_OK;
 }
 
-void fill_common(KP &kp, const T4DProblem &p, const Layout &L, char *st)
+// The inputs both directions read (T4DForwardIO and T4DBackwardIO name them alike): exactly one colour source and exactly one
+// covariance source, then the eight pointers.
+template <typename IO>
+int take_inputs(KP &kp, const IO &io)
+{
+    if ((io.shs == nullptr) == (io.colors_precomp == nullptr))
+        return fail(T4D_ERR_ARG, "provide exactly one of shs / colors_precomp");
+    if (io.cov3D_precomp ? (io.scales || io.rotations) : (!io.scales || !io.rotations))
+        return fail(T4D_ERR_ARG, "provide exactly one of (scales, rotations) / cov3D_precomp");
+    kp.views = io.views; kp.means3D = io.means3D; kp.opacities = io.opacities; kp.scales = io.scales;
+    kp.rotations = io.rotations; kp.cov3D_precomp = io.cov3D_precomp; kp.colors_precomp = io.colors_precomp;
+    kp.shs = io.shs;
+    return T4D_OK;
+}
+
+// the problem, its regime (t4d_raster_plan.h) and the state buffer's arrays; false: no exact multiplier for this tile grid
+bool fill_common(KP &kp, const T4DProblem &p, const Regime &r, const Layout &L, char *st)
 {
     kp.V = p.n_views; kp.P = p.P; kp.H = p.H; kp.W = p.W;
-    kp.gx = (p.W + T4D_TILE_X - 1) / T4D_TILE_X;
-    kp.gy = (p.H + T4D_TILE_Y - 1) / T4D_TILE_Y;
-    kp.T = kp.gx * kp.gy;
+    kp.gx = r.gx; kp.gy = r.gy; kp.T = r.T;
     kp.deg = p.sh_degree; kp.M = p.sh_coeffs;
     kp.scale_modifier = p.scale_modifier;
     kp.raw_params = (p.flags & T4D_FLAG_RAW_PARAMS) ? 1 : 0;
-    kp.views_per_set = (p.views_per_param_set != 0u && p.views_per_param_set < (uint32_t)p.n_views) ? p.views_per_param_set : 0u;
     kp.cap = (uint32_t)p.pair_capacity;
-    {
-        const uint32_t n_wg = (uint32_t)((p.P + kBlock - 1) / kBlock);
-        kp.nseg = 1;
-        while (kp.nseg < (uint32_t)kCursorSegs && n_wg >= 16u * kp.nseg) kp.nseg <<= 1;       // >= 8 workgroups per cursor
-        kp.seg_cap = kp.cap / kp.nseg;
-    }
+    kp.views_per_set = r.views_per_set;
+    kp.nseg = r.nseg; kp.seg_cap = r.seg_cap;
+    kp.n_chunks = r.n_chunks;
+    kp.long_bins_elsewhere = r.long_bins_elsewhere;
+    kp.slots_per_view = r.slots_per_view;
+    kp.seg_shift = r.seg_shift;
+    kp.slots_by_offset = r.slots_by_offset;
+    kp.seg_min_pairs = r.seg_min_pairs;
     kp.status = reinterpret_cast<DevStatus *>(st + L.status);
     kp.view_total = reinterpret_cast<uint32_t *>(st + L.view_total);
     kp.view_cursor = reinterpret_cast<uint32_t *>(st + L.view_cursor);
@@ -634,8 +538,6 @@ void fill_common(KP &kp, const T4DProblem &p, const Layout &L, char *st)
     kp.cut_r2 = reinterpret_cast<float *>(st + L.pair_rank);
     kp.tile_off = reinterpret_cast<uint32_t *>(st + L.tile_off);
     kp.chunk_sum = reinterpret_cast<uint32_t *>(st + L.chunk_sum);
-    kp.n_chunks = (kp.T + kScanChunk - 1) / kScanChunk;
-    kp.long_bins_elsewhere = (p.flags & T4D_FLAG_NO_LONG_BINS) ? 0 : 1;
     kp.pair_off = reinterpret_cast<uint32_t *>(st + L.pair_off);
     kp.xy = reinterpret_cast<float2 *>(st + L.xy);
     kp.depth = reinterpret_cast<float *>(st + L.depth);
@@ -649,16 +551,31 @@ void fill_common(KP &kp, const T4DProblem &p, const Layout &L, char *st)
     kp.slot_tab = reinterpret_cast<uint4 *>(st + L.slot_tab);
     kp.snap = reinterpret_cast<float *>(st + L.snap);
     kp.live = reinterpret_cast<uint32_t *>(st + L.live);
-    kp.slots_per_view = seg_capable(p) ? (uint32_t)seg_slots_per_view(p, (size_t)kp.T) : 0u;
-    kp.seg_shift = seg_positions(p) == 64 ? 6u : 7u;
-    kp.slots_by_offset = seg_mode(p) == 2 ? 1u : 0u;
-    // seg_mode 2: the caller's word that no list is long (T4D_FLAG_NO_LONG_BINS) keeps every tile whole
-    kp.seg_min_pairs = seg_mode(p) == 2 ? ((p.flags & T4D_FLAG_NO_LONG_BINS) ? 0xffffffffu : (uint32_t)kSegLongMin) : 0u;
-    static_assert(kSegOne == 64 && kSeg == 128, "seg_shift assumes segment lengths of 64 and 128");
     // (check_problem keeps every index below 2^30, so a multiplier always exists: see t4d_tile_div.h)
     kp.div_ok = (t4d_div_make((uint32_t)kp.gx, (uint64_t)kp.T, kp.div_gx) &&
                  t4d_div_make((uint32_t)kp.gy, (uint64_t)kp.V * (uint64_t)kp.gy, kp.div_gy) &&
                  t4d_div_make(empty_spans(kp.T), (uint64_t)kp.V * empty_spans(kp.T), kp.div_spans)) ? 1u : 0u;
+    return kp.div_ok != 0u;
+}
+
+void to_status(const DevStatus &hs, T4DStatus &out)
+{
+    out.max_pairs_per_view = hs.max_pairs;
+    out.total_pairs = (int64_t)hs.total_pairs;
+    out.overflow = (int32_t)hs.overflow;
+    out.max_tile_pairs = (int32_t)min(hs.max_tile_pairs, 0x7fffffffu);
+}
+
+int device_cus()
+{
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;                                             // MI355X
+        cus = n;
+    }
+    return cus;
 }
 
 }  // namespace
@@ -681,7 +598,7 @@ size_t tile_dot_bytes(const T4DProblem &p, size_t n_tiles) { return align_up((si
 T4D_EXPORT size_t t4d_backward_scratch_bytes(const T4DProblem *prob)
 {
     if (check_problem(prob) != T4D_OK) return 0;
-    const size_t n_tiles = (size_t)((prob->W + T4D_TILE_X - 1) / T4D_TILE_X) * ((prob->H + T4D_TILE_Y - 1) / T4D_TILE_Y);
+    const size_t n_tiles = (size_t)tile_dims(prob->W, prob->H).T;
     // pair records | per-wave tile dots | (SH colours) dL/dcolour per (view, Gaussian), handed from k_preprocess_bwd to k_sh_bwd
     return grad_pair_bytes(*prob) + tile_dot_bytes(*prob, n_tiles) +
            (prob->sh_coeffs > 0 ? align_up((size_t)prob->n_views * (size_t)prob->P * 3 * sizeof(float)) : 0);
@@ -722,179 +639,168 @@ static unsigned front_small_resident_blocks()
     return cached;
 }
 
+// Both entry points read top to bottom: validate, plan (t4d_raster_plan.h decides every kernel, build and grid), fill KP, launch
+// what the plan says.
+typedef void (*render_kernel_t)(const KP);
+#define T4D_LAUNCH(kernel, grid, block, params) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, params)
+
+// the k_render_fwd instantiation of a plan's tuple (nullptr: one that no plan asks for, so none was compiled)
+static render_kernel_t render_fwd_kernel(const FwdBuild b)
+{
+    switch (build_key(b)) {
+    case build_key(FwdBuild{ false, kFwdBatch, 0, true, true }):    return k_render_fwd<false, kFwdBatch, 0, true, true>;
+    case build_key(FwdBuild{ true, kBlock, kSegOne, true, false }): return k_render_fwd<true, kBlock, kSegOne, true>;
+    case build_key(FwdBuild{ true, kBlock, kSeg, true, false }):    return k_render_fwd<true, kBlock, kSeg, true>;
+    case build_key(FwdBuild{ true, kBlock, 0, true, false }):       return k_render_fwd<true, kBlock, 0, true>;
+    case build_key(FwdBuild{ false, kBlock, kSegOne, true, false }): return k_render_fwd<false, kBlock, kSegOne, true>;
+    case build_key(FwdBuild{ false, kBlock, kSeg, true, false }):   return k_render_fwd<false, kBlock, kSeg, true>;
+    case build_key(FwdBuild{ false, kFwdBatch, 0, true, false }):   return k_render_fwd<false, kFwdBatch, 0, true>;
+    case build_key(FwdBuild{ false, kFwdBatch, 0, false, false }):  return k_render_fwd<false, kFwdBatch, 0, false>;
+    default: return nullptr;
+    }
+}
+
+// ... and the k_render_bwd instantiation
+static render_kernel_t render_bwd_kernel(const BwdBuild b)
+{
+    switch (build_key(b)) {
+    case build_key(BwdBuild{ true, false, 0, true }):          return k_render_bwd<true, false, 0, true>;
+    case build_key(BwdBuild{ false, false, 0, true }):         return k_render_bwd<false, false, 0, true>;
+    case build_key(BwdBuild{ true, false, kSeg, true }):       return k_render_bwd<true, false, kSeg, true>;
+    case build_key(BwdBuild{ false, false, kSeg, true }):      return k_render_bwd<false, false, kSeg, true>;
+    case build_key(BwdBuild{ true, false, kSegOne, false }):   return k_render_bwd<true, false, kSegOne>;
+    case build_key(BwdBuild{ false, false, kSegOne, false }):  return k_render_bwd<false, false, kSegOne>;
+    case build_key(BwdBuild{ true, false, kSeg, false }):      return k_render_bwd<true, false, kSeg>;
+    case build_key(BwdBuild{ false, false, kSeg, false }):     return k_render_bwd<false, false, kSeg>;
+    case build_key(BwdBuild{ true, true, 0, false }):          return k_render_bwd<true, true, 0>;
+    case build_key(BwdBuild{ false, true, 0, false }):         return k_render_bwd<false, true, 0>;
+    case build_key(BwdBuild{ true, false, 0, false }):         return k_render_bwd<true, false, 0>;
+    case build_key(BwdBuild{ false, false, 0, false }):        return k_render_bwd<false, false, 0>;
+    default: return nullptr;
+    }
+}
+
 T4D_EXPORT int t4d_rasterize_forward(const T4DProblem *prob, const T4DForwardIO *io, T4DStatus *status, void *hip_stream)
 {
+    // validate
     int rc = check_problem(prob);
     if (rc != T4D_OK) return rc;
     if (!io || !io->views || !io->means3D || !io->opacities || !io->out_color || !io->out_depth || !io->out_alpha ||
         !io->out_radii || !io->state)
         return fail(T4D_ERR_ARG, "null required pointer in T4DForwardIO");
-    if ((io->shs == nullptr) == (io->colors_precomp == nullptr))
-        return fail(T4D_ERR_ARG, "provide exactly one of shs / colors_precomp");
-    if (io->cov3D_precomp ? (io->scales || io->rotations) : (!io->scales || !io->rotations))
-        return fail(T4D_ERR_ARG, "provide exactly one of (scales, rotations) / cov3D_precomp");
+    KP kp;
+    memset(&kp, 0, sizeof(kp));
+    if ((rc = take_inputs(kp, *io)) != T4D_OK) return rc;
     if (io->shs && prob->sh_coeffs < 1) return fail(T4D_ERR_ARG, "shs given but sh_coeffs == 0");
     T4DProblem p = *prob;
     if (!io->shs) p.sh_coeffs = 0;
     const Layout L = make_layout(p);
     if (io->state_bytes < L.total) return fail(T4D_ERR_STATE_SIZE, "state buffer smaller than t4d_state_bytes()");
+
+    // plan
+    const Overrides ov = read_overrides();
+    const DeviceFacts dev = { device_cus(), front_small_candidate(p, ov) ? front_small_resident_blocks() : 0u };
+    const bool planes_aligned16 = (((uintptr_t)io->out_color | (uintptr_t)io->out_depth | (uintptr_t)io->out_alpha) & 15u) == 0;
+    const ForwardPlan plan = plan_forward(p, dev, ov, planes_aligned16);
+    const render_kernel_t render = render_fwd_kernel(plan.render);
+    if (!render) return fail(T4D_ERR_ARG, "internal: the plan asks for a k_render_fwd build that does not exist");
+
+    // fill KP
     hipStream_t stream = (hipStream_t)hip_stream;
     const bool debug = (p.flags & T4D_FLAG_DEBUG_SYNC) != 0;
     const bool checked = debug || (p.flags & T4D_FLAG_CHECKED) != 0;
     char *st = (char *)io->state;
-
-    KP kp;
-    memset(&kp, 0, sizeof(kp));
-    fill_common(kp, p, L, st);
-    if (!kp.div_ok) return fail(T4D_ERR_ARG, "no exact multiplier for this tile grid");
-    kp.views = io->views; kp.means3D = io->means3D; kp.opacities = io->opacities; kp.scales = io->scales;
-    kp.rotations = io->rotations; kp.cov3D_precomp = io->cov3D_precomp; kp.colors_precomp = io->colors_precomp;
-    kp.shs = io->shs;
+    if (!fill_common(kp, p, plan.regime, L, st)) return fail(T4D_ERR_ARG, "no exact multiplier for this tile grid");
     kp.out_color = io->out_color; kp.out_depth = io->out_depth; kp.out_alpha = io->out_alpha; kp.radii = io->out_radii;
-
+    kp.fused_sort = plan.fused_sort;
+    kp.tile_blocks = plan.tile_blocks; kp.fill_blocks = plan.fill_blocks; kp.fill_vec = plan.fill_vec;
+    const uint32_t render_grid = kp.tile_blocks + kp.fill_blocks;
+    const uint64_t top = (uint64_t)render_grid * kp.fill_blocks;              // the largest numerator: (last workgroup + 1) * fill_blocks
+    kp.div_blocks_ok = (top < (1ull << 32) && t4d_div_make(render_grid, top + 1u, kp.div_blocks)) ? 1u : 0u;
     // un-synchronised one-view call with a pinned status block: the binning kernel writes it itself (publish_status)
-    bool status_published = false;
-    if (!checked && (p.flags & T4D_FLAG_ASYNC_STATUS) && status && p.n_views == 1 && kp.T <= kSmallTiles &&
-        getenv("T4D_NO_SMALL_VIEW") == nullptr && getenv("T4D_STATUS_BY_COPY") == nullptr) {
+    if (plan.status_by_kernel && status) {
         void *dptr = nullptr;
-        if (hipHostGetDevicePointer(&dptr, (void *)status, 0) == hipSuccess && dptr != nullptr) {
-            kp.host_status = (unsigned long long *)dptr;
-            status_published = true;
-        } else {
-            (void)hipGetLastError();
-        }
+        if (hipHostGetDevicePointer(&dptr, (void *)status, 0) == hipSuccess && dptr != nullptr) kp.host_status = (unsigned long long *)dptr;
+        else (void)hipGetLastError();
     }
+
+    // launch: the front end (cull, project, bin) ...
     T4D_HIP(hipMemsetAsync(st, 0, L.zero_end, stream));
-    // one view of at most 1,024 tiles (Topo4D's own call shape): scan and scatter are ONE launch (k_scan_scatter_small), and with
-    // at most 128 workgroups of Gaussians (all resident at once) preprocess joins them behind a grid-wide barrier (k_front_small)
-    const bool small_view = p.n_views == 1 && kp.T <= kSmallTiles && getenv("T4D_NO_SMALL_VIEW") == nullptr;
-    // (the grid barrier is only safe when every workgroup of the launch is resident at once: checked against what the DEVICE can
-    // hold - a CU mask or a compute partition of 32 CUs shows up in device_cus() - not assumed from the workgroup count)
-    const bool front = small_view && gaussian_grid(p.P, 1) + 1u <= 128u && gaussian_grid(p.P, 1) + 1u <= front_small_resident_blocks() &&
-                       getenv("T4D_NO_FRONT_FUSION") == nullptr;
-    { ProfScope ps_(stream, K_PREPROCESS);
-    if (front) hipLaunchKernelGGL(k_front_small, dim3(gaussian_grid(p.P, 1) + 1), dim3(kBlock), 0, stream, kp);
-    else hipLaunchKernelGGL(k_preprocess, dim3(gaussian_grid(p.P, p.n_views)), dim3(kBlock), 0, stream, kp);
+    {
+        ProfScope ps_(stream, K_PREPROCESS);
+        if (plan.front == FrontEnd::Fused) T4D_LAUNCH(k_front_small, plan.preprocess_grid, kBlock, kp);
+        else T4D_LAUNCH(k_preprocess, plan.preprocess_grid, kBlock, kp);
     }
-    T4D_LAUNCH_CHECK("k_preprocess");
-    if (front) {
-    } else if (small_view) {
+    T4D_LAUNCH_CHECK("k_preprocess", debug);
+    if (plan.front == FrontEnd::SmallView) {
         ProfScope ps_(stream, K_SCATTER);
-        hipLaunchKernelGGL(k_scan_scatter_small, dim3(gaussian_grid(p.P, 1) + 1), dim3(kBlock), 0, stream, kp);
-    } else {
+        T4D_LAUNCH(k_scan_scatter_small, plan.small_grid, kBlock, kp);
+    } else if (plan.front == FrontEnd::General) {
         ProfScope ps_(stream, K_SCAN_TILES);
-        if (kp.n_chunks > 1) hipLaunchKernelGGL(k_tile_chunk_sums, dim3(kp.n_chunks, p.n_views), dim3(kScanChunk), 0, stream, kp);
-        hipLaunchKernelGGL(k_scan_tiles, dim3(kp.n_chunks, p.n_views), dim3(kScanChunk), 0, stream, kp);
+        if (plan.chunk_sums) T4D_LAUNCH(k_tile_chunk_sums, dim3(plan.scan_grid_x, plan.scan_grid_y), kScanChunk, kp);
+        T4D_LAUNCH(k_scan_tiles, dim3(plan.scan_grid_x, plan.scan_grid_y), kScanChunk, kp);
     }
-    T4D_LAUNCH_CHECK("k_scan_tiles");
+    T4D_LAUNCH_CHECK("k_scan_tiles", debug);
     if (checked) {
         DevStatus hs;
         T4D_HIP(hipMemcpyAsync(&hs, st + L.status, sizeof(hs), hipMemcpyDeviceToHost, stream));
         T4D_HIP(hipStreamSynchronize(stream));
-        if (status) {
-            status->max_pairs_per_view = hs.max_pairs;
-            status->total_pairs = (int64_t)hs.total_pairs;
-            status->overflow = (int32_t)hs.overflow;
-            status->max_tile_pairs = (int32_t)min(hs.max_tile_pairs, 0x7fffffffu);
-        }
+        if (status) to_status(hs, *status);
         if (hs.overflow) return fail(T4D_ERR_PAIR_OVERFLOW, "pair_capacity too small for this scene");
-    } else if ((p.flags & T4D_FLAG_ASYNC_STATUS) && status && !status_published) {
+    } else if ((p.flags & T4D_FLAG_ASYNC_STATUS) && status && !kp.host_status) {
         // no synchronisation: the 16-byte raw status block lands in the caller's PINNED host memory once the scan kernel
         // has run; the caller looks at it after an event of its own (topo4d_amd's "auto" sync mode does, one call later)
         T4D_HIP(hipMemcpyAsync((void *)status, st + L.status, 16, hipMemcpyDeviceToHost, stream));     // the documented 16 bytes
     }
-    if (!small_view) {
+    if (plan.front == FrontEnd::General) {
         ProfScope ps_(stream, K_SCATTER);
-        hipLaunchKernelGGL(k_scatter, dim3(gaussian_grid(p.P, p.n_views) + (unsigned)(((size_t)kp.T * p.n_views + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, kp);
+        T4D_LAUNCH(k_scatter, plan.scatter_grid, kBlock, kp);
     }
-    T4D_LAUNCH_CHECK("k_scatter");
-    // Who sorts the bins.  A big launch: k_sort_tiles on 256 threads.  A small launch (at most kSegMaxTiles tiles) waits for its
-    // longest bin: 1024 threads per bin - unless the forward runs its latency build AND the caller knows that every bin fits the
-    // one-pass ranking sort (T4D_FLAG_SHORT_BINS): then the render workgroup of a tile sorts its own bin (no launch at all).
-    const bool lat = latency_launch_fwd(kp.T * p.n_views, p.flags);
-    kp.fused_sort = (lat && (p.flags & T4D_FLAG_SHORT_BINS) != 0 && getenv("T4D_NO_FUSED_SORT") == nullptr) ? 1u : 0u;
-    // a big one-view launch that may hold long lists: its long tiles go through the depth-parallel kernels, and the throughput forward
-    // that renders the others sorts its own tiles' bins first (k_render_fwd, FUSE): no k_sort_tiles launch
-    const bool long_fwd = kp.slots_per_view != 0u && kp.seg_min_pairs != 0xffffffffu && seg_mode(p) == 2 && !lat && getenv("T4D_NO_LONG_FWD") == nullptr;
-    if (long_fwd && getenv("T4D_NO_FUSED_SORT") == nullptr) kp.fused_sort = 1u;
-    if (!kp.fused_sort) {
+    T4D_LAUNCH_CHECK("k_scatter", debug);
+    // ... the bin sort, unless the render workgroups do it ...
+    if (plan.sorter != Sorter::Fused) {
         ProfScope ps_(stream, K_SORT_TILES);
-        // (1024 threads per bin only pay when some bin is long: with the caller's word that every bin fits the ranking sort, a
-        // small launch of several views keeps the 256-thread kernel - 4 views of Topo4D's size: 9.7 against 12.6 us)
-        if (seg_mode(p) == 1 && (p.flags & T4D_FLAG_SHORT_BINS) == 0 && getenv("T4D_SORT_256") == nullptr)
-            hipLaunchKernelGGL(k_sort_tiles<kLongBlock>, dim3(min(kp.T * p.n_views, 4 * device_cus())), dim3(kLongBlock), 0, stream, kp);
-        else
-            hipLaunchKernelGGL(k_sort_tiles<kBlock>, dim3(tile_grid(kp.T * p.n_views, 5, 2)), dim3(kBlock), 0, stream, kp);
+        if (plan.sorter == Sorter::Block1024) T4D_LAUNCH(k_sort_tiles<kLongBlock>, plan.sort_grid, kLongBlock, kp);
+        else T4D_LAUNCH(k_sort_tiles<kBlock>, plan.sort_grid, kBlock, kp);
     }
-    T4D_LAUNCH_CHECK("k_sort_tiles");
-    // bins beyond the LDS sort buffer (the caller has not said that there are none): their chunks, then the merges
-    if (kp.long_bins_elsewhere) {
+    T4D_LAUNCH_CHECK("k_sort_tiles", debug);
+    if (plan.long_bins) {
         ProfScope ps_(stream, K_SORT_LONG);
-        hipLaunchKernelGGL(k_sort_long_chunks, dim3(min(kp.T * p.n_views, 2 * device_cus())), dim3(kLongBlock), 0, stream, kp);
-        hipLaunchKernelGGL(k_merge_long, dim3(min(kp.T * p.n_views, 2 * device_cus())), dim3(kLongBlock), 0, stream, kp);
+        T4D_LAUNCH(k_sort_long_chunks, plan.long_bins_grid, kLongBlock, kp);
+        T4D_LAUNCH(k_merge_long, plan.long_bins_grid, kLongBlock, kp);
     }
-    T4D_LAUNCH_CHECK("k_sort_long");
+    T4D_LAUNCH_CHECK("k_sort_long", debug);
+    // ... and the blend
     {
-    kp.tile_blocks = (uint32_t)(lat ? kp.T * p.n_views : tile_grid(kp.T * p.n_views, 6, 2));
-    kp.fill_blocks = (uint32_t)(kp.gy * p.n_views);
-    kp.fill_vec = (p.W % 4 == 0 && (((uintptr_t)io->out_color | (uintptr_t)io->out_depth | (uintptr_t)io->out_alpha) & 15u) == 0) ? 1u : 0u;
-    if (getenv("T4D_FILL_SCALAR")) kp.fill_vec = 0u;       // tests: the 4-byte path on images that would take the 16-byte one
-    const dim3 fgrid(kp.tile_blocks + kp.fill_blocks);
-    {
-        const uint64_t top = (uint64_t)fgrid.x * kp.fill_blocks;              // the largest numerator: (last workgroup + 1) * fill_blocks
-        kp.div_blocks_ok = (top < (1ull << 32) && t4d_div_make(fgrid.x, top + 1u, kp.div_blocks)) ? 1u : 0u;
+        ProfScope ps_(stream, K_RENDER_FWD);
+        T4D_LAUNCH(render, render_grid, kBlock, kp);
     }
-    // small launch, or a big one-view launch that may hold long lists: snapshots for the segmented backward (kSeg)
-    const bool seg = kp.slots_per_view != 0u && kp.seg_min_pairs != 0xffffffffu;
-    const bool seg_one = seg && seg_positions(p) == kSegOne;
-    // a big one-view launch that may hold long lists: those tiles go through the depth-parallel kernels (three launches over the
-    // slot table, t4d_raster_render_fwd_long.h); the others through the throughput build, which leaves the long ones out
-    if (long_fwd) {
-        { ProfScope ps_(stream, K_RENDER_FWD);
-        hipLaunchKernelGGL((k_render_fwd<false, kFwdBatch, 0, true, true>), fgrid, dim3(kBlock), 0, stream, kp);
-        }
-        T4D_LAUNCH_CHECK("k_render_fwd");
-        ProfScope psl_(stream, K_FWD_LONG);
+    T4D_LAUNCH_CHECK("k_render_fwd", debug);
+    if (plan.long_fwd) {
+        ProfScope ps_(stream, K_FWD_LONG);
         KP kl = kp;
-        kl.tile_blocks = min(kp.slots_per_view, (uint32_t)(8 * device_cus()));
-        hipLaunchKernelGGL(k_fwd_long_seg<false>, dim3(kl.tile_blocks), dim3(kBlock), 0, stream, kl);
-        T4D_LAUNCH_CHECK("k_fwd_long_seg");
-        hipLaunchKernelGGL(k_fwd_long_prefix, dim3(min((uint32_t)kp.T, (uint32_t)(4 * device_cus()))), dim3(kBlock), 0, stream, kl);
-        T4D_LAUNCH_CHECK("k_fwd_long_prefix");
-        hipLaunchKernelGGL(k_fwd_long_seg<true>, dim3(kl.tile_blocks), dim3(kBlock), 0, stream, kl);
-    } else {
-    ProfScope ps_(stream, K_RENDER_FWD);
-    if (lat) {
-        if (seg_one) hipLaunchKernelGGL((k_render_fwd<true, kBlock, kSegOne, true>), fgrid, dim3(kBlock), 0, stream, kp);
-        else if (seg) hipLaunchKernelGGL((k_render_fwd<true, kBlock, kSeg, true>), fgrid, dim3(kBlock), 0, stream, kp);
-        else hipLaunchKernelGGL((k_render_fwd<true, kBlock, 0, true>), fgrid, dim3(kBlock), 0, stream, kp);
-    } else if (seg_one) {
-        hipLaunchKernelGGL((k_render_fwd<false, kBlock, kSegOne, true>), fgrid, dim3(kBlock), 0, stream, kp);
-    } else if (seg) {
-        hipLaunchKernelGGL((k_render_fwd<false, kBlock, kSeg, true>), fgrid, dim3(kBlock), 0, stream, kp);
-    } else if (kp.long_bins_elsewhere && getenv("T4D_NO_PRUNE") == nullptr) {
-        // a big launch that may hold long lists (the caller has not passed T4D_FLAG_NO_LONG_BINS): a dense pass
-        hipLaunchKernelGGL((k_render_fwd<false, kFwdBatch, 0, true>), fgrid, dim3(kBlock), 0, stream, kp);
-    } else {
-        hipLaunchKernelGGL((k_render_fwd<false, kFwdBatch, 0, false>), fgrid, dim3(kBlock), 0, stream, kp);
+        kl.tile_blocks = plan.long_seg_grid;
+        T4D_LAUNCH(k_fwd_long_seg<false>, plan.long_seg_grid, kBlock, kl);
+        T4D_LAUNCH_CHECK("k_fwd_long_seg", debug);
+        T4D_LAUNCH(k_fwd_long_prefix, plan.long_prefix_grid, kBlock, kl);
+        T4D_LAUNCH_CHECK("k_fwd_long_prefix", debug);
+        T4D_LAUNCH(k_fwd_long_seg<true>, plan.long_seg_grid, kBlock, kl);
+        T4D_LAUNCH_CHECK("k_fwd_long_seg", debug);
     }
-    }
-    }
-    T4D_LAUNCH_CHECK("k_render_fwd");
     return T4D_OK;
 }
 
 T4D_EXPORT int t4d_rasterize_backward(const T4DProblem *prob, const T4DBackwardIO *io, void *hip_stream)
 {
+    // validate
     int rc = check_problem(prob);
     if (rc != T4D_OK) return rc;
     if (!io || !io->views || !io->means3D || !io->opacities || !io->radii || !io->state || !io->dL_dcolor ||
         !io->dL_dmeans3D || !io->dL_dmeans2D || !io->dL_dopacities || !io->scratch)
         return fail(T4D_ERR_ARG, "null required pointer in T4DBackwardIO");
-    if ((io->shs == nullptr) == (io->colors_precomp == nullptr))
-        return fail(T4D_ERR_ARG, "provide exactly one of shs / colors_precomp");
-    if (io->cov3D_precomp ? (io->scales || io->rotations) : (!io->scales || !io->rotations))
-        return fail(T4D_ERR_ARG, "provide exactly one of (scales, rotations) / cov3D_precomp");
+    KP kp;
+    memset(&kp, 0, sizeof(kp));
+    if ((rc = take_inputs(kp, *io)) != T4D_OK) return rc;
     if (io->shs ? !io->dL_dshs : !io->dL_dcolors) return fail(T4D_ERR_ARG, "missing colour gradient output");
     if (io->cov3D_precomp ? !io->dL_dcov3D : (!io->dL_dscales || !io->dL_drotations))
         return fail(T4D_ERR_ARG, "missing covariance gradient output");
@@ -904,17 +810,20 @@ T4D_EXPORT int t4d_rasterize_backward(const T4DProblem *prob, const T4DBackwardI
     if (io->state_bytes < L.total) return fail(T4D_ERR_STATE_SIZE, "state buffer smaller than t4d_state_bytes()");
     if (io->scratch_bytes < t4d_backward_scratch_bytes(&p))
         return fail(T4D_ERR_STATE_SIZE, "scratch smaller than t4d_backward_scratch_bytes()");
+
+    // plan (from the forward's problem: see the contract in t4d_raster_plan.h)
+    const Overrides ov = read_overrides();
+    const DeviceFacts dev = { device_cus(), 0u };
+    const BackwardPlan plan = plan_backward(p, dev, ov, io->dL_ddepth || io->dL_dalpha, io->cotangent_dot != nullptr, io->shs != nullptr);
+    render_kernel_t render[2] = { nullptr, nullptr };
+    for (int i = 0; i < plan.n_render; i++)
+        if (!(render[i] = render_bwd_kernel(plan.render[i].build)))
+            return fail(T4D_ERR_ARG, "internal: the plan asks for a k_render_bwd build that does not exist");
+
+    // fill KP
     hipStream_t stream = (hipStream_t)hip_stream;
     const bool debug = (p.flags & T4D_FLAG_DEBUG_SYNC) != 0;
-    char *st = (char *)io->state;
-
-    KP kp;
-    memset(&kp, 0, sizeof(kp));
-    fill_common(kp, p, L, st);
-    if (!kp.div_ok) return fail(T4D_ERR_ARG, "no exact multiplier for this tile grid");
-    kp.views = io->views; kp.means3D = io->means3D; kp.opacities = io->opacities; kp.scales = io->scales;
-    kp.rotations = io->rotations; kp.cov3D_precomp = io->cov3D_precomp; kp.colors_precomp = io->colors_precomp;
-    kp.shs = io->shs;
+    if (!fill_common(kp, p, plan.regime, L, (char *)io->state)) return fail(T4D_ERR_ARG, "no exact multiplier for this tile grid");
     kp.radii = const_cast<int32_t *>(io->radii);
     kp.dL_dcolor = io->dL_dcolor; kp.dL_ddepth = io->dL_ddepth; kp.dL_dalpha = io->dL_dalpha;
     kp.grad_pair = (float *)io->scratch;
@@ -926,69 +835,27 @@ T4D_EXPORT int t4d_rasterize_backward(const T4DProblem *prob, const T4DBackwardI
     kp.dL_dshs = io->dL_dshs; kp.dL_dopacities = io->dL_dopacities; kp.dL_dscales = io->dL_dscales;
     kp.dL_drotations = io->dL_drotations; kp.dL_dcov3D = io->dL_dcov3D;
 
-    {
-    const bool da = kp.dL_ddepth || kp.dL_dalpha;
-    const bool lat = latency_launch(kp.T * p.n_views);
-    // small launches: one workgroup per segment slot (kSeg; T4D_NO_SEGMENTS=1: whole tiles, for tests and experiments - the
-    // forward's state serves both)
-    // (seg_mode 2 - the long tiles of a big one-view launch - only when the caller has not said that there are none: the forward
-    // of a call that says so keeps no snapshots, and a forward that kept them is simply not used)
-    const bool seg_long = seg_mode(p) == 2 && kp.seg_min_pairs != 0xffffffffu && getenv("T4D_NO_SEGMENTS") == nullptr;
-    const bool seg = seg_mode(p) == 1 && getenv("T4D_NO_SEGMENTS") == nullptr;
-    kp.tile_blocks = seg ? (uint32_t)p.n_views * kp.slots_per_view
-                         : (uint32_t)(lat ? kp.T * p.n_views : tile_grid(kp.T * p.n_views, 4, 2));
-    uint32_t grid = kp.tile_blocks + (kp.tile_dot ? (uint32_t)p.n_views * ((kp.T + kEmptySpan - 1) / kEmptySpan) : 0u);
-#define T4D_BWD_LAUNCH(DA_, LAT_, SEG_) hipLaunchKernelGGL((k_render_bwd<DA_, LAT_, SEG_>), dim3(grid), dim3(kBlock), 0, stream, kp)
-    if (seg_long) {
-        // two launches: the whole-tile throughput build leaves out the tiles that own segments (the forward wrote their slot-table
-        // entries), then the segmented build walks the slot table with a fixed number of workgroups (most of its cap / kSeg + T
-        // slots are empty: one workgroup per slot would be 79,000 launches for a few thousand segments)
-        { ProfScope ps_(stream, K_RENDER_BWD);
-        if (da) hipLaunchKernelGGL((k_render_bwd<true, false, 0, true>), dim3(grid), dim3(kBlock), 0, stream, kp);
-        else hipLaunchKernelGGL((k_render_bwd<false, false, 0, true>), dim3(grid), dim3(kBlock), 0, stream, kp);
+    // launch: the replay (a big one-view launch that kept snapshots: whole tiles, then the long tiles' segments) ...
+    for (int i = 0; i < plan.n_render; i++) {
+        {
+            ProfScope ps_(stream, i == 0 ? K_RENDER_BWD : K_RENDER_BWD_LONG);
+            kp.tile_blocks = plan.render[i].tile_blocks;
+            T4D_LAUNCH(render[i], plan.render[i].grid, kBlock, kp);
         }
-        T4D_LAUNCH_CHECK("k_render_bwd");
-        ProfScope psl_(stream, K_RENDER_BWD_LONG);
-        kp.tile_blocks = min(kp.slots_per_view, (uint32_t)(8 * device_cus()));
-        grid = kp.tile_blocks;
-        if (da) hipLaunchKernelGGL((k_render_bwd<true, false, kSeg, true>), dim3(grid), dim3(kBlock), 0, stream, kp);
-        else hipLaunchKernelGGL((k_render_bwd<false, false, kSeg, true>), dim3(grid), dim3(kBlock), 0, stream, kp);
-    } else {
-    ProfScope ps_(stream, K_RENDER_BWD);
-    if (seg && seg_positions(p) == kSegOne) {
-        if (da) T4D_BWD_LAUNCH(true, false, kSegOne); else T4D_BWD_LAUNCH(false, false, kSegOne);
-    } else if (seg) {
-        // Segments always run the throughput build: the latency build's one slab per DPP row is 82 KiB of LDS, ONE workgroup per
-        // CU, and a one-view launch has more segments than CUs (432 at Topo4D's size: two rounds, 47 us against 29 us measured)
-        if (da) T4D_BWD_LAUNCH(true, false, kSeg); else T4D_BWD_LAUNCH(false, false, kSeg);
-    } else {
-        if (lat) { if (da) T4D_BWD_LAUNCH(true, true, 0); else T4D_BWD_LAUNCH(false, true, 0); }
-        else { if (da) T4D_BWD_LAUNCH(true, false, 0); else T4D_BWD_LAUNCH(false, false, 0); }
+        T4D_LAUNCH_CHECK("k_render_bwd", debug);
     }
-    }
-#undef T4D_BWD_LAUNCH
-    }
-    T4D_LAUNCH_CHECK("k_render_bwd");
-    { ProfScope ps_(stream, K_PREPROCESS_BWD);
-    const dim3 pgrid(gaussian_grid(p.P, p.n_views) + (kp.tile_dot ? p.n_views : 0));
-    if (kp.shs)          // SH colours: the per-Gaussian kernel leaves dL/dcolour in the scratch, k_sh_bwd takes it from there
-        kp.dL_dcolors = (float *)((char *)io->scratch + grad_pair_bytes(p) + tile_dot_bytes(p, (size_t)kp.T));
-    hipLaunchKernelGGL(k_preprocess_bwd, pgrid, dim3(kBlock), 0, stream, kp);
-    if (kp.shs)
+    // ... and the per-Gaussian chain rule
     {
-        const bool plain = getenv("T4D_SH_BWD_PLAIN") != nullptr;                // tests / experiments: the general kernel also for degree 3
-        // (k_sh_bwd16 serves T4D_SHB_VIEWS views from one fetch of the coefficient rows: they must belong to one parameter set)
-        if (kp.M == 16 && kp.deg == 3 && !plain && (kp.views_per_set == 0u || kp.views_per_set % T4D_SHB_VIEWS == 0u))
-            hipLaunchKernelGGL(k_sh_bwd16, dim3(gaussian_grid(p.P, (p.n_views + T4D_SHB_VIEWS - 1) / T4D_SHB_VIEWS)), dim3(kBlock), 0, stream, kp);
-        else
-            hipLaunchKernelGGL(k_sh_bwd, dim3(gaussian_grid(p.P, p.n_views)), dim3(kBlock), 0, stream, kp);
+        ProfScope ps_(stream, K_PREPROCESS_BWD);
+        if (kp.shs)          // SH colours: the per-Gaussian kernel leaves dL/dcolour in the scratch, k_sh_bwd takes it from there
+            kp.dL_dcolors = (float *)((char *)io->scratch + grad_pair_bytes(p) + tile_dot_bytes(p, (size_t)kp.T));
+        T4D_LAUNCH(k_preprocess_bwd, plan.gaussian_grid, kBlock, kp);
+        if (plan.sh == ShBackward::Degree3x16) T4D_LAUNCH(k_sh_bwd16, plan.sh_grid, kBlock, kp);
+        else if (plan.sh == ShBackward::General) T4D_LAUNCH(k_sh_bwd, plan.sh_grid, kBlock, kp);
     }
-    }
-    T4D_LAUNCH_CHECK("k_preprocess_bwd");
+    T4D_LAUNCH_CHECK("k_preprocess_bwd", debug);
     return T4D_OK;
 }
-
-
 
 T4D_EXPORT int t4d_profile_begin(void)
 {
@@ -1030,10 +897,7 @@ T4D_EXPORT int t4d_fetch_status(const T4DProblem *prob, const void *state, T4DSt
     DevStatus hs;
     T4D_HIP(hipMemcpyAsync(&hs, state, sizeof(hs), hipMemcpyDeviceToHost, stream));
     T4D_HIP(hipStreamSynchronize(stream));
-    out->max_pairs_per_view = hs.max_pairs;
-    out->total_pairs = (int64_t)hs.total_pairs;
-    out->overflow = (int32_t)hs.overflow;
-    out->max_tile_pairs = (int32_t)min(hs.max_tile_pairs, 0x7fffffffu);
+    to_status(hs, *out);
     return T4D_OK;
 }
 
@@ -1044,12 +908,11 @@ T4D_EXPORT int t4d_view_dot(int32_t n_views, int64_t n_per_view, const float *a,
 {
     if (n_views < 1 || n_per_view < 1 || !a || !b || !out || !scratch) return fail(T4D_ERR_ARG, "bad arguments");
     hipStream_t stream = (hipStream_t)hip_stream;
-    const bool debug = false;
     hipLaunchKernelGGL(k_view_dot_partial, dim3(kDotBlocks, n_views), dim3(kBlock), 0, stream, a, b, (size_t)n_per_view,
                        (float *)scratch);
-    T4D_LAUNCH_CHECK("k_view_dot_partial");
+    T4D_LAUNCH_CHECK("k_view_dot_partial", false);
     hipLaunchKernelGGL(k_view_dot_final, dim3(n_views), dim3(64), 0, stream, (const float *)scratch, out);
-    T4D_LAUNCH_CHECK("k_view_dot_final");
+    T4D_LAUNCH_CHECK("k_view_dot_final", false);
     return T4D_OK;
 }
 
@@ -1058,8 +921,7 @@ T4D_EXPORT int t4d_mark_visible(int32_t P, const float *means3D, const float *vi
     if (P < 0 || (P > 0 && (!means3D || !view || !present))) return fail(T4D_ERR_ARG, "bad arguments");
     if (P == 0) return T4D_OK;
     hipStream_t stream = (hipStream_t)hip_stream;
-    const bool debug = false;
     hipLaunchKernelGGL(k_mark_visible, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, P, means3D, view, present);
-    T4D_LAUNCH_CHECK("k_mark_visible");
+    T4D_LAUNCH_CHECK("k_mark_visible", false);
     return T4D_OK;
 }

@@ -417,8 +417,8 @@ __global__ __launch_bounds__(kBlock) void k_scatter(const KP kp)
 // workgroup does what else the scan kernel leaves behind - the offsets in memory, the view's total, the status block and
 // the length-ordered work items (built in LDS: a single workgroup sees every tile, so the per-class lists of k_scan_tiles
 // and the flattening pass of k_scatter are not needed).
+// (kSmallTiles: t4d_raster_plan.h)
 // ---------------------------------------------------------------------------------------------------------
-constexpr int kSmallTiles = 4 * kBlock;
 
 // T4D_FLAG_ASYNC_STATUS on a one-view launch: the 16-byte status { overflow, max pairs per view, total pairs } goes to the caller's
 // PINNED host memory straight from the thread that knows it - two system-scope stores instead of a copy kernel on the stream

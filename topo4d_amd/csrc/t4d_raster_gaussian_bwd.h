@@ -321,10 +321,7 @@ __global__ __launch_bounds__(kBlock) void k_sh_bwd(const KP kp)
 // rows of all resident waves (240 KB per CU) do not survive in the 32 KB L1 from one load to the next, and every view fetches
 // them again.  Here a workgroup takes its 256 rows ONCE, as one contiguous 48 KiB stream (16 bytes per lane, consecutive lanes
 // consecutive addresses), turns them through LDS into one row per lane held in registers, and then serves T4D_SHB_VIEWS views
-// from them; the staging area is reused for the basis / dL/dcolour exchange of the write-out.
-#ifndef T4D_SHB_VIEWS
-#define T4D_SHB_VIEWS 8
-#endif
+// (t4d_raster_plan.h) from them; the staging area is reused for the basis / dL/dcolour exchange of the write-out.
 __global__ __launch_bounds__(kBlock) void k_sh_bwd16(const KP kp)
 {
     constexpr int kPitch = 52;                           // floats per staged row: 16-byte aligned, 13 (odd) 16-byte words -> no bank conflicts

@@ -200,7 +200,7 @@ __device__ __forceinline__ uint32_t row_max_u32(uint32_t v)      // every lane g
 #define T4D_BWD_NW (LAT ? 2 : (SEGN != 0 ? T4D_SEG_WAVES : (DA ? T4D_BWD_DA_WAVES : T4D_BWD_WAVES)))
 #define T4D_BWD_ATTR __attribute__((amdgpu_waves_per_eu(LAT ? 1 : T4D_BWD_NW, T4D_BWD_NW)))
 constexpr int kAcc = 10;                 // sums per (wave, staged splat) slab entry
-constexpr int kEmptySpan = 64;           // tiles per spare workgroup of the empty-tile share of cotangent_dot
+// (kEmptySpan, the tiles per spare workgroup of the empty-tile share of cotangent_dot: t4d_raster_plan.h)
 __host__ __device__ inline uint32_t empty_spans(const int T) { return (uint32_t)(T + kEmptySpan - 1) / kEmptySpan; }      // spare workgroups per view
 // LAT: the latency build (see k_render_fwd): one slab per DPP ROW instead of one per wave (82 KB of LDS: one workgroup per CU
 // is all such a launch has anyway), so two rows holding the same splat in the same step never meet and the conflict
