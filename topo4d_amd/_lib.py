@@ -5,8 +5,9 @@ The library is built in-tree by `__graft_entry__.build()` / `python -m topo4d_am
 `hipcc --offload-arch=gfx950`.  There is NO fallback: if the shared object is missing or does not load, every
 entry point of the product raises — a rasterizer that silently ran on the CPU would void every parity claim.
 
-Every entry point is bound from one table, SIGNATURES (tests/test_abi.py pins it to the header); `ptr`, `stream`, `call` and
-`error` are what the wrappers of the other modules share.
+Every entry point is bound from one table, SIGNATURES (tests/test_abi.py pins it to the header); `ptr`, `stream`, `call`,
+`error`, `hip_device`, `on_device`, `scratch` and `read_back` are what the wrappers of the other modules share (their argument
+checks for images and masks are in _args.py).
 """
 from __future__ import annotations
 
@@ -315,3 +316,52 @@ def call(name: str, *args) -> None:
     rc = getattr(load(), name)(*args)
     if rc != T4D_OK:
         raise error(name, rc)
+
+
+def hip_device(device, what: str, exc=RuntimeError) -> torch.device:
+    """The HIP device a wrapper works on: None is the current one and a device without an index gets the current index.  A device
+    of another kind, or a process that sees no HIP device, raises `exc` (the modules differ in the class their tests pin)."""
+    dev = torch.device(device if device is not None else "cuda")
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise exc(f"topo4d_amd has no CPU path: {what} needs a HIP device")
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def on_device(t: torch.Tensor, what: str, device=None, whose: str = "the same") -> torch.Tensor:
+    """`t` as the library takes it, contiguous and a bool mask as uint8, once it is known to live on a HIP device (`device` None)
+    or on `device`, "`whose` HIP device" in the message; RuntimeError otherwise.  Shapes and dtypes are checked before this."""
+    if not t.is_cuda or (device is not None and t.device != device):
+        raise RuntimeError(f"topo4d_amd has no CPU path: {what} must live on {'a' if device is None else whose} HIP device")
+    return (t.to(torch.uint8) if t.dtype == torch.bool else t).contiguous()
+
+
+def scratch(query: str, device, *args, exc=ValueError, reuse: torch.Tensor = None):
+    """(uint8 scratch tensor on `device`, its size in bytes) for the size query `query`, called with `args`.  No size query of the
+    library answers 0 for a problem its entry point takes (an empty problem is returned before the query, at the call site), so 0
+    is the library's refusal and raises error(query, exc=exc) before anything is allocated.  reuse: the caller's cached tensor,
+    returned as it is when it is large enough."""
+    nbytes = int(getattr(load(), query)(*args))
+    if nbytes == 0:
+        raise error(query, exc=exc)
+    if reuse is not None and reuse.numel() >= nbytes:
+        return reuse, nbytes
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
+# read_back's host buffer, one for the package: only the thread that launches reads back (the prefetch pools of ingest, evaluate
+# and projtex submit file reads and parsers, nothing that touches the device)
+_pinned = None
+
+
+def read_back(out: torch.Tensor, length: torch.Tensor, cap: int, name: str, empty_ok: bool = False) -> bytes:
+    """The bytes entry point `name` wrote: `out` (uint8, capacity `cap`) up to the int64 `length` it left on the device.  Reading
+    the length is the one synchronisation; then exactly that many bytes are copied through the reused pinned buffer.  A length
+    outside 1..cap (0..cap with empty_ok) raises RuntimeError."""
+    global _pinned
+    n = int(length.item())
+    if n < (0 if empty_ok else 1) or n > cap:
+        raise RuntimeError(f"{name}: bad output length {n} (capacity {cap})")
+    if _pinned is None or _pinned.numel() < n:
+        _pinned = torch.empty(max(n, 1 << 20), dtype=torch.uint8, pin_memory=True)
+    _pinned[:n].copy_(out[:n])
+    return _pinned[:n].numpy().tobytes()

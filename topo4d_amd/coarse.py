@@ -64,11 +64,7 @@ REGION_WEIGHT_BLOCKS = {
 }
 
 
-def _device(device=None) -> torch.device:
-    dev = torch.device(device if device is not None else "cuda")
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("topo4d_amd has no CPU path: the coarse setup needs a HIP device")
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+_WHAT = "the coarse setup"
 
 
 def _status(t: torch.Tensor) -> List[int]:
@@ -200,7 +196,7 @@ def load_texture(texture, device=None) -> torch.Tensor:
     PIL), anything else through PIL.  texture: a path, the file's bytes, or an array / tensor already decoded.  ValueError for
     any mode but RGB / RGBA (get_color_from_texture indexes three channels of getpixel's tuple)."""
     from . import ingest
-    dev = _device(device)
+    dev = _lib.hip_device(device, _WHAT)
     if isinstance(texture, (np.ndarray, torch.Tensor)):
         img = torch.from_numpy(np.array(texture)) if isinstance(texture, np.ndarray) else texture
         if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] not in (3, 4):
@@ -222,16 +218,12 @@ class _TriangleCSR:
     """t4d_obj_vertex_faces over int32 triangles [F,3]: offsets [n_vert+1], entries (corner ids 3*f+k ascending per vertex)."""
 
     def __init__(self, faces: np.ndarray, n_vert: int, dev):
-        lib = _lib.load()
         self.faces = torch.from_numpy(np.ascontiguousarray(faces, np.int32)).to(dev)
         n_faces = int(self.faces.shape[0])
         self.offsets = torch.empty(n_vert + 1, dtype=torch.int32, device=dev)
         self.entries = torch.empty(3 * n_faces, dtype=torch.int32, device=dev)
         status = torch.empty(2, dtype=torch.int32, device=dev)
-        nscratch = int(lib.t4d_obj_csr_scratch_bytes(n_vert))
-        if nscratch == 0:
-            raise _lib.error("t4d_obj_csr_scratch_bytes", exc=ValueError)
-        scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+        scratch, nscratch = _lib.scratch("t4d_obj_csr_scratch_bytes", dev, n_vert)
         _lib.call("t4d_obj_vertex_faces", ptr(self.faces), n_faces, n_vert, ptr(self.offsets), ptr(self.entries), ptr(status),
                   ptr(scratch), nscratch, _lib.stream(dev))
         self.bad, self.unreferenced = _status(status)
@@ -243,17 +235,13 @@ def vertex_colors(texture, mesh: ObjMesh, device=None):
     """compute_vertex_colors (helpers.py:181-209): (colors int32 [N,3], the integer means as the reference returns them, and
     rgb_colors float32 [N,3] = colors / 255.0), both on the device.  ValueError where get_color_from_texture would raise: a
     corner whose UV lands on column `width` or row `height` (x1 == width: u % 1 == 1.0 after rounding), or a NaN UV."""
-    dev = _device(device)
+    dev = _lib.hip_device(device, _WHAT)
     img = load_texture(texture, dev)
-    lib = _lib.load()
     n_vert = int(mesh.vertices.shape[0])
     csr = _TriangleCSR(mesh.faces, n_vert, dev)
     uv = torch.from_numpy(np.ascontiguousarray(mesh.corner_uvs, np.float64)).to(dev)
     n_corners = int(uv.shape[0])
-    nscratch = int(lib.t4d_setup_colors_scratch_bytes(n_corners))
-    if nscratch == 0:
-        raise _lib.error("t4d_setup_colors_scratch_bytes", exc=ValueError)
-    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+    scratch, nscratch = _lib.scratch("t4d_setup_colors_scratch_bytes", dev, n_corners)
     colors = torch.empty(n_vert, 3, dtype=torch.int32, device=dev)
     rgb = torch.empty(n_vert, 3, dtype=torch.float32, device=dev)
     status = torch.empty(3, dtype=torch.int32, device=dev)
@@ -342,14 +330,10 @@ def region_weights(neighbor_weight: torch.Tensor, facial_regions: dict, losses_w
     """iso_w, rig_w, rot_w of train.py:545-581: copies of neighbor_weight with `w[mask, :] *= c / losses_weights[k]` applied in
     the reference's order, each a float32 multiply by float32(c / w) that a row takes once per mask however often the mask lists
     it.  A block whose weight is 0 leaves its copy as it is."""
-    lib = _lib.load()
     w = neighbor_weight.detach().float().contiguous()
     dev = w.device
     P, K = (int(s) for s in w.shape)
-    nscratch = int(lib.t4d_setup_region_scratch_bytes(P))
-    if nscratch == 0:
-        raise _lib.error("t4d_setup_region_scratch_bytes", exc=ValueError)
-    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+    scratch, nscratch = _lib.scratch("t4d_setup_region_scratch_bytes", dev, P)
     out = []
     for name, (key, blocks) in REGION_WEIGHT_BLOCKS.items():
         lw = losses_weights[key]
@@ -382,8 +366,7 @@ def flatten_edges(faces, n_vert: Optional[int] = None, device=None):
     like the modules' buffers.  Edges of more than two faces are dropped, v2 / v3 are the third corners of the lowest and the
     next face id, and only the two-face edges are kept, in candidate order.  As in the reference, v0s / v1s are read at the
     edge's rank among the edges NOT dropped, which is the edge itself unless an earlier edge had more than two faces."""
-    dev = _device(device)
-    lib = _lib.load()
+    dev = _lib.hip_device(device, _WHAT)
     f = np.asarray(faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else faces)
     if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] == 0 or not np.issubdtype(f.dtype, np.integer):
         raise ValueError(f"faces must be a non-empty integer [F,3] array, got {f.dtype} {f.shape}")
@@ -395,10 +378,7 @@ def flatten_edges(faces, n_vert: Optional[int] = None, device=None):
     edges = flatten_candidate_edges(f)
     csr = _TriangleCSR(f, n, dev)
     E = int(edges.shape[0])
-    nscratch = int(lib.t4d_setup_edges_scratch_bytes(E))
-    if nscratch == 0:
-        raise _lib.error("t4d_setup_edges_scratch_bytes", exc=ValueError)
-    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+    scratch, nscratch = _lib.scratch("t4d_setup_edges_scratch_bytes", dev, E)
     edges_d = torch.from_numpy(edges.astype(np.int32)).to(dev)
     out = torch.empty(4, E, dtype=torch.int64, device=dev)
     n_out = torch.empty(1, dtype=torch.int64, device=dev)
@@ -416,7 +396,7 @@ def region_topology(neighbor_indices_ori, facial_regions: dict, mask_list=(), pr
     """FlattenLoss_v2(variables, mask_list, pre_mask, ex_mask) (loss_util.py:223-255): (neighbor_num int64 [P], mask int64
     [P,K,3] = slot < neighbor_num, region_mask int64) on the device.  region_mask is the reference's own
     list(set(list(set(regions + pre_mask) - set(ex_mask)))), or range(P) when that is empty."""
-    dev = _device(device)
+    dev = _lib.hip_device(device, _WHAT)
     nnum = torch.tensor([len(lst) for lst in neighbor_indices_ori]).to(dev)
     P, K = int(nnum.shape[0]), max(len(lst) for lst in neighbor_indices_ori)
     mask = torch.empty(P, K, 3, dtype=torch.int64, device=dev)
@@ -462,7 +442,7 @@ def coarse_params(mesh: ObjMesh, trans_g, texture=None, device=None):
     """The coarse parameters and variables of train.py:115-206 from a read OBJ: (params, variables, colors) with params the
     reference's seven nn.Parameters (float32, device) and variables its keys up to neighbor_dist (facial_regions excluded);
     colors the integer vertex colours.  texture: mesh.texture by default."""
-    dev = _device(device)
+    dev = _lib.hip_device(device, _WHAT)
     from .densify import coarse_scales
     from .objexport import vertex_normals
     trans_g = np.linalg.inv(trans_g)                                                 # train.py:124-126, float64 on the host
@@ -499,7 +479,7 @@ def initialize_params(args, trans_g, facial_regions: Optional[dict] = None, devi
     <args.input_dir>/<args.seq>/face_v5.obj, its texture and facial_regions (default: ./assets/facial_regions.pkl, as the
     reference).  The dense half is densify.init_dense_gaussians(..., args.density if args.gen_tex else 1)."""
     from .densify import init_dense_gaussians
-    dev = _device(device)
+    dev = _lib.hip_device(device, _WHAT)
     rt_dir = os.path.join(args.input_dir, args.seq)
     mesh = read_obj(os.path.join(rt_dir, "face_v5.obj"))
     params, variables, _ = coarse_params(mesh, trans_g, device=dev)
@@ -520,8 +500,8 @@ def initialize_losses(variables: dict, device=None):
     """train.py:511-587: (variables, losses, losses_weights, losses_weights_dense).  losses maps the reference's nine names, in
     its order, to FlattenTopology / RegionTopology objects with the modules' buffers; variables gains iso_w, rig_w, rot_w."""
     fr = variables["facial_regions"]
-    dev = _device(device if device is not None else (variables["neighbor_weight"].device
-                                                     if torch.is_tensor(variables.get("neighbor_weight")) else None))
+    dev = _lib.hip_device(device if device is not None else (variables["neighbor_weight"].device
+                                                             if torch.is_tensor(variables.get("neighbor_weight")) else None), _WHAT)
     edge = lambda k, soft: FlattenTopology(fr[FLAT_EDGE_TERMS[k]], threshold=180 if soft else 0, device=dev)
     losses = {
         'flat': edge('flat', False),

@@ -35,8 +35,8 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import ptr
+from . import _args, _lib
+from ._lib import on_device, ptr
 
 ZERO = 32768
 STEPS = 32767
@@ -73,30 +73,15 @@ def _map(t, what: str, dtypes, tail=()) -> Tuple[int, int]:
     return h, w
 
 
-def _same(t, what: str, h: int, w: int) -> None:
-    if tuple(t.shape[:2]) != (h, w):
-        raise ValueError(f"{what} {tuple(t.shape)} does not match the map's [{h},{w}]")
-
-
-def _dev(t: torch.Tensor, what: str, device=None) -> torch.Tensor:
-    if not t.is_cuda or (device is not None and t.device != device):
-        raise RuntimeError(f"topo4d_amd has no CPU path: {what} must live on {'a' if device is None else 'the same'} HIP device")
-    return (t.to(torch.uint8) if t.dtype == torch.bool else t).contiguous()
-
-
-_MASK = (torch.uint8, torch.bool)
-
-
 def quantize(disp: torch.Tensor, hit: torch.Tensor, dist: float) -> Tuple[torch.Tensor, torch.Tensor]:
     """(code int32 [h,w], has uint8 [h,w]) of a displacement map (float32 [h,w], scan units) and its hit mask under the reach
     `dist`: where hit and disp is finite, code = 32768 + clamp(rint(disp / dist * 32767), -32767, 32767) in float64 with ties to
     even, and has = 1; elsewhere 32768 and 0."""
     h, w = _map(disp, "disp", (torch.float32,))
-    _map(hit, "hit", _MASK)
-    _same(hit, "hit", h, w)
+    _args.mask(hit, "hit", h, w)
     check_options(dist)
-    d = _dev(disp, "disp")
-    m = _dev(hit, "hit", d.device)
+    d = on_device(disp, "disp")
+    m = on_device(hit, "hit", d.device)
     code = torch.empty(h, w, dtype=torch.int32, device=d.device)
     has = torch.empty(h, w, dtype=torch.uint8, device=d.device)
     _lib.call("t4d_disp_quantize", ptr(d), ptr(m), h, w, float(dist), ptr(code), ptr(has), _lib.stream(d.device))
@@ -105,10 +90,8 @@ def quantize(disp: torch.Tensor, hit: torch.Tensor, dist: float) -> Tuple[torch.
 
 def _code_args(code, has, labels) -> Tuple[int, int]:
     h, w = _map(code, "code", (torch.int32,))
-    _map(has, "has", _MASK)
-    _same(has, "has", h, w)
-    _map(labels, "labels", (torch.uint8,))
-    _same(labels, "labels", h, w)
+    _args.mask(has, "has", h, w)
+    _args.mask(labels, "labels", h, w, (torch.uint8,))
     return h, w
 
 
@@ -117,12 +100,9 @@ def smooth(code: torch.Tensor, has: torch.Tensor, labels: torch.Tensor, rounds: 
     half up, of the taps inside the image that have a value and carry its label; every other texel is copied through."""
     h, w = _code_args(code, has, labels)
     check_options(1.0, rounds)
-    c = _dev(code, "code")
-    m, lab = _dev(has, "has", c.device), _dev(labels, "labels", c.device)
-    nbytes = int(_lib.load().t4d_disp_smooth_scratch_bytes(h, w))
-    if nbytes == 0:
-        raise _lib.error("t4d_disp_smooth_scratch_bytes", exc=ValueError)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=c.device)
+    c = on_device(code, "code")
+    m, lab = on_device(has, "has", c.device), on_device(labels, "labels", c.device)
+    scratch, nbytes = _lib.scratch("t4d_disp_smooth_scratch_bytes", c.device, h, w)
     out = torch.empty_like(c)
     _lib.call("t4d_disp_smooth", ptr(c), ptr(m), ptr(lab), h, w, int(rounds), ptr(out), ptr(scratch), nbytes, _lib.stream(c.device))
     return out
@@ -133,12 +113,13 @@ def normals(code: torch.Tensor, has: torch.Tensor, labels: torch.Tensor, pos: to
     displaced by (code - 32768) * unit along its normal; see the module's known limits."""
     h, w = _code_args(code, has, labels)
     _map(pos, "pos", (torch.float32,), (3,))
-    _same(pos, "pos", h, w)
+    if tuple(pos.shape[:2]) != (h, w):
+        raise ValueError(f"pos {tuple(pos.shape)} does not match the map's [{h},{w}]")
     u = float(unit)
     if not (math.isfinite(u) and u > 0.0):
         raise ValueError(f"unit must be finite and > 0, got {unit}")
-    c = _dev(code, "code")
-    m, lab, p = _dev(has, "has", c.device), _dev(labels, "labels", c.device), _dev(pos, "pos", c.device)
+    c = on_device(code, "code")
+    m, lab, p = on_device(has, "has", c.device), on_device(labels, "labels", c.device), on_device(pos, "pos", c.device)
     out = torch.empty(h, w, 3, dtype=torch.int32, device=c.device)
     _lib.call("t4d_disp_normals", ptr(c), ptr(m), ptr(lab), ptr(p), h, w, u, ptr(out), _lib.stream(c.device))
     return out
@@ -154,12 +135,11 @@ def finish(face_obj, vertices, disp: torch.Tensor, hit: torch.Tensor, dist: floa
     texfinish.fill16_islands over projtex.island_labels with the texels that have a value as the valid ones, after which the filled
     texels have a value too (has = has | filled); `smooth` rounds of smoothing; with `normals`, the normal map over
     projtex.surface_maps' points with unit = dist / 32767."""
-    from . import projtex, scanscore, texfinish
+    from . import projtex, texfinish
     h, w = _map(disp, "disp", (torch.float32,))                # argument errors first, with or without a device
-    _map(hit, "hit", _MASK)
-    _same(hit, "hit", h, w)
+    _args.mask(hit, "hit", h, w)
     check_options(dist, smooth)
-    dev = scanscore._device(device)
+    dev = _lib.hip_device(device, "the displacement map", ValueError)
     with torch.cuda.device(dev):
         code, has = quantize(disp.to(dev), hit.to(dev), dist)
         filled = torch.zeros(h, w, dtype=torch.uint8, device=dev)

@@ -72,8 +72,8 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import ptr
+from . import _args, _lib
+from ._lib import on_device, ptr
 
 MIN_BLOCK, MAX_BLOCK, MAX_RADIUS = 8, 64, 16
 MAX_LEVEL, MAX_REACH, MAX_NODE, MAX_TENT = 8, 4, 1 << 22, 46340
@@ -107,33 +107,10 @@ def blocks(h: int, w: int, block: int, stride: int) -> Tuple[int, int]:
     return ((h - block) // stride + 1 if h >= block else 0), ((w - block) // stride + 1 if w >= block else 0)
 
 
-def _image(image, what: str) -> Tuple[int, int]:
-    if not isinstance(image, torch.Tensor) or image.dtype != torch.uint8 or image.dim() not in (2, 3):
-        raise ValueError(f"{what} must be a uint8 [h,w] or [h,w,c] tensor")
-    h, w = int(image.shape[0]), int(image.shape[1])
-    c = 1 if image.dim() == 2 else int(image.shape[2])
-    if h < 1 or w < 1 or c not in (1, 3, 4):
-        raise ValueError(f"{what} must be [h,w] or [h,w,c] with h, w >= 1 and c in (1, 3, 4); got {tuple(image.shape)}")
-    return h, w
-
-
-def _mask(mask, what: str, h: int, w: int, dtypes=(torch.uint8, torch.bool)) -> None:
-    if not isinstance(mask, torch.Tensor) or mask.dtype not in dtypes or tuple(mask.shape) != (h, w):
-        kinds = " or ".join(str(d).replace("torch.", "") for d in dtypes)
-        raise ValueError(f"{what} must be a {kinds} [{h},{w}] tensor, got {getattr(mask, 'dtype', type(mask))} "
-                         f"{list(getattr(mask, 'shape', ()))}")
-
-
-def _on_device(t: torch.Tensor, what: str, device=None) -> torch.Tensor:
-    if not t.is_cuda or (device is not None and t.device != device):
-        raise RuntimeError(f"topo4d_amd has no CPU path: {what} must live on {'a' if device is None else 'the same'} HIP device")
-    return (t.to(torch.uint8) if t.dtype == torch.bool else t).contiguous()
-
-
 def luma(image: torch.Tensor) -> torch.Tensor:
     """uint8 [h,w]: (77 R + 150 G + 29 B + 128) >> 8 of a uint8 [h,w,3] image (RGBA: its first three channels), in integer torch
     ops; a one-channel image is its own luma."""
-    h, w = _image(image, "image")
+    h, w = _args.image(image, "image")[:2]
     if image.dim() == 2 or image.shape[2] == 1:
         return image.reshape(h, w).contiguous()
     rgb = image[..., :3].to(torch.int32)
@@ -147,26 +124,23 @@ def match(image_a: torch.Tensor, valid_a: torch.Tensor, image_b: torch.Tensor, v
     (include/topo4d_raster.h states the rule and the table, tests/drift_ref.py restates it).  images uint8 [h,w] or [h,w,c];
     valid_a, valid_b uint8 or bool [h,w], non-zero = the texel holds a photograph; labels uint8 [h,w] (projtex.island_labels;
     0: no island).  A shape without a whole block gives an empty table."""
-    h, w = _image(image_a, "image_a")                          # argument errors first, with or without a device
-    if _image(image_b, "image_b") != (h, w):
+    h, w = _args.image(image_a, "image_a")[:2]                 # argument errors first, with or without a device
+    if _args.image(image_b, "image_b")[:2] != (h, w):
         raise ValueError(f"image_b {tuple(image_b.shape)} does not match image_a's [{h},{w}]")
-    _mask(valid_a, "valid_a", h, w)
-    _mask(valid_b, "valid_b", h, w)
-    _mask(labels, "labels", h, w, dtypes=(torch.uint8,))
+    _args.mask(valid_a, "valid_a", h, w)
+    _args.mask(valid_b, "valid_b", h, w)
+    _args.mask(labels, "labels", h, w, dtypes=(torch.uint8,))
     block, stride, radius, min_count = check_options(block, stride, radius, min_count)
-    img_a = _on_device(image_a, "image_a")
+    img_a = on_device(image_a, "image_a")
     dev = img_a.device
-    img_b, val_a, val_b = _on_device(image_b, "image_b", dev), _on_device(valid_a, "valid_a", dev), _on_device(valid_b, "valid_b", dev)
-    lab = _on_device(labels, "labels", dev)
+    img_b, val_a, val_b = on_device(image_b, "image_b", dev), on_device(valid_a, "valid_a", dev), on_device(valid_b, "valid_b", dev)
+    lab = on_device(labels, "labels", dev)
     nby, nbx = blocks(h, w, block, stride)
     if nby == 0 or nbx == 0:
         return torch.zeros(nby, nbx, TABLE_WIDTH, dtype=torch.int32, device=dev)
-    nbytes = int(_lib.load().t4d_drift_scratch_bytes(h, w, block, stride, radius))
-    if nbytes == 0:
-        raise _lib.error("t4d_drift_scratch_bytes", exc=ValueError)
     with torch.cuda.device(dev):
+        scratch, nbytes = _lib.scratch("t4d_drift_scratch_bytes", dev, h, w, block, stride, radius)
         la, lb = luma(img_a), luma(img_b)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         out = torch.empty(nby, nbx, TABLE_WIDTH, dtype=torch.int32, device=dev)
         _lib.call("t4d_drift_match", ptr(la), ptr(val_a), ptr(lb), ptr(val_b), ptr(lab), h, w, block, stride, radius, min_count,
                   ptr(out), ptr(scratch), nbytes, _lib.stream(dev))
@@ -211,7 +185,7 @@ def metric(d: torch.Tensor, kept: torch.Tensor, pos: torch.Tensor, labels: torch
     if not isinstance(pos, torch.Tensor) or pos.dim() != 3 or pos.shape[2] != 3 or not pos.is_floating_point():
         raise ValueError("pos must be a float [h,w,3] tensor")
     h, w = int(pos.shape[0]), int(pos.shape[1])
-    _mask(labels, "labels", h, w, dtypes=(torch.uint8,))
+    _args.mask(labels, "labels", h, w, dtypes=(torch.uint8,))
     nby, nbx = blocks(h, w, block, stride)
     if not isinstance(d, torch.Tensor) or tuple(d.shape) != (nby, nbx, 2) or tuple(kept.shape) != (nby, nbx):
         raise ValueError(f"d and kept must be flow's [{nby},{nbx},2] and [{nby},{nbx}] for this size, block and stride")
@@ -251,7 +225,7 @@ def frame_pair(obj_a, tex_a: torch.Tensor, valid_a: torch.Tensor, tex_b: torch.T
     texels alone); island_labels and surface_maps of that size come from frame a's face.obj (meshrender.FaceObj)."""
     from . import projtex, texfinish
     level = int(level)
-    h, w = _image(tex_a, "tex_a")
+    h, w = _args.image(tex_a, "tex_a")[:2]
     block, stride, radius, min_count = check_options(block, stride, radius, min_count)
     if not 0 <= level <= 8 or h % (1 << level) or w % (1 << level):
         raise ValueError(f"level must be in [0, 8] with {h} x {w} divisible by 2^level, got {level}")
@@ -316,11 +290,11 @@ def dense_flow(d: torch.Tensor, kept: torch.Tensor, labels: torch.Tensor, block:
     nby, nbx = blocks(H >> level, W >> level, block, stride)
     if not isinstance(d, torch.Tensor) or d.dtype != torch.float64 or tuple(d.shape) != (nby, nbx, 2):
         raise ValueError(f"d must be flow's float64 [{nby},{nbx},2] for this size, level, block and stride")
-    _mask(kept, "kept", nby, nbx)
+    _args.mask(kept, "kept", nby, nbx)
     q = node_values(d, level, check)
-    lab = _on_device(labels, "labels")
+    lab = on_device(labels, "labels")
     dev = lab.device
-    q, keep = _on_device(q, "d", dev), _on_device(kept, "kept", dev)
+    q, keep = on_device(q, "d", dev), on_device(kept, "kept", dev)
     with torch.cuda.device(dev):
         out = torch.empty(H, W, 2, dtype=torch.int32, device=dev)
         support = torch.empty(H, W, dtype=torch.uint8, device=dev)
@@ -339,14 +313,13 @@ def warp(image: torch.Tensor, valid: torch.Tensor, labels: torch.Tensor, flow: t
     """(image uint8 of the given shape, valid uint8 [H,W]) on the device: frame b's texture resampled through dense_flow's field
     by the rule of t4d_drift_warp (four taps in 1/256 texel, restricted to the texel's island and to valid texels), so that a
     feature sits on the texel it has in frame a.  The inputs are left as they are."""
-    h, w = _image(image, "image")                              # argument errors first, with or without a device
-    _mask(valid, "valid", h, w)
-    _mask(labels, "labels", h, w, dtypes=(torch.uint8,))
+    h, w, c = _args.image(image, "image")                      # argument errors first, with or without a device
+    _args.mask(valid, "valid", h, w)
+    _args.mask(labels, "labels", h, w, dtypes=(torch.uint8,))
     _flow_field(flow, h, w)
-    img = _on_device(image, "image")
+    img = on_device(image, "image")
     dev = img.device
-    val, lab, fl = _on_device(valid, "valid", dev), _on_device(labels, "labels", dev), _on_device(flow, "flow", dev)
-    c = 1 if image.dim() == 2 else int(image.shape[2])
+    val, lab, fl = on_device(valid, "valid", dev), on_device(labels, "labels", dev), on_device(flow, "flow", dev)
     with torch.cuda.device(dev):
         out, out_valid = torch.empty_like(img), torch.empty(h, w, dtype=torch.uint8, device=dev)
         _lib.call("t4d_drift_warp", ptr(img), ptr(val), ptr(lab), ptr(fl), h, w, c, ptr(out), ptr(out_valid), _lib.stream(dev))
@@ -391,7 +364,7 @@ def correct_vertices(face_obj, vertices, flow: torch.Tensor, support: torch.Tens
         raise ValueError("labels must be a uint8 [H,W] tensor")
     H, W = int(labels.shape[0]), int(labels.shape[1])
     _flow_field(flow, H, W)
-    _mask(support, "support", H, W)
+    _args.mask(support, "support", H, W)
     verts = torch.as_tensor(vertices) if isinstance(vertices, np.ndarray) else vertices
     if not isinstance(verts, torch.Tensor) or verts.dim() != 2 or verts.shape[1] != 3 or not verts.is_floating_point():
         raise ValueError("vertices must be a float [N,3] tensor or array")
@@ -399,9 +372,9 @@ def correct_vertices(face_obj, vertices, flow: torch.Tensor, support: torch.Tens
     faces, uv_faces = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
     if faces.size and (faces.min() < 0 or faces.max() >= n_vert):
         raise ValueError(f"faces name vertex {int(faces.max())} but only {n_vert} vertices were given")
-    lab = _on_device(labels, "labels")
+    lab = on_device(labels, "labels")
     dev = lab.device
-    fl, sup = _on_device(flow, "flow", dev), _on_device(support, "support", dev)
+    fl, sup = on_device(flow, "flow", dev), on_device(support, "support", dev)
     owner = projtex.uv_vertex_owner(faces, uv_faces, len(face_obj.uvs))
     used = np.nonzero(owner >= 0)[0]                            # ascending UV index
     own = owner[used]
@@ -441,10 +414,10 @@ def stabilise_pair(obj_a, tex_a: torch.Tensor, valid_a: torch.Tensor, obj_b, tex
     stabilised image measures."""
     from . import projtex
     reach = check_reach(reach)
-    h, w = _image(tex_a, "tex_a")
-    if _image(tex_b, "tex_b") != (h, w):
+    h, w = _args.image(tex_a, "tex_a")[:2]
+    if _args.image(tex_b, "tex_b")[:2] != (h, w):
         raise ValueError(f"tex_b {tuple(tex_b.shape)} does not match tex_a's [{h},{w}]")
-    _mask(valid_b, "valid_b", h, w)
+    _args.mask(valid_b, "valid_b", h, w)
     r = frame_pair(obj_a, tex_a, valid_a, tex_b, valid_b, level, block, stride, radius, min_count, ratio, device=device)
     dev = r["table"].device
     block, stride, _, _ = check_options(block, stride, radius, min_count)

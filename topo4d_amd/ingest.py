@@ -258,15 +258,6 @@ def _descriptor(h: JpegHeader, data_offset: int, out_offset: int) -> _lib.T4DJpe
     return d
 
 
-def _device(device) -> torch.device:
-    dev = torch.device(device if device is not None else "cuda")
-    if dev.type != "cuda":
-        raise RuntimeError("topo4d_amd has no CPU path: ingest needs a HIP device")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
-
-
 def _to_device_bytes(buf: bytes, dev) -> torch.Tensor:
     return torch.frombuffer(bytearray(buf), dtype=torch.uint8).to(dev)
 
@@ -281,7 +272,7 @@ def decode_jpeg(files: Sequence[bytes], chunk_bits: Optional[int] = None, device
     """uint8 device tensors equal to np.asarray(Image.open(f)) for each file's bytes: [H,W,3] from the GPU decoder, or whatever
     PIL gives for the files it does not take.  chunk_bits: the chunk of the self-synchronising decode (None: the library's
     default).  headers / host_images: parse_jpeg results and PIL arrays already made (FramePrefetcher), per file or None."""
-    dev = _device(device)
+    dev = _lib.hip_device(device, "ingest")
     files = [bytes(f) for f in files]
     headers = list(headers) if headers is not None else [None] * len(files)
     host_images = list(host_images) if host_images is not None else [None] * len(files)
@@ -296,7 +287,6 @@ def decode_jpeg(files: Sequence[bytes], chunk_bits: Optional[int] = None, device
             host_images[i] = _pil_array(f)
         out[i] = torch.from_numpy(np.ascontiguousarray(host_images[i])).to(dev)
     if gpu:
-        lib = _lib.load()
         descs = (_lib.T4DJpegImage * len(gpu))()
         data_off = out_off = 0
         for k, (i, hd) in enumerate(gpu):
@@ -313,10 +303,7 @@ def decode_jpeg(files: Sequence[bytes], chunk_bits: Optional[int] = None, device
         data = host.to(dev, non_blocking=True)
         d_descs = _to_device_bytes(bytes(descs), dev)
         cb = 0 if chunk_bits is None else int(chunk_bits)
-        nscratch = int(lib.t4d_jpeg_scratch_bytes(descs, len(gpu), cb))
-        if nscratch == 0:
-            raise _lib.error("t4d_jpeg_scratch_bytes", exc=ValueError)
-        scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+        scratch, nscratch = _lib.scratch("t4d_jpeg_scratch_bytes", dev, descs, len(gpu), cb)
         pixels = torch.empty(max(out_off, 1), dtype=torch.uint8, device=dev)
         status = torch.empty(len(gpu), dtype=torch.int32, device=dev)
         _lib.call("t4d_jpeg_decode", descs, ptr(d_descs), len(gpu), ptr(data), cb, ptr(pixels), pixels.numel(), ptr(status), ptr(scratch), nscratch,
@@ -414,9 +401,7 @@ def warp_views(sources: Sequence[torch.Tensor], matrices, shapes, crops=None, ou
         for k in range(6):
             v.matrix[k] = float(m[k // 3, k % 3])
         v.cval = float(cval)
-    lib = _lib.load()
-    nscratch = int(lib.t4d_warp_scratch_bytes(n))
-    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+    scratch, nscratch = _lib.scratch("t4d_warp_scratch_bytes", dev, n)
     d_views = _to_device_bytes(bytes(views), dev)
     _lib.call("t4d_warp_views", views, ptr(d_views), n, ptr(scratch), nscratch, _lib.stream(dev))
     return outs
@@ -615,7 +600,7 @@ def _read_view(path: str, mask_path: Optional[str]) -> _HostView:
 def _assemble(views: List[_HostView], cameras, use_mask, rotate_mask, setup_camera, device, chunk_bits=None, lenses=None,
               supersample=1):
     """The device half of get_dataset: decode, warp, cameras; launches on the caller's thread and stream."""
-    dev = _device(device)
+    dev = _lib.hip_device(device, "ingest")
     decoded = decode_jpeg([v.data for v in views], chunk_bits=chunk_bits, device=dev, headers=[v.header for v in views],
                           host_images=[v.image for v in views])
     names = [os.path.basename(v.path) for v in views]

@@ -99,15 +99,6 @@ def triangulate(faces_ori, uv_faces_ori) -> Tuple[np.ndarray, np.ndarray]:
     return np.asarray(tri, np.int32).reshape(-1, 3), np.asarray(uv_tri, np.int32).reshape(-1, 3)
 
 
-def _device(device) -> torch.device:
-    dev = torch.device(device if device is not None else "cuda")
-    if dev.type != "cuda":
-        raise ValueError("topo4d_amd has no CPU path: the mesh renderer needs a HIP device")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
-
-
 def _int_rows(x, what: str, dev) -> torch.Tensor:
     t = torch.as_tensor(np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x))
     if t.dim() != 2 or t.shape[1] != 3 or t.is_floating_point():
@@ -121,7 +112,7 @@ class MeshRenderer:
     raise ValueError here, once."""
 
     def __init__(self, faces, uv_faces, uvs, texture, device=None):
-        self.dev = _device(device)
+        self.dev = _lib.hip_device(device, "the mesh renderer", ValueError)
         self.faces = _int_rows(faces, "faces", self.dev)
         self.uv_faces = _int_rows(uv_faces, "uv_faces", self.dev)
         if self.faces.shape != self.uv_faces.shape:
@@ -173,11 +164,7 @@ class MeshRenderer:
         is_f32 = 1 if self.texture.dtype == torch.float32 else 0
         stream = _lib.stream(self.dev)
         for _ in range(4):
-            nbytes = int(lib.t4d_mesh_render_scratch_bytes(V, F, H, W, cap))
-            if nbytes == 0:
-                raise _lib.error("t4d_mesh_render_scratch_bytes", exc=ValueError)
-            if self._scratch is None or self._scratch.numel() < nbytes:
-                self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+            self._scratch, nbytes = _lib.scratch("t4d_mesh_render_scratch_bytes", self.dev, V, F, H, W, cap, reuse=self._scratch)
             rc = lib.t4d_mesh_render(ptr(v), int(v.shape[0]), ptr(self.faces), ptr(self.uv_faces), F, ptr(self.uvs),
                                      int(self.uvs.shape[0]), ptr(self.texture), is_f32, int(self.texture.shape[0]),
                                      int(self.texture.shape[1]), ptr(views), V, H, W, host_bg, _MAPPINGS[mapping], ptr(image),
@@ -239,14 +226,8 @@ def image_metrics(render: torch.Tensor, target: torch.Tensor, coverage: Optional
         if mask.shape != (V, 1, H, W) or mask.device != render.device or not mask.is_floating_point():
             raise ValueError(f"mask must be float [{V},1,{H},{W}] on {render.device}")
         m = mask.to(torch.float32).contiguous()
-    lib = _lib.load()
-    nbytes = int(lib.t4d_image_metrics_scratch_bytes(V, H, W))
-    if nbytes == 0:
-        raise _lib.error("t4d_image_metrics_scratch_bytes", exc=ValueError)
-    key = render.device
-    scratch = _METRIC_SCRATCH.get(key)
-    if scratch is None or scratch.numel() < nbytes:
-        scratch = _METRIC_SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=render.device)
+    scratch, nbytes = _lib.scratch("t4d_image_metrics_scratch_bytes", render.device, V, H, W, reuse=_METRIC_SCRATCH.get(render.device))
+    _METRIC_SCRATCH[render.device] = scratch
     out = torch.empty(V, T4D_METRICS_FIELDS, dtype=torch.float64, device=render.device)
     r, t = render.contiguous(), target.contiguous()
     _lib.call("t4d_image_metrics", V, H, W, ptr(r), ptr(t), ptr(m), ptr(cov), ptr(out), ptr(scratch), nbytes,

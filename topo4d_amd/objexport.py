@@ -29,32 +29,8 @@ from ._lib import ptr
 T4D_OBJ_V, T4D_OBJ_VT, T4D_OBJ_F = 0, 1, 2
 FLOAT_CHARS = 24
 
-_PINNED = {}
 _EXPORTERS = []
-
-
-def _device(device=None) -> torch.device:
-    dev = torch.device(device if device is not None else "cuda")
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("topo4d_amd has no CPU path: the OBJ export needs a HIP device")
-    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-def _pinned(nbytes: int) -> torch.Tensor:
-    buf = _PINNED.get("host")
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        _PINNED["host"] = buf
-    return buf
-
-
-def _to_host(out: torch.Tensor, length: torch.Tensor, cap: int) -> bytes:
-    n = int(length.item())                                     # the one synchronisation of a block
-    if n < 0 or n > cap:
-        raise RuntimeError(f"OBJ text: bad output length {n} (capacity {cap})")
-    host = _pinned(n)
-    host[:n].copy_(out[:n])
-    return host[:n].numpy().tobytes()
+_WHAT = "the OBJ export"
 
 
 def _float64(x, dev, what: str) -> torch.Tensor:
@@ -81,14 +57,13 @@ def _float_lines(values: torch.Tensor, kind: int) -> bytes:
     rows = int(values.shape[0])
     if rows == 0:
         return b""
-    lib, dev = _lib.load(), values.device
+    dev = values.device
     cap = _max_bytes(kind, rows)
-    nscratch = int(lib.t4d_obj_text_scratch_bytes(kind, rows, 0))
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+    scratch, nscratch = _lib.scratch("t4d_obj_text_scratch_bytes", dev, kind, rows, 0)
     length = torch.empty(1, dtype=torch.int64, device=dev)
     _lib.call("t4d_obj_float_lines", kind, ptr(values), rows, ptr(out), cap, ptr(length), ptr(scratch), nscratch, _lib.stream(dev))
-    return _to_host(out, length, cap)
+    return _lib.read_back(out, length, cap, "t4d_obj_float_lines", empty_ok=True)
 
 
 def _corner_lists(faces, uv_faces):
@@ -120,18 +95,16 @@ def _face_lines(faces, uv_faces, dev) -> bytes:
     n_faces, corners = len(off) - 1, int(off[-1])
     if n_faces == 0:
         return b""
-    lib = _lib.load()
     cap = _max_bytes(T4D_OBJ_F, n_faces, corners)
-    nscratch = int(lib.t4d_obj_text_scratch_bytes(T4D_OBJ_F, n_faces, corners))
     d_off, d_v, d_uv = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (off, v, uv))
     if corners == 0:
         d_v = d_uv = torch.zeros(1, dtype=torch.int64, device=dev)
     out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+    scratch, nscratch = _lib.scratch("t4d_obj_text_scratch_bytes", dev, T4D_OBJ_F, n_faces, corners)
     length = torch.empty(1, dtype=torch.int64, device=dev)
     _lib.call("t4d_obj_face_lines", ptr(d_off), ptr(d_v), ptr(d_uv), n_faces, corners, ptr(out), cap, ptr(length), ptr(scratch),
               nscratch, _lib.stream(dev))
-    return _to_host(out, length, cap)
+    return _lib.read_back(out, length, cap, "t4d_obj_face_lines", empty_ok=True)
 
 
 def _rows(x, cols: int, what: str, dev) -> torch.Tensor:
@@ -146,7 +119,7 @@ def _rows(x, cols: int, what: str, dev) -> torch.Tensor:
 def write_obj_with_uv(file_path, vertices, faces, uvs, uv_faces) -> None:
     """helpers.py:258-272: the same bytes.  vertices [n,3] and uvs [m,2] float64 (numpy arrays or tensors; only the first 3 /
     2 columns are printed, as the f-strings do), faces / uv_faces lists of lists of any length, int arrays or tensors."""
-    dev = vertices.device if isinstance(vertices, torch.Tensor) and vertices.is_cuda else _device()
+    dev = vertices.device if isinstance(vertices, torch.Tensor) and vertices.is_cuda else _lib.hip_device(None, _WHAT)
     data = _float_lines(_rows(vertices, 3, "vertices", dev), T4D_OBJ_V) + _float_lines(_rows(uvs, 2, "uvs", dev), T4D_OBJ_VT) + \
         _face_lines(faces, uv_faces, dev)
     with open(file_path, "wb") as f:
@@ -157,7 +130,7 @@ def format_float_repr(x: torch.Tensor) -> list:
     """[repr(float(v)) for v in x] from the device formatter; x a float64 tensor (moved to the device if it is not there)."""
     if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
         raise ValueError("format_float_repr expects a float64 tensor")
-    dev = x.device if x.is_cuda else _device()
+    dev = x.device if x.is_cuda else _lib.hip_device(None, _WHAT)
     vals = x.detach().reshape(-1).to(dev).contiguous()
     n = vals.numel()
     if n == 0:
@@ -187,15 +160,12 @@ class _VertexFaces:
     """The vertex -> corner CSR of one triangle list on the device (t4d_obj_vertex_faces)."""
 
     def __init__(self, faces: torch.Tensor, n_vert: int):
-        lib, dev = _lib.load(), faces.device
+        dev = faces.device
         self.faces, self.n_vert, self.n_faces = faces, int(n_vert), int(faces.shape[0])
         self.offsets = torch.empty(self.n_vert + 1, dtype=torch.int32, device=dev)
         self.entries = torch.empty(3 * self.n_faces, dtype=torch.int32, device=dev)
         status = torch.empty(2, dtype=torch.int32, device=dev)
-        nscratch = int(lib.t4d_obj_csr_scratch_bytes(self.n_vert))
-        if nscratch == 0:
-            raise _lib.error("t4d_obj_csr_scratch_bytes", exc=ValueError)
-        scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
+        scratch, nscratch = _lib.scratch("t4d_obj_csr_scratch_bytes", dev, self.n_vert)
         _lib.call("t4d_obj_vertex_faces", ptr(faces), self.n_faces, self.n_vert, ptr(self.offsets), ptr(self.entries), ptr(status),
                   ptr(scratch), nscratch, _lib.stream(dev))
         bad, unref = (int(v) for v in status.cpu())
@@ -203,7 +173,7 @@ class _VertexFaces:
             raise ValueError(f"faces: {bad} corners index a vertex outside [0, {self.n_vert})")
         if unref:
             raise ValueError(f"{unref} of {self.n_vert} vertices are in no face; trimesh would drop them")
-        self.face_scratch = torch.empty(int(lib.t4d_obj_normals_scratch_bytes(self.n_faces)), dtype=torch.uint8, device=dev)
+        self.face_scratch = _lib.scratch("t4d_obj_normals_scratch_bytes", dev, self.n_faces)[0]
 
     def normals(self, vertices: torch.Tensor) -> torch.Tensor:
         if vertices.dtype not in (torch.float32, torch.float64) or tuple(vertices.shape) != (self.n_vert, 3):
@@ -253,7 +223,7 @@ class MeshExporter:
         self.variables = variables
         self.n_vert = n_vert
         self.transform = (C.c_double * 12)(*tg[:3, :3].ravel().tolist(), *tg[:3, 3].tolist())
-        self.dev = _device(device)
+        self.dev = _lib.hip_device(device, _WHAT)
         self.csr = _VertexFaces(torch.from_numpy(faces32).to(self.dev), n_vert)
         self.static = _float_lines(_rows(variables["uvs_ori"], 2, "uvs_ori", self.dev), T4D_OBJ_VT) + \
             _face_lines(variables["faces_ori"], variables["uv_faces_ori"], self.dev)

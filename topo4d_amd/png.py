@@ -19,41 +19,28 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from ._lib import ptr
 
-_PINNED = {}
 
-
-def _shape(h: int, w: int, c: int) -> None:
+def _max_bytes(query: str, h: int, w: int, c: int) -> int:
+    h, w, c = int(h), int(w), int(c)
     if h < 1 or w < 1 or c not in (1, 3, 4):
         raise ValueError(f"PNG image must be [H,W] or [H,W,C] with H, W >= 1 and C in (1, 3, 4); got {(h, w, c)}")
+    n = getattr(_lib.load(), query)(h, w, c)
+    if n == 0:
+        raise _lib.error(query, exc=ValueError)
+    return int(n)
 
 
 def max_encoded_bytes(h: int, w: int, c: int) -> int:
     """Upper bound on the file size for an [h,w,c] image: every segment stored uncompressed, plus the chunk framing."""
-    _shape(int(h), int(w), int(c))
-    n = _lib.load().t4d_png_max_bytes(int(h), int(w), int(c))
-    if n == 0:
-        raise _lib.error("t4d_png_max_bytes", exc=ValueError)
-    return int(n)
+    return _max_bytes("t4d_png_max_bytes", h, w, c)
 
 
-def _check(image) -> tuple:
-    if not isinstance(image, torch.Tensor):
-        raise ValueError("encode_png expects a torch tensor")
-    if image.dtype not in (torch.uint8, torch.float32):
-        raise ValueError(f"encode_png expects uint8 or float32, got {image.dtype}")
-    if image.dim() == 2:
-        h, w, c = int(image.shape[0]), int(image.shape[1]), 1
-    elif image.dim() == 3:
-        h, w, c = (int(d) for d in image.shape)
-    else:
-        raise ValueError(f"encode_png expects [H,W] or [H,W,C], got shape {tuple(image.shape)}")
-    _shape(h, w, c)
-    if not image.is_cuda:
-        raise RuntimeError("topo4d_amd has no CPU path: encode_png needs the image on a HIP device")
-    return h, w, c
+def max_encoded_bytes16(h: int, w: int, c: int) -> int:
+    """max_encoded_bytes for the 16-bit file of an [h,w,c] image."""
+    return _max_bytes("t4d_png_max_bytes16", h, w, c)
 
 
 def _check_chw(image) -> tuple:
@@ -61,107 +48,52 @@ def _check_chw(image) -> tuple:
         raise ValueError("encode_png(chw=True) expects a torch tensor")
     if image.dtype != torch.float32:
         raise ValueError(f"encode_png(chw=True) expects float32, got {image.dtype}")
-    if image.dim() != 3 or int(image.shape[0]) != 3:
-        raise ValueError(f"encode_png(chw=True) expects a [3,H,W] image, got shape {tuple(image.shape)}")
-    h, w = int(image.shape[1]), int(image.shape[2])
-    _shape(h, w, 3)
-    if not image.is_cuda:
-        raise RuntimeError("topo4d_amd has no CPU path: encode_png needs the image on a HIP device")
-    return h, w, 3
+    if image.dim() != 3 or int(image.shape[0]) != 3 or int(image.shape[1]) < 1 or int(image.shape[2]) < 1:
+        raise ValueError(f"encode_png(chw=True) expects a [3,H,W] image with H, W >= 1, got shape {tuple(image.shape)}")
+    return int(image.shape[1]), int(image.shape[2]), 3
 
 
-def max_encoded_bytes16(h: int, w: int, c: int) -> int:
-    """max_encoded_bytes for the 16-bit file of an [h,w,c] image."""
-    _shape(int(h), int(w), int(c))
-    n = _lib.load().t4d_png_max_bytes16(int(h), int(w), int(c))
-    if n == 0:
-        raise _lib.error("t4d_png_max_bytes16", exc=ValueError)
-    return int(n)
-
-
-def _check16(image) -> tuple:
-    if not isinstance(image, torch.Tensor):
-        raise ValueError("encode_png16 expects a torch tensor")
-    if image.dtype != torch.int32:
-        raise ValueError(f"encode_png16 expects int32 holding 0..65535, got {image.dtype}")
-    if image.dim() == 2:
-        h, w, c = int(image.shape[0]), int(image.shape[1]), 1
-    elif image.dim() == 3:
-        h, w, c = (int(d) for d in image.shape)
-    else:
-        raise ValueError(f"encode_png16 expects [H,W] or [H,W,C], got shape {tuple(image.shape)}")
-    _shape(h, w, c)
-    if not image.is_cuda:
-        raise RuntimeError("topo4d_amd has no CPU path: encode_png16 needs the image on a HIP device")
-    return h, w, c
-
-
-def _pinned(nbytes: int) -> torch.Tensor:
-    buf = _PINNED.get("host")
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        _PINNED["host"] = buf
-    return buf
+def _encode(what: str, entry: str, bits: str, image: torch.Tensor, shape: tuple, *lead) -> bytes:
+    """The file entry point `entry` writes for `image` (checked: `shape` is its (h, w, c)); bits: "" or "16", the suffix of the
+    size queries; lead: the entry point's arguments between the image and the output."""
+    img = _lib.on_device(image, what)
+    dev = img.device
+    cap = _max_bytes("t4d_png_max_bytes" + bits, *shape)
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    scratch, nscratch = _lib.scratch("t4d_png_scratch_bytes" + bits, dev, *shape)
+    length = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.call(entry, ptr(img), *lead, ptr(out), cap, ptr(length), ptr(scratch), nscratch, _lib.stream(dev))
+    return _lib.read_back(out, length, cap, entry)
 
 
 def encode_png(image: torch.Tensor, chw: bool = False) -> bytes:
     """The PNG file of `image` (see the module docstring; `chw`: a [3,H,W] float32 render, as torchvision's save_image writes it).
     Runs on torch's current stream; synchronises once to read the length, then copies exactly that many bytes through a reused
     pinned buffer."""
-    h, w, c = _check_chw(image) if chw else _check(image)
-    lib = _lib.load()
-    dev = image.device
-    img = image.contiguous()
-    cap = max_encoded_bytes(h, w, c)
-    nscratch = int(lib.t4d_png_scratch_bytes(h, w, c))
-    out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
-    length = torch.empty(1, dtype=torch.int64, device=dev)
     if chw:
-        name = "t4d_png_encode_chw"
-        _lib.call(name, ptr(img), h, w, ptr(out), cap, ptr(length), ptr(scratch), nscratch, _lib.stream(dev))
-    else:
-        name = "t4d_png_encode"
-        _lib.call(name, ptr(img), 1 if img.dtype == torch.float32 else 0, h, w, c, ptr(out), cap, ptr(length), ptr(scratch),
-                  nscratch, _lib.stream(dev))
-    n = int(length.item())                                        # the one synchronisation
-    if n <= 0 or n > cap:
-        raise RuntimeError(f"{name}: bad output length {n} (capacity {cap})")
-    host = _pinned(n)
-    host[:n].copy_(out[:n])
-    return host[:n].numpy().tobytes()
+        h, w, c = _check_chw(image)
+        return _encode("encode_png's image", "t4d_png_encode_chw", "", image, (h, w, c), h, w)
+    h, w, c = _args.image(image, "encode_png's image", (torch.uint8, torch.float32), axes="HWC")
+    return _encode("encode_png's image", "t4d_png_encode", "", image, (h, w, c), 1 if image.dtype == torch.float32 else 0, h, w, c)
 
 
 def encode_png16(image: torch.Tensor) -> bytes:
     """The 16-bit PNG file of an int32 image (the low 16 bits of every word; see the module docstring).  Runs and synchronises as
     encode_png does."""
-    h, w, c = _check16(image)
-    lib = _lib.load()
-    dev = image.device
-    img = image.contiguous()
-    cap = max_encoded_bytes16(h, w, c)
-    nscratch = int(lib.t4d_png_scratch_bytes16(h, w, c))
-    out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev)
-    length = torch.empty(1, dtype=torch.int64, device=dev)
-    _lib.call("t4d_png_encode16", ptr(img), h, w, c, ptr(out), cap, ptr(length), ptr(scratch), nscratch, _lib.stream(dev))
-    n = int(length.item())                                        # the one synchronisation
-    if n <= 0 or n > cap:
-        raise RuntimeError(f"t4d_png_encode16: bad output length {n} (capacity {cap})")
-    host = _pinned(n)
-    host[:n].copy_(out[:n])
-    return host[:n].numpy().tobytes()
+    h, w, c = _args.image(image, "encode_png16's image", (torch.int32,), " holding 0..65535", axes="HWC")
+    return _encode("encode_png16's image", "t4d_png_encode16", "16", image, (h, w, c), h, w, c)
+
+
+def _write(path, data: bytes) -> None:
+    with open(path, "wb") as f:
+        f.write(data)
 
 
 def write_png16(path, image: torch.Tensor) -> None:
     """encode_png16(image) written to `path`."""
-    data = encode_png16(image)
-    with open(path, "wb") as f:
-        f.write(data)
+    _write(path, encode_png16(image))
 
 
 def write_png(path, image: torch.Tensor, chw: bool = False) -> None:
     """encode_png(image, chw) written to `path`."""
-    data = encode_png(image, chw)
-    with open(path, "wb") as f:
-        f.write(data)
+    _write(path, encode_png(image, chw))

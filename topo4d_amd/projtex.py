@@ -207,7 +207,7 @@ def _view_group(dev, cams, depth, **images) -> tuple:
 
 
 def _skip(skip, skip_base, h: int, w: int, V: int) -> list:
-    """[] for no mask, or [("skip", skip)] for _on_device: skip an int32 [h,w] tensor (consistency's), skip_base an integer with
+    """[] for no mask, or [("skip", skip)] for _placed: skip an int32 [h,w] tensor (consistency's), skip_base an integer with
     skip_base >= 0 and skip_base + V <= 32; ValueError for anything else"""
     if isinstance(skip_base, bool) or not isinstance(skip_base, (int, np.integer)):
         raise ValueError(f"skip_base must be an integer, got {skip_base!r}")
@@ -222,7 +222,7 @@ def _skip(skip, skip_base, h: int, w: int, V: int) -> list:
     return [("skip", skip)]
 
 
-def _on_device(dev, pos, nrm, coverage, others, g) -> tuple:
+def _placed(dev, pos, nrm, coverage, others, g) -> tuple:
     """The last step before a launch, after every argument error: the named tensors `others` live where pos does (ValueError), and
     that is a HIP device (RuntimeError).  (pos, nrm, coverage as uint8, others' tensors), all contiguous, and the gains uploaded."""
     for name, t in [("nrm", nrm), ("coverage", coverage), *others]:
@@ -253,7 +253,7 @@ def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, 
     views, V, H, W = _view_group(dev, cams, depth, photos=photos)
     g = _gains(gains, V)
     mask = _skip(skip, skip_base, h, w, V)
-    pos, nrm, cov, (photos, depth, *mask), g = _on_device(dev, pos, nrm, coverage, [("photos", photos), ("depth", depth), *mask], g)
+    pos, nrm, cov, (photos, depth, *mask), g = _placed(dev, pos, nrm, coverage, [("photos", photos), ("depth", depth), *mask], g)
     color = torch.empty(h, w, 3, dtype=torch.float32, device=dev)
     weight = torch.empty(h, w, dtype=torch.float32, device=dev)
     count = torch.empty(h, w, dtype=torch.uint8, device=dev)
@@ -302,7 +302,7 @@ def project_bands(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, 
     views, V, H, W = _view_group(dev, cams, depth, photos=photos, low=low)
     g = _gains(gains, V)
     mask = _skip(skip, skip_base, h, w, V)
-    pos, nrm, cov, (photos, low, depth, *mask), g = _on_device(dev, pos, nrm, coverage,
+    pos, nrm, cov, (photos, low, depth, *mask), g = _placed(dev, pos, nrm, coverage,
                                                               [("photos", photos), ("low", low), ("depth", depth), *mask], g)
     low_color, high = (torch.empty(h, w, 3, dtype=torch.float32, device=dev) for _ in range(2))
     weight, best_weight = (torch.empty(h, w, dtype=torch.float32, device=dev) for _ in range(2))
@@ -314,7 +314,7 @@ def project_bands(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, 
 
 
 def _mixed_views(dev, groups: list, name: str, what: str) -> tuple:
-    """(packed records per group, (H, W) per view, [(what, photos), (what, depth)] per group for _on_device) of the groups pair_stats
+    """(packed records per group, (H, W) per view, [(what, photos), (what, depth)] per group for _placed) of the groups pair_stats
     and consistency take: (cams, photos, depth) per image size, at most 32 views in all; ValueError for anything else"""
     if not groups:
         raise ValueError(f"{name}: no views")
@@ -333,7 +333,7 @@ def _mixed_views(dev, groups: list, name: str, what: str) -> tuple:
 
 def _view_tables(dev, records, sizes, held) -> tuple:
     """(views [V,40], sizes [V,2] int32, tables [2,V] int64: the views' photograph and depth pointers) on the device.  held: the
-    contiguous photographs and depth maps of _on_device, group after group; the caller keeps them alive until the launch is queued
+    contiguous photographs and depth maps of _placed, group after group; the caller keeps them alive until the launch is queued
     on their stream."""
     photo_ptrs = [p[k].data_ptr() for p in held[0::2] for k in range(p.shape[0])]
     depth_ptrs = [d[k].data_ptr() for d in held[1::2] for k in range(d.shape[0])]
@@ -362,7 +362,7 @@ def pair_stats(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, gro
         count, sums = out
         _map(count, "out[0]", (V, V), torch.int64)
         _map(sums, "out[1]", (V, V, 3), torch.int64)
-    pos, nrm, cov, held, g = _on_device(dev, pos, nrm, coverage, held + [("photos, depth and out", t) for t in out or ()], g)
+    pos, nrm, cov, held, g = _placed(dev, pos, nrm, coverage, held + [("photos, depth and out", t) for t in out or ()], g)
     if out is None:
         count, sums = torch.zeros(V, V, dtype=torch.int64, device=dev), torch.zeros(V, V, 3, dtype=torch.int64, device=dev)
     elif not (count.is_contiguous() and sums.is_contiguous()):
@@ -395,7 +395,7 @@ def consistency(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, gr
     records, sizes, held = _mixed_views(dev, groups, "consistency", "photos and depth")
     V = len(sizes)
     g = _gains(gains, V)
-    pos, nrm, cov, held, g = _on_device(dev, pos, nrm, coverage, held, g)
+    pos, nrm, cov, held, g = _placed(dev, pos, nrm, coverage, held, g)
     views, sizes_t, tables = _view_tables(dev, records, sizes, held)
     skip = torch.empty(h, w, dtype=torch.int32, device=dev)
     votes = torch.empty(h, w, dtype=torch.uint8, device=dev)
@@ -479,7 +479,7 @@ def surface_maps(face_obj, vertices: torch.Tensor, res, device=None):
     h, w = _size(res)
     if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_floating_point():
         raise ValueError("vertices must be a float [N,3] tensor")
-    dev = meshrender._device(device if device is not None else (vertices.device if vertices.is_cuda else None))
+    dev = _lib.hip_device(device if device is not None else (vertices.device if vertices.is_cuda else None), "the mesh renderer", ValueError)
     if vertices.device != dev:
         raise RuntimeError(f"topo4d_amd has no CPU path: vertices must live on {dev}, got {vertices.device}")
     faces, uv_faces = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
@@ -538,7 +538,7 @@ def island_labels(face_obj, h: int, w: int, device=None) -> torch.Tensor:
     from . import meshrender, texfinish, texture
     h, w = _size((h, w))
     ids = uv_islands(face_obj)                                 # argument errors first, with or without a device
-    dev = meshrender._device(device)
+    dev = _lib.hip_device(device, "the mesh renderer", ValueError)
     _, uv_tris = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
     uv_verts = texture.process_uv(face_obj.uvs, h, w)
     img = texture.render_colors(uv_verts, uv_tris, ids.astype(np.float32)[:, None], h, w, c=1, device=dev)
@@ -559,7 +559,7 @@ def _frame_inputs(face_obj, vertices: torch.Tensor, dataset, res, device):
     depth (meshrender.MeshRenderer over a 1x1 dummy texture)."""
     from . import meshrender
     faces, uv_faces = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
-    dev = meshrender._device(device if device is not None else (vertices.device if vertices.is_cuda else None))
+    dev = _lib.hip_device(device if device is not None else (vertices.device if vertices.is_cuda else None), "the mesh renderer", ValueError)
     renderer = meshrender.MeshRenderer(faces, uv_faces, face_obj.uvs, np.zeros((1, 1, 3), np.uint8), device=dev)
 
     def groups():

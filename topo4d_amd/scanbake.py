@@ -23,7 +23,7 @@ import os
 import numpy as np
 import torch
 
-from . import scanscore
+from . import _lib, scanscore
 
 DISP_NAME = "face_disp.npy"
 HIT_NAME = "face_disp_hit.png"
@@ -52,7 +52,7 @@ def bake_displacement(face_obj, vertices, scan: scanscore.Scan, res, dist: float
     dist = float(dist)
     if not (math.isfinite(dist) and dist >= 0.0):
         raise ValueError(f"dist must be a finite distance >= 0, got {dist}")
-    dev = scanscore._device(device)
+    dev = _lib.hip_device(device, "the displacement bake", ValueError)
     v = vertices if isinstance(vertices, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(vertices, np.float64))
     v = v.detach().to(dev)
     with torch.cuda.device(dev):

@@ -248,13 +248,7 @@ def read_scan(path) -> Scan:
 
 
 # ---- the index --------------------------------------------------------------------------------------------------------------
-def _device(device) -> torch.device:
-    dev = torch.device(device if device is not None else "cuda")
-    if dev.type != "cuda":
-        raise ValueError("topo4d_amd has no CPU path: the closest-point query needs a HIP device")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
+_WHAT = "the closest-point query"
 
 
 def _points(x, what: str, dev) -> torch.Tensor:
@@ -272,7 +266,7 @@ class ClosestPointIndex:
     vertices, or a face index beyond the vertices."""
 
     def __init__(self, vertices, faces=None, device=None):
-        self.dev = _device(device)
+        self.dev = _lib.hip_device(device, _WHAT, ValueError)
         v = _points(vertices, "vertices", self.dev)
         if not bool(torch.isfinite(v).all()):
             raise ValueError("vertices hold non-finite coordinates")
@@ -318,11 +312,7 @@ class ClosestPointIndex:
         self._scratch = None
 
     def _query_scratch(self, n: int) -> torch.Tensor:
-        nbytes = _lib.load().t4d_closest_query_scratch_bytes(n)
-        if nbytes == 0:
-            raise _lib.error("t4d_closest_query_scratch_bytes", exc=ValueError)
-        if self._scratch is None or self._scratch.numel() < nbytes:
-            self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        self._scratch = _lib.scratch("t4d_closest_query_scratch_bytes", self.dev, n, reuse=self._scratch)[0]
         return self._scratch
 
     def query(self, points, max_dist: Optional[float] = None, input_order: bool = False):
@@ -429,7 +419,7 @@ def score_scan(mesh_vertices, mesh_faces, scan: Scan, max_dist: Optional[float] 
         raise ValueError(f"shoot must be a finite distance >= 0 or None, got {shoot}")
     if shoot is not None and (scan.faces is None or len(scan.faces) == 0):
         raise ValueError("shoot needs a scan with faces: a ray meets only triangles")
-    dev = _device(device)
+    dev = _lib.hip_device(device, _WHAT, ValueError)
     mv = _points(torch.as_tensor(np.asarray(mesh_vertices, np.float64)) if not isinstance(mesh_vertices, torch.Tensor) else mesh_vertices,
                  "mesh_vertices", dev)
     sv = _points(torch.from_numpy(np.ascontiguousarray(scan.vertices, np.float64)), "scan vertices", dev)

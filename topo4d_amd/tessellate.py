@@ -40,8 +40,8 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import ptr
+from . import _args, _lib
+from ._lib import on_device, ptr
 
 MAX_LEVEL = 64
 OBJ_NAME = "face_hi.obj"
@@ -58,13 +58,11 @@ def check_level(level) -> int:
 def check_maps(code, has, labels=None) -> Tuple[int, int]:
     """(h, w) of a code map (int32 [h,w]) with its `has` (uint8 or bool) and, if given, its labels (uint8), all of one size;
     ValueError otherwise (callable without a device)."""
-    from .dispmap import _MASK, _map, _same
+    from .dispmap import _map
     h, w = _map(code, "code", (torch.int32,))
-    _map(has, "has", _MASK)
-    _same(has, "has", h, w)
+    _args.mask(has, "has", h, w)
     if labels is not None:
-        _map(labels, "labels", (torch.uint8,))
-        _same(labels, "labels", h, w)
+        _args.mask(labels, "labels", h, w, (torch.uint8,))
     return h, w
 
 
@@ -108,7 +106,7 @@ class Tessellation:
     all before a device is looked for."""
 
     def __init__(self, face_obj, level: int, device=None):
-        from . import meshrender, projtex, scanscore
+        from . import meshrender, projtex
         self.level = check_level(level)
         faces, uv_faces = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
         self.n_corner, self.n_uv_corner = int(len(face_obj.vertices)), int(len(face_obj.uvs))
@@ -122,7 +120,7 @@ class Tessellation:
         corner_owner[named] = first
         islands = projtex.uv_islands(face_obj)
         self._topology = (faces, uv_faces, np.array(face_obj.uvs, np.float64))
-        self.dev = scanscore._device(device)
+        self.dev = _lib.hip_device(device, "the tessellation", ValueError)
         put = lambda a, dtype: torch.from_numpy(np.ascontiguousarray(a, dtype)).to(self.dev)
         self._tri, self._uv_tri = put(faces, np.int32), put(uv_faces, np.int32)
         self._edges, self._uv_edges = put(edges, np.int32), put(uv_edges, np.int32)
@@ -190,14 +188,13 @@ class Tessellation:
         [h,w]; has uint8 or bool, labels uint8: projtex.island_labels at the map's size) with `unit` scan units per code step.
         sampled is 0 where no tap counted (the vertex stays on the flat tessellation), or the normal was zero or anything was
         non-finite."""
-        from .dispmap import _dev
         h, w = check_maps(code, has, labels)
         u = float(unit)
         if not math.isfinite(u):
             raise ValueError(f"unit must be finite, got {unit}")
         v = _vertices(vertices, self.n_corner, self.dev)
-        c = _dev(code, "code", self.dev)
-        m, lab = _dev(has, "has", self.dev), _dev(labels, "labels", self.dev)
+        c = on_device(code, "code", self.dev)
+        m, lab = on_device(has, "has", self.dev), on_device(labels, "labels", self.dev)
         with torch.cuda.device(self.dev):
             normals = self._normals(v)
             out = torch.empty((self.n_vertices, 3), dtype=torch.float64, device=self.dev)
@@ -212,13 +209,13 @@ def displace_frame(face_obj, vertices, code: torch.Tensor, has: torch.Tensor, le
     """{"tess": Tessellation, "vertices": float64 [M,3], "sampled": uint8 [M]}: `face_obj` with `vertices` tessellated at `level`
     and displaced by a finished code map (dispmap.finish's "code" and "has") baked with the reach `dist`; the labels are
     projtex.island_labels at the map's size.  tess: a Tessellation to reuse when it matches the topology and the level."""
-    from . import dispmap, projtex, scanscore
+    from . import dispmap, projtex
     h, w = check_maps(code, has)                                # argument errors first, with or without a device
     n = check_level(level)
     dispmap.check_options(dist)
     if tess is None or not tess.matches(face_obj, n):
         tess = Tessellation(face_obj, n, device=device)
-    dev = scanscore._device(device) if device is not None else tess.dev
+    dev = _lib.hip_device(device, "the tessellation", ValueError) if device is not None else tess.dev
     with torch.cuda.device(dev):
         labels = projtex.island_labels(face_obj, h, w, device=dev)
         fine, sampled = tess.displace(vertices, code.to(dev), has.to(dev), labels, dispmap.code_unit(dist))

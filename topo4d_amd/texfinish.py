@@ -43,43 +43,25 @@ from typing import Dict, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import ptr
+from . import _args, _lib
+from ._lib import on_device, ptr
 
 MAX_PAD, MAX_ERODE = 64, 4
+_NOTE = {torch.uint8: "", torch.int32: " holding 0..65535"}    # what _args.image says of an image of 8-bit / of 16-bit samples
 
 
-def _image(image, what: str, need_device: bool = True) -> Tuple[torch.Tensor, int, int, int]:
-    if not isinstance(image, torch.Tensor) or image.dtype != torch.uint8 or image.dim() not in (2, 3):
-        raise ValueError(f"{what} must be a uint8 [h,w] or [h,w,c] tensor")
-    h, w = int(image.shape[0]), int(image.shape[1])
-    c = 1 if image.dim() == 2 else int(image.shape[2])
-    if h < 1 or w < 1 or c not in (1, 3, 4):
-        raise ValueError(f"{what} must be [h,w] or [h,w,c] with h, w >= 1 and c in (1, 3, 4); got {tuple(image.shape)}")
-    if need_device and not image.is_cuda:
-        raise RuntimeError(f"topo4d_amd has no CPU path: {what} must live on a HIP device")
-    return image.contiguous(), h, w, c
-
-
-def _coverage(coverage, h: int = None, w: int = None, device=None) -> torch.Tensor:
-    if not isinstance(coverage, torch.Tensor) or coverage.dtype not in (torch.uint8, torch.bool) or coverage.dim() != 2:
-        raise ValueError("coverage must be a uint8 or bool [h,w] tensor")
-    if h is not None and tuple(coverage.shape) != (h, w):
-        raise ValueError(f"coverage {tuple(coverage.shape)} does not match the image's [{h},{w}]")
-    if not coverage.is_cuda or (device is not None and coverage.device != device):
-        raise RuntimeError("topo4d_amd has no CPU path: coverage must live on the image's HIP device")
-    if coverage.dtype == torch.bool:
-        coverage = coverage.to(torch.uint8)
-    return coverage.contiguous()
+def _image_and_coverage(image, coverage) -> Tuple[torch.Tensor, torch.Tensor, int, int, int]:
+    h, w, c = _args.image(image, "image")
+    img = on_device(image, "image")
+    _args.mask(coverage, "coverage", h, w)
+    return img, on_device(coverage, "coverage", img.device, "the image's"), h, w, c
 
 
 def coverage_from_depth(depth: torch.Tensor) -> torch.Tensor:
     """uint8 [h,w], 1 where the bake whose depth buffer this is (render_colors(..., return_depth=True)) wrote a texel."""
     if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or depth.dim() != 2:
         raise ValueError("coverage_from_depth expects the float32 [h,w] depth buffer of a bake")
-    if not depth.is_cuda:
-        raise RuntimeError("topo4d_amd has no CPU path: the depth buffer must live on a HIP device")
-    d = depth.contiguous()
+    d = on_device(depth, "the depth buffer")
     h, w = int(d.shape[0]), int(d.shape[1])
     out = torch.empty(h, w, dtype=torch.uint8, device=d.device)
     _lib.call("t4d_texture_coverage", ptr(d), h, w, ptr(out), _lib.stream(d.device))
@@ -90,9 +72,7 @@ def quantize(image_f32: torch.Tensor) -> torch.Tensor:
     """float32 [h,w] / [h,w,c] -> uint8 of the same shape, exactly as png.encode_png quantises a float32 image."""
     if not isinstance(image_f32, torch.Tensor) or image_f32.dtype != torch.float32 or image_f32.dim() not in (2, 3):
         raise ValueError("quantize expects a float32 [h,w] or [h,w,c] tensor")
-    if not image_f32.is_cuda:
-        raise RuntimeError("topo4d_amd has no CPU path: the image must live on a HIP device")
-    img = image_f32.contiguous()
+    img = on_device(image_f32, "the image")
     h, w = int(img.shape[0]), int(img.shape[1])
     c = 1 if img.dim() == 2 else int(img.shape[2])
     if h < 1 or w < 1 or c not in (1, 3, 4):
@@ -107,8 +87,8 @@ def erode(coverage: torch.Tensor, rounds: int) -> torch.Tensor:
     rounds = int(rounds)
     if not 0 <= rounds <= MAX_ERODE:
         raise ValueError(f"erode: rounds must be in [0, {MAX_ERODE}], got {rounds}")
-    cov = _coverage(coverage)
-    h, w = int(cov.shape[0]), int(cov.shape[1])
+    h, w = _args.mask(coverage, "coverage")
+    cov = on_device(coverage, "coverage")
     out = torch.empty_like(cov)
     _lib.call("t4d_texture_erode", ptr(cov), h, w, rounds, ptr(out), _lib.stream(cov.device))
     return out
@@ -119,12 +99,8 @@ def pad(image: torch.Tensor, coverage: torch.Tensor, radius: int) -> Tuple[torch
     radius = int(radius)
     if not 0 <= radius <= MAX_PAD:
         raise ValueError(f"pad: radius must be in [0, {MAX_PAD}], got {radius}")
-    img, h, w, c = _image(image, "image")
-    cov = _coverage(coverage, h, w, img.device)
-    nbytes = int(_lib.load().t4d_texture_pad_scratch_bytes(h, w))
-    if nbytes == 0:
-        raise _lib.error("t4d_texture_pad_scratch_bytes", exc=ValueError)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+    img, cov, h, w, c = _image_and_coverage(image, coverage)
+    scratch, nbytes = _lib.scratch("t4d_texture_pad_scratch_bytes", img.device, h, w)
     out, out_cov = torch.empty_like(img), torch.empty_like(cov)
     _lib.call("t4d_texture_pad", ptr(img), ptr(cov), h, w, c, radius, ptr(out), ptr(out_cov), ptr(scratch), nbytes,
               _lib.stream(img.device))
@@ -133,8 +109,7 @@ def pad(image: torch.Tensor, coverage: torch.Tensor, radius: int) -> Tuple[torch
 
 def halve(image: torch.Tensor, coverage: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """(image [h/2,w/2(,c)], coverage [h/2,w/2]): per 2x2 block the mean of its covered texels, rounded half up; 0 without any."""
-    img, h, w, c = _image(image, "image")
-    cov = _coverage(coverage, h, w, img.device)
+    img, cov, h, w, c = _image_and_coverage(image, coverage)
     if h % 2 or w % 2:
         raise ValueError(f"halve: h and w must be even, got {h} x {w}")
     out = torch.empty((h // 2, w // 2) + tuple(img.shape[2:]), dtype=torch.uint8, device=img.device)
@@ -143,42 +118,15 @@ def halve(image: torch.Tensor, coverage: torch.Tensor) -> Tuple[torch.Tensor, to
     return out, out_cov
 
 
-def _image16(image, what: str, need_device: bool = True) -> Tuple[torch.Tensor, int, int, int]:
-    if not isinstance(image, torch.Tensor) or image.dtype != torch.int32 or image.dim() not in (2, 3):
-        raise ValueError(f"{what} must be an int32 [h,w] or [h,w,c] tensor holding 0..65535")
-    h, w = int(image.shape[0]), int(image.shape[1])
-    c = 1 if image.dim() == 2 else int(image.shape[2])
-    if h < 1 or w < 1 or c not in (1, 3, 4):
-        raise ValueError(f"{what} must be [h,w] or [h,w,c] with h, w >= 1 and c in (1, 3, 4); got {tuple(image.shape)}")
-    if need_device and not image.is_cuda:
-        raise RuntimeError(f"topo4d_amd has no CPU path: {what} must live on a HIP device")
-    return image.contiguous(), h, w, c
-
-
-def _mask(mask, what: str, h: int, w: int) -> None:
-    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool) or tuple(mask.shape) != (h, w):
-        raise ValueError(f"{what} must be a uint8 or bool [{h},{w}] tensor, got {getattr(mask, 'dtype', type(mask))} "
-                         f"{list(getattr(mask, 'shape', ()))}")
-
-
-def _on_device(mask: torch.Tensor, what: str, device) -> torch.Tensor:
-    if mask.device != device:
-        raise RuntimeError(f"topo4d_amd has no CPU path: {what} must live on the image's HIP device")
-    return (mask.to(torch.uint8) if mask.dtype == torch.bool else mask).contiguous()
-
-
-def _fill(image, valid, domain, check, entry: str) -> Tuple[torch.Tensor, torch.Tensor]:
-    _, h, w, c = check(image, "image", need_device=False)      # argument errors first, with or without a device
-    _mask(valid, "valid", h, w)
+def _fill(image, valid, domain, dtype, entry: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    h, w, c = _args.image(image, "image", (dtype,), _NOTE[dtype])  # argument errors first, with or without a device
+    _args.mask(valid, "valid", h, w)
     if domain is not None:
-        _mask(domain, "domain", h, w)
-    img = check(image, "image")[0]
-    val = _on_device(valid, "valid", img.device)
-    dom = None if domain is None else _on_device(domain, "domain", img.device)
-    nbytes = int(getattr(_lib.load(), entry + "_scratch_bytes")(h, w, c))
-    if nbytes == 0:
-        raise _lib.error(entry + "_scratch_bytes", exc=ValueError)
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+        _args.mask(domain, "domain", h, w)
+    img = on_device(image, "image")
+    val = on_device(valid, "valid", img.device, "the image's")
+    dom = None if domain is None else on_device(domain, "domain", img.device, "the image's")
+    scratch, nbytes = _lib.scratch(entry + "_scratch_bytes", img.device, h, w, c)
     out = torch.empty_like(img)
     filled = torch.empty(h, w, dtype=torch.uint8, device=img.device)
     _lib.call(entry, ptr(img), ptr(val), ptr(dom), h, w, c, ptr(out), ptr(filled), ptr(scratch), nbytes, _lib.stream(img.device))
@@ -189,13 +137,13 @@ def fill(image: torch.Tensor, valid: torch.Tensor, domain: torch.Tensor = None) 
     """(image, filled uint8 [h,w]): every texel of `domain` (None: every texel) that is not `valid` takes the push-pull
     interpolation of the valid texels (include/topo4d_raster.h states the rule, tests/texfill_ref.py restates it); every other
     texel is copied through.  filled is 1 at the texels written.  Without any valid texel the image comes back as it is."""
-    return _fill(image, valid, domain, _image, "t4d_texture_fill")
+    return _fill(image, valid, domain, torch.uint8, "t4d_texture_fill")
 
 
 def fill16(image_i32: torch.Tensor, valid: torch.Tensor, domain: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """fill for an int32 image of 16-bit samples (0..65535; the low 16 bits of every word count), over t4d_texture_fill16: the
     same rule in units of 1/256 of a 16-bit step (tests/dispmap_ref.py restates it)."""
-    return _fill(image_i32, valid, domain, _image16, "t4d_texture_fill16")
+    return _fill(image_i32, valid, domain, torch.int32, "t4d_texture_fill16")
 
 
 def fill_islands(image: torch.Tensor, valid: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -204,23 +152,21 @@ def fill_islands(image: torch.Tensor, valid: torch.Tensor, labels: torch.Tensor)
     island's colours never enter another island's holes, and an island without any valid texel stays as it is.  Every pass runs on
     the whole image (a crop would shift the pyramid and change the bits).  The labels that need a pass are found by one read of
     two flags per label from the device."""
-    return _fill_islands(image, valid, labels, _image, fill)
+    return _fill_islands(image, valid, labels, torch.uint8, fill)
 
 
 def fill16_islands(image_i32: torch.Tensor, valid: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """fill_islands for an int32 image of 16-bit samples: exactly its per-island rule, with fill16 for every pass."""
-    return _fill_islands(image_i32, valid, labels, _image16, fill16)
+    return _fill_islands(image_i32, valid, labels, torch.int32, fill16)
 
 
-def _fill_islands(image, valid, labels, check, fill) -> Tuple[torch.Tensor, torch.Tensor]:
-    _, h, w, _ = check(image, "image", need_device=False)
-    _mask(valid, "valid", h, w)
-    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or tuple(labels.shape) != (h, w):
-        raise ValueError(f"labels must be a uint8 [{h},{w}] tensor, got {getattr(labels, 'dtype', type(labels))} "
-                         f"{list(getattr(labels, 'shape', ()))}")
-    img = check(image, "image")[0]
-    val = _on_device(valid, "valid", img.device) != 0
-    lab = _on_device(labels, "labels", img.device)
+def _fill_islands(image, valid, labels, dtype, fill) -> Tuple[torch.Tensor, torch.Tensor]:
+    h, w, _ = _args.image(image, "image", (dtype,), _NOTE[dtype])
+    _args.mask(valid, "valid", h, w)
+    _args.mask(labels, "labels", h, w, (torch.uint8,))
+    img = on_device(image, "image")
+    val = on_device(valid, "valid", img.device, "the image's") != 0
+    lab = on_device(labels, "labels", img.device, "the image's")
     flat = lab.reshape(-1).to(torch.int64)
     flags = torch.stack([torch.bincount(flat, weights=val.reshape(-1).to(torch.float64), minlength=256),
                          torch.bincount(flat, weights=(~val).reshape(-1).to(torch.float64), minlength=256)]).cpu().numpy()
@@ -265,13 +211,12 @@ def finish(image_u8: torch.Tensor, coverage: torch.Tensor, pad: int = 0, erode: 
     """{res: image} for res = the image's height and every entry of `sizes` (each res / 2^k).  The coverage is eroded `erode`
     rounds once; level 0 is the image padded by `pad` under that coverage; every further level halves the UNPADDED image and the
     eroded coverage repeatedly and is then padded by the same `pad`, in its own texels."""
-    _, h, w, _ = _image(image_u8, "image", need_device=False)  # argument errors first, with or without a device
+    h, w, _ = _args.image(image_u8, "image")                   # argument errors first, with or without a device
     levels = _levels(h, w, sizes)
     pad_r, rounds = int(pad), int(erode)
     if not 0 <= pad_r <= MAX_PAD or not 0 <= rounds <= MAX_ERODE:
         raise ValueError(f"finish: pad must be in [0, {MAX_PAD}] and erode in [0, {MAX_ERODE}], got {pad_r}, {rounds}")
-    img = _image(image_u8, "image")[0]
-    cov = _coverage(coverage, h, w, img.device)
+    img, cov = _image_and_coverage(image_u8, coverage)[:2]
     cov0 = _erode(cov, rounds)
     out = {}
     cur, cur_cov = img, cov0

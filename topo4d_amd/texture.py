@@ -35,7 +35,7 @@ def process_uv(uv_coords, uv_h: int = 256, uv_w: int = 256):
     return np.hstack((uv, np.zeros((uv.shape[0], 1))))
 
 
-def _dev(x, dtype, device):
+def _upload(x, dtype, device):
     if isinstance(x, torch.Tensor):
         return x.to(device=device, dtype=dtype).contiguous()
     return torch.as_tensor(np.ascontiguousarray(x), dtype=dtype).to(device).contiguous()
@@ -46,17 +46,15 @@ def render_colors(vertices, triangles, colors, h: int, w: int, c: int = 3, BG=No
     """face3d/mesh/render.py:52-86 on the GPU.  vertices [nver,3] (pixel x, pixel y, depth), triangles [ntri,3],
     colors [nver,c]; returns the image [h,w,c] (float32, on `device`).  `rows=(begin,end)` bakes only that band
     (everything else keeps BG / zeros) — the unit a multi-GPU bake shards."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("topo4d_amd has no CPU path: the texture bake needs a HIP device")
+    device = _lib.hip_device(device, "the texture bake")
     lib = _lib.load()
-    v = _dev(vertices, torch.float32, device)
-    t = _dev(triangles, torch.int32, device)
-    col = _dev(colors, torch.float32, device)
+    v = _upload(vertices, torch.float32, device)
+    t = _upload(triangles, torch.int32, device)
+    col = _upload(colors, torch.float32, device)
     if v.dim() != 2 or v.shape[1] != 3 or t.dim() != 2 or t.shape[1] != 3 or col.shape != (v.shape[0], c):
         raise ValueError("vertices [nver,3], triangles [ntri,3], colors [nver,c] expected")
     r0, r1 = (0, h) if rows is None else (int(rows[0]), int(rows[1]))
-    bg = None if BG is None else _dev(BG, torch.float32, device)
+    bg = None if BG is None else _upload(BG, torch.float32, device)
     if bg is not None:
         assert bg.shape == (h, w, c)
     if (r0, r1) == (0, h):
@@ -72,8 +70,7 @@ def render_colors(vertices, triangles, colors, h: int, w: int, c: int = 3, BG=No
     need = C.c_int64(0)
     stream = _lib.stream(device)
     for _ in range(4):
-        nbytes = lib.t4d_texture_bake_scratch_bytes(h, w, cap)
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        scratch, nbytes = _lib.scratch("t4d_texture_bake_scratch_bytes", device, h, w, cap, exc=RuntimeError)
         rc = lib.t4d_texture_render_colors(ptr(v), ptr(t), ptr(col), ptr(bg), int(v.shape[0]), int(t.shape[0]), h, w, c, r0, r1,
                                            ptr(image), ptr(depth), ptr(scratch), nbytes, cap, C.byref(need), stream)
         if rc == T4D_OK:

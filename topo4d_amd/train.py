@@ -300,7 +300,7 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
     random.Random every get_batch draws from.  `on_frame(t, state)`: called at the end of every frame with state = {params,
     variables, optimizer, priors, pins, frames}.  `timings`: a dict that receives seconds per phase (setup, ingest, geometry,
     transition, texture, progress, export; synchronising at every phase boundary).  Returns that state, or None when the output directory already exists."""
-    from . import coarse, ingest, loop, objexport, progress
+    from . import _lib, coarse, ingest, loop, objexport, progress
     from .priors import TopologyPriors
     out_dir = os.path.join(args.output_dir, args.exp, args.seq)
     if os.path.exists(out_dir):                                                             # train.py:591-593
@@ -327,7 +327,7 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
         raise SystemExit("--tex_fill fills the holes of the projected texture: it needs --tex_project")
     if getattr(args, "tex_reject", False) and not tex_project:
         raise SystemExit("--tex_reject rejects inconsistent views of the projected texture: it needs --tex_project")
-    dev = coarse._device(device)
+    dev = _lib.hip_device(device, "the coarse setup")
     clock = _Clock(timings, dev)
     with torch.cuda.device(dev), clock("setup"):
         undistort, low_from_full = getattr(args, "undistort", False), getattr(args, "low_from_full", False)
