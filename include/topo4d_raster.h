@@ -518,6 +518,32 @@ int t4d_drift_dense(const int32_t *nodes, const uint8_t *kept, const uint8_t *la
 int t4d_drift_warp(const uint8_t *image, const uint8_t *valid, const uint8_t *labels, const int32_t *flow, int32_t h, int32_t w, int32_t c,
                    uint8_t *out_image, uint8_t *out_valid, void *hip_stream);
 
+/* A sequence's stabilised textures fused over time (topo4d_amd/seqtex.py, csrc/t4d_seqtex.hip): after t4d_drift_warp one texel shows
+ * the same point of skin in every frame, so its samples over the frames are a time series.  Integer arithmetic, so both results are
+ * pure functions of their inputs; tests/seqtex_ref.py restates the rule in numpy.
+ * t4d_seqtex_select: images and valids are host arrays of n_frames device pointers (as photos of t4d_projtex_consistency), 1 <=
+ * n_frames <= T4D_SEQTEX_MAX_FRAMES; images[t] uint8 [h,w,c], c in (1, 3, 4); valids[t] uint8 [h,w], non-zero = the texel holds a
+ * photograph; 0 <= num <= den, 1 <= den <= 64.  Per texel, S is the set of frames whose validity is non-zero there and n = |S|:
+ * out_count uint8 [h,w] = n.  With n = 0 every channel of out_image uint8 [h,w,c] is 0; otherwise k = ((n - 1) num) / den in integer
+ * division and out_image[ch] is the value of rank k (0-based, ascending) among the n samples images[t][texel][ch], t in S.  (num, den)
+ * = (1, 2) is the lower median, (0, 1) the minimum, (1, 1) the maximum.  With c = 4 alpha is a channel like the others.  The rank is
+ * taken per channel, so the result need not be any one frame's colour.  What lies under an invalid texel is never read into a
+ * result.  The same pointer may appear more than once in images or valids, and an input may have any alignment.
+ * t4d_seqtex_complete: one frame against the sequence.  image uint8 [h,w,c] and valid uint8 [h,w] are the frame's, base uint8 [h,w,c]
+ * and count uint8 [h,w] t4d_seqtex_select's; min_count and min_votes in 1..64, tol in 0..255 (255 never rejects).  Per texel, with
+ * v = valid != 0 and n = count: outlier = v and n >= min_votes and max over the channels of |image[ch] - base[ch]| > tol.  If v and
+ * not outlier, out_image = image and out_source = 1; else if n >= min_count, out_image = base and out_source = 2 where the frame had
+ * nothing (v = 0), 3 where its sample was rejected; else out_image = 0 and out_source = 0.
+ * Both: the outputs must not be inputs and must be aligned to 4 bytes; T4D_ERR_ARG with a message, before anything touches a
+ * device, for a NULL buffer or table entry, a size or option outside the bounds above, a misaligned output or an output that is an
+ * input.  Neither synchronises the stream. */
+#define T4D_SEQTEX_MAX_FRAMES 64
+int t4d_seqtex_select(const uint8_t *const *images, const uint8_t *const *valids, int32_t n_frames, int32_t h, int32_t w, int32_t c,
+                      int32_t num, int32_t den, uint8_t *out_image, uint8_t *out_count, void *hip_stream);
+int t4d_seqtex_complete(const uint8_t *image, const uint8_t *valid, const uint8_t *base, const uint8_t *count, int32_t h, int32_t w,
+                        int32_t c, int32_t min_count, int32_t min_votes, int32_t tol, uint8_t *out_image, uint8_t *out_source,
+                        void *hip_stream);
+
 /* Lossless PNG encoder for a device image (write_texture(..., encoder="gpu"): the last CPU step of save_mesh, helpers.py:953-960).
  * image [h,w,c] on the device, uint8 (is_float32 = 0) or float32 (is_float32 = 1, quantised exactly like numpy's
  * (x*255).astype(np.uint8) on x86-64: truncation toward zero to int32, low byte kept, NaN -> 0); c in {1, 3, 4} gives colour

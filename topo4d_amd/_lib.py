@@ -177,6 +177,8 @@ SIGNATURES = {
     "t4d_drift_match": (_INT, [_VP] * 5 + [_I32] * 6 + [_VP, _VP, _SZ, _VP]),
     "t4d_drift_dense": (_INT, [_VP] * 3 + [_I32] * 6 + [_VP] * 3),
     "t4d_drift_warp": (_INT, [_VP] * 4 + [_I32] * 3 + [_VP] * 3),
+    "t4d_seqtex_select": (_INT, [C.POINTER(_VP), C.POINTER(_VP)] + [_I32] * 6 + [_VP] * 3),
+    "t4d_seqtex_complete": (_INT, [_VP] * 4 + [_I32] * 6 + [_VP] * 3),
     "t4d_png_max_bytes": (_SZ, [_I32] * 3),
     "t4d_png_scratch_bytes": (_SZ, [_I32] * 3),
     "t4d_png_encode": (_INT, [_VP] + [_I32] * 4 + [_VP, _SZ, _VP, _VP, _SZ, _VP]),
