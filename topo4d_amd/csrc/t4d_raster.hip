@@ -29,7 +29,9 @@
 //                          status, longest list, length buckets (the first kernel only when a view has more than one chunk)
 //   k_scatter         A.2  per (view,Gaussian): key -> tile_off + rank (no atomics); tail blocks build the work items
 //   k_sort_tiles      A.2  per work item: sort the bin by (depth bits, index): runs of 64 sorted in registers, merged by
-//                          ranking (<= 512 keys: one pass; <= 2048: log levels in LDS)
+//                          ranking (<= 512 keys: one pass; <= 2048: log levels in LDS); the 256-thread build of a big launch sorts
+//                          bins of fewer than 512 keys one per wave, a bitonic network over 1, 2, 4 or 8 keys per lane in
+//                          registers (t4d_raster_sort_net.h)
 //   k_sort_long_chunks, k_merge_long  A.2  bins beyond 2048 keys (dense passes): every 2048-key chunk sorted through LDS by whichever
 //                          workgroup it falls to, then ONE ranking pass (a key's slot = its place in its chunk + the keys below it in
 //                          every other chunk) scatters the keys to their final places - any bin length, chunks in parallel
@@ -41,6 +43,7 @@
 //   k_sh_bwd16, k_sh_bwd   SH colours: dL/dshs and the view-direction term of dL/dmeans3D (degree 3 / any degree)
 //   k_view_dot_*, k_mark_visible: small utilities of the ABI
 #include "t4d_raster_plan.h"
+#include "t4d_raster_sort_net.h"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -184,6 +187,7 @@ struct KP {
     unsigned long long *host_status;  // T4D_FLAG_ASYNC_STATUS on a one-view launch: the caller's pinned 16 bytes, written by the kernel itself
     // (behind everything else: the kernels of every other launch shape read their arguments from the offsets they always had)
     uint32_t seg_min_pairs;          // tiles of fewer pairs are not segmented (0: every tile is - small launches; kSegLongMin: seg_mode 2)
+    uint32_t wave_bins;              // k_sort_tiles<kBlock> only: bins of fewer than 512 keys are sorted one per wave in registers (in four bytes that were padding: no other field moves)
     uint32_t *live;                  // seg_mode 2: slot-table indices of the live segments, status->live_segments of them (order: as the item builders got to them)
     uint32_t slots_by_offset;        // seg_mode 2: a long tile's first slot is off / kSeg + off / kSegLongMin (seg_slot0), not off / kSeg + tile
     uint32_t views_per_set;          // T4DProblem.views_per_param_set: view v reads the per-Gaussian inputs of parameter set v / views_per_set (0: one set for all views)
@@ -713,6 +717,7 @@ T4D_EXPORT int t4d_rasterize_forward(const T4DProblem *prob, const T4DForwardIO 
     if (!fill_common(kp, p, plan.regime, L, st)) return fail(T4D_ERR_ARG, "no exact multiplier for this tile grid");
     kp.out_color = io->out_color; kp.out_depth = io->out_depth; kp.out_alpha = io->out_alpha; kp.radii = io->out_radii;
     kp.fused_sort = plan.fused_sort;
+    kp.wave_bins = plan.wave_bins ? 1u : 0u;
     kp.tile_blocks = plan.tile_blocks; kp.fill_blocks = plan.fill_blocks; kp.fill_vec = plan.fill_vec;
     const uint32_t render_grid = kp.tile_blocks + kp.fill_blocks;
     const uint64_t top = (uint64_t)render_grid * kp.fill_blocks;              // the largest numerator: (last workgroup + 1) * fill_blocks

@@ -185,6 +185,7 @@ struct Overrides {
     bool no_small_view = false;      // T4D_NO_SMALL_VIEW: one small view takes the general front end
     bool fill_scalar = false;        // T4D_FILL_SCALAR: empty tiles written with 4-byte stores
     bool sh_bwd_plain = false;       // T4D_SH_BWD_PLAIN: the general SH backward also for degree 3
+    bool no_wave_sort = false;       // T4D_NO_WAVE_SORT: the 256-thread k_sort_tiles sorts bins of 64 keys and more through LDS, one per workgroup
 };
 inline Overrides read_overrides()
 {
@@ -207,6 +208,7 @@ inline Overrides read_overrides()
     o.no_small_view = getenv("T4D_NO_SMALL_VIEW") != nullptr;
     o.fill_scalar = getenv("T4D_FILL_SCALAR") != nullptr;
     o.sh_bwd_plain = getenv("T4D_SH_BWD_PLAIN") != nullptr;
+    o.no_wave_sort = getenv("T4D_NO_WAVE_SORT") != nullptr;
     return o;
 }
 
@@ -282,6 +284,7 @@ struct ForwardPlan {
     bool status_by_kernel;           // the binning kernel writes the caller's pinned status block itself (publish_status), if it can be mapped
     Sorter sorter;
     unsigned sort_grid;
+    bool wave_bins;                  // KP field: Block256 sorts the bins of fewer than 512 keys one per wave, in registers
     bool long_bins;                  // k_sort_long_chunks + k_merge_long
     unsigned long_bins_grid;
     FwdBuild render;
@@ -324,6 +327,8 @@ inline ForwardPlan plan_forward(const T4DProblem &p, const DeviceFacts &dev, con
     if (f.fused_sort) { f.sorter = Sorter::Fused; f.sort_grid = 0; }
     else if (r.seg_mode == 1 && (p.flags & T4D_FLAG_SHORT_BINS) == 0 && !ov.sort_256) { f.sorter = Sorter::Block1024; f.sort_grid = (unsigned)std::min(n_tiles, 4 * dev.cus); }
     else { f.sorter = Sorter::Block256; f.sort_grid = (unsigned)tile_grid(n_tiles, 5, 2, dev, ov); }
+    // (the 256-thread sorter takes bins of fewer than 512 keys one per wave: same launch, same grid - t4d_raster_sort.h)
+    f.wave_bins = f.sorter == Sorter::Block256 && !ov.no_wave_sort;
     // bins beyond the LDS sort buffer (the caller has not said that there are none): their chunks, then the merges
     f.long_bins = r.long_bins_elsewhere != 0;
     f.long_bins_grid = (unsigned)std::min(n_tiles, 2 * dev.cus);

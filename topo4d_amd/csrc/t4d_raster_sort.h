@@ -195,6 +195,67 @@ __device__ __forceinline__ void sort_one_bin(const KP &kp, const int v, const ui
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// One bin per WAVE, entirely in registers (bins of fewer than 64 kMaxKeysPerLane = 512 keys in the launches that run the
+// 256-thread k_sort_tiles, whose small-bin units these are): the bitonic network of t4d_raster_sort_net.h over 64 K keys,
+// K = 1, 2, 4, 8 consecutive keys per lane.  No LDS, no barrier, no ranking searches; stages at a distance below K are a
+// compare and four selects on the lane's own registers, the others the DPP / bpermute exchange of wave_sort64 once per key.
+// Padding with +inf as everywhere.  Static vector instructions, load and store included: 179 / 303 / 659 / 1,479 for
+// K = 1 / 2 / 4 / 8, in 11 / 14 / 19 / 32 registers when compiled alone, no scratch.
+// ---------------------------------------------------------------------------------------------------------
+template <int K, int S>
+__device__ __forceinline__ void net_stages(unsigned long long (&key)[K], const int lane)
+{
+    namespace sn = t4d_sort_net;
+    constexpr sn::Stage st = sn::stage_at(S);
+    if constexpr (sn::in_lane(st, K)) {
+#pragma unroll
+        for (int e = 0; e < K; e++) {
+            if ((e & st.j) != 0) continue;
+            const unsigned long long a = key[e], b = key[e | st.j];
+            const bool swap = (b < a) == sn::keeps_min(st, K, lane, e);
+            key[e] = swap ? b : a;
+            key[e | st.j] = swap ? a : b;
+        }
+    } else {
+        constexpr int J = sn::lane_distance(st, K);
+        const bool keep_min = sn::keeps_min(st, K, lane, 0);           // the same for all K keys of a lane
+#pragma unroll
+        for (int e = 0; e < K; e++) {
+            const unsigned long long other = ((unsigned long long)lane_xor<J>((uint32_t)(key[e] >> 32)) << 32) | lane_xor<J>((uint32_t)key[e]);
+            key[e] = ((other < key[e]) == keep_min) ? other : key[e];
+        }
+    }
+    if constexpr (S + 1 < sn::stage_count(sn::elements(K))) net_stages<K, S + 1>(key, lane);
+}
+
+template <int K>
+__device__ __forceinline__ void sort_bin_wave(unsigned long long *keys, const uint32_t n, const int lane)
+{
+    unsigned long long key[K];
+    const uint32_t i0 = (uint32_t)lane * K;
+#pragma unroll
+    for (int e = 0; e < K; e++) key[e] = i0 + e < n ? keys[i0 + e] : ~0ull;
+    if constexpr (K == 1) wave_sort64(key[0], lane);                   // (the same network: net_stages<1, 0> compiles to the same code)
+    else net_stages<K, 0>(key, lane);
+#pragma unroll
+    for (int e = 0; e < K; e++)
+        if (i0 + e < n) keys[i0 + e] = key[e];
+}
+
+// 65 <= n < 512.  A function of its own, not inlined: k_sort_tiles' other paths keep the code they had (inlined, the compiler
+// re-laid the ranking sort: 13.3 M -> 15.5 M vector instructions on the old path) and 70 registers instead of 79 (parent: 65).
+__device__ __noinline__ void sort_bin_wave_long(unsigned long long *keys, const uint32_t n, const int lane)
+{
+    if (n <= 128u) sort_bin_wave<2>(keys, n, lane);                    // (wave-uniform)
+    else if (n <= 256u) sort_bin_wave<4>(keys, n, lane);
+    else sort_bin_wave<8>(keys, n, lane);
+}
+
+// index in bucket_fill of the longest class that is sorted one bin per wave: floor(log2 n) = 8, n in [256, 511]
+constexpr int kClassWaveTop = (kBuckets - 2) - 8;
+static_assert((2 << 8) == 64 * t4d_sort_net::kMaxKeysPerLane, "the classes up to kClassWaveTop fit the largest network");
+
 // BLOCK = 256: the throughput build (a 24-view launch holds thousands of bins: four waves per bin keep every SIMD busy).
 // BLOCK = 1024: small launches (at most kSegMaxTiles tiles), whose sort lasts as long as its LONGEST bin takes one workgroup:
 // a lone wave issues an instruction every four cycles, so a bin of 1,286 keys took 28 us on four waves (six register sorts of
@@ -209,12 +270,20 @@ __global__ __launch_bounds__(BLOCK) void k_sort_tiles(const KP kp)
     // class: bins of 64 keys and more are one unit per workgroup; bins of 2..63 keys fit one register-sorted run, need neither LDS
     // nor a barrier, and go one PER WAVE to a unit (a high-resolution pass has mostly such bins: config 4 averages 65 keys
     // per non-empty tile, and three of the four waves of a one-bin workgroup did nothing).
+    // The 256-thread build (kp.wave_bins) takes every bin of fewer than 512 keys that way: 2, 4 or 8 keys per lane through
+    // sort_bin_wave instead of runs of 64 and a ranking pass over LDS (a config-2 launch: 12.96 M -> 9.21 M vector instructions).
+    // The longer bins stay whole-workgroup units IN FRONT of them in the same launch: the launch lasts as long as its longest
+    // bin (28 us for 1,286 keys, above), and the per-wave bins fill the chip beside it - as a launch of their own in front of
+    // this one they cost the sequential step 16 us (tools/experiments/README.md).
     constexpr int kClass63 = (kBuckets - 2) - 5, kClass1 = kBuckets - 2;       // classes of n in [32, 63] and of n == 1
     uint32_t n_big = 0, n_small = 0;
+    bool wave_bins = false;
+    if constexpr (BLOCK == kBlock) wave_bins = kp.wave_bins != 0u;
 #pragma unroll
     for (int k = 0; k < kBuckets - 1; k++) {
         const uint32_t f = kp.bucket_fill[k];
-        if (k < kClass63) n_big += f;
+        if (k < kClassWaveTop) n_big += f;
+        else if (k < kClass63) { if (wave_bins) n_small += f; else n_big += f; }
         else if (k < kClass1) n_small += f;
     }
     const uint32_t n_units = n_big + ((n_small + kWaves - 1u) / kWaves);
@@ -225,6 +294,12 @@ __global__ __launch_bounds__(BLOCK) void k_sort_tiles(const KP kp)
                 const uint4 it = kp.items[item];
                 const uint32_t n = it.z;
                 unsigned long long *keys = kp.keys + (size_t)(it.x >> 20) * kp.cap + it.y;
+                if constexpr (BLOCK == kBlock) {
+                    if (n > 64u) {                                     // (only with wave_bins; wave-uniform)
+                        sort_bin_wave_long(keys, n, lane);
+                        continue;
+                    }
+                }
                 unsigned long long k0 = (uint32_t)lane < n ? keys[lane] : ~0ull;
                 wave_sort64(k0, lane);
                 if ((uint32_t)lane < n) keys[lane] = k0;
