@@ -35,7 +35,7 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _args, _lib, _run
 from ._lib import on_device, ptr
 
 ZERO = 32768
@@ -176,14 +176,9 @@ def png_info(dist: float, fill: bool, smooth: int, normals: bool) -> dict:
 
 # ---- command line ----------------------------------------------------------------------------------------------------------
 def build_parser() -> argparse.ArgumentParser:
-    from .evaluate import _frames
-    from .train import build_parser as train_parser
     p = argparse.ArgumentParser(prog="python -m topo4d_amd.dispmap",
                                 description="Finish every frame's baked displacement map: 16-bit PNG, hole fill, smoothing, normal map.")
-    for a in train_parser()._actions:                         # -e/-s/-od exactly as topo4d_amd.train has them
-        if a.dest in ("exp", "seq", "output_dir"):
-            p.add_argument(*a.option_strings, type=a.type, default=a.default, help=a.help)
-    p.add_argument("--frames", type=_frames, default=None, help="Frames to finish: '1-10', '1,5,9' (default: every frame directory).")
+    _run.add_run_flags(p, "exp", "seq", "output_dir", frames_help="Frames to finish: '1-10', '1,5,9' (default: every frame directory).")
     p.add_argument("--dist", type=float, required=True, metavar="DIST", help="The reach the maps were baked with (evaluate --bake_disp).")
     p.add_argument("--fill", action="store_true", help="Fill the texels the bake's rays missed, per UV island (push-pull).")
     p.add_argument("--smooth", type=int, default=0, metavar="K", help=f"Rounds of smoothing within the islands, 0..{MAX_ROUNDS} (default 0).")
@@ -193,27 +188,23 @@ def build_parser() -> argparse.ArgumentParser:
 
 def finish_tree(args, device=None) -> list:
     """The files written for the run <od>/<exp>/<seq>; frames without face.obj, face_disp.npy or face_disp_hit.png are left alone."""
-    from PIL import Image
-    from . import meshrender, scanbake
+    from . import scanbake
     try:
         check_options(args.dist, args.smooth)
     except ValueError as e:
         raise SystemExit(f"--dist / --smooth: {e}") from None
     dev = torch.device(device if device is not None else "cuda")
-    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
-    if not os.path.isdir(run_dir):
-        raise SystemExit(f"no run at {run_dir}")
-    frames = args.frames or sorted(int(d) for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
+    run_dir = _run.run_dir_of(args)
     written = []
     with torch.cuda.device(dev):
-        for t in frames:
-            frame_dir = os.path.join(run_dir, "%06d" % t)
-            paths = [os.path.join(frame_dir, n) for n in ("face.obj", scanbake.DISP_NAME, scanbake.HIT_NAME)]
-            if not all(os.path.exists(p) for p in paths):
+        for t in _run.frames_of(args, run_dir):
+            paths = _run.frame_files(run_dir, t, "face.obj", scanbake.DISP_NAME, scanbake.HIT_NAME)
+            if paths is None:
                 continue
-            obj = meshrender.read_face_obj(paths[0])
+            frame_dir = _run.frame_dir(run_dir, t)
+            obj = _run.read_frame_obj(frame_dir)
             disp = np.load(paths[1])
-            hit = np.ascontiguousarray(np.array(Image.open(paths[2]).convert("L")) != 0).astype(np.uint8)
+            hit = _run.read_hit_mask(paths[2])
             if disp.dtype != np.float32 or disp.ndim != 2 or hit.shape != disp.shape:
                 raise SystemExit(f"{frame_dir}: {scanbake.DISP_NAME} must be float32 [h,w] and {scanbake.HIT_NAME} of the same size")
             result = finish(obj, obj.vertices, torch.from_numpy(disp).to(dev), torch.from_numpy(hit).to(dev), args.dist,
@@ -223,9 +214,7 @@ def finish_tree(args, device=None) -> list:
 
 
 def main(argv=None) -> None:
-    args = build_parser().parse_args(argv)
-    for p in finish_tree(args):
-        print(p)
+    _run.print_written(finish_tree(build_parser().parse_args(argv)))
 
 
 if __name__ == "__main__":

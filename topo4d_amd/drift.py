@@ -72,7 +72,7 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _args, _lib, _run
 from ._lib import on_device, ptr
 
 MIN_BLOCK, MAX_BLOCK, MAX_RADIUS = 8, 64, 16
@@ -454,14 +454,9 @@ def options_of(args, prefix: str = "") -> dict:
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .evaluate import _frames
-    from .train import build_parser as train_parser
     p = argparse.ArgumentParser(prog="python -m topo4d_amd.drift",
                                 description="Measure tracking drift between the frames of a run by matching their UV textures.")
-    for a in train_parser()._actions:                         # -e/-s/-od exactly as topo4d_amd.train has them
-        if a.dest in ("exp", "seq", "output_dir"):
-            p.add_argument(*a.option_strings, type=a.type, default=a.default, help=a.help)
-    p.add_argument("--frames", type=_frames, default=None, help="Frames to measure: '1-10', '1,5,9' (default: every frame directory).")
+    _run.add_run_flags(p, "exp", "seq", "output_dir", frames_help="Frames to measure: '1-10', '1,5,9' (default: every frame directory).")
     add_options(p)
     p.add_argument("--save_fields", action="store_true", help=f"Also write %%06d/{FIELDS_NAME} (table, d, kept, drift).")
     p.add_argument("--stabilise", action="store_true",
@@ -502,23 +497,18 @@ def _stabilise_frame(args, o: dict, frame_dir: str, ref, cur, r: dict, options: 
     return entry, {"flow": flow_, "support": support}
 
 
-def _read_frame(frame_dir: str, texture: str, dev):
-    """(FaceObj, texture uint8 [h,w,3], valid uint8 [h,w], "weight" | "obj") of one frame directory; None without its files."""
-    from PIL import Image
-    from . import meshrender, texfinish
-    obj_path, png_path = os.path.join(frame_dir, "face.obj"), os.path.join(frame_dir, texture)
-    if not (os.path.exists(obj_path) and os.path.exists(png_path)):
+def read_frame(frame_dir: str, texture: str, dev):
+    """(FaceObj, texture uint8 [h,w,3], valid uint8 [h,w], "weight" | "obj") of one frame directory, the arrays on the device;
+    None without its files.  valid: where the directory's weight image is above 0, else the coverage of its face.obj."""
+    from . import texfinish
+    obj, tex = _run.read_textured_frame(frame_dir, texture)
+    if obj is None or tex is None:
         return None
-    obj = meshrender.read_face_obj(obj_path)
-    tex = torch.from_numpy(np.ascontiguousarray(np.array(Image.open(png_path).convert("RGB")))).to(dev)
     weight_path = os.path.join(frame_dir, WEIGHT_FILE)
     if os.path.exists(weight_path):
-        weight = np.array(Image.open(weight_path))
-        if weight.shape[:2] != tuple(tex.shape[:2]):
-            raise SystemExit(f"{weight_path}: {weight.shape[:2]} does not match {texture}'s {tuple(tex.shape[:2])}")
-        valid = torch.from_numpy(np.ascontiguousarray((weight.reshape(weight.shape[0], weight.shape[1], -1) > 0).any(-1))).to(dev)
-        return obj, tex, valid.to(torch.uint8), "weight"
-    return obj, tex, texfinish.coverage_from_obj(obj, int(tex.shape[0]), int(tex.shape[1]), device=dev), "obj"
+        valid = _run.read_validity(weight_path, tex.shape[:2], texture)
+        return obj, torch.from_numpy(tex).to(dev), torch.from_numpy(valid).to(dev), "weight"
+    return obj, torch.from_numpy(tex).to(dev), texfinish.coverage_from_obj(obj, tex.shape[0], tex.shape[1], device=dev), "obj"
 
 
 def tree_options(args, options: dict = None) -> Tuple[dict, Tuple[int, int, int, int]]:
@@ -551,16 +541,13 @@ def drift_tree(args, device=None, options: dict = None) -> dict:
     o, (block, stride, radius, min_count) = tree_options(args, options)
     stabilise = "stabilise" in o
     dev = torch.device(device if device is not None else "cuda")
-    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
-    if not os.path.isdir(run_dir):
-        raise SystemExit(f"no run at {run_dir}")
-    frames = getattr(args, "frames", None) or sorted(int(d) for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
+    run_dir = _run.run_dir_of(args)
     out = {"options": o, "frames": {}}
     ref = None                                                # (key, files) of the frame matched against
     with torch.cuda.device(dev):
-        for t in frames:
-            key = "%06d" % t
-            cur = _read_frame(os.path.join(run_dir, key), o["texture"], dev)
+        for t in _run.frames_of(args, run_dir):
+            key = _run.frame_key(t)
+            cur = read_frame(os.path.join(run_dir, key), o["texture"], dev)
             if cur is None:
                 continue
             if ref is not None:

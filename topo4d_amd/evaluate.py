@@ -56,48 +56,19 @@ import functools
 import json
 import math
 import os
-from concurrent.futures import ThreadPoolExecutor
 from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
+from . import _run
 from . import cameras as C
 from . import meshrender
 
 MASK_LABELS = ["inner_mouth"]                 # train.py get_loss's target_labels
 
 
-def _frames(spec: str) -> List[int]:
-    out = []
-    for part in spec.split(","):
-        part = part.strip()
-        if not part:
-            continue
-        if "-" in part:
-            a, b = part.split("-", 1)
-            out.extend(range(int(a), int(b) + 1))
-        else:
-            out.append(int(part))
-    if not out or min(out) < 1:
-        raise argparse.ArgumentTypeError(f"--frames: {spec!r} is not a list or range of frames >= 1")
-    return out
-
-
 TEXTURE_FILE = "face.png"
-
-
-def _read_frame_files(frame_dir: str, texture: str = TEXTURE_FILE):
-    """(FaceObj or None, uint8 [H,W,3] texture or None) of one frame directory: the host half, run on the prefetch thread."""
-    obj_path, png_path = os.path.join(frame_dir, "face.obj"), os.path.join(frame_dir, texture)
-    if not os.path.exists(obj_path):
-        return None, None
-    obj = meshrender.read_face_obj(obj_path)
-    tex = None
-    if os.path.exists(png_path):
-        from PIL import Image
-        tex = np.ascontiguousarray(np.array(Image.open(png_path).convert("RGB")))
-    return obj, tex
 
 
 def training_vertices(vertices: np.ndarray, trans_g) -> np.ndarray:
@@ -172,77 +143,56 @@ def _summary(frames: dict) -> dict:
 
 def score_set(args, which: str, device) -> dict:
     from . import ingest
-    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
-    data_dir = args.input_dir if which == "low" else args.dense_input_dir
-    # the calibration and the camera list come from the geometry inputs for both sets, as train.py takes them
-    cameras, _, trans_g = C.get_cameras(args.input_dir, args.seq, resize_factor=args.down_ratio if which == "low" else 1)
-    lenses = None
-    if getattr(args, "undistort", False):                      # the photographs are undistorted as training loaded them
-        lenses = C.get_lenses(args.input_dir, args.seq, args.down_ratio)[0 if which == "low" else 1]
-    names = [n.split(".")[0] for n in cameras]
-    chosen = names if args.views is None else [n for n in names if n in args.views]
-    if args.views is not None and len(chosen) != len(args.views):
-        raise SystemExit(f"--views: {sorted(set(args.views) - set(names))} not among the cameras of {data_dir}/{args.seq}")
-    skip = [n for n in cameras if n.split(".")[0] not in chosen]           # full file names: a prefix that matches only itself
+    run_dir = _run.run_dir_of(args)
+    # every camera without --views; the photographs are undistorted as training loaded them
+    cameras, trans_g, lenses, data_dir, chosen, skip = _run.select_cameras(args, which, absent="all")
     trained = {n: not any(n.startswith(b) for b in C.BLACKLIST) for n in chosen}
     cam_fn = functools.partial(C.setup_camera, device=device)
-    frames = args.frames or sorted(int(d) for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
-    result = {}
+    texture_file = getattr(args, "texture", TEXTURE_FILE)
+    result, use_mask = {}, {}
 
-    def mask_dir_ok(t):
-        md = os.path.join(data_dir, args.seq, "mask", "%06d" % t)
-        return all(os.path.exists(os.path.join(md, n + ".png")) for n in chosen)
+    def views_ahead(t):                                        # the frame's views with their masks where every view has one
+        md = os.path.join(data_dir, args.seq, "mask", _run.frame_key(t))
+        use_mask[t] = all(os.path.exists(os.path.join(md, n + ".png")) for n in chosen)
+        pf[use_mask[t]].prefetch(t)
 
-    pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="t4d-eval")
     pf = {flag: ingest.FramePrefetcher(data_dir, args.seq, cameras, use_mask=flag, blacklist=skip, rotate_mask=C.ROTATE_MASK,
                                        setup_camera=cam_fn, device=device, lenses=lenses) for flag in (False, True)}
     try:
-        pending = {}
-
-        def prefetch(t):
-            if t not in pending:
-                pending[t] = (pool.submit(_read_frame_files, os.path.join(run_dir, "%06d" % t), getattr(args, "texture", TEXTURE_FILE)),
-                              mask_dir_ok(t))
-                pf[pending[t][1]].prefetch(t)
-
-        for i, t in enumerate(frames):
-            prefetch(t)
-            if i + 1 < len(frames):
-                prefetch(frames[i + 1])
-            fut, use_mask = pending.pop(t)
-            obj, tex = fut.result()
-            dataset = pf[use_mask].get(t)
-            key = "%06d" % t
-            if obj is None:
-                result[key] = {"skipped": "no face.obj"}
-                continue
-            if not dataset:
-                result[key] = {"skipped": "no views"}
-                continue
-            faces, uv_faces = meshrender.triangulate(obj.faces_ori, obj.uv_faces_ori)
-            texture = tex if tex is not None else np.full((2, 2, 3), 128, np.uint8)
-            if tex is not None and getattr(args, "tex_pad", None) is not None:
-                from . import texfinish
-                th, tw = int(tex.shape[0]), int(tex.shape[1])
-                texture = texfinish.finish(torch.from_numpy(tex).to(device), texfinish.coverage_from_obj(obj, th, tw, device=device),
-                                           pad=args.tex_pad, erode=getattr(args, "tex_erode", 1))[th]
-            renderer = meshrender.MeshRenderer(faces, uv_faces, obj.uvs, texture, device=device)
-            verts = torch.from_numpy(training_vertices(obj.vertices, trans_g)).to(device)
-            masks = pixel_masks(dataset)
-            scores, renders = evaluate_frame(renderer, verts, dataset, masks, keep_renders=True)
-            for name, row in scores.items():
-                row["trained"] = trained.get(name, True)
-                for n in list(row):
-                    if isinstance(row[n], float):
-                        row[n] = _finite(row[n])
-            result[key] = {"texture": tex is not None, "masked": masks is not None, "views": scores}
-            if args.save_renders:
-                from .png import write_png
-                tag = "" if args.set != "both" else f"_{which}"
-                for name, img in renders.items():
-                    write_png(os.path.join(run_dir, key, f"mesh{tag}_{name}.png"), img, chw=True)
+        with _run.prefetched(_run.frames_of(args, run_dir), lambda t: _run.read_textured_frame(_run.frame_dir(run_dir, t), texture_file),
+                             ahead=views_ahead, thread_name="t4d-eval") as walk:
+            for t, (obj, tex) in walk:
+                dataset = pf[use_mask[t]].get(t)
+                key = _run.frame_key(t)
+                if obj is None:
+                    result[key] = {"skipped": "no face.obj"}
+                    continue
+                if not dataset:
+                    result[key] = {"skipped": "no views"}
+                    continue
+                faces, uv_faces = meshrender.triangulate(obj.faces_ori, obj.uv_faces_ori)
+                texture = tex if tex is not None else np.full((2, 2, 3), 128, np.uint8)
+                if tex is not None and getattr(args, "tex_pad", None) is not None:
+                    from . import texfinish
+                    th, tw = int(tex.shape[0]), int(tex.shape[1])
+                    texture = texfinish.finish(torch.from_numpy(tex).to(device), texfinish.coverage_from_obj(obj, th, tw, device=device),
+                                               pad=args.tex_pad, erode=getattr(args, "tex_erode", 1))[th]
+                renderer = meshrender.MeshRenderer(faces, uv_faces, obj.uvs, texture, device=device)
+                verts = torch.from_numpy(training_vertices(obj.vertices, trans_g)).to(device)
+                masks = pixel_masks(dataset)
+                scores, renders = evaluate_frame(renderer, verts, dataset, masks, keep_renders=True)
+                for name, row in scores.items():
+                    row["trained"] = trained.get(name, True)
+                    for n in list(row):
+                        if isinstance(row[n], float):
+                            row[n] = _finite(row[n])
+                result[key] = {"texture": tex is not None, "masked": masks is not None, "views": scores}
+                if args.save_renders:
+                    from .png import write_png
+                    tag = "" if args.set != "both" else f"_{which}"
+                    for name, img in renders.items():
+                        write_png(os.path.join(run_dir, key, f"mesh{tag}_{name}.png"), img, chw=True)
     finally:
-        pool.shutdown(wait=True)
         for p in pf.values():
             p.close()
     return {"frames": result, "summary": _summary(result)}
@@ -251,8 +201,7 @@ def score_set(args, which: str, device) -> dict:
 def _read_scan_files(run_dir: str, scan_dir: str, t: int, transform):
     """(FaceObj or None, Scan or None) of frame t: the host half, run on the prefetch thread."""
     from . import scanscore
-    obj_path = os.path.join(run_dir, "%06d" % t, "face.obj")
-    obj = meshrender.read_face_obj(obj_path) if os.path.exists(obj_path) else None
+    obj = _run.read_frame_obj(_run.frame_dir(run_dir, t))
     scan = None
     for ext in (".ply", ".obj"):
         path = os.path.join(scan_dir, "%06d%s" % (t, ext))
@@ -302,8 +251,7 @@ def _scan_summary(frames: dict) -> dict:
 def score_scans(args, device) -> dict:
     """The "scan" block of eval.json: per frame the two directions of scanscore.score_scan, and their summary."""
     from . import scanscore
-    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
-    frames = args.frames or sorted(int(d) for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
+    run_dir = _run.run_dir_of(args)
     transform = None
     if args.scan_transform is not None:
         transform = np.loadtxt(args.scan_transform, dtype=np.float64)
@@ -314,20 +262,10 @@ def score_scans(args, device) -> dict:
     disp_png = disp_png_options(args)
     disp_apply = getattr(args, "disp_apply", None) if disp_png is not None else None
     tess = None
-    pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="t4d-eval-scan")
-    try:
-        pending = {}
-
-        def prefetch(t):
-            if t not in pending:
-                pending[t] = pool.submit(_read_scan_files, run_dir, args.scans, t, transform)
-
-        for i, t in enumerate(frames):
-            prefetch(t)
-            if i + 1 < len(frames):
-                prefetch(frames[i + 1])
-            obj, scan = pending.pop(t).result()
-            key = "%06d" % t
+    with _run.prefetched(_run.frames_of(args, run_dir), lambda t: _read_scan_files(run_dir, args.scans, t, transform),
+                         thread_name="t4d-eval-scan") as walk:
+        for t, (obj, scan) in walk:
+            key = _run.frame_key(t)
             if obj is None:
                 result[key] = {"skipped": "no face.obj"}
                 continue
@@ -375,8 +313,6 @@ def score_scans(args, device) -> dict:
             for d, stats in score.items():
                 row[d] = {n: (_finite(v) if isinstance(v, float) else v) for n, v in stats.items()}
             result[key] = row
-    finally:
-        pool.shutdown(wait=True)
     out = {"unit": args.scan_unit, "max_dist": args.scan_max_dist, "frames": result, "summary": _scan_summary(result)}
     if bake_disp is not None:
         out["bake"] = {"dist": bake_disp, "res": args.bake_res, "same_side": not args.bake_both_sides}
@@ -409,15 +345,11 @@ def _floats(spec: str) -> List[float]:
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .train import build_parser as train_parser
-    base = train_parser()
     p = argparse.ArgumentParser(prog="python -m topo4d_amd.evaluate",
                                 description="Render each frame's face.obj + face.png into the capture views and score it.")
-    for a in base._actions:                                   # -e/-s/-id/-did/-od/-dr exactly as topo4d_amd.train has them
-        if a.dest in ("exp", "seq", "input_dir", "dense_input_dir", "output_dir", "down_ratio"):
-            p.add_argument(*a.option_strings, type=a.type, default=a.default, help=a.help)
-    p.add_argument("--frames", type=_frames, default=None, help="Frames to score: '1-10', '1,5,9' (default: every frame directory).")
-    p.add_argument("--views", type=lambda s: [v.strip() for v in s.split(",") if v.strip()], default=None,
+    _run.add_run_flags(p, "exp", "seq", "input_dir", "dense_input_dir", "output_dir", "down_ratio",
+                       frames_help="Frames to score: '1-10', '1,5,9' (default: every frame directory).")
+    p.add_argument("--views", type=_run.view_list, default=None,
                    help="Cameras to score, comma-separated (default: every camera, blacklisted ones included).")
     p.add_argument("--set", choices=("low", "dense", "both", "none"), default="low",
                    help="Views to score against: the geometry inputs (-id), the texture inputs (-did), both, or none (scans only).")
@@ -468,10 +400,8 @@ def build_parser() -> argparse.ArgumentParser:
 
 def evaluate(args, device=None) -> dict:
     dev = torch.device(device if device is not None else "cuda")
-    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
-    if not os.path.isdir(run_dir):
-        raise SystemExit(f"no run at {run_dir}")
-    sets = {"both": ["low", "dense"], "none": []}.get(args.set, [args.set])
+    run_dir = _run.run_dir_of(args)
+    sets ={"both": ["low", "dense"], "none": []}.get(args.set, [args.set])
     scans = getattr(args, "scans", None)
     if scans is not None and not os.path.isdir(scans):
         raise SystemExit(f"--scans: no directory {scans}")

@@ -73,13 +73,12 @@ import argparse
 import functools
 import json
 import os
-from concurrent.futures import ThreadPoolExecutor
 from typing import Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _run
 from ._lib import ptr
 
 T4D_PROJTEX_WEIGHTED, T4D_PROJTEX_BEST = 0, 1
@@ -908,15 +907,11 @@ def load_gains(path: str) -> dict:
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .evaluate import _frames
-    from .train import _size_list, build_parser as train_parser
     p = argparse.ArgumentParser(prog="python -m topo4d_amd.projtex",
                                 description="Project the capture photographs into every frame's UV texture: face_proj.png.")
-    for a in train_parser()._actions:                         # -e/-s/-id/-did/-od/-dr/-tr exactly as topo4d_amd.train has them
-        if a.dest in ("exp", "seq", "input_dir", "dense_input_dir", "output_dir", "down_ratio", "tex_res"):
-            p.add_argument(*a.option_strings, type=a.type, default=a.default, help=a.help)
-    p.add_argument("--frames", type=_frames, default=None, help="Frames to project: '1-10', '1,5,9' (default: every frame directory).")
-    p.add_argument("--views", type=lambda s: [v.strip() for v in s.split(",") if v.strip()], default=None,
+    _run.add_run_flags(p, "exp", "seq", "input_dir", "dense_input_dir", "output_dir", "down_ratio", "tex_res",
+                       frames_help="Frames to project: '1-10', '1,5,9' (default: every frame directory).")
+    p.add_argument("--views", type=_run.view_list, default=None,
                    help="Cameras to project, comma-separated (default: the cameras training uses).")
     p.add_argument("--set", choices=("low", "dense"), default="dense",
                    help="Photographs to project: the texture inputs (-did, the default) or the geometry inputs (-id).")
@@ -927,13 +922,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--equalize", action="store_true",
                    help="Equalise the cameras' exposure and white balance: estimate one gain per camera and channel, write "
                         "proj_gains.json into the run directory and project every frame with these gains.")
-    p.add_argument("--equalize_frames", type=_frames, default=None,
+    p.add_argument("--equalize_frames", type=_run.frame_list, default=None,
                    help="With --equalize: the frames the statistics are gathered over (default: the first frame projected).")
     p.add_argument("--gains", default=None, metavar="FILE", help="Project with the gains of a saved proj_gains.json instead of estimating.")
     add_eq_options(p)
     p.add_argument("--tex_pad", type=int, default=0, metavar="R",
                    help="Fill a gutter of R texels (0..64) round the projected texels (texfinish.finish).")
-    p.add_argument("--tex_sizes", type=_size_list, default=[],
+    p.add_argument("--tex_sizes", type=_run.size_list, default=[],
                    help="Smaller levels to write too, comma-separated, each tex_res / 2^k: face_proj_<size>.png.")
     p.add_argument("--save_weight", action="store_true", help="Also write %%06d/face_proj_weight.png: the number of views per texel.")
     p.add_argument("--tex_fill", action="store_true",
@@ -965,19 +960,11 @@ def _check_args(args, res: int) -> dict:
     return {**opts, **(band if opts["mode"] == "twoband" else {}), **(consist if reject else {})}
 
 
-def _read_obj(frame_dir: str):
-    from . import meshrender
-    path = os.path.join(frame_dir, "face.obj")
-    return meshrender.read_face_obj(path) if os.path.exists(path) else None
-
-
 def project_tree(args, device=None) -> list:
     """The files written for the run <od>/<exp>/<seq>; frames without face.obj or without views are left alone."""
     from . import cameras as C, ingest
     dev = torch.device(device if device is not None else "cuda")
-    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
-    if not os.path.isdir(run_dir):
-        raise SystemExit(f"no run at {run_dir}")
+    run_dir = _run.run_dir_of(args)
     opts = _check_args(args, args.tex_res)
     save_rejected = getattr(args, "save_rejected", False)
     if save_rejected and not getattr(args, "reject", False):
@@ -986,31 +973,17 @@ def project_tree(args, device=None) -> list:
     if equalize and gains_file:
         raise SystemExit("--equalize estimates the gains and --gains reads them: give one of the two")
     stat, solve = eq_options_of(args)
-    low = args.set == "low"
-    data_dir = args.input_dir if low else args.dense_input_dir
-    cameras, _, trans_g = C.get_cameras(args.input_dir, args.seq, resize_factor=args.down_ratio if low else 1)
-    lenses = C.get_lenses(args.input_dir, args.seq, args.down_ratio)[0 if low else 1] if args.undistort else None
-    names = [n.split(".")[0] for n in cameras]
-    if args.views is None:
-        skip = C.BLACKLIST
-    else:
-        if set(args.views) - set(names):
-            raise SystemExit(f"--views: {sorted(set(args.views) - set(names))} not among the cameras of {data_dir}/{args.seq}")
-        skip = [n for n in cameras if n.split(".")[0] not in args.views]
-    frames = args.frames or sorted(int(d) for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
+    cameras, trans_g, lenses, data_dir, _, skip = _run.select_cameras(args, args.set, absent="trained")    # the cameras training uses
+    frames = _run.frames_of(args, run_dir)
     written = []
-    pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="t4d-projtex")
+
+    def read_obj(t):
+        return _run.read_frame_obj(_run.frame_dir(run_dir, t))
+
     with torch.cuda.device(dev):
         pf = ingest.FramePrefetcher(data_dir, args.seq, cameras, use_mask=False, blacklist=skip, rotate_mask=C.ROTATE_MASK,
                                     setup_camera=functools.partial(C.setup_camera, device=dev), device=dev, lenses=lenses)
         try:
-            pending = {}
-
-            def prefetch(t):
-                if t not in pending:
-                    pending[t] = pool.submit(_read_obj, os.path.join(run_dir, "%06d" % t))
-                    pf.prefetch(t)
-
             gains = None
             try:
                 if gains_file:
@@ -1018,7 +991,7 @@ def project_tree(args, device=None) -> list:
                 elif equalize:
                     est = GainEstimator(args.tex_res, opts, stat, solve, device=dev)
                     for t in getattr(args, "equalize_frames", None) or frames:
-                        obj, dataset = _read_obj(os.path.join(run_dir, "%06d" % t)), pf.get(t)
+                        obj, dataset = read_obj(t), pf.get(t)
                         if obj is None or not dataset:
                             continue
                         est.add(obj, trans_g, dataset)
@@ -1028,30 +1001,24 @@ def project_tree(args, device=None) -> list:
                     written.append(os.path.join(run_dir, GAINS_NAME))
             except (OSError, ValueError) as e:
                 raise SystemExit(f"equalisation: {e}") from None
-            for i, t in enumerate(frames):
-                prefetch(t)
-                if i + 1 < len(frames):
-                    prefetch(frames[i + 1])
-                obj = pending.pop(t).result()
-                dataset = pf.get(t)
-                if obj is None or not dataset:
-                    continue
-                if gains is not None and any(n not in gains for n in _names(dataset)):
-                    raise SystemExit(f"equalisation: no gains for camera(s) {', '.join(n for n in _names(dataset) if n not in gains)}")
-                check_frame_views(dataset, opts)
-                written += write_frame(os.path.join(run_dir, "%06d" % t), obj, trans_g, dataset, args.tex_res, opts,
-                                       pad=args.tex_pad, sizes=args.tex_sizes, save_weight=args.save_weight, device=dev, gains=gains,
-                                       fill=getattr(args, "tex_fill", False), save_rejected=save_rejected)
+            with _run.prefetched(frames, read_obj, ahead=pf.prefetch, thread_name="t4d-projtex") as walk:
+                for t, obj in walk:
+                    dataset = pf.get(t)
+                    if obj is None or not dataset:
+                        continue
+                    if gains is not None and any(n not in gains for n in _names(dataset)):
+                        raise SystemExit(f"equalisation: no gains for camera(s) {', '.join(n for n in _names(dataset) if n not in gains)}")
+                    check_frame_views(dataset, opts)
+                    written += write_frame(_run.frame_dir(run_dir, t), obj, trans_g, dataset, args.tex_res, opts,
+                                           pad=args.tex_pad, sizes=args.tex_sizes, save_weight=args.save_weight, device=dev, gains=gains,
+                                           fill=getattr(args, "tex_fill", False), save_rejected=save_rejected)
         finally:
-            pool.shutdown(wait=True)
             pf.close()
     return written
 
 
 def main(argv=None) -> None:
-    args = build_parser().parse_args(argv)
-    for p in project_tree(args):
-        print(p)
+    _run.print_written(project_tree(build_parser().parse_args(argv)))
 
 
 if __name__ == "__main__":

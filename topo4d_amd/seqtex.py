@@ -45,10 +45,9 @@ import json
 import os
 from typing import List, Sequence, Tuple
 
-import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _args, _lib, _run
 from ._lib import on_device, ptr
 
 MAX_FRAMES = 64
@@ -169,14 +168,9 @@ def _quantile(spec: str) -> Tuple[int, int]:
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .evaluate import _frames
-    from .train import build_parser as train_parser
     p = argparse.ArgumentParser(prog="python -m topo4d_amd.seqtex",
                                 description="Fuse the stabilised textures of a run over time: per-texel quantiles, and every frame completed from them.")
-    for a in train_parser()._actions:                         # -e/-s/-od exactly as topo4d_amd.train has them
-        if a.dest in ("exp", "seq", "output_dir"):
-            p.add_argument(*a.option_strings, type=a.type, default=a.default, help=a.help)
-    p.add_argument("--frames", type=_frames, default=None, help="Frames to fuse: '1-10', '1,5,9' (default: every frame there is).")
+    _run.add_run_flags(p, "exp", "seq", "output_dir", frames_help="Frames to fuse: '1-10', '1,5,9' (default: every frame there is).")
     p.add_argument("--texture", default=DEFAULTS["texture"], metavar="NAME", help="The projected texture of every frame directory (default face_proj.png).")
     p.add_argument("--source", choices=("stab", "raw"), default=DEFAULTS["source"],
                    help="stab: the files `drift --stabilise` wrote, by the run's drift.json (default); raw: the frames' own textures.")
@@ -224,8 +218,7 @@ def _plan(args, o: dict, run_dir: str) -> Tuple[str, List[Tuple[str, str, str]]]
     reference first); SystemExit where the tree does not hold what --source asks for.  Touches no device."""
     chosen = getattr(args, "frames", None)
     if o["source"] == "raw":
-        keys = ["%06d" % t for t in chosen] if chosen else sorted(d for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
-        keys = [k for k in sorted(set(keys)) if os.path.exists(os.path.join(run_dir, k, "face.obj")) and os.path.exists(os.path.join(run_dir, k, o["texture"]))]
+        keys = [_run.frame_key(t) for t in sorted(set(_run.frames_of(args, run_dir))) if _run.frame_files(run_dir, t, "face.obj", o["texture"])]
         if not keys:
             raise SystemExit(f"seqtex: no frame of {run_dir} has face.obj and {o['texture']}")
         return keys[0], [(k, o["texture"], None) for k in keys]
@@ -251,11 +244,10 @@ def _plan(args, o: dict, run_dir: str) -> Tuple[str, List[Tuple[str, str, str]]]
 
 def _read(run_dir: str, entry: Tuple[str, str, str], dev):
     """(texture uint8 [h,w,3], valid uint8 [h,w]) on the device for one entry of _plan"""
-    from PIL import Image
     from . import drift
     key, name, weight_name = entry
     if weight_name is None:
-        cur = drift._read_frame(os.path.join(run_dir, key), name, dev)
+        cur = drift.read_frame(os.path.join(run_dir, key), name, dev)
         if cur is None:
             raise SystemExit(f"seqtex: {os.path.join(run_dir, key)} lacks face.obj or {name}")
         return cur[1], cur[2]
@@ -263,11 +255,8 @@ def _read(run_dir: str, entry: Tuple[str, str, str], dev):
     for p in paths:
         if not os.path.exists(p):
             raise SystemExit(f"seqtex: {p} not found: run `python -m topo4d_amd.drift --stabilise` on this tree again")
-    tex = np.ascontiguousarray(np.array(Image.open(paths[0]).convert("RGB")))
-    weight = np.array(Image.open(paths[1]))
-    if weight.shape[:2] != tex.shape[:2]:
-        raise SystemExit(f"{paths[1]}: {weight.shape[:2]} does not match {name}'s {tex.shape[:2]}")
-    valid = np.ascontiguousarray((weight.reshape(weight.shape[0], weight.shape[1], -1) > 0).any(-1).astype(np.uint8))
+    tex = _run.read_texture(paths[0])
+    valid = _run.read_validity(paths[1], tex.shape[:2], name)
     return torch.from_numpy(tex).to(dev), torch.from_numpy(valid).to(dev)
 
 
@@ -276,9 +265,7 @@ def seqtex_tree(args, device=None) -> dict:
     selected frame's completed texture (the module docstring lists the files and keys)."""
     from . import meshrender, png, projtex
     o = tree_options(args)
-    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
-    if not os.path.isdir(run_dir):
-        raise SystemExit(f"no run at {run_dir}")
+    run_dir = _run.run_dir_of(args)
     ref_key, entries = _plan(args, o, run_dir)                 # everything the tree lacks ends the run before a device is touched
     by_key = {e[0]: e for e in entries}
     fused = pick_frames(list(by_key), o["max_frames"])

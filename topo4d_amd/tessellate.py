@@ -40,7 +40,7 @@ from typing import Tuple
 import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _args, _lib, _run
 from ._lib import on_device, ptr
 
 MAX_LEVEL = 64
@@ -237,14 +237,9 @@ def write_frame(frame_dir: str, tess: Tessellation, fine_vertices: torch.Tensor)
 
 # ---- command line ----------------------------------------------------------------------------------------------------------
 def build_parser() -> argparse.ArgumentParser:
-    from .evaluate import _frames
-    from .train import build_parser as train_parser
     p = argparse.ArgumentParser(prog="python -m topo4d_amd.tessellate",
                                 description="Apply every frame's face_disp.png to its face.obj: tessellate, displace, write face_hi.obj.")
-    for a in train_parser()._actions:                         # -e/-s/-od exactly as topo4d_amd.train has them
-        if a.dest in ("exp", "seq", "output_dir"):
-            p.add_argument(*a.option_strings, type=a.type, default=a.default, help=a.help)
-    p.add_argument("--frames", type=_frames, default=None, help="Frames to displace: '1-10', '1,5,9' (default: every frame directory).")
+    _run.add_run_flags(p, "exp", "seq", "output_dir", frames_help="Frames to displace: '1-10', '1,5,9' (default: every frame directory).")
     p.add_argument("--level", type=int, required=True, metavar="N", help=f"Segments per edge of the tessellation, 1..{MAX_LEVEL}.")
     p.add_argument("--dist", type=float, required=True, metavar="DIST", help="The reach the maps were baked with (evaluate --bake_disp).")
     p.add_argument("--use_hit", action="store_true",
@@ -256,35 +251,32 @@ def apply_tree(args, device=None) -> list:
     """The files written for the run <od>/<exp>/<seq>; frames without face.obj or face_disp.png (with --use_hit: or
     face_disp_hit.png) are left alone."""
     from PIL import Image
-    from . import dispmap, meshrender, projtex, scanbake
+    from . import dispmap, projtex, scanbake
     try:
         check_level(args.level)
         dispmap.check_options(args.dist)
     except ValueError as e:
         raise SystemExit(f"--level / --dist: {e}") from None
     dev = torch.device(device if device is not None else "cuda")
-    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
-    if not os.path.isdir(run_dir):
-        raise SystemExit(f"no run at {run_dir}")
-    frames = args.frames or sorted(int(d) for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
+    run_dir = _run.run_dir_of(args)
     written, tess = [], None
     with torch.cuda.device(dev):
-        for t in frames:
-            frame_dir = os.path.join(run_dir, "%06d" % t)
-            paths = [os.path.join(frame_dir, n) for n in ("face.obj", dispmap.PNG_NAME) + ((scanbake.HIT_NAME,) if args.use_hit else ())]
-            if not all(os.path.exists(p) for p in paths):
+        for t in _run.frames_of(args, run_dir):
+            paths = _run.frame_files(run_dir, t, "face.obj", dispmap.PNG_NAME, *((scanbake.HIT_NAME,) if args.use_hit else ()))
+            if paths is None:
                 continue
-            obj = meshrender.read_face_obj(paths[0])
+            frame_dir = _run.frame_dir(run_dir, t)
+            obj = _run.read_frame_obj(frame_dir)
             png = np.array(Image.open(paths[1]))
             if png.dtype != np.uint16 or png.ndim != 2:
                 raise SystemExit(f"{paths[1]}: not a 16-bit grey PNG")
             h, w = png.shape
             code = torch.from_numpy(png.astype(np.int32)).to(dev)
             if args.use_hit:
-                hit = np.array(Image.open(paths[2]).convert("L")) != 0
+                hit = _run.read_hit_mask(paths[2])
                 if hit.shape != (h, w):
                     raise SystemExit(f"{paths[2]}: not of {dispmap.PNG_NAME}'s size")
-                has = torch.from_numpy(np.ascontiguousarray(hit).astype(np.uint8)).to(dev)
+                has = torch.from_numpy(hit).to(dev)
             else:
                 has = (projtex.island_labels(obj, h, w, device=dev) != 0).to(torch.uint8)
             result = displace_frame(obj, obj.vertices, code, has, args.level, args.dist, device=dev, tess=tess)
@@ -294,9 +286,7 @@ def apply_tree(args, device=None) -> list:
 
 
 def main(argv=None) -> None:
-    args = build_parser().parse_args(argv)
-    for p in apply_tree(args):
-        print(p)
+    _run.print_written(apply_tree(build_parser().parse_args(argv)))
 
 
 if __name__ == "__main__":

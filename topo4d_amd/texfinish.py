@@ -40,10 +40,9 @@ import argparse
 import os
 from typing import Dict, Sequence, Tuple
 
-import numpy as np
 import torch
 
-from . import _args, _lib
+from . import _args, _lib, _run
 from ._lib import on_device, ptr
 
 MAX_PAD, MAX_ERODE = 64, 4
@@ -260,54 +259,42 @@ def write_levels(path, levels: Dict[int, torch.Tensor]) -> list:
 
 # ---- command line ----------------------------------------------------------------------------------------------------------
 def build_parser() -> argparse.ArgumentParser:
-    from .evaluate import _frames
-    from .train import _size_list, build_parser as train_parser
     p = argparse.ArgumentParser(prog="python -m topo4d_amd.texfinish",
                                 description="Pad the UV islands of every frame's face.png and write smaller levels.")
-    for a in train_parser()._actions:                         # -e/-s/-od exactly as topo4d_amd.train has them
-        if a.dest in ("exp", "seq", "output_dir"):
-            p.add_argument(*a.option_strings, type=a.type, default=a.default, help=a.help)
-    p.add_argument("--frames", type=_frames, default=None, help="Frames to finish: '1-10', '1,5,9' (default: every frame directory).")
+    _run.add_run_flags(p, "exp", "seq", "output_dir", frames_help="Frames to finish: '1-10', '1,5,9' (default: every frame directory).")
     p.add_argument("--pad", type=int, required=True, metavar="R", help=f"Gutter radius in texels, 0..{MAX_PAD}.")
     p.add_argument("--erode", type=int, default=1, metavar="E",
                    help=f"Rounds of erosion of the face.obj coverage before padding, 0..{MAX_ERODE} (default 1).")
-    p.add_argument("--sizes", type=_size_list, default=[], help="Smaller levels to write too, comma-separated: res / 2^k each.")
+    p.add_argument("--sizes", type=_run.size_list, default=[], help="Smaller levels to write too, comma-separated: res / 2^k each.")
     p.add_argument("--in_place", action="store_true", help="Overwrite face.png (and write face_<res>.png) instead of face_pad*.png.")
     return p
 
 
 def finish_tree(args, device=None) -> list:
     """The files written for the run <od>/<exp>/<seq>; frames without face.obj or face.png are left alone."""
-    from PIL import Image
-    from . import meshrender
     dev = torch.device(device if device is not None else "cuda")
-    run_dir = os.path.join(args.output_dir, args.exp, args.seq)
-    if not os.path.isdir(run_dir):
-        raise SystemExit(f"no run at {run_dir}")
-    frames = args.frames or sorted(int(d) for d in os.listdir(run_dir) if d.isdigit() and len(d) == 6)
+    run_dir = _run.run_dir_of(args)
     written = []
     with torch.cuda.device(dev):
-        for t in frames:
-            frame_dir = os.path.join(run_dir, "%06d" % t)
-            obj_path, png_path = os.path.join(frame_dir, "face.obj"), os.path.join(frame_dir, "face.png")
-            if not (os.path.exists(obj_path) and os.path.exists(png_path)):
+        for t in _run.frames_of(args, run_dir):
+            frame_dir = _run.frame_dir(run_dir, t)
+            obj, tex = _run.read_textured_frame(frame_dir, "face.png")
+            if obj is None or tex is None:
                 continue
-            tex = np.ascontiguousarray(np.array(Image.open(png_path).convert("RGB")))
+            png_path = os.path.join(frame_dir, "face.png")
             try:
                 check_options(args.pad, args.erode, args.sizes, tex.shape[0])
             except ValueError as e:
                 raise SystemExit(f"{png_path}: {e}") from None
             image = torch.from_numpy(tex).to(dev)
-            cov = coverage_from_obj(meshrender.read_face_obj(obj_path), tex.shape[0], tex.shape[1], device=dev)
+            cov = coverage_from_obj(obj, tex.shape[0], tex.shape[1], device=dev)
             levels = finish(image, cov, pad=args.pad, erode=args.erode, sizes=args.sizes)
             written += write_levels(png_path if args.in_place else os.path.join(frame_dir, "face_pad.png"), levels)
     return written
 
 
 def main(argv=None) -> None:
-    args = build_parser().parse_args(argv)
-    for p in finish_tree(args):
-        print(p)
+    _run.print_written(finish_tree(build_parser().parse_args(argv)))
 
 
 if __name__ == "__main__":

@@ -50,6 +50,7 @@ import torch
 import torch.nn.functional as F
 
 from . import cameras as C
+from ._run import size_list, view_list
 
 # train.py:272-289 (initialize_optimizer)
 LRS = {
@@ -469,20 +470,6 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
 
 
 # ---- command line ----------------------------------------------------------------------------------------------------------
-def _view_list(s: str) -> List[str]:
-    return [v.strip() for v in s.split(",") if v.strip()]
-
-
-def _size_list(s: str) -> List[int]:
-    try:
-        out = [int(v) for v in s.split(",") if v.strip()]
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"{s!r} is not a comma-separated list of sizes") from None
-    if any(v < 1 for v in out):
-        raise argparse.ArgumentTypeError(f"{s!r}: sizes must be positive")
-    return out
-
-
 def build_parser() -> argparse.ArgumentParser:
     """train.py:759-780: the same flags, names and defaults (--log_views: comma-separated)."""
     p = argparse.ArgumentParser(prog="python -m topo4d_amd.train")
@@ -508,7 +495,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('-lf', '--log_freq', type=int, default=500, help="Frequence of saving gaussian rendering results per frame.")
     p.add_argument('-dlf', '--dense_log_freq', type=int, default=300,
                    help="Frequence of saving dense gaussian rendering results per frame.")
-    p.add_argument('-lv', '--log_views', type=_view_list, default=["K98707293"],
+    p.add_argument('-lv', '--log_views', type=view_list, default=["K98707293"],
                    help="Views of the saved renderings, comma-separated.")
     p.add_argument('-cf', '--ckp_freq', type=int, default=5, help="Frequence of saving gaussian attributes.")
     # the flags the reference does not have stay out of the namespace unless given (read with getattr)
@@ -521,7 +508,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--tex_pad', type=int, default=argparse.SUPPRESS, metavar='R',
                    help="With --gen_tex: fill a gutter of R texels (0..64) round the UV islands of face.png from the nearest "
                         "baked texel, so that bilinear taps on the seams no longer mix in the black background.")
-    p.add_argument('--tex_sizes', type=_size_list, default=argparse.SUPPRESS,
+    p.add_argument('--tex_sizes', type=size_list, default=argparse.SUPPRESS,
                    help="With --gen_tex: texture sizes to write, comma-separated, each tex_res / 2^k: face.png holds tex_res, "
                         "face_<size>.png the others, averaged over baked texels only.")
     p.add_argument('--tex_project', action='store_true', default=argparse.SUPPRESS,
