@@ -7,8 +7,8 @@ its own single source file: the CPU UV-space triangle rasterizer `_render_colors
 The source is compiled WHERE IT LIES (never copied into this repo), with the flags the reference's own
 setup.py/distutils would use for the arithmetic (-O2, no fast-math), into oracle/_ref/libmesh_core_ref.so
 (git-ignored; travels to the GPU box with the snapshot).  The C++ symbol is called through its mangled name, so no
-shim source is needed.  `python oracle/build_ref.py` also (re)writes tests/golden/g5_render_colors.npz and
-g11_render_colors_uv_meshes.npz from that library.
+shim source is needed.  `python oracle/build_ref.py` also (re)writes tests/golden/g5_render_colors.npz,
+g11_render_colors_uv_meshes.npz and g17_bake_edges.npz from that library.
 
 Run:  python oracle/build_ref.py          (only works where /root/reference exists)
 """
@@ -78,10 +78,26 @@ def write_golden_uv_meshes():
     np.savez_compressed(os.path.join(ROOT, "tests", "golden", "g11_render_colors_uv_meshes.npz"), **out)
 
 
+def write_golden_bake_edges():
+    """tests/golden/g17_bake_edges.npz: sha256 digests (shape + raw float32 bytes, so signed zeros and NaN payloads count) of the
+    reference's image and depth for every case of texture_oracle.edge_cases().  tests/test_bake_cases_host.py holds the port to
+    them, and the port is the GPU tests' truth where oracle/_ref is absent."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    from oracle import texture_oracle as TX
+    names, images, depths = [], [], []
+    for name, (args, kw) in TX.edge_cases().items():
+        image, depth = TX.render_colors_ref(*args, **kw)
+        names.append(name); images.append(TX.digest(image)); depths.append(TX.digest(depth))
+    np.savez_compressed(os.path.join(ROOT, "tests", "golden", "g17_bake_edges.npz"), names=np.array(names), image=np.array(images),
+                        depth=np.array(depths))
+
+
 if __name__ == "__main__":
     p = build(force="--force" in sys.argv)
     print("reference mesh_core:", p)
     if p:
         write_golden()
         write_golden_uv_meshes()
-        print("wrote tests/golden/g5_render_colors.npz, tests/golden/g11_render_colors_uv_meshes.npz")
+        write_golden_bake_edges()
+        print("wrote tests/golden/g5_render_colors.npz, tests/golden/g11_render_colors_uv_meshes.npz, tests/golden/g17_bake_edges.npz")

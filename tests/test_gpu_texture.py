@@ -1,4 +1,9 @@
-"""GPU: t4d_texture_bake through the C ABI == the reference's CPU rasterizer, bit for bit."""
+"""GPU: t4d_texture_bake through the C ABI == the reference's CPU rasterizer, bit for bit.
+
+Every mesh here is scaffold.scene.uv_mesh, a jittered grid of pixel-sized triangles (plus one giant triangle).  What such a grid cannot
+reach - every box width of the texel loop, three staging rounds, ties between different triangles, signed zeros / denormals / inf /
+NaN depths, degenerate and lattice-aligned triangles, other channel counts, tiny images, both binning paths above 1024 tiles, a hostile
+caller's buffer, the exact pair capacity - is in tests/test_gpu_bake_edges.py, compared on the uint32 view."""
 import numpy as np
 import pytest
 import torch
