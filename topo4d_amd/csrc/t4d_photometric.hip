@@ -13,7 +13,8 @@
 //                   (the window is symmetric: adjoint = same filter) -> dL/dx' = G*D1 + 2x'(G*D2) + y(G*D3) + L1 term of
 //                   the row eleven behind; affine backward; partial sums for cam_m / cam_c.  No intermediate in memory.
 //   k_photo_final   fixed-order sums of the partials (deterministic)
-// Pinned by tests against topo4d_amd/loss.py, itself pinned by golden G3 captured from the real reference functions.
+// Pinned by tests against oracle/loss_oracle.py, itself pinned by golden G3 captured from the real reference functions, and pixel
+// by pixel against a float64 restatement on capture-like images (tests/photo_cases.py, tests/test_gpu_photo_cases.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -75,13 +76,16 @@ __device__ __forceinline__ void ssim_adjoint(const float mu1, const float mu2, c
     d2 = -gi * S * B1;
     d3 = gi2 * A1;
 }
-// x' = em * im + cc, y = gt, (r0, r1, r2) = G*D1, G*D2, G*D3 at the pixel: returns dL/dx', leaves |x' - y| in `ad`
+// x' = em * im + cc, y = gt, (r0, r1, r2) = G*D1, G*D2, G*D3 at the pixel: returns dL/dx', leaves |x' - y| in `ad`.
+// Both kernels evaluate the pixel for the view weight's MAGNITUDE (gsc and l1w from |w|: copysignf(l1w, d) would drop the sign of
+// a negative l1w) and give the results its sign where that costs nothing per pixel: in the factor of the store (ems) and on the
+// workgroup's two camera sums.
 __device__ __forceinline__ float pixel_gradient(const float x, const float y, const float r0, const float r1, const float r2,
                                                 const float l1w, float &ad)
 {
     const float d = x - y;
     ad = fabsf(d);
-    const float gl1 = d == 0.f ? 0.f : copysignf(l1w, d);                        // 0.8 / N * sign(x' - y)
+    const float gl1 = d == 0.f ? 0.f : copysignf(l1w, d);                        // 0.8 |w| / N * sign(x' - y): l1w >= 0
     return fmaf(x + x, r1, r0) + fmaf(y, r2, gl1);
 }
 
@@ -126,9 +130,10 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
     };
     const float em = P.cam_m ? expf(P.cam_m[vc]) : 1.f, cc = P.cam_c ? P.cam_c[vc] : 0.f;
-    const float N = 3.f * (float)HW, wv = P.weight ? P.weight[v] : 1.f;
-    const float g = -0.2f * wv / N;                      // dL/dS
-    const float l1w = 0.8f * wv / N;
+    const float N = 3.f * (float)HW, wv = P.weight ? P.weight[v] : 1.f, wa = fabsf(wv);
+    const float g = -0.2f * wa / N;                      // dL/dS
+    const float l1w = 0.8f * wa / N;
+    const float ems = copysignf(em, wv), wsg = copysignf(1.f, wv);
     float w[11];
 #pragma unroll
     for (int k = 0; k < 11; k++) w[k] = P.win[k];
@@ -239,7 +244,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 const float xi = em * o_im;
                 float ad;
                 const float gg = pixel_gradient(fmaf(em, o_im, cc), o_gt, r01.x, r01.y, r2, l1w, ad);      // dL/dx'
-                if (col2) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, em * gg), r_out, off_out, oro, 0);
+                if (col2) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ems * gg), r_out, off_out, oro, 0);
                 sum_l1 += ad;
                 sum_gm = fmaf(gg, xi, sum_gm);           // d x'/d cam_m = exp(cam_m) * im
                 sum_gc += gg;
@@ -259,7 +264,7 @@ __global__ __launch_bounds__(kFT) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     if (tid == 0) {
         const size_t t = ((size_t)vc * P.ty + blockIdx.y) * P.tx + blockIdx.x;
         P.part_loss[2 * t] = tl1; P.part_loss[2 * t + 1] = tss;
-        P.part_cam[2 * t] = tgm; P.part_cam[2 * t + 1] = tgc;
+        P.part_cam[2 * t] = wsg * tgm; P.part_cam[2 * t + 1] = wsg * tgc;
     }
 }
 
@@ -296,8 +301,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const float *im = P.im + (size_t)vc * HW, *gt = P.gt + (size_t)vc * HW;
     float *dout = P.dL_dim + (size_t)vc * HW;
     const float em = P.cam_m ? expf(P.cam_m[vc]) : 1.f, cc = P.cam_c ? P.cam_c[vc] : 0.f;
-    const float N = 3.f * (float)HW, wv = P.weight ? P.weight[v] : 1.f;
-    const float g = -0.2f * wv / N, l1w = 0.8f * wv / N;
+    const float N = 3.f * (float)HW, wv = P.weight ? P.weight[v] : 1.f, wa = fabsf(wv);
+    const float g = -0.2f * wa / N, l1w = 0.8f * wa / N;
+    const float ems = copysignf(em, wv), wsg = copysignf(1.f, wv);
     float w[11];
 #pragma unroll
     for (int k = 0; k < 11; k++) w[k] = P.win[k];
@@ -398,7 +404,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 const float xi = em * o_im[j];
                 float ad;
                 const float gg = pixel_gradient(fmaf(em, o_im[j], cc), o_gt[j], r01.x, r01.y, r2, l1w, ad);
-                dout[(size_t)gy * P.W + gx] = em * gg;
+                dout[(size_t)gy * P.W + gx] = ems * gg;
                 sum_l1 += ad;
                 sum_gm = fmaf(gg, xi, sum_gm);
                 sum_gc += gg;
@@ -410,7 +416,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     if (tid == 0) {
         const size_t t = ((size_t)vc * P.ty + blockIdx.y) * P.tx + blockIdx.x;
         P.part_loss[2 * t] = tl1; P.part_loss[2 * t + 1] = tss;
-        P.part_cam[2 * t] = tgm; P.part_cam[2 * t + 1] = tgc;
+        P.part_cam[2 * t] = wsg * tgm; P.part_cam[2 * t + 1] = wsg * tgc;
     }
 }
 
@@ -614,10 +620,15 @@ T4D_EXPORT int t4d_photometric_loss(int32_t n_views, int32_t H, int32_t W, const
     char *sc = (char *)scratch;
     P.part_loss = (float *)sc;
     P.part_cam = (float *)(sc + align_up(tiles * 8));
-    // the reference's window: exp(-(i-5)^2 / (2*1.5^2)) for i = 0..10, as float32, normalised in float32 (external.py:73-76)
-    float g[11], sum = 0.f;
-    for (int i = 0; i < 11; i++) { g[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); sum += g[i]; }
-    for (int i = 0; i < 11; i++) P.win[i] = g[i] / sum;
+    // the reference's window: exp(-(i-5)^2 / (2*1.5^2)) for i = 0..10, as float32, normalised in float32 (external.py:73-76).
+    // torch's float32 sum of the eleven taps is the correctly rounded one, 3.7592328; adding them one after the other in float
+    // gives 3.7592325, nine taps one bit off and a window that sums to 1 + 4.4e-8 instead of 1 - 3.1e-8 - which mu^2 carries
+    // four times and E[x^2] twice, a BIAS of 1.5e-7 mu^2 in every variance (2.3e-5 of mean SSIM, 4.6e-6 of the loss, where the
+    // variances are of the size of c2: tests/photo_cases.py `anti`).  Hence the sum in double, rounded once.
+    float g[11];
+    double sum = 0.0;
+    for (int i = 0; i < 11; i++) { g[i] = (float)exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5)); sum += (double)g[i]; }
+    for (int i = 0; i < 11; i++) P.win[i] = g[i] / (float)sum;
     hipStream_t stream = (hipStream_t)hip_stream;
     const dim3 grid(P.tx, P.ty, n_views * 3);
     if (ft == 0 && P.th == 64) hipLaunchKernelGGL((k_photo_tile<64, 1024>), grid, dim3(1024), 0, stream, P);
