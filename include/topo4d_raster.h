@@ -289,7 +289,7 @@ int t4d_priors_eval(const T4DPriors *pr, int32_t is_initial, const float *means3
  * pins (torch skips parameters without a gradient). */
 #define T4D_ADAM_MAX_TENSORS 12
 typedef struct T4DAdamTensor {
-    float *param;               /* [rows, width] updated in place */
+    float *param;               /* [rows, width] updated in place (rows == 0: a no-op, may be NULL) */
     const float *grad;          /* same shape or NULL */
     float *exp_avg, *exp_avg_sq;/* Adam state, same shape (required when grad != NULL) */
     const uint8_t *pin_mask;    /* [rows] or NULL */

@@ -91,7 +91,8 @@ int adam_launch(const T4DAdamTensor *tensors, int32_t n_tensors, float beta1, fl
     long long blocks = 0;
     for (int k = 0; k < n_tensors; k++) {
         const T4DAdamTensor &t = tensors[k];
-        if (!t.param || t.rows < 0 || t.width < 1 || (t.grad && (!t.exp_avg || !t.exp_avg_sq)) || ((t.pin_mask == nullptr) != (t.pin_values == nullptr)))
+        // (a tensor without rows is a no-op and has no storage: torch hands out a NULL data pointer for it)
+        if ((!t.param && t.rows > 0) || t.rows < 0 || t.width < 1 || (t.grad && (!t.exp_avg || !t.exp_avg_sq)) || ((t.pin_mask == nullptr) != (t.pin_values == nullptr)))
             return t4d_fail(T4D_ERR_ARG, "t4d_adam_pin_step: inconsistent tensor descriptor");
         if (!step_dev && t.grad && t.step < 1) return t4d_fail(T4D_ERR_ARG, "t4d_adam_pin_step: step must be >= 1");
         A.t[k] = t;

@@ -17,6 +17,18 @@ from . import _lib
 from ._lib import ptr
 
 
+def _rows_width(p: torch.Tensor):
+    """(rows, width) of a parameter as the fused step sees it: [rows, width] with one pin per row; a 0-dim tensor is one row of
+    one.  The width comes from the shape, not from numel() // rows: an empty (0, 3) tensor has width 3 and no rows, which the step
+    takes as a no-op like torch.optim.Adam does (a width of 0 is refused by the library)."""
+    if p.dim() == 0:
+        return 1, 1
+    width = 1
+    for s in p.shape[1:]:
+        width *= s
+    return (p.shape[0] if p.numel() > 0 else 0), max(width, 1)
+
+
 class FusedAdamPins:
     def __init__(self, param_groups: List[dict], lr: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-15,
                  capturable: bool = False):
@@ -37,7 +49,8 @@ class FusedAdamPins:
         # recorded in a HIP graph and replayed (loop.GraphedViews); call sync_hyper() after changing a group's 'lr'
         self.capturable = capturable
         # names of the tensors whose gradient buffer step() leaves ZEROED (T4D_ADAM_CLEAR_GRAD): persistent buffers that an
-        # iteration fills only in part (loop.GraphedViews: the per-camera rows of cam_m / cam_c)
+        # iteration fills only in part (loop.GraphedViews: the per-camera rows of cam_m / cam_c).  The kernel zeroes the buffer it
+        # reads, so such a gradient must be contiguous: step() raises ValueError for a non-contiguous one instead of zeroing a copy
         self.clear_grad: set = set()
         self._step_dev: Optional[torch.Tensor] = None
         self._layout = None                 # (first counter of every tensor, their number) the counter array was built for
@@ -167,9 +180,9 @@ class FusedAdamPins:
                 raise RuntimeError("topo4d_amd has no CPU path: parameters must live on a HIP device")
             if not p.is_contiguous() or p.dtype != torch.float32:
                 raise ValueError("parameters must be contiguous float32")
-            rows = p.shape[0] if p.dim() > 0 else 1
+            rows, width = _rows_width(p)
             mask, vals = self._pins[g["name"]]
-            arr[k] = _lib.T4DAdamTensor(ptr(p), None, None, None, ptr(mask), ptr(vals), rows, p.numel() // max(rows, 1), 0.0, 0, 0)
+            arr[k] = _lib.T4DAdamTensor(ptr(p), None, None, None, ptr(mask), ptr(vals), rows, width, 0.0, 0, 0)
         dev = todo[0]["params"][0].device
         _lib.call("t4d_adam_pin_step", arr, len(todo), float(self.betas[0]), float(self.betas[1]), float(self.eps), _lib.stream(dev))
 
@@ -191,10 +204,12 @@ class FusedAdamPins:
             if not p.is_contiguous() or p.dtype != torch.float32:
                 raise ValueError("parameters must be contiguous float32")
             dev = p.device
-            rows = p.shape[0] if p.dim() > 0 else 1
-            width = p.numel() // max(rows, 1)
+            rows, width = _rows_width(p)
             grad = None
             if p.grad is not None:
+                if g["name"] in self.clear_grad and not p.grad.is_contiguous():
+                    # the kernel would zero the contiguous COPY below and p.grad would keep its values
+                    raise ValueError(f"clear_grad: the gradient of {g['name']} must be contiguous (it is zeroed in place)")
                 grad = p.grad.contiguous()
                 st = self.state.setdefault(p, {})
                 if "exp_avg" not in st:
