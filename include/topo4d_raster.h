@@ -726,6 +726,41 @@ size_t t4d_jpeg_scratch_bytes(const T4DJpegImage *images, int32_t n, int32_t chu
 int t4d_jpeg_decode(const T4DJpegImage *images, const T4DJpegImage *d_images, int32_t n, const uint8_t *data, int32_t chunk_bits,
                     uint8_t *out, size_t out_capacity, int32_t *status, void *scratch, size_t scratch_bytes, void *hip_stream);
 
+/* ---- PNG decode (csrc/t4d_pngdec.hip, csrc/t4d_inflate.h; topo4d_amd/png.py) ----
+ * T4DPngImage: one non-interlaced PNG of colour type 0 (grey, 8 or 16 bits), 2 (RGB), 4 (grey + alpha) or 6 (RGBA) at 8 bits, as
+ * the host parsed its chunks: channels 1..4, bytes_per_sample 1, or 2 with channels 1.  Its IDAT payloads are the n_chunks rows
+ * from first_chunk of the batch's chunk table d_chunks, int64 [n_chunks_total, 2] = (offset into data, bytes), in file order; the
+ * images of a batch hold consecutive ranges of the table in image order.  A payload of 0 bytes is legal.  Joined, the payloads are
+ * one zlib stream that inflates to height rows of row = 1 + width*channels*bytes_per_sample bytes: a filter byte 0..4, then the
+ * filtered row.  The image is written at out + out_offset as uint8 [height, width, channels], or for 16-bit grey as uint16
+ * [height, width] in little-endian order (out_offset even), equal to np.array(PIL.Image.open(file)).
+ *
+ * Two schedules decode a stream.  Chunk-parallel (path 1): one wave per payload decodes it as if it began at a block boundary with
+ * no history; the image takes this path when the zlib header and the Adler-32 trailer lie in payloads of their own and every other
+ * payload verifies - whole blocks, all bytes consumed, a byte-aligned end after a block end, no distance before its own first byte,
+ * at most 65536 bytes made, BFINAL exactly in the last - and the sizes sum to height*row; then the parse is the stream's own.
+ * Serial (path 2): any other image, the whole stream by one wave.  path[i] (device) receives 1 or 2.
+ * status[i] (device) receives 0 or an OR of the T4D_PNG_ERR_* bits.  No read is made outside the payloads and no write outside
+ * the image's height*row bytes of scratch and its bytes of out, whatever the payloads hold; an image with a non-zero status has
+ * unspecified pixels.  images is the host copy of d_images; d_chunks, data, out, status, path and scratch are device memory. */
+#define T4D_PNG_ERR_END 1      /* the stream ended early, or made more than height*row bytes */
+#define T4D_PNG_ERR_BLOCK 2    /* a bad zlib header, block type 3, or a stored block with LEN != ~NLEN */
+#define T4D_PNG_ERR_TABLE 4    /* a code table zlib refuses: too many codes, over-subscribed, incomplete, no end-of-block, bad repeat */
+#define T4D_PNG_ERR_CODE 8     /* an invalid code, or a distance that reaches before the start of the output */
+#define T4D_PNG_ERR_LENGTH 16  /* the stream ended with fewer than height*row bytes */
+#define T4D_PNG_ERR_FILTER 32  /* a filter byte above 4 */
+#define T4D_PNG_ERR_ADLER 64   /* the Adler-32 of the inflated bytes is not the stream's trailer */
+typedef struct T4DPngImage {
+    int32_t width, height;
+    int32_t channels, bytes_per_sample;
+    int32_t first_chunk, n_chunks;
+    int64_t out_offset;
+} T4DPngImage;
+size_t t4d_pngdec_scratch_bytes(const T4DPngImage *images, int32_t n, int32_t n_chunks);
+int t4d_png_decode(const T4DPngImage *images, const T4DPngImage *d_images, int32_t n, const int64_t *d_chunks, int32_t n_chunks,
+                   const uint8_t *data, uint8_t *out, size_t out_capacity, int32_t *status, int32_t *path, void *scratch,
+                   size_t scratch_bytes, void *hip_stream);
+
 /* T4DWarpView: skimage.transform.warp(image, matrix, order=1, mode="constant", cval, clip=True) of one uint8 HWC image read as
  * image / 255.0 in float64, rounded to float32 and written as [channels, out_rows, out_cols] to dst.  src: rows x cols x
  * channels samples, src_pitch bytes per row (a crop of a wider image: src_pitch > cols * channels).  matrix: the first two rows

@@ -109,6 +109,11 @@ class T4DJpegImage(C.Structure):
         ("huff_vals", (C.c_uint8 * 256) * 8)]
 
 
+class T4DPngImage(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "channels", "bytes_per_sample", "first_chunk", "n_chunks")] + [
+        ("out_offset", C.c_int64)]
+
+
 class T4DWarpView(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)] + [(n, C.c_int32) for n in (
         "rows", "cols", "channels", "src_pitch", "out_rows", "out_cols")] + [("matrix", C.c_double * 6), ("cval", C.c_double)]
@@ -205,6 +210,8 @@ SIGNATURES = {
     "t4d_obj_face_lines": (_INT, [_VP] * 3 + [_I64, _I64, _VP, _SZ, _VP, _VP, _SZ, _VP]),
     "t4d_jpeg_scratch_bytes": (_SZ, [C.POINTER(T4DJpegImage), _I32, _I32]),
     "t4d_jpeg_decode": (_INT, [C.POINTER(T4DJpegImage), _VP, _I32, _VP, _I32, _VP, _SZ, _VP, _VP, _SZ, _VP]),
+    "t4d_pngdec_scratch_bytes": (_SZ, [C.POINTER(T4DPngImage), _I32, _I32]),
+    "t4d_png_decode": (_INT, [C.POINTER(T4DPngImage), _VP, _I32, _VP, _I32, _VP, _VP, _SZ, _VP, _VP, _VP, _SZ, _VP]),
     "t4d_warp_scratch_bytes": (_SZ, [_I32]),
     "t4d_warp_views": (_INT, [C.POINTER(T4DWarpView), _VP, _I32, _VP, _SZ, _VP]),
     "t4d_undistort_views": (_INT, [C.POINTER(T4DLensView), _VP, _I32, _VP]),

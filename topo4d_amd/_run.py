@@ -2,7 +2,8 @@
 What the command-line tools over a finished run <output_dir>/<exp>/<seq>/%06d/ share (texfinish, dispmap, tessellate, drift, seqtex,
 projtex, evaluate): the flags they take from topo4d_amd.train, which frames the run holds, which files a frame directory holds and
 how they are read, the one-ahead read of the next frame's files, and which cameras --views selects.  Host only: everything here
-returns paths, lists and numpy arrays, and the tool moves them to its device.  Nothing device-side is imported at module level.
+returns paths, lists and numpy arrays, and the tool moves them to its device - but for read_texture and read_validity given a
+device, which decode the PNG there (png.decode_png) and return tensors.  Nothing device-side is imported at module level.
 """
 from __future__ import annotations
 
@@ -50,14 +51,30 @@ def size_list(s: str) -> List[int]:
     return out
 
 
-def add_run_flags(p: argparse.ArgumentParser, *dests: str, frames_help: str) -> None:
+def add_run_flags(p: argparse.ArgumentParser, *dests: str, frames_help: str, png_decoder: bool = False) -> None:
     """The flags of topo4d_amd.train with these dests (-e/-s/-od, -id/-did/-dr/-tr), exactly as train has them and in its order,
-    then --frames."""
+    then --frames; png_decoder: and --png_decoder, for the tools that read textures with read_texture / read_validity."""
     from .train import build_parser as train_parser
     for a in train_parser()._actions:
         if a.dest in dests:
             p.add_argument(*a.option_strings, type=a.type, default=a.default, help=a.help)
     p.add_argument("--frames", type=frame_list, default=None, help=frames_help)
+    if png_decoder:
+        p.add_argument("--png_decoder", choices=PNG_DECODERS, default=PNG_DECODERS[0],
+                       help="Where the frames' textures and weight images are decoded: gpu (default; png.decode_png, PIL for the kinds "
+                            "it does not take) or pil (on the host).  The outputs are the same bytes either way.")
+
+
+PNG_DECODERS = ("gpu", "pil")
+
+
+def reader_device(args, dev):
+    """the `device` the readers below take for a tool running on `dev`: dev under --png_decoder gpu (also the default of a
+    namespace without the flag), None - numpy, PIL - under pil"""
+    choice = getattr(args, "png_decoder", PNG_DECODERS[0])
+    if choice not in PNG_DECODERS:
+        raise SystemExit(f"--png_decoder must be one of {', '.join(PNG_DECODERS)}, got {choice!r}")
+    return dev if choice == "gpu" else None
 
 
 def print_written(paths) -> None:
@@ -94,16 +111,49 @@ def frame_files(run_dir: str, t: int, *names: str) -> Optional[List[str]]:
 
 
 # ---- readers -----------------------------------------------------------------------------------------------------------------
-def read_texture(path: str) -> np.ndarray:
-    """uint8 [h,w,3]"""
+def _decoded_on_device(path: str, device):
+    """The file as png.decode_png gives it on `device` (uint8 [h,w] or [h,w,c]), or None for a file the GPU decoder does not
+    take, that is not a PNG, or that holds 16-bit samples: those stay with PIL."""
+    from . import png
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != png.SIGNATURE:
+        return None
+    header = png.parse_png(data)
+    if not header.gpu or header.bytes_per_sample != 1:
+        return None
+    return png.decode_png([data], device=device, headers=[header])[0]
+
+
+def read_texture(path: str, device=None):
+    """uint8 [h,w,3]: numpy, read by PIL; with a device, the same values as a tensor there, decoded on it (png.decode_png) and
+    brought to three channels as PIL's convert("RGB") does it - grey replicated, alpha dropped."""
     from PIL import Image
+    if device is not None:
+        import torch
+        t = _decoded_on_device(path, device)
+        if t is None:
+            return torch.from_numpy(read_texture(path)).to(device)
+        if t.dim() == 2 or t.shape[2] == 2:
+            grey = t if t.dim() == 2 else t[..., 0]
+            return grey.unsqueeze(-1).expand(-1, -1, 3).contiguous()
+        return t[..., :3].contiguous()
     return np.ascontiguousarray(np.array(Image.open(path).convert("RGB")))
 
 
-def read_validity(path: str, shape: Sequence[int], of: str) -> np.ndarray:
+def read_validity(path: str, shape: Sequence[int], of: str, device=None):
     """uint8 [h,w] from a weight image of any mode: 1 where any channel is above 0.  shape: the (h, w) it must have, those of the
-    texture `of`."""
+    texture `of`.  Numpy, read by PIL; with a device, the same values as a tensor there, decoded on it."""
     from PIL import Image
+    if device is not None:
+        import torch
+        t = _decoded_on_device(path, device)
+        if t is None:
+            return torch.from_numpy(read_validity(path, shape, of)).to(device)
+        got = tuple(int(x) for x in t.shape[:2])
+        if got != tuple(shape):
+            raise SystemExit(f"{path}: {got} does not match {of}'s {tuple(shape)}")
+        return (t.reshape(got[0], got[1], -1) != 0).any(-1).to(torch.uint8)
     weight = np.array(Image.open(path))
     if weight.shape[:2] != tuple(shape):
         raise SystemExit(f"{path}: {weight.shape[:2]} does not match {of}'s {tuple(shape)}")
@@ -123,11 +173,12 @@ def read_frame_obj(frame_dir: str):
     return meshrender.read_face_obj(path) if os.path.exists(path) else None
 
 
-def read_textured_frame(frame_dir: str, texture: str) -> Tuple[object, Optional[np.ndarray]]:
-    """(FaceObj or None, uint8 [h,w,3] texture or None) of one frame directory; without face.obj the texture is not read."""
+def read_textured_frame(frame_dir: str, texture: str, device=None) -> Tuple[object, Optional[np.ndarray]]:
+    """(FaceObj or None, uint8 [h,w,3] texture or None) of one frame directory; without face.obj the texture is not read.  device:
+    as read_texture takes it."""
     obj = read_frame_obj(frame_dir)
     path = os.path.join(frame_dir, texture)
-    return obj, read_texture(path) if obj is not None and os.path.exists(path) else None
+    return obj, read_texture(path, device) if obj is not None and os.path.exists(path) else None
 
 
 # ---- one frame ahead ---------------------------------------------------------------------------------------------------------

@@ -456,7 +456,8 @@ def options_of(args, prefix: str = "") -> dict:
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m topo4d_amd.drift",
                                 description="Measure tracking drift between the frames of a run by matching their UV textures.")
-    _run.add_run_flags(p, "exp", "seq", "output_dir", frames_help="Frames to measure: '1-10', '1,5,9' (default: every frame directory).")
+    _run.add_run_flags(p, "exp", "seq", "output_dir", frames_help="Frames to measure: '1-10', '1,5,9' (default: every frame directory).",
+                       png_decoder=True)
     add_options(p)
     p.add_argument("--save_fields", action="store_true", help=f"Also write %%06d/{FIELDS_NAME} (table, d, kept, drift).")
     p.add_argument("--stabilise", action="store_true",
@@ -497,18 +498,21 @@ def _stabilise_frame(args, o: dict, frame_dir: str, ref, cur, r: dict, options: 
     return entry, {"flow": flow_, "support": support}
 
 
-def read_frame(frame_dir: str, texture: str, dev):
+def read_frame(frame_dir: str, texture: str, dev, decode_on=None):
     """(FaceObj, texture uint8 [h,w,3], valid uint8 [h,w], "weight" | "obj") of one frame directory, the arrays on the device;
-    None without its files.  valid: where the directory's weight image is above 0, else the coverage of its face.obj."""
+    None without its files.  valid: where the directory's weight image is above 0, else the coverage of its face.obj.
+    decode_on: the device that decodes the PNGs (_run.reader_device), None: PIL on the host."""
     from . import texfinish
-    obj, tex = _run.read_textured_frame(frame_dir, texture)
+    obj, tex = _run.read_textured_frame(frame_dir, texture, decode_on)
     if obj is None or tex is None:
         return None
+    h, w = int(tex.shape[0]), int(tex.shape[1])
+    on_dev = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(a).to(dev)
     weight_path = os.path.join(frame_dir, WEIGHT_FILE)
     if os.path.exists(weight_path):
-        valid = _run.read_validity(weight_path, tex.shape[:2], texture)
-        return obj, torch.from_numpy(tex).to(dev), torch.from_numpy(valid).to(dev), "weight"
-    return obj, torch.from_numpy(tex).to(dev), texfinish.coverage_from_obj(obj, tex.shape[0], tex.shape[1], device=dev), "obj"
+        valid = _run.read_validity(weight_path, (h, w), texture, decode_on)
+        return obj, on_dev(tex), on_dev(valid), "weight"
+    return obj, on_dev(tex), texfinish.coverage_from_obj(obj, h, w, device=dev), "obj"
 
 
 def tree_options(args, options: dict = None) -> Tuple[dict, Tuple[int, int, int, int]]:
@@ -547,7 +551,7 @@ def drift_tree(args, device=None, options: dict = None) -> dict:
     with torch.cuda.device(dev):
         for t in _run.frames_of(args, run_dir):
             key = _run.frame_key(t)
-            cur = read_frame(os.path.join(run_dir, key), o["texture"], dev)
+            cur = read_frame(os.path.join(run_dir, key), o["texture"], dev, _run.reader_device(args, dev))
             if cur is None:
                 continue
             if ref is not None:
@@ -590,6 +594,9 @@ def main(argv=None) -> None:
     with open(os.path.join(args.output_dir, args.exp, args.seq, "drift.json"), "w") as f:
         json.dump(out, f, indent=1)
     print("drift", json.dumps(out["summary"]))
+    if args.png_decoder == "gpu":
+        from . import png
+        print("drift", png.schedule_report())
 
 
 if __name__ == "__main__":

@@ -14,12 +14,14 @@ csrc/t4d_undistort.hip, csrc/t4d_lens.h).
                                           Metashape's frame-camera model, the turn and an s x s box filter in one resampling
     get_dataset(data_dir, seq, frame, cameras, use_mask=False, blacklist=[], *, rotate_mask, setup_camera)
     FramePrefetcher                       reads frame t+1's files in a background pool while frame t trains
+    load_images, get_dataset and FramePrefetcher take png_decoder="pil" | "gpu" (default "pil"): with "gpu" the masks and PNG views
+    that png.parse_png takes are decoded on the device by png.decode_png, one batch per frame
     load_images, get_dataset and FramePrefetcher take lenses= ({file name: cameras.Lens}), supersample= and mask_dir=; with
     their defaults (None, 1, None) nothing changes, and a view whose lens has no distortion still takes t4d_warp_views
 
 The GPU decoder takes baseline (SOF0/SOF1) 8-bit Huffman JPEGs with 3 YCbCr components, luma sampling 1x1, 2x1 or 2x2 and 1x1
 chroma, in one interleaved scan, with or without restart intervals.  Every other file (progressive, arithmetic-coded, 12-bit,
-grayscale, CMYK, other samplings, PNG) is decoded by PIL on the host and goes through the same upload and warp.  Malformed
+grayscale, CMYK, other samplings, PNG unless png_decoder="gpu") is decoded by PIL on the host and goes through the same upload and warp.  Malformed
 headers raise ValueError; an entropy-coded segment the decoder rejects (truncated, over-long, bad codes, bad restart markers)
 raises ValueError too.  The warp reproduces skimage 0.19-0.22's order-1 `warp` (mode constant, cval 0, clip) bit for bit.
 """
@@ -40,6 +42,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import png as _png
 from ._lib import ptr
 
 # jpeg_natural_order: zig-zag index -> natural index
@@ -513,21 +516,23 @@ def _resample_all(images, angles, crops, out, lenses, supersample, nearest):
 
 
 def load_images(paths: Sequence[str], angles: Sequence[float], crop=None, out=None, device=None, chunk_bits=None, *,
-                lenses=None, supersample=1, mask_dir=None):
+                lenses=None, supersample=1, mask_dir=None, png_decoder="pil"):
     """torch.tensor(rotate(np.array(Image.open(p))[:h, :w] / 255.0, angle, resize=True)).float().permute(2, 0, 1) for each path,
     as contiguous float32 device tensors.  crop: per path (h, w) or None (or None for all); out: per path a float32 tensor to
     write into (e.g. the buffers a GraphedViews reads), or None.
     lenses: cameras.Lens per path (a sequence, or a dict keyed by file name as cameras.get_lenses returns) - the photographs are
     undistorted and turned in one resampling; supersample s: every output pixel is the mean of s x s samples and the output is
-    the turned shape floor-divided by s.  mask_dir is accepted for symmetry with get_dataset (no masks are read here)."""
+    the turned shape floor-divided by s.  mask_dir is accepted for symmetry with get_dataset (no masks are read here).
+    png_decoder: "pil", or "gpu" - the PNG files png.parse_png takes are decoded on the device, in one batch."""
+    _check_png_decoder(png_decoder)
     n = len(paths)
     crops = [None] * n if crop is None else list(crop)
     files, imgs = [], [None] * n
     for i, p in enumerate(paths):
         with open(p, "rb") as f:
             files.append(f.read())
-    decoded = decode_jpeg(files, chunk_bits=chunk_bits, device=device,
-                          headers=[_header_or_none(b) for b in files], host_images=imgs)
+    decoded = _decode_files(files, [_header_or_none(b, png_decoder) for b in files], imgs, _lib.hip_device(device, "ingest"),
+                            chunk_bits)
     if lenses is None and supersample == 1:
         return _rotate_all(decoded, angles, crops, out)
     if isinstance(lenses, dict):
@@ -542,11 +547,37 @@ def _lens_of(lenses: dict, name: str):
     return lenses[name]
 
 
-def _header_or_none(data: bytes):
-    """parse_jpeg for a JPEG (a non-JPEG file: None, so that PIL decodes it)."""
+def _header_or_none(data: bytes, png_decoder: str = "pil"):
+    """parse_jpeg for a JPEG; with png_decoder "gpu", png.parse_png for a PNG; any other file: a header no GPU decoder takes, so
+    that PIL decodes it."""
     if data[:2] != b"\xff\xd8":
+        if png_decoder == "gpu" and data[:8] == _png.SIGNATURE:
+            return _png.parse_png(data)
         return _NotJpeg
     return parse_jpeg(data)
+
+
+def _check_png_decoder(png_decoder: str) -> None:
+    if png_decoder not in ("pil", "gpu"):
+        raise ValueError(f"png_decoder must be 'pil' or 'gpu', got {png_decoder!r}")
+
+
+def _decode_files(files, headers, host_images, dev, chunk_bits=None) -> List[torch.Tensor]:
+    """decode_jpeg for the files whose header is a JpegHeader (or no GPU decoder's), and png.decode_png, in one batch, for those
+    whose header is a PngHeader the GPU decoder takes; in the order given."""
+    is_png = [isinstance(h, _png.PngHeader) and h.gpu and img is None for h, img in zip(headers, host_images)]
+    if not any(is_png):
+        return decode_jpeg(files, chunk_bits=chunk_bits, device=dev, headers=headers, host_images=host_images)
+    out: List[Optional[torch.Tensor]] = [None] * len(files)
+    pick = lambda seq, idx: [seq[i] for i in idx]
+    rest, pngs = [i for i, p in enumerate(is_png) if not p], [i for i, p in enumerate(is_png) if p]
+    if rest:
+        for i, t in zip(rest, decode_jpeg(pick(files, rest), chunk_bits=chunk_bits, device=dev, headers=pick(headers, rest),
+                                          host_images=pick(host_images, rest))):
+            out[i] = t
+    for i, t in zip(pngs, _png.decode_png(pick(files, pngs), device=dev, headers=pick(headers, pngs))):
+        out[i] = t
+    return out
 
 
 class _NotJpegHeader:
@@ -582,33 +613,46 @@ class _HostView:
     data: bytes
     header: object
     image: Optional[np.ndarray]                     # PIL's array when the GPU decoder does not take the file
-    mask: Optional[np.ndarray]
+    mask: Optional[np.ndarray]                      # PIL's array of the mask, unless the GPU decoder takes it:
+    mask_data: Optional[bytes] = None               # then the mask file's bytes
+    mask_header: object = None                      # and its png.PngHeader
 
 
-def _read_view(path: str, mask_path: Optional[str]) -> _HostView:
+def _read_view(path: str, mask_path: Optional[str], png_decoder: str = "pil") -> _HostView:
     with open(path, "rb") as f:
         data = f.read()
-    header = _header_or_none(data)
+    header = _header_or_none(data, png_decoder)
     image = None if header.gpu else _pil_array(data)
-    mask = None
+    mask = mask_data = mask_header = None
     if mask_path is not None:
-        from PIL import Image
-        mask = np.array(Image.open(mask_path))
-    return _HostView(path, data, header, image, mask)
+        if png_decoder == "gpu":
+            with open(mask_path, "rb") as f:
+                mask_data = f.read()
+            mask_header = _header_or_none(mask_data, png_decoder)
+            if not (isinstance(mask_header, _png.PngHeader) and mask_header.gpu):
+                mask, mask_data, mask_header = _pil_array(mask_data), None, None
+        else:
+            from PIL import Image
+            mask = np.array(Image.open(mask_path))
+    return _HostView(path, data, header, image, mask, mask_data, mask_header)
 
 
 def _assemble(views: List[_HostView], cameras, use_mask, rotate_mask, setup_camera, device, chunk_bits=None, lenses=None,
               supersample=1):
     """The device half of get_dataset: decode, warp, cameras; launches on the caller's thread and stream."""
     dev = _lib.hip_device(device, "ingest")
-    decoded = decode_jpeg([v.data for v in views], chunk_bits=chunk_bits, device=dev, headers=[v.header for v in views],
-                          host_images=[v.image for v in views])
+    gpu_masks = [v for v in views if use_mask and v.mask_data is not None]          # png_decoder "gpu": one batch with the views
+    both = _decode_files([v.data for v in views] + [v.mask_data for v in gpu_masks],
+                         [v.header for v in views] + [v.mask_header for v in gpu_masks],
+                         [v.image for v in views] + [None] * len(gpu_masks), dev, chunk_bits)
+    decoded = both[:len(views)]
+    mask_of = {id(v): t for v, t in zip(gpu_masks, both[len(views):])}
     names = [os.path.basename(v.path) for v in views]
     angles = [rotate_mask[nm.split(".")[0]] * 90 for nm in names]
     srcs, angs, crops = list(decoded), list(angles), [None] * len(views)
     if use_mask:
         for v, img, a in zip(views, decoded, angles):
-            srcs.append(torch.from_numpy(np.ascontiguousarray(v.mask)).to(dev))
+            srcs.append(mask_of[id(v)] if id(v) in mask_of else torch.from_numpy(np.ascontiguousarray(v.mask)).to(dev))
             angs.append(a)
             crops.append((int(img.shape[0]) // int(supersample), int(img.shape[1]) // int(supersample)))
     if lenses is None and supersample == 1:
@@ -646,7 +690,7 @@ def _view_lenses(names, decoded, srcs, lenses, s):
 
 
 def get_dataset(data_dir, seq, frame, cameras, use_mask=False, blacklist=[], *, rotate_mask: Dict[str, int],
-                setup_camera: Callable, device=None, chunk_bits=None, lenses=None, supersample=1, mask_dir=None):
+                setup_camera: Callable, device=None, chunk_bits=None, lenses=None, supersample=1, mask_dir=None, png_decoder="pil"):
     """The reference's get_dataset (train.py:73-103) with the decode and the rotation on the GPU.  rotate_mask and setup_camera
     are the dict and the function train.py takes from its own module and from helpers; setup_camera is called as train.py:98
     calls it.  'im' and 'mask' hold the values of the reference's tensors, contiguous [C,H,W] instead of permuted views.
@@ -655,8 +699,11 @@ def get_dataset(data_dir, seq, frame, cameras, use_mask=False, blacklist=[], *, 
     are s times the size `cameras` describes and every target pixel is the mean of s x s samples (masks stay at the target's
     size).  A mask is taken to be at the target's resolution, the photograph's divided by `supersample`, and its lens is
     scaled by that factor; a mask tree at any other resolution than that is refused (ValueError), not rescaled.  mask_dir: the
-    root of <seq>/mask/ (default data_dir).  With the defaults nothing of this runs."""
-    views = [_read_view(p, m) for p, m in frame_files(data_dir, seq, frame, use_mask, blacklist, mask_dir)]
+    root of <seq>/mask/ (default data_dir).  png_decoder: "pil", or "gpu" - the masks and the *.png views that png.parse_png
+    takes are decoded on the device, in one batch per frame (png.decode_png); the others still come from PIL.  With the defaults
+    nothing of this runs."""
+    _check_png_decoder(png_decoder)
+    views = [_read_view(p, m, png_decoder) for p, m in frame_files(data_dir, seq, frame, use_mask, blacklist, mask_dir)]
     if not views:
         return []                                   # a frame past the end of the sequence (train.py:654 stops there)
     return _assemble(views, cameras, use_mask, rotate_mask, setup_camera, device, chunk_bits, lenses, supersample)
@@ -682,7 +729,9 @@ class FramePrefetcher:
     """
 
     def __init__(self, data_dir, seq, cameras, use_mask=False, blacklist=(), *, rotate_mask, setup_camera, device=None,
-                 workers: Optional[int] = None, lenses=None, supersample=1, mask_dir=None):
+                 workers: Optional[int] = None, lenses=None, supersample=1, mask_dir=None, png_decoder="pil"):
+        _check_png_decoder(png_decoder)
+        self.png_decoder = png_decoder               # "gpu": the pool only reads and parses the PNGs the GPU decoder takes
         self.data_dir, self.seq, self.cameras = data_dir, seq, cameras
         self.lenses, self.supersample, self.mask_dir = lenses, supersample, mask_dir
         self.use_mask, self.blacklist = use_mask, tuple(blacklist)
@@ -693,7 +742,7 @@ class FramePrefetcher:
     def prefetch(self, frame: int) -> None:
         if frame not in self.pending:
             files = frame_files(self.data_dir, self.seq, frame, self.use_mask, self.blacklist, self.mask_dir)
-            self.pending[frame] = [self.pool.submit(_read_view, p, m) for p, m in files]
+            self.pending[frame] = [self.pool.submit(_read_view, p, m, self.png_decoder) for p, m in files]
 
     def get(self, frame: int):
         self.prefetch(frame)

@@ -170,7 +170,8 @@ def _quantile(spec: str) -> Tuple[int, int]:
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m topo4d_amd.seqtex",
                                 description="Fuse the stabilised textures of a run over time: per-texel quantiles, and every frame completed from them.")
-    _run.add_run_flags(p, "exp", "seq", "output_dir", frames_help="Frames to fuse: '1-10', '1,5,9' (default: every frame there is).")
+    _run.add_run_flags(p, "exp", "seq", "output_dir", frames_help="Frames to fuse: '1-10', '1,5,9' (default: every frame there is).",
+                       png_decoder=True)
     p.add_argument("--texture", default=DEFAULTS["texture"], metavar="NAME", help="The projected texture of every frame directory (default face_proj.png).")
     p.add_argument("--source", choices=("stab", "raw"), default=DEFAULTS["source"],
                    help="stab: the files `drift --stabilise` wrote, by the run's drift.json (default); raw: the frames' own textures.")
@@ -242,12 +243,13 @@ def _plan(args, o: dict, run_dir: str) -> Tuple[str, List[Tuple[str, str, str]]]
     return refs[0], [(refs[0], o["texture"], None)] + [(k, name, weight_name) for k in keys]
 
 
-def _read(run_dir: str, entry: Tuple[str, str, str], dev):
-    """(texture uint8 [h,w,3], valid uint8 [h,w]) on the device for one entry of _plan"""
+def _read(run_dir: str, entry: Tuple[str, str, str], dev, decode_on=None):
+    """(texture uint8 [h,w,3], valid uint8 [h,w]) on the device for one entry of _plan; decode_on: the device that decodes the
+    PNGs (_run.reader_device), None: PIL on the host"""
     from . import drift
     key, name, weight_name = entry
     if weight_name is None:
-        cur = drift.read_frame(os.path.join(run_dir, key), name, dev)
+        cur = drift.read_frame(os.path.join(run_dir, key), name, dev, decode_on)
         if cur is None:
             raise SystemExit(f"seqtex: {os.path.join(run_dir, key)} lacks face.obj or {name}")
         return cur[1], cur[2]
@@ -255,8 +257,10 @@ def _read(run_dir: str, entry: Tuple[str, str, str], dev):
     for p in paths:
         if not os.path.exists(p):
             raise SystemExit(f"seqtex: {p} not found: run `python -m topo4d_amd.drift --stabilise` on this tree again")
-    tex = _run.read_texture(paths[0])
-    valid = _run.read_validity(paths[1], tex.shape[:2], name)
+    tex = _run.read_texture(paths[0], decode_on)
+    valid = _run.read_validity(paths[1], (int(tex.shape[0]), int(tex.shape[1])), name, decode_on)
+    if decode_on is not None:
+        return tex, valid
     return torch.from_numpy(tex).to(dev), torch.from_numpy(valid).to(dev)
 
 
@@ -270,9 +274,10 @@ def seqtex_tree(args, device=None) -> dict:
     by_key = {e[0]: e for e in entries}
     fused = pick_frames(list(by_key), o["max_frames"])
     dev = torch.device(device if device is not None else "cuda")
+    decode_on = _run.reader_device(args, dev)
     out = {"options": o, "reference": ref_key, "frames": fused, "selected": len(entries)}
     with torch.cuda.device(dev):
-        loaded = {k: _read(run_dir, by_key[k], dev) for k in fused}
+        loaded = {k: _read(run_dir, by_key[k], dev, decode_on) for k in fused}
         shape = tuple(loaded[fused[0]][0].shape)
         for k in fused:
             if tuple(loaded[k][0].shape) != shape:
@@ -286,7 +291,7 @@ def seqtex_tree(args, device=None) -> dict:
         obj = meshrender.read_face_obj(os.path.join(run_dir, ref_key, "face.obj"))
         labelled = projtex.island_labels(obj, shape[0], shape[1], device=dev) != 0
         total = int(labelled.sum())
-        ref_valid = loaded[ref_key][1] if ref_key in loaded else _read(run_dir, by_key[ref_key], dev)[1]
+        ref_valid = loaded[ref_key][1] if ref_key in loaded else _read(run_dir, by_key[ref_key], dev, decode_on)[1]
         covered = int((labelled & (count >= o["min_count"])).sum())
         ref_covered = int((labelled & (ref_valid != 0)).sum()) if o["min_count"] <= 1 else 0
         out["covered_fraction"] = covered / total if total else 0.0
@@ -298,7 +303,7 @@ def seqtex_tree(args, device=None) -> dict:
             out["completed"] = {}
             for entry in entries:
                 key, name = entry[0], entry[1]
-                image, valid = loaded[key] if key in loaded else _read(run_dir, entry, dev)
+                image, valid = loaded[key] if key in loaded else _read(run_dir, entry, dev, decode_on)
                 if tuple(image.shape) != shape:
                     raise SystemExit(f"{key}/{name}: {tuple(image.shape)} does not match frame {fused[0]}'s {shape}")
                 full, source = complete(image, valid, base, count, o["min_count"], o["min_votes"], o["tol"])
@@ -315,6 +320,9 @@ def main(argv=None) -> None:
     with open(os.path.join(args.output_dir, args.exp, args.seq, "seqtex.json"), "w") as f:
         json.dump(out, f, indent=1)
     print("seqtex", json.dumps({k: out[k] for k in ("reference", "selected", "covered_fraction", "reference_covered_fraction", "mean_spread")}))
+    if args.png_decoder == "gpu":
+        from . import png
+        print("seqtex", png.schedule_report())
 
 
 if __name__ == "__main__":

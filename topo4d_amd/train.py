@@ -344,16 +344,18 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
         pins = RegionPins(params, variables["facial_regions"])                                             # :619-629
         inner_mouth = C.parsing_colormap_bgr(14)[[C.CMAP_INDEX["inner_mouth"]]]                           # :633, helpers.py:806
         cam_fn = functools.partial(C.setup_camera, device=dev)
+        png_decoder = "gpu" if getattr(args, "gpu_png", False) else "pil"
         if low_from_full:                  # the geometry targets are down_ratio x down_ratio means of the full-size photographs
             pf = ingest.FramePrefetcher(args.dense_input_dir, args.seq, cameras, use_mask=USE_MASK, blacklist=C.BLACKLIST,
                                         rotate_mask=C.ROTATE_MASK, setup_camera=cam_fn, device=dev, lenses=lenses_dense,
-                                        supersample=args.down_ratio, mask_dir=args.input_dir)
+                                        supersample=args.down_ratio, mask_dir=args.input_dir, png_decoder=png_decoder)
         else:
             pf = ingest.FramePrefetcher(args.input_dir, args.seq, cameras, use_mask=USE_MASK, blacklist=C.BLACKLIST,
-                                        rotate_mask=C.ROTATE_MASK, setup_camera=cam_fn, device=dev, lenses=lenses)
+                                        rotate_mask=C.ROTATE_MASK, setup_camera=cam_fn, device=dev, lenses=lenses,
+                                        png_decoder=png_decoder)
         pf_dense = ingest.FramePrefetcher(args.dense_input_dir, args.seq, cameras_dense, use_mask=USE_MASK_DENSE,
                                           blacklist=C.BLACKLIST, rotate_mask=C.ROTATE_MASK, setup_camera=cam_fn, device=dev,
-                                          lenses=lenses_dense)
+                                          lenses=lenses_dense, png_decoder=png_decoder)
     rng = Random(seed)
     output_params = []
     state = {"params": params, "variables": variables, "optimizer": optimizer, "priors": priors, "pins": pins, "frames": 0}
@@ -505,6 +507,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--low_from_full', action='store_true', default=argparse.SUPPRESS,
                    help="Make the geometry inputs from $dense_input_dir's photographs (down_ratio x down_ratio means) instead "
                         "of reading $input_dir's; $input_dir then holds cameras.xml, the mesh and the masks only.")
+    p.add_argument('--gpu_png', action='store_true', default=argparse.SUPPRESS,
+                   help="Decode the masks and the *.png views of $input_dir and $dense_input_dir on the GPU (topo4d_amd.png); the "
+                        "kinds its decoder does not take (palette, under 8 bits, 16-bit colour, interlaced) still come from PIL.")
     p.add_argument('--tex_pad', type=int, default=argparse.SUPPRESS, metavar='R',
                    help="With --gen_tex: fill a gutter of R texels (0..64) round the UV islands of face.png from the nearest "
                         "baked texel, so that bilinear taps on the seams no longer mix in the black background.")
