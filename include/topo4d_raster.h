@@ -807,6 +807,31 @@ typedef struct T4DLensView {
 #define T4D_LENS_MAX_SUPERSAMPLE 64
 int t4d_undistort_views(const T4DLensView *views, const T4DLensView *d_views, int32_t n_views, void *hip_stream);
 
+/* ---- JPEG encode (csrc/t4d_jpegenc.hip, csrc/t4d_jpeg_fdct.h; topo4d_amd/jpeg.py, topo4d_amd/prepare.py) ----
+ * T4DJpegEncImage: one uint8 [height, width, 3] RGB image on the device, src_pitch bytes per row, 1..65535 pixels a side; its file
+ * is written at out + out_offset, and the ranges [out_offset, out_offset + t4d_jpeg_enc_max_bytes) of a batch must not overlap.
+ * t4d_jpeg_encode writes n complete baseline JFIF files (SOI, JFIF APP0, two DQT, SOF0, the four Annex K DHT, SOS, one interleaved
+ * scan without restart markers, EOI), byte for byte what libjpeg-turbo writes after jpeg_set_quality(quality, TRUE) with
+ * luma sampling 1x1 (subsampling 0, 4:4:4), 2x1 (1, 4:2:2) or 2x2 (2, 4:2:0) and JDCT_ISLOW - PIL's
+ * save(f, "JPEG", quality=quality, subsampling=subsampling) - and the length of file i to out_bytes[i] (device, int64; -1 if it
+ * did not fit, which t4d_jpeg_enc_max_bytes rules out).  The bytes are a pure function of pixels, shape, quality and subsampling;
+ * nothing is written beyond a file's length; the stream is not synchronised.  images is the host copy of d_images; scratch may
+ * hold anything.  t4d_jpeg_enc_max_bytes / t4d_jpeg_enc_scratch_bytes depend on the shapes alone (0: refused).
+ * t4d_views_to_u8: float32 [channels, height, width] -> uint8 [height, width, channels],
+ * clip(floor(float64(x) * 255 + 0.5), 0, 255) (NaN: 0): a resampled view as the encoders read it. */
+typedef struct T4DJpegEncImage {
+    const uint8_t *src;
+    int32_t width, height;
+    int32_t src_pitch;
+    int32_t reserved;
+    int64_t out_offset;
+} T4DJpegEncImage;
+size_t t4d_jpeg_enc_max_bytes(int32_t height, int32_t width, int32_t subsampling);
+size_t t4d_jpeg_enc_scratch_bytes(const T4DJpegEncImage *images, int32_t n, int32_t subsampling);
+int t4d_jpeg_encode(const T4DJpegEncImage *images, const T4DJpegEncImage *d_images, int32_t n, int32_t quality, int32_t subsampling,
+                    uint8_t *out, size_t out_capacity, int64_t *out_bytes, void *scratch, size_t scratch_bytes, void *hip_stream);
+int t4d_views_to_u8(const float *src, int32_t channels, int32_t height, int32_t width, uint8_t *dst, void *hip_stream);
+
 /* ---- Coarse setup: initialize_params' coarse half and initialize_losses' topology (csrc/t4d_setup.hip; topo4d_amd/coarse.py) ----
  * t4d_setup_vertex_colors: compute_vertex_colors (helpers.py:181-209).  image: uint8 [height, width, channels] (3 or 4);
  * corner_uv [n_corners,2] float64: the UV of triangle corner 3*face+k; offsets / entries: t4d_obj_vertex_faces' CSR of the same

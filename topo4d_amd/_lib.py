@@ -128,7 +128,12 @@ class T4DLensView(C.Structure):
         ("matrix", C.c_double * 6), ("lens", C.c_double * 11), ("cval", C.c_double)]
 
 
-_VP, _I32, _I64, _F32, _SZ, _INT = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t, C.c_int
+class T4DJpegEncImage(C.Structure):
+    _fields_ = [("src", C.c_void_p)] + [(n, C.c_int32) for n in ("width", "height", "src_pitch", "reserved")] + [
+        ("out_offset", C.c_int64)]
+
+
+_VP, _I32, _I64, _F32, _SZ, _INT =C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t, C.c_int
 _PROB = C.POINTER(T4DProblem)
 
 # name -> (restype, argtypes) of every function include/topo4d_raster.h declares, in header order (tests/test_abi.py checks the
@@ -215,6 +220,10 @@ SIGNATURES = {
     "t4d_warp_scratch_bytes": (_SZ, [_I32]),
     "t4d_warp_views": (_INT, [C.POINTER(T4DWarpView), _VP, _I32, _VP, _SZ, _VP]),
     "t4d_undistort_views": (_INT, [C.POINTER(T4DLensView), _VP, _I32, _VP]),
+    "t4d_jpeg_enc_max_bytes": (_SZ, [_I32] * 3),
+    "t4d_jpeg_enc_scratch_bytes": (_SZ, [C.POINTER(T4DJpegEncImage), _I32, _I32]),
+    "t4d_jpeg_encode": (_INT, [C.POINTER(T4DJpegEncImage), _VP, _I32, _I32, _I32, _VP, _SZ, _VP, _VP, _SZ, _VP]),
+    "t4d_views_to_u8": (_INT, [_VP, _I32, _I32, _I32, _VP, _VP]),
     "t4d_setup_colors_scratch_bytes": (_SZ, [_I64]),
     "t4d_setup_vertex_colors": (_INT, [_VP] + [_I32] * 3 + [_VP, _I64, _VP, _VP, _I32] + [_VP] * 4 + [_SZ, _VP]),
     "t4d_setup_quaternions": (_INT, [_VP, _I32, _VP, _VP]),

@@ -739,14 +739,22 @@ class FramePrefetcher:
         self.pool = ThreadPoolExecutor(max_workers=workers or pool_size(), thread_name_prefix="t4d-ingest")
         self.pending: Dict[int, list] = {}
 
+    def files(self, frame: int):
+        """[(image path, mask path or None)] of a frame: frame_files (topo4d_amd.prepare overrides it for trees with masks for
+        some frames only)."""
+        return frame_files(self.data_dir, self.seq, frame, self.use_mask, self.blacklist, self.mask_dir)
+
     def prefetch(self, frame: int) -> None:
         if frame not in self.pending:
-            files = frame_files(self.data_dir, self.seq, frame, self.use_mask, self.blacklist, self.mask_dir)
-            self.pending[frame] = [self.pool.submit(_read_view, p, m, self.png_decoder) for p, m in files]
+            self.pending[frame] = [self.pool.submit(_read_view, p, m, self.png_decoder) for p, m in self.files(frame)]
+
+    def read(self, frame: int) -> list:
+        """The host half alone: the frame's views as read, parsed and (where no GPU decoder takes a file) decoded by the pool."""
+        self.prefetch(frame)
+        return [f.result() for f in self.pending.pop(frame)]
 
     def get(self, frame: int):
-        self.prefetch(frame)
-        views = [f.result() for f in self.pending.pop(frame)]
+        views = self.read(frame)
         if not views:
             return []
         return _assemble(views, self.cameras, self.use_mask, self.rotate_mask, self.setup_camera, self.device,
