@@ -1061,6 +1061,57 @@ int t4d_closest_raycast(void *index, size_t index_bytes, const double *origins, 
                         double t_hi, int32_t flags, double *out_t, int32_t *out_prim, double *out_uv, void *scratch,
                         size_t scratch_bytes, void *hip_stream);
 
+/* Rigid / similarity alignment of a scan to a mesh by iterated closest points (csrc/t4d_align.hip): the device half of
+ * topo4d_amd/scanalign.py.  One iteration moves the scan (t4d_align_transform), asks t4d_closest_query for every moved point's
+ * closest point on the mesh, and reduces the pairs into one record of float64 sums (t4d_align_accumulate) that the host solves.
+ * Everything is float64 without contraction, dot3(u,v) = (u0 v0 + u1 v1) + u2 v2, and every output is a function of the inputs
+ * alone; tests/scanalign_ref.py states both in numpy, bit for bit.  Device buffers unless stated; the stream comes last.
+ * t4d_align_transform: out[i] = M p[i] + t for n_points float64 [n,3] points; matrix (host, 12 doubles) holds the rows
+ * (m0 m1 m2 t) of [M | t], finite, M any 3x3 (a scale included).  Each component is ((m0 x + m1 y) + m2 z) + t.  out may be
+ * points.  n_points == 0 is T4D_OK.
+ * t4d_align_accumulate: points are the moved points and d2, prim_index, closest what t4d_closest_query gave for them on the
+ * triangle index `index` (an index of bare points is T4D_ERR_ARG).  Per pair, with (a, b, c) the corners of triangle prim_index
+ * as the index holds them: e = p - closest, n = (b - a) x (c - a) (the products of t4d_closest_signed), nn = dot3(n, n).  The
+ * pair's class is the first that applies:
+ *   unmatched   prim_index < 0 (or beyond the index's triangles)
+ *   gated       gate2 >= 0 and d2 > gate2 (gate2 < 0: no gate; d2 == gate2 is kept)
+ *   degenerate  nn == 0
+ *   off-normal  d2 > 0 and en * en < (cos2 * d2) * nn, en = dot3(e, n): the residual lies across the surface, as it does for a
+ *               point whose closest point sits on an open rim of the mesh
+ *   kept        every other pair
+ * A kept pair adds, with s = sqrt(nn), nh = n / s (three quotients), r = dot3(e, nh), q = p - origin, g = closest - origin
+ * (origin: host, 3 finite doubles), x = q x nh = (q1 nh2 - q2 nh1, q2 nh0 - q0 nh2, q0 nh1 - q1 nh0) and J = (x, nh):
+ *   record[T4D_ALIGN_SUM_D2] += d2                       record[T4D_ALIGN_SUM_R2] += r r
+ *   record[T4D_ALIGN_JTR + i] += r J[i]                  record[T4D_ALIGN_JTJ + k] += J[i] J[j], k counting i <= j row by row
+ *   record[T4D_ALIGN_SUM_Q + i] += q[i]                  record[T4D_ALIGN_SUM_G + i] += g[i]
+ *   record[T4D_ALIGN_SUM_QG + 3 i + j] += q[i] g[j]      record[T4D_ALIGN_SUM_QQ] += dot3(q, q), [T4D_ALIGN_SUM_GG] += dot3(g, g)
+ * and every pair adds 1 to record[T4D_ALIGN_COUNT + class] (float64 as the sums: exact below 2^53).  That is the point-to-plane
+ * Gauss-Newton system (JTJ, JTR) and the Kabsch / Umeyama system of one pass.  record: T4D_ALIGN_RECORD_DOUBLES doubles.
+ * Reduction order, fixed: G = min(ceil(n / 256), T4D_ALIGN_MAX_GROUPS) workgroups of 256 lanes; lane l of all L = 256 G adds
+ * the pairs l, l + L, l + 2 L, ... to zeros, in that order; within each wave of 64 lanes v[t] = v[t] + v[t + w] for
+ * w = 32, 16, 8, 4, 2, 1; a workgroup's four waves give (w0 + w1) + (w2 + w3); a second launch adds the G workgroup sums to
+ * zeros in index order.  No atomics.  n_points == 0 writes a record of zeros.  scratch: t4d_align_scratch_bytes(n_points)
+ * bytes (0 and a message for n_points < 0 or >= 2^30).
+ * Refused before anything touches a device: NULL buffers, a negative count, scratch too small (T4D_ERR_STATE_SIZE), a gate2 or
+ * cos2 that is not finite, cos2 outside [0, 1], a matrix or origin that is not finite. */
+#define T4D_ALIGN_RECORD_DOUBLES 51
+#define T4D_ALIGN_MAX_GROUPS 1024
+#define T4D_ALIGN_COUNT 0       /* unmatched, gated, degenerate, off-normal, kept */
+#define T4D_ALIGN_SUM_D2 5
+#define T4D_ALIGN_SUM_R2 6
+#define T4D_ALIGN_JTR 7
+#define T4D_ALIGN_JTJ 13
+#define T4D_ALIGN_SUM_Q 34
+#define T4D_ALIGN_SUM_G 37
+#define T4D_ALIGN_SUM_QG 40
+#define T4D_ALIGN_SUM_QQ 49
+#define T4D_ALIGN_SUM_GG 50
+int t4d_align_transform(const double *points, int64_t n_points, const double *matrix, double *out, void *hip_stream);
+size_t t4d_align_scratch_bytes(int64_t n_points);
+int t4d_align_accumulate(const void *index, size_t index_bytes, const double *points, int64_t n_points, const double *d2,
+                         const int32_t *prim_index, const double *closest, const double *origin, double gate2, double cos2,
+                         double *record, void *scratch, size_t scratch_bytes, void *hip_stream);
+
 /* Optional per-kernel timing with HIP events recorded on the stream the kernels are launched on.  Between
  * t4d_profile_begin() and t4d_profile_end() every kernel launch of this library is bracketed by two events;
  * t4d_profile_end() synchronises them and returns, per kernel, the summed elapsed time and the launch count.

@@ -257,6 +257,9 @@ SIGNATURES = {
     "t4d_closest_query": (_INT, [_VP, _SZ, _VP, _I64, C.c_double, _I32, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "t4d_closest_signed": (_INT, [_VP, _SZ, _VP, _I64] + [_VP] * 4 + [_VP]),
     "t4d_closest_raycast": (_INT, [_VP, _SZ, _VP, _VP, _I64, C.c_double, C.c_double, _I32, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "t4d_align_transform": (_INT, [_VP, _I64, _VP, _VP, _VP]),
+    "t4d_align_scratch_bytes": (_SZ, [_I64]),
+    "t4d_align_accumulate": (_INT, [_VP, _SZ, _VP, _I64] + [_VP] * 4 + [C.c_double, C.c_double, _VP, _VP, _SZ, _VP]),
     "t4d_profile_begin": (_INT, []),
     "t4d_profile_end": (_INT, [C.POINTER(T4DKernelTime), _INT, C.POINTER(_INT)]),
     "t4d_debug_state_layout": (_INT, [_PROB, _INT, C.POINTER(C.c_uint64), _INT]),

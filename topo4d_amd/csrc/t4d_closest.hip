@@ -711,6 +711,20 @@ int read_index(const char *entry, const void *index, size_t index_bytes, hipStre
 }
 }  // namespace
 
+// t4d_align.hip reads the triangles of a finished index through this (hidden: declared in t4d_host.h, not part of the ABI)
+int t4d_closest_index_records(const char *entry, const void *index, size_t index_bytes, void *hip_stream, const double **records,
+                              int64_t *n_prims, int *is_tri)
+{
+    CGrid g;
+    CLayout L;
+    const int rc = read_index(entry, index, index_bytes, (hipStream_t)hip_stream, &g, &L);
+    if (rc != T4D_OK) return rc;
+    *records = (const double *)((const char *)index + L.rec);
+    *n_prims = g.n_prims;
+    *is_tri = g.is_tri;
+    return T4D_OK;
+}
+
 T4D_EXPORT int t4d_closest_query(void *index, size_t index_bytes, const double *points, int64_t n_queries, double max_dist,
                                  int32_t flags, double *d2, int32_t *prim_index, double *closest, void *scratch, size_t scratch_bytes,
                                  void *hip_stream)

@@ -39,4 +39,9 @@ static inline int t4d_launch_status(const char *entry)
         if (e_ != hipSuccess) return t4d_fail(T4D_ERR_HIP, #call ": %s", hipGetErrorString(e_));    \
     } while (0)
 
+// t4d_closest.hip: where a finished closest-point index keeps its primitives (device float64, nine coordinates a b c per
+// triangle, or three per point), after one small copy of the index's header to the host; T4D_OK or the refusal of `entry`
+int t4d_closest_index_records(const char *entry, const void *index, size_t index_bytes, void *hip_stream, const double **records,
+                              int64_t *n_prims, int *is_tri);
+
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }

@@ -1,7 +1,7 @@
 """
 Score a finished run: `python -m topo4d_amd.evaluate -e EXP -s SEQ [-id ... -did ... -od ...] [--frames 1-10] [--views A,B]
 [--set low|dense|both|none] [--save_renders] [--scans DIR [--scan_max_dist X] [--scan_unit S] [--scan_thresholds a,b,c]
-[--scan_transform FILE] [--save_scan_errors] [--bake_disp DIST [--bake_res N] [--bake_both_sides] [--disp_png] [--disp_fill]
+[--scan_transform FILE] [--scan_align first|each] [--save_scan_errors] [--bake_disp DIST [--bake_res N] [--bake_both_sides] [--disp_png] [--disp_fill]
 [--disp_smooth K] [--disp_normals] [--disp_apply N [--disp_save_obj]]]] [--tex_pad R [--tex_erode E]]
 [--texture NAME] [--drift [--drift_texture NAME] [--drift_ref first|previous] [--drift_level K] [--drift_block B] [--drift_stride S]
 [--drift_radius R] [--drift_ratio Q] [--drift_unit U]]`.
@@ -17,6 +17,13 @@ reference's train.py as well: the layout and save_mesh's formats are the same.
 With --scans DIR every frame's face.obj is also measured against that frame's 3D scan, DIR/%06d.ply or else DIR/%06d.obj
 (scanscore.score_scan: scan -> mesh and mesh -> scan distances).  face.obj is compared as written: save_mesh writes world
 coordinates, the frame Metashape exports its scans in.  eval.json gains the key "scan"; --set none scores scans alone.
+
+With --scan_align first|each the scan is first aligned rigidly to the mesh (scanalign.align_scan: iterated closest points from the
+pose of --scan_transform; --scan_align_scale, --scan_align_metric, --scan_align_iters, --scan_align_stride): per frame (each), or
+by the first scored frame's transform for all (first: an offset between the scanner's frame and the tracking's is constant).
+Scoring, the bake and scan_score.npz see the aligned scan.  The frame's row gains "alignment", the scan block "align", and the
+composed matrix is written at %.17g to %06d/scan_align.txt (each) or scan_align.txt (first): given back as --scan_transform
+without --scan_align, it reproduces the scores.
 
 With --bake_disp DIST (scan file units) every scored frame's scan detail is also baked into the UV layout of its face.obj
 (scanbake.bake_displacement: per texel a ray along the surface normal, both ways, within DIST; --scan_transform applies first):
@@ -56,6 +63,7 @@ import functools
 import json
 import math
 import os
+import sys
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -213,6 +221,17 @@ def _read_scan_files(run_dir: str, scan_dir: str, t: int, transform):
     return obj, scan
 
 
+def _align_scan(args, vertices, faces, scan, transform, device):
+    """scanalign.align_scan of one frame under the --scan_align_* options, --scan_transform as the starting pose and
+    --scan_max_dist as the first gate; what it refuses ends the run with the frame's message."""
+    from . import scanalign
+    try:
+        return scanalign.align_scan(vertices, faces, scan, init=transform, metric=args.scan_align_metric, scale=args.scan_align_scale,
+                                    max_iter=args.scan_align_iters, max_dist=args.scan_max_dist, stride=args.scan_align_stride, device=device)
+    except ValueError as e:
+        raise SystemExit(f"--scan_align: {e}") from None
+
+
 def texfinish_coverage(obj, res: int, device) -> torch.Tensor:
     """The coverage the displacement bake walked: projtex.surface_maps' (texfinish.coverage_from_obj), uint8 [res,res]."""
     from . import texfinish
@@ -262,7 +281,10 @@ def score_scans(args, device) -> dict:
     disp_png = disp_png_options(args)
     disp_apply = getattr(args, "disp_apply", None) if disp_png is not None else None
     tess = None
-    with _run.prefetched(_run.frames_of(args, run_dir), lambda t: _read_scan_files(run_dir, args.scans, t, transform),
+    align = getattr(args, "scan_align", "none")
+    shared = None                                               # --scan_align first: (frame key, composed matrix)
+    with _run.prefetched(_run.frames_of(args, run_dir),
+                         lambda t: _read_scan_files(run_dir, args.scans, t, transform if align == "none" else None),
                          thread_name="t4d-eval-scan") as walk:
         for t, (obj, scan) in walk:
             key = _run.frame_key(t)
@@ -273,6 +295,19 @@ def score_scans(args, device) -> dict:
                 result[key] = {"skipped": "no scan"}
                 continue
             faces, _ = meshrender.triangulate(obj.faces_ori, obj.uv_faces_ori)
+            alignment = None
+            if align != "none":
+                # the scan as read, then the composed matrix exactly as a later --scan_transform of the written file applies it
+                if align == "each" or shared is None:
+                    alignment, path = _align_scan(args, obj.vertices, faces, scan, transform, device), "scan_align.txt"
+                    if align == "first":
+                        shared = (key, alignment.matrix)
+                    if not alignment.converged:
+                        print(f"--scan_align: frame {key} ended at --scan_align_iters {args.scan_align_iters} without converging"
+                              + (" (--scan_align_scale approaches a scale only linearly)" if args.scan_align_scale else ""), file=sys.stderr)
+                    np.savetxt(os.path.join(run_dir, path if align == "first" else os.path.join(key, path)), alignment.matrix, fmt="%.17g")
+                matrix = alignment.matrix if align == "each" else shared[1]
+                scan = scanscore.Scan(scan.vertices @ matrix[:3, :3].T + matrix[:3, 3], scan.faces)
             bake = bake_disp is not None and scan.faces is not None
             score = scanscore.score_scan(obj.vertices, faces, scan, max_dist=args.scan_max_dist, thresholds=args.scan_thresholds,
                                          unit=args.scan_unit, device=device, per_element=args.save_scan_errors,
@@ -312,8 +347,15 @@ def score_scans(args, device) -> dict:
             row = {"scan_vertices": int(len(scan.vertices)), "scan_faces": 0 if scan.faces is None else int(len(scan.faces))}
             for d, stats in score.items():
                 row[d] = {n: (_finite(v) if isinstance(v, float) else v) for n, v in stats.items()}
+            if alignment is not None:
+                row["alignment"] = alignment.as_dict()
             result[key] = row
     out = {"unit": args.scan_unit, "max_dist": args.scan_max_dist, "frames": result, "summary": _scan_summary(result)}
+    if align != "none":
+        out["align"] = {"mode": align, "metric": args.scan_align_metric, "scale": bool(args.scan_align_scale),
+                        "iters": int(args.scan_align_iters), "stride": int(args.scan_align_stride)}
+        if align == "first":
+            out["align"]["frame"] = None if shared is None else shared[0]
     if bake_disp is not None:
         out["bake"] = {"dist": bake_disp, "res": args.bake_res, "same_side": not args.bake_both_sides}
         if disp_png is not None:
@@ -372,6 +414,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--scan_transform", default=None, metavar="FILE", help="Scan scoring: a 4x4 text matrix applied to every scan.")
     p.add_argument("--save_scan_errors", action="store_true",
                    help="Scan scoring: also write %%06d/scan_score.npz (face_count, face_mean, vertex_dist).")
+    p.add_argument("--scan_align", choices=("none", "first", "each"), default="none",
+                   help="Scan scoring: align each scan rigidly to its frame's mesh before it is scored (scanalign.align_scan, with "
+                        "--scan_transform as the starting pose): 'each' frame on its own, or the 'first' scored frame's transform for "
+                        "all frames.  Writes scan_align.txt (first) or %%06d/scan_align.txt (each), which --scan_transform reads.")
+    p.add_argument("--scan_align_scale", action="store_true", help="--scan_align: also estimate one scale (a similarity).  The scale is approached only linearly: more than a few "
+                        "per cent off needs hundreds of --scan_align_iters, and a change of unit belongs in --scan_transform; a phase "
+                        "that ends at the limit is reported (\"converged\": false, and a warning).")
+    p.add_argument("--scan_align_metric", choices=("plane", "point"), default="plane",
+                   help="--scan_align: distances along the mesh normals (default) or to the closest points.")
+    p.add_argument("--scan_align_iters", type=int, default=30, metavar="N", help="--scan_align: iterations at the most (default 30).")
+    p.add_argument("--scan_align_stride", type=int, default=1, metavar="K", help="--scan_align: use every K-th scan vertex (default 1).")
     p.add_argument("--bake_disp", type=float, default=None, metavar="DIST",
                    help="With --scans: bake each frame's scan into %%06d/face_disp.npy and face_disp_hit.png, a displacement map in the "
                         "UV layout of face.obj, with rays of reach DIST (scan file units) along the surface normal, both ways.")
@@ -408,6 +461,14 @@ def evaluate(args, device=None) -> dict:
     with_drift = bool(getattr(args, "drift", False))
     if not sets and scans is None and not with_drift:
         raise SystemExit("--set none scores nothing without --scans or --drift")
+    if getattr(args, "scan_align", "none") != "none":
+        if scans is None:
+            raise SystemExit("--scan_align needs --scans")
+        from . import scanalign
+        try:
+            scanalign.check_options(args.scan_align_metric, args.scan_align_iters, args.scan_max_dist, stride=args.scan_align_stride)
+        except ValueError as e:
+            raise SystemExit(f"--scan_align: {e}") from None
     bake_disp = getattr(args, "bake_disp", None)
     if bake_disp is not None:
         if scans is None:
