@@ -72,17 +72,6 @@ def decode_png16(data: bytes):
 def best_filters(image) -> np.ndarray:
     """The filter byte the encoder's rule picks for every row of an int [H,W,C] image of 16-bit samples: the least sum of |int8
     residual| over the row's 2 W C big-endian bytes, the lowest filter number on a tie."""
-    image = np.asarray(image).astype(np.int64) & 0xFFFF
-    h, w, c = image.shape
-    bpp = 2 * c
-    by = np.stack([image >> 8, image & 255], -1).reshape(h, -1)
-    z = np.zeros((h, bpp), np.int64)
-    left = np.concatenate([z, by[:, :-bpp]], 1)                # a row holds at least one pixel: bpp bytes
-    up = np.concatenate([np.zeros((1, by.shape[1]), np.int64), by[:-1]], 0)
-    upleft = np.concatenate([z, up[:, :-bpp]], 1)
-    p = left + up - upleft
-    pa, pb, pc = np.abs(p - left), np.abs(p - up), np.abs(p - upleft)
-    paeth = np.where((pa <= pb) & (pa <= pc), left, np.where(pb <= pc, up, upleft))
-    preds = [np.zeros_like(by), left, up, (left + up) >> 1, paeth]
-    cost = np.stack([np.abs((((by - q) & 255) ^ 128) - 128).sum(1) for q in preds], 1)
-    return np.argmin(cost, 1).astype(np.uint8)                # argmin: the first of equal minima
+    from tests import png_ref                                 # one statement of the filter rule for 8 and 16 bits
+    by, bpp, _ = png_ref.image_bytes(np.asarray(image), 16)
+    return png_ref.filter_rows(by, bpp)[0]

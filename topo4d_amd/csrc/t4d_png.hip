@@ -28,6 +28,7 @@
 
 #include "../../include/topo4d_raster.h"
 #include "t4d_host.h"
+#include "t4d_png_huff.h"
 #include "t4d_quant.h"
 
 namespace {
@@ -37,7 +38,7 @@ constexpr int kSeg = 16384;                      // filtered bytes per segment (
 constexpr int kSegMaxOut = kSeg + 5;             // stored fallback: one 5-byte block header + the bytes
 constexpr int kSlot = 16448;                     // scratch bytes per segment's encoded output (>= kSegMaxOut, 64-B multiple)
 constexpr int kOutWords = kSlot / 4;
-constexpr int kLit = 286;                        // literal/length alphabet
+constexpr int kLit = kPngLit;                    // literal/length alphabet (t4d_png_huff.h)
 constexpr int kCl = 19;                          // code-length alphabet
 constexpr int kHeadBytes = 8 + 25 + 14;          // signature, IHDR chunk, IDAT(zlib header)
 constexpr int kTailBytes = 16 + 12;              // IDAT(Adler-32), IEND
@@ -277,17 +278,6 @@ __device__ uint32_t crc_slow(uint32_t crc, const uint8_t *p, int n)
 // ---------------------------------------------------------------------------------------------------------------------------
 // Huffman code lengths
 // ---------------------------------------------------------------------------------------------------------------------------
-struct HuffScratch {
-    uint16_t sorted[kLit];                       // used symbols by (freq, symbol) ascending
-    uint32_t w_leaf[kLit];                       // their frequencies
-    uint32_t bl[32];                             // leaves per code length
-    uint32_t next[16];                           // canonical_codes: next code per length
-    uint32_t w_int[kLit];                        // internal-node weights
-    uint16_t par_leaf[kLit], par_int[kLit];
-    uint8_t depth_int[kLit];
-    int count;
-};
-
 // Length-limited code lengths for freq[0..n) (max_bits), written to len[0..n).  A used set of fewer than two symbols is padded to two
 // by the caller.  Huffman lengths from the two-queue method over the sorted leaves; leaves deeper than max_bits are clamped and the
 // Kraft excess is removed one unit at a time (a leaf at depth b < max_bits moves to b + 1 and takes a clamped leaf as its sibling);
@@ -311,60 +301,8 @@ __device__ void huff_lengths(const uint32_t *freq, int n, int max_bits, uint8_t 
         atomicAdd(&hs.count, 1);
     }
     __syncthreads();
-    if (t == 0) {
-        const int m = hs.count;
-        int i = 0, j = 0;
-        for (int k = 0; k < m - 1; ++k) {
-            uint32_t w = 0;
-            for (int pick = 0; pick < 2; ++pick) {
-                const bool leaf = i < m && (j >= k || hs.w_leaf[i] <= hs.w_int[j]);
-                if (leaf) { w += hs.w_leaf[i]; hs.par_leaf[i++] = (uint16_t)k; }
-                else { w += hs.w_int[j]; hs.par_int[j++] = (uint16_t)k; }
-            }
-            hs.w_int[k] = w;
-        }
-        uint32_t *bl = hs.bl;                                         // LDS: a private array here would live in scratch memory
-        for (int b = 0; b < 32; ++b) bl[b] = 0;
-        if (m >= 2) {
-            hs.depth_int[m - 2] = 0;
-            for (int k = m - 3; k >= 0; --k) hs.depth_int[k] = (uint8_t)min(hs.depth_int[hs.par_int[k]] + 1, 31);
-            for (int q = 0; q < m; ++q) bl[min(hs.depth_int[hs.par_leaf[q]] + 1, 31)]++;
-        } else if (m == 1) {
-            bl[1] = 1;
-        }
-        for (int b = max_bits + 1; b < 32; ++b) { bl[max_bits] += bl[b]; bl[b] = 0; }
-        uint64_t kraft = 0;
-        for (int b = 1; b <= max_bits; ++b) kraft += (uint64_t)bl[b] << (max_bits - b);
-        const uint64_t one = (uint64_t)1 << max_bits;
-        while (kraft > one) {
-            int b = max_bits - 1;
-            while (b > 0 && bl[b] == 0) --b;
-            if (b == 0) break;                                        // cannot happen for n <= 2^max_bits
-            bl[b]--; bl[b + 1] += 2; bl[max_bits]--;
-            kraft -= 1;
-        }
-        int q = 0;                                                    // least frequent first: the longest lengths
-        for (int b = max_bits; b >= 1; --b)
-            for (uint32_t k = 0; k < bl[b] && q < m; ++k) len[hs.sorted[q++]] = (uint8_t)b;
-    }
+    if (t == 0) t4d_png_huff_assign(max_bits, len, hs);                // t4d_png_huff.h
     __syncthreads();
-}
-
-// canonical codes, bit-reversed for LSB-first output (RFC 1951 3.2.2); one thread
-__device__ void canonical_codes(const uint8_t *len, int n, uint16_t *code, HuffScratch &hs)
-{
-    uint32_t *bl = hs.bl, *next = hs.next;
-    for (int b = 0; b < 16; ++b) bl[b] = next[b] = 0;
-    for (int s = 0; s < n; ++s) bl[len[s]]++;
-    bl[0] = 0;
-    uint32_t c = 0;
-    for (int b = 1; b < 16; ++b) { c = (c + bl[b - 1]) << 1; next[b] = c; }
-    for (int s = 0; s < n; ++s) {
-        const int l = len[s];
-        if (!l) { code[s] = 0; continue; }
-        const uint32_t v = next[l]++;
-        code[s] = (uint16_t)(__brev(v) >> (32 - l));
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -526,7 +464,7 @@ __global__ __launch_bounds__(kBlock) void k_png_encode(const uint8_t *filt, Shap
     __syncthreads();
     huff_lengths(S.lit_freq, kLit, 15, S.lit_len, S.hs);
     if (t == 0) {
-        canonical_codes(S.lit_len, kLit, S.lit_code, S.hs);
+        t4d_png_canonical_codes(S.lit_len, kLit, S.lit_code, S.hs);
         int nl = kLit;
         while (nl > 257 && S.lit_len[nl - 1] == 0) --nl;
         S.n_lit = nl;
@@ -539,7 +477,7 @@ __global__ __launch_bounds__(kBlock) void k_png_encode(const uint8_t *filt, Shap
     __syncthreads();
     huff_lengths(S.cl_freq, kCl, 7, S.cl_len, S.hs);
     if (t == 0) {
-        canonical_codes(S.cl_len, kCl, S.cl_code, S.hs);
+        t4d_png_canonical_codes(S.cl_len, kCl, S.cl_code, S.hs);
         int nc = kCl;
         while (nc > 4 && S.cl_len[c_cl_order[nc - 1]] == 0) --nc;
         S.n_cl = nc;
