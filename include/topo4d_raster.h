@@ -702,13 +702,19 @@ int t4d_obj_face_lines(const int64_t *face_off, const int64_t *v_idx, const int6
  * packed back to back in image order (data_offset = the sum of the previous data_bytes).  quant: the DQT tables in natural
  * order; huff_bits/huff_vals: DHT tables, slots 0-3 DC tables 0-3 and 4-7 AC tables 0-3; comp_*: the table ids of Y, Cb, Cr.
  * The image is written as uint8 [height, width, 3] RGB at out + out_offset, byte-identical to libjpeg-turbo's ISLOW IDCT,
- * fancy upsampling and YCbCr->RGB.
+ * fancy upsampling and YCbCr->RGB.  That is libjpeg's C arithmetic, whose 10-bit range table wraps an IDCT output beyond
+ * [-512, 511]; libjpeg-turbo's SIMD IDCT (what PIL runs) saturates there.  The two agree, and the output equals PIL's, for
+ * blocks whose exact IDCT samples (before the +128 shift) stay within +-500 and whose |coefficient * q| stays below 32768.
  *
  * t4d_jpeg_decode: images (host) and d_images (a device copy of the same array), n of them.  chunk_bits (0: the default 4096,
- * else >= 64) is the length of a lane's chunk in the self-synchronising decode of images without restart intervals.
+ * else any value >= 64, byte multiple or not; smaller values are T4D_ERR_ARG) is the length of a lane's chunk in the
+ * self-synchronising decode of images without restart intervals.  Every accepted value decodes every valid file: a chunk
+ * boundary may fall anywhere, the 1-7 padding bits after the last block included.
  * status[i] (device) receives 0 or an OR of 1 (entropy segment ended early), 2 (more MCUs than the frame holds), 4 (a code no
  * Huffman table holds, or a DHT table that over-fills the code space), 8 (RSTn markers missing, extra or out of sequence).
- * No read outside data[data_offset, data_offset + data_bytes) is made whatever the bytes hold. */
+ * A DHT table that over-fills the code space or lists more than 256 symbols is refused: the image gets bit 4, its table is
+ * replaced by one that matches no code, its pixels are unspecified, and the other images of the batch are unaffected.
+ * No read outside data[data_offset, data_offset + data_bytes) is made whatever the bytes hold, and scratch may hold anything. */
 typedef struct T4DJpegImage {
     int32_t width, height;
     int32_t h_samp, v_samp;

@@ -46,6 +46,7 @@ int main()
     int rc = 0;
     if (im.restart_interval > 0) {
         if ((int64_t)rst.size() != g.n_seg - 1) return status | kErrRestart;
+        if (status & kErrRestart) return status;               // as k_jpeg_decode: no lane of an image whose markers are out of order
         for (int64_t s = 0; s < g.n_seg; s++) {
             const int64_t a = s == 0 ? 0 : rst[s - 1], b = s + 1 < g.n_seg ? rst[s] : clen;
             const int64_t lim = (s + 1) * im.restart_interval < g.n_mcu ? (s + 1) * im.restart_interval : g.n_mcu;
@@ -67,7 +68,7 @@ int main()
             E[t] = s;
         }
         bool changed = last > 0;
-        for (int r = 1; r < 12 && changed; r++) {               // the GPU's rounds: lane t restarts from lane t-1's last exit
+        for (int r = 1; r < kRounds && changed; r++) {               // the GPU's rounds: lane t restarts from lane t-1's last exit
             changed = false;
             En = E;
             for (int64_t t = 1; t <= last; t++) {
@@ -94,7 +95,7 @@ int main()
             int32_t pred[3] = {pre[0], pre[1], pre[2]};
             status |= decode_lane(d.data(), clen, tb, g, S[t], end_of(t), end_of(t) >= bits, blk - 1, g.n_blocks, pred, coef.data());
             blk += cnt[t].blocks;
-            for (int c = 0; c < 3; c++) pre[c] += cnt[t].dc[c];
+            for (int c = 0; c < 3; c++) pre[c] = (int32_t)((uint32_t)pre[c] + (uint32_t)cnt[t].dc[c]);
         }
     }
     if (status) return status;

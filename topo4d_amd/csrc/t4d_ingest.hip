@@ -8,7 +8,7 @@
 //   k_stuff_count/scan/write   remove FF00 stuffing and RSTn markers (parallel scan + compaction) and record where each
 //                        restart interval starts
 //   k_jpeg_sync (rounds) chunked self-synchronising decode of images without restart intervals: every lane decodes its chunk
-//                        from the exit state of the lane before it, until no start state changes (at most kRounds launches;
+//                        from the exit state of the lane before it, until no start state changes (at most t4d_jpeg::kRounds launches;
 //                        k_jpeg_sync_fallback decodes the chunks of an image that did not converge one after another)
 //   k_jpeg_lane_scan     per image: exclusive prefix of the lanes' block counts and DC-difference sums
 //   k_jpeg_decode        every lane (a chunk, or a restart interval) decodes again from its synchronised state and writes its
@@ -33,7 +33,6 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kTileBytes = kBlock * 16;  // bytes per stuffing tile (16 per thread)
-constexpr int kRounds = 12;              // sync launches before the sequential fallback
 constexpr int kMinChunkBits = 64;
 constexpr int kDefaultChunkBits = 4096;
 

@@ -9,6 +9,15 @@
 // Decoding state between two symbols is (bit position, block within the MCU, coefficient index): k = 0 means the next symbol is
 // a DC category, 1..63 an AC run/size.  Chunked decoding (Weissenberger & Schmidt, ICPP 2018) starts a lane at a guessed state
 // and relies on these states re-synchronising; t4d_ingest.hip iterates the lanes' start states to a fixed point.
+//
+// Three rules ("View ingest"; tests/jpeg_dec_cases.py holds each):
+//   - a chunk is any number of bits >= 64, byte multiple or not, and every such value decodes every valid file: a boundary inside
+//     the 1..7 padding bits after the last block is handled in decode_lane;
+//   - a DHT table build_huff refuses is still written in full, as a table that matches no code: the image reports kErrCode, every
+//     later step reads defined values and always advances, the other images of a batch are unaffected;
+//   - the output equals PIL's (libjpeg-turbo's SIMD IDCT) while a block's exact IDCT samples stay within +-500 and
+//     |coefficient * q| below 32768; beyond that it is libjpeg's C range-table wrap (range_limit).
+// Whatever the bytes hold, the arithmetic is defined (the IDCT wraps in 32 bits, `Wrap`) and no read or write leaves its arrays.
 #pragma once
 
 #include <stdint.h>
@@ -16,14 +25,16 @@
 #include "../../include/topo4d_raster.h"
 
 #if defined(__HIPCC__)
-#define T4D_JPEG_FN __host__ __device__ static inline
+#define T4D_JPEG_HD __host__ __device__
 #else
-#define T4D_JPEG_FN static inline
+#define T4D_JPEG_HD
 #endif
+#define T4D_JPEG_FN T4D_JPEG_HD static inline
 
 namespace t4d_jpeg {
 
 constexpr int kLookBits = 9;
+constexpr int kRounds = 12;       // start-state rounds of the chunk lanes before they are decoded one after another instead
 
 // jpeg_make_d_derived_tbl: canonical codes of one DHT table
 struct Huff {
@@ -33,7 +44,23 @@ struct Huff {
     uint8_t val[256];
 };
 
-// false: the BITS counts overflow the code space (an all-ones code included) or list more than 256 symbols, as libjpeg refuses
+// a table no code matches: every lookup is "bad" (symbol 0, 16 bits), so a decode that goes on over it reads defined values,
+// always advances and reports kErrCode
+T4D_JPEG_FN bool refuse_huff(Huff *h)
+{
+    for (int l = 0; l < 18; l++) {
+        h->maxcode[l] = -1;
+        h->valoffset[l] = 0;
+    }
+    h->maxcode[17] = 0xFFFFF;
+    for (int i = 0; i < (1 << kLookBits); i++) h->look[i] = 0;
+    for (int i = 0; i < 256; i++) h->val[i] = 0;
+    return false;
+}
+
+// false: the BITS counts overflow the code space (an all-ones code included) or list more than 256 symbols, as libjpeg refuses.
+// A refused table is still written in full (refuse_huff): the image's status gets kErrCode and nothing downstream reads an
+// unwritten record.
 T4D_JPEG_FN bool build_huff(const uint8_t *bits, const uint8_t *vals, Huff *h)
 {
     uint8_t size[257];
@@ -41,7 +68,7 @@ T4D_JPEG_FN bool build_huff(const uint8_t *bits, const uint8_t *vals, Huff *h)
     int p = 0;
     for (int l = 1; l <= 16; l++)
         for (int i = 0; i < bits[l - 1]; i++) {
-            if (p >= 256) return false;
+            if (p >= 256) return refuse_huff(h);
             size[p++] = (uint8_t)l;
         }
     size[p] = 0;
@@ -51,7 +78,7 @@ T4D_JPEG_FN bool build_huff(const uint8_t *bits, const uint8_t *vals, Huff *h)
     p = 0;
     while (p < n) {
         while (p < n && size[p] == si) code[p++] = (uint16_t)c++;
-        if (c >= (1u << si)) return false;        // libjpeg: no all-ones code
+        if (c >= (1u << si)) return refuse_huff(h);  // libjpeg: no all-ones code
         c <<= 1;
         si++;
     }
@@ -175,14 +202,32 @@ T4D_JPEG_FN int natural(int k)
 // ---- jidctint.c (jpeg_idct_islow) -------------------------------------------------------------------------------------------
 constexpr int kConstBits = 13, kPass1Bits = 2;
 
-// IDCT_range_limit[x & 1023]: the 10-bit wrap of the descaled value, then clamp(x + 128, 0, 255)
+// IDCT_range_limit[x & 1023]: the 10-bit wrap of the descaled value, then clamp(x + 128, 0, 255).
+// The table is a clamp for descaled values in [-512, 511] and wraps beyond, as libjpeg's C code does; libjpeg-turbo's SIMD IDCT,
+// which PIL's builds run, saturates instead.  So "byte-identical to PIL" holds for blocks whose exact (real-valued) IDCT samples,
+// before the +128 level shift, stay within +-500 (512 less ISLOW's error) and whose |coefficient * q| stays below 32768; no
+// encoder writes others.  tests/jpeg_dec_cases.py keeps its designed blocks inside this range and records one outside it.
 T4D_JPEG_FN uint8_t range_limit(int x)
 {
     const int s = ((x + 512) & 1023) - 512 + 128;
     return (uint8_t)(s < 0 ? 0 : s > 255 ? 255 : s);
 }
 
-T4D_JPEG_FN int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+// libjpeg's `int` arithmetic as 32-bit two's complement that wraps: the same bits wherever `int` does not overflow, which covers
+// every block of the documented range, and defined behaviour for the coefficients of a corrupt stream, which do overflow it
+struct Wrap {
+    uint32_t v;
+    T4D_JPEG_HD Wrap(int x = 0) : v((uint32_t)x) {}
+    T4D_JPEG_HD int i() const { return (int)v; }
+};
+T4D_JPEG_FN Wrap wrap_of(uint32_t v) { Wrap r; r.v = v; return r; }
+T4D_JPEG_FN Wrap operator+(Wrap a, Wrap b) { return wrap_of(a.v + b.v); }
+T4D_JPEG_FN Wrap operator-(Wrap a, Wrap b) { return wrap_of(a.v - b.v); }
+T4D_JPEG_FN Wrap operator*(Wrap a, Wrap b) { return wrap_of(a.v * b.v); }
+T4D_JPEG_FN Wrap &operator+=(Wrap &a, Wrap b) { a.v += b.v; return a; }
+T4D_JPEG_FN Wrap &operator*=(Wrap &a, Wrap b) { a.v *= b.v; return a; }
+
+T4D_JPEG_FN int descale(Wrap x, int n) { return (x + (1 << (n - 1))).i() >> n; }
 
 // one 8x8 block: coef in natural order (dequantised by q, natural order) -> out[row * pitch + col]
 T4D_JPEG_FN void idct_islow(const int16_t *coef, const uint16_t *q, uint8_t *out, int64_t pitch)
@@ -194,19 +239,19 @@ T4D_JPEG_FN void idct_islow(const int16_t *coef, const uint16_t *q, uint8_t *out
         bool ac0 = true;
         for (int r = 1; r < 8; r++) ac0 = ac0 && in[8 * r] == 0;
         if (ac0) {
-            const int dc = (in[0] * qq[0]) * (1 << kPass1Bits);
+            const int dc = (Wrap(in[0] * qq[0]) * (1 << kPass1Bits)).i();
             for (int r = 0; r < 8; r++) ws[8 * r + c] = dc;
             continue;
         }
-        int z2 = in[16] * qq[16], z3 = in[48] * qq[48];
-        int z1 = (z2 + z3) * 4433;
-        int tmp2 = z1 + z3 * -15137;
-        int tmp3 = z1 + z2 * 6270;
+        Wrap z2 = in[16] * qq[16], z3 = in[48] * qq[48];
+        Wrap z1 = (z2 + z3) * 4433;
+        Wrap tmp2 = z1 + z3 * -15137;
+        Wrap tmp3 = z1 + z2 * 6270;
         z2 = in[0] * qq[0];
         z3 = in[32] * qq[32];
-        int tmp0 = (z2 + z3) * (1 << kConstBits);
-        int tmp1 = (z2 - z3) * (1 << kConstBits);
-        const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+        Wrap tmp0 = (z2 + z3) * (1 << kConstBits);
+        Wrap tmp1 = (z2 - z3) * (1 << kConstBits);
+        const Wrap tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
         tmp0 = in[56] * qq[56];
         tmp1 = in[40] * qq[40];
         tmp2 = in[24] * qq[24];
@@ -214,8 +259,8 @@ T4D_JPEG_FN void idct_islow(const int16_t *coef, const uint16_t *q, uint8_t *out
         z1 = tmp0 + tmp3;
         z2 = tmp1 + tmp2;
         z3 = tmp0 + tmp2;
-        int z4 = tmp1 + tmp3;
-        const int z5 = (z3 + z4) * 9633;
+        Wrap z4 = tmp1 + tmp3;
+        const Wrap z5 = (z3 + z4) * 9633;
         tmp0 *= 2446;
         tmp1 *= 16819;
         tmp2 *= 25172;
@@ -248,13 +293,13 @@ T4D_JPEG_FN void idct_islow(const int16_t *coef, const uint16_t *q, uint8_t *out
             for (int c = 0; c < 8; c++) o[c] = v;
             continue;
         }
-        int z2 = w[2], z3 = w[6];
-        int z1 = (z2 + z3) * 4433;
-        int tmp2 = z1 + z3 * -15137;
-        int tmp3 = z1 + z2 * 6270;
-        int tmp0 = (w[0] + w[4]) * (1 << kConstBits);
-        int tmp1 = (w[0] - w[4]) * (1 << kConstBits);
-        const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+        Wrap z2 = w[2], z3 = w[6];
+        Wrap z1 = (z2 + z3) * 4433;
+        Wrap tmp2 = z1 + z3 * -15137;
+        Wrap tmp3 = z1 + z2 * 6270;
+        Wrap tmp0 = (Wrap(w[0]) + w[4]) * (1 << kConstBits);
+        Wrap tmp1 = (Wrap(w[0]) - w[4]) * (1 << kConstBits);
+        const Wrap tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
         tmp0 = w[7];
         tmp1 = w[5];
         tmp2 = w[3];
@@ -262,8 +307,8 @@ T4D_JPEG_FN void idct_islow(const int16_t *coef, const uint16_t *q, uint8_t *out
         z1 = tmp0 + tmp3;
         z2 = tmp1 + tmp2;
         z3 = tmp0 + tmp2;
-        int z4 = tmp1 + tmp3;
-        const int z5 = (z3 + z4) * 9633;
+        Wrap z4 = tmp1 + tmp3;
+        const Wrap z5 = (z3 + z4) * 9633;
         tmp0 *= 2446;
         tmp1 *= 16819;
         tmp2 *= 25172;
@@ -401,7 +446,7 @@ T4D_JPEG_FN void run_counts(const uint8_t *d, int64_t nb, const Tables &tb, cons
         int v;
         if (step(d, nb, tb.dc[c], tb.ac[c], s, &v, &bad) == 0) {
             cnt.blocks++;
-            cnt.dc[c] += v;
+            cnt.dc[c] = (int32_t)((uint32_t)cnt.dc[c] + (uint32_t)v);   // wraps, as the lanes' prefix sums do
         }
         next_block(s, g.bpm);
     }
@@ -409,17 +454,22 @@ T4D_JPEG_FN void run_counts(const uint8_t *d, int64_t nb, const Tables &tb, cons
 
 // decode from s and write coefficients (natural order, DC predicted from pred[]) of MCU-order blocks into cf[blk * 64 ...]:
 // blk is the block before the lane's first DC symbol.  A lane that is not the last of its segment stops at bit `end`; the last
-// one stops when block blk_limit - 1 is complete, and the segment is truncated if that takes it past `end`.  Returns status bits.
+// one stops when block blk_limit - 1 is complete, and the segment is truncated if that takes it past `end`.  A chunk boundary
+// may fall inside the 1..7 padding bits after the last block: the lane before it is done once block blk_limit - 1 is complete
+// and fewer than 8 bits of the segment are left (it does not read the padding as a symbol, though run_counts counted one), and
+// the lane after it, whose first block would lie past blk_limit, has nothing to decode.  Eight or more bits after the last block
+// are not padding: kErrOverrun.  Returns status bits.
 T4D_JPEG_FN int decode_lane(const uint8_t *d, int64_t nb, const Tables &tb, const Geom &g, State s, int64_t end, bool last,
                             int64_t blk, int64_t blk_limit, int32_t *pred, int16_t *cf)
 {
     bool bad = false;
     int err = 0;
+    if (blk + 1 > blk_limit) return 0;
     for (;;) {
         if (last) {
             if (s.k == 0 && blk + 1 >= blk_limit) break;
             if (s.pos > end + 32) break;
-        } else if (s.pos >= end) {
+        } else if (s.pos >= end || (s.k == 0 && blk + 1 >= blk_limit && nb * 8 - s.pos < 8)) {
             break;
         }
         const int c = block_component(g, s.blk);
@@ -430,7 +480,7 @@ T4D_JPEG_FN int decode_lane(const uint8_t *d, int64_t nb, const Tables &tb, cons
                 err |= kErrOverrun;
                 break;
             }
-            pred[c] += v;
+            pred[c] = (int32_t)((uint32_t)pred[c] + (uint32_t)v);
             cf[blk * 64] = (int16_t)pred[c];
         } else if (idx > 0 && blk >= 0 && blk < blk_limit) {
             cf[blk * 64 + natural(idx)] = (int16_t)v;

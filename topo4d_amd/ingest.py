@@ -274,7 +274,8 @@ def decode_jpeg(files: Sequence[bytes], chunk_bits: Optional[int] = None, device
                 host_images=None) -> List[torch.Tensor]:
     """uint8 device tensors equal to np.asarray(Image.open(f)) for each file's bytes: [H,W,3] from the GPU decoder, or whatever
     PIL gives for the files it does not take.  chunk_bits: the chunk of the self-synchronising decode (None: the library's
-    default).  headers / host_images: parse_jpeg results and PIL arrays already made (FramePrefetcher), per file or None."""
+    default; else any value >= 64, a byte multiple or not - a smaller one raises ValueError before anything is launched).  The
+    equality with PIL holds within the sample range include/topo4d_raster.h states.  headers / host_images: parse_jpeg results and PIL arrays already made (FramePrefetcher), per file or None."""
     dev = _lib.hip_device(device, "ingest")
     files = [bytes(f) for f in files]
     headers = list(headers) if headers is not None else [None] * len(files)
