@@ -151,7 +151,7 @@ def stop_edge(seed):
 
 def head_dense(seed):
     """the dense vertices of a lat-long head (about 2k frontal quads) at density 24: the smallest capture-like lattice with
-    n > 2^20 (a table of 2^22 slots: four carry passes of k_scan_sums)"""
+    n > 2^20 (a table of 2^22 slots: four carry passes of k_scan_i32_sums)"""
     from tests.test_gpu_densify import head_mesh
     from topo4d_amd import densify
     params, faces, uv_faces, uvs, uv_counts, masks = head_mesh(40, 100, seed=seed)

@@ -102,6 +102,29 @@ def test_h_row_band_at_size(name):
         assert (depth[part] == BC.FRESH_DEPTH).all()
 
 
+def _far_apart_soups(h, w, corners, n=100, side=96, seed=81):
+    """One-channel soups of n large triangles in side x side boxes whose top-left corners are `corners` (x, y)."""
+    parts = [BC.soup(n, side, side, seed + k, margin=8, c=1) for k in range(len(corners))]
+    verts = np.concatenate([p.verts + np.float32([x, y, 0]) for p, (x, y) in zip(parts, corners)])
+    tris = np.concatenate([p.tris + 3 * n * k for k, p in enumerate(parts)]).astype(np.int32)
+    return verts, tris, np.concatenate([p.colors for p in parts])
+
+
+@pytest.mark.parametrize("h,w", [pytest.param(8192, 8448, id="67584_bins_second_trip_over_the_chunk_sums")])
+def test_scan_of_more_than_64_chunks(h, w):
+    """264 x 256 tiles are 66 scan chunks: the workgroup of chunk 65 takes a second trip through the sums of the chunks before it
+    (the h cases stop at three chunks, an 8192^2 bake at 64).  Triangles lie in chunk 0, in chunk 64 and in chunk 65 up to the last
+    bin, so the second trip's term is not zero and the last offset is used."""
+    verts, tris, colors = _far_apart_soups(h, w, [(0, 0), (4000, 8000), (w - 96, h - 96)])
+    counts = BC.bin_model(verts, tris, h, w).counts.ravel()
+    assert counts.size == 66 * BC.SCAN_CHUNK and counts[:BC.SCAN_CHUNK].any() and counts[-1] > 0
+    assert counts[64 * BC.SCAN_CHUNK:65 * BC.SCAN_CHUNK].any() and counts[65 * BC.SCAN_CHUNK:].any()
+    from topo4d_amd import texture
+    image, depth = texture.render_colors(verts, tris, colors, h, w, c=1, return_depth=True)
+    want = TX.render_colors_cpu(verts, tris, colors, h, w, c=1, return_depth=True)
+    _check("66 chunks", (image.cpu().numpy(), depth.cpu().numpy()), want)
+
+
 def test_i_in_out_entry_over_a_hostile_buffer():
     """t4d_texture_bake over a caller's random image and a depth buffer that beats some triangles everywhere, is at the initial depth
     in a quarter of the texels and at +inf in a few, in the band (5, 70): the reference's result inside the band, the caller's

@@ -92,6 +92,27 @@ def test_bit_equal_at_full_capture_size():
     assert (idx >= 0).mean() > 0.05
 
 
+@pytest.mark.parametrize("H,W", [pytest.param(512, 512, id="1024_bins_one_full_chunk_no_chunk_sums"),
+                                 pytest.param(512, 528, id="1056_bins_partial_last_chunk_of_two")])
+def test_bit_equal_at_the_bin_scan_chunk_edge(H, W):
+    """One view of exactly one scan chunk of 16 x 16 tiles, and of one chunk and 32 bins: the sizes above (at most 72 bins, and
+    94 full chunks at capture size) have neither a full single chunk nor a last chunk that is partly beyond the bins.  The last
+    triangle covers the view's last tile, so the last bin's offset is read."""
+    rng = np.random.default_rng(W)
+    verts, tris, uvs = _random_mesh(rng, 12, scale=0.7)
+    verts = np.concatenate([verts, np.float32([[-9, -9, 2], [9, -9, 2], [0, 18, 2]])])      # a backdrop over the whole view
+    tris = np.concatenate([tris, [[36, 37, 38]]])
+    uvs = np.concatenate([uvs, np.float32([[0, 0], [1, 0], [0.5, 1]])])
+    tex = _texture(rng, "uint8", 64, 64)
+    view = look_at_view([0.2, 0.1, -2.5], [0, 0, 0], H, W, f=0.9 * W)
+    img, depth, idx = _gpu_render(verts, tris, tris, uvs, tex, [view], H, W)
+    c, d, i = ref.render(verts, tris, tris, uvs, tex, view, H, W)
+    assert (i[-16:, -16:] >= 0).any() and (i[:16, :16] >= 0).any()
+    assert np.array_equal(i, idx[0])
+    assert np.array_equal(d.view(np.uint32), depth[0].view(np.uint32))
+    assert np.array_equal(c.view(np.uint32), img[0].view(np.uint32))
+
+
 def test_identical_bytes_over_repeated_launches_with_dirty_scratch():
     rng = np.random.default_rng(3)
     verts, tris, uvs = _random_mesh(rng, 300, spread=0.3, scale=0.4)

@@ -84,6 +84,40 @@ def test_bit_equal_to_the_yardstick(kind, n, nq):
         assert np.array_equal(_bits(s), _bits(ref.signed_distance(q, v, f, *want)))
 
 
+def _grid_cells(extent, n, mean_extent=0.0):
+    """closest_grid of csrc/t4d_closest.hip: the cells of the grid over n primitives in a box of the given extents."""
+    e = [float(x) for x in extent]
+    area = 2.0 * (e[0] * e[1] + e[1] * e[2] + e[0] * e[2])
+    cell = 2.0 * np.sqrt(area / n) if area > 0.0 else 2.0 * max(e) / n
+    cell = max(cell, mean_extent, max(e) * 2.0 ** -10)
+    if not (cell > 0.0 and np.isfinite(cell)):
+        cell = 1.0
+    while True:
+        dim = [min(int(np.floor((x + cell) / cell)) + 1, 4096) for x in e]
+        if dim[0] * dim[1] * dim[2] <= 1 << 22 and max(dim) < 4096:
+            return dim[0] * dim[1] * dim[2]
+        cell *= 1.25
+
+
+# the index scans n_cells + 1 words in blocks of 1024, the blocks' sums 1024 a trip
+@pytest.mark.parametrize("extent,n,cells", [
+    pytest.param((1.5, 9.5, 29.5), 2710, 1023, id="1024_words_one_full_block"),
+    pytest.param((6.5, 6.5, 14.5), 1846, 1024, id="1025_words_the_total_alone_in_block_two"),
+    pytest.param((1.0, 1.0, 1.0), 250_000, 104 ** 3, id="over_2^20_words_second_trip_over_the_block_sums")])
+def test_bit_equal_at_the_index_scan_edges(extent, n, cells):
+    """Point clouds whose grid has a chosen number of cells (the sizes above reach 786 blocks at the most, none of them full to
+    the last word).  A wrong offset anywhere shows as a wrong list, so the queries spread over the whole box."""
+    assert _grid_cells(extent, n) == cells
+    rng = np.random.default_rng(n)
+    v = rng.uniform(0.0, 1.0, size=(n, 3)) * np.float64(extent)
+    v[0], v[1] = 0.0, np.float64(extent)                         # the box's corners: its extents are exact
+    q = np.concatenate([rng.uniform(0.0, 1.0, size=(192, 3)) * np.float64(extent), v[:2], v[-64:] + 1e-3])
+    index = scanscore.ClosestPointIndex(torch.from_numpy(v), None, device=DEV)
+    want = ref.closest_point(q, v)
+    _assert_bit_equal(index.query(torch.from_numpy(q).to(DEV)), want, cells)
+    _assert_bit_equal(index.query(torch.from_numpy(q).to(DEV), input_order=True), want, (cells, "input order"))
+
+
 def test_grid_path_and_brute_force_path():
     """Queries next to a dense surface end inside the shells; queries 10^3 extents away cannot (the first primitives come into
     view long after the last shell) and take the block-parallel pass.  Both equal the yardstick."""

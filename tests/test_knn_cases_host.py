@@ -88,7 +88,7 @@ def test_cases_reach_the_brute_pass_and_the_degenerate_grids():
     tc = plan("two_clusters")
     assert np.unique(np.floor((kc.cloud("two_clusters") - kc.cloud("two_clusters").min(0)) / tc["cell"]), axis=0).shape[0] <= 4
     assert (plan("volume")["radius"] >= 1).all()                                                      # not a surface
-    # scan_edge: one block of k_scan_blocks against two; the large ones, one pass of k_scan_sums against two (1024 sums a pass)
+    # scan_edge: one block of k_scan_i32_blocks against two; the large ones, one pass of k_scan_i32_sums against two (1024 sums a pass)
     table = lambda n: 1 << int(np.ceil(np.log2(2 * n)))
     assert [table(n) // 1024 for n in (512, 513, 1 << 19, (1 << 19) + 1, 1269256)] == [1, 2, 1024, 2048, 4096]
 

@@ -33,7 +33,6 @@
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kScanBlock = 1024;
 constexpr int kMaxShells = 8;
 constexpr int64_t kMaxCells = (int64_t)1 << 22;
 constexpr int kBruteBlocks = 1024;
@@ -52,7 +51,6 @@ constexpr uint64_t kMagic = 0x7434645f636c6f73ull;
 
 struct CLayout {
     size_t head, rec, start, work, bsum, entries, total;
-    int64_t nscan;                                                  // scan blocks over n_cells + 1 words
 };
 
 unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
@@ -107,13 +105,12 @@ CLayout closest_layout(const CGrid &g, int64_t entry_capacity)
 {
     CLayout L;
     const int64_t words = g.n_cells + 1;
-    L.nscan = (words + kScanBlock - 1) / kScanBlock;
     size_t o = 0;
     L.head = o;    o += 256;
     L.rec = o;     o += align_up(sizeof(double) * (g.is_tri ? 9 : 3) * (size_t)g.n_prims);
     L.start = o;   o += align_up(sizeof(int32_t) * (size_t)words);
     L.work = o;    o += align_up(sizeof(int32_t) * (size_t)words);
-    L.bsum = o;    o += align_up(sizeof(int32_t) * (size_t)(L.nscan + 1));
+    L.bsum = o;    o += align_up(sizeof(int32_t) * (size_t)t4d_scan_i32_sum_words(words));
     L.entries = o; o += align_up(sizeof(int32_t) * (size_t)entry_capacity);
     L.total = o;
     return L;
@@ -194,63 +191,6 @@ __global__ __launch_bounds__(kBlock) void k_closest_bin(const CGrid *gp, const d
                 const int32_t pos = atomicAdd(&cnt_or_cursor[cell_id(g, x, y, z)], 1);
                 if (fill && (int64_t)pos < capacity) entries[pos] = (int32_t)i;
             }
-}
-
-// in-place exclusive scan of `words` int32 (per-block scans, a scan of the block sums, then the block offsets); with a zero in
-// the last word, that word ends up holding the total
-__global__ __launch_bounds__(kScanBlock) void k_closest_scan_blocks(int32_t *a, int32_t *bsum, int64_t words)
-{
-    __shared__ int32_t s[kScanBlock];
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    const int32_t v = i < words ? a[i] : 0;
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 1; w < kScanBlock; w <<= 1) {
-        const int32_t add = (int)threadIdx.x >= w ? s[threadIdx.x - w] : 0;
-        __syncthreads();
-        s[threadIdx.x] += add;
-        __syncthreads();
-    }
-    if (i < words) a[i] = s[threadIdx.x] - v;
-    if (threadIdx.x == kScanBlock - 1) bsum[blockIdx.x] = s[threadIdx.x];
-}
-
-__global__ __launch_bounds__(kScanBlock) void k_closest_scan_sums(int32_t *bsum, int64_t nb)
-{
-    __shared__ int32_t s[kScanBlock];
-    int32_t carry = 0;
-    for (int64_t base = 0; base < nb; base += kScanBlock) {
-        const int64_t i = base + threadIdx.x;
-        const int32_t v = i < nb ? bsum[i] : 0;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int w = 1; w < kScanBlock; w <<= 1) {
-            const int32_t add = (int)threadIdx.x >= w ? s[threadIdx.x - w] : 0;
-            __syncthreads();
-            s[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (i < nb) bsum[i] = carry + s[threadIdx.x] - v;
-        const int32_t tot = s[kScanBlock - 1];
-        __syncthreads();
-        carry += tot;
-    }
-}
-
-__global__ __launch_bounds__(kScanBlock) void k_closest_scan_add(int32_t *a, int32_t *copy, const int32_t *bsum, int64_t words)
-{
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    if (i < words) {
-        a[i] += bsum[blockIdx.x];
-        if (copy) copy[i] = a[i];
-    }
-}
-
-void exclusive_scan(int32_t *a, int32_t *copy, int32_t *bsum, int64_t words, int64_t nscan, hipStream_t stream)
-{
-    hipLaunchKernelGGL(k_closest_scan_blocks, dim3((unsigned)nscan), dim3(kScanBlock), 0, stream, a, bsum, words);
-    hipLaunchKernelGGL(k_closest_scan_sums, dim3(1), dim3(kScanBlock), 0, stream, bsum, nscan);
-    hipLaunchKernelGGL(k_closest_scan_add, dim3((unsigned)nscan), dim3(kScanBlock), 0, stream, a, copy, bsum, words);
 }
 
 // each cell's list in ascending primitive index (the atomics of the fill leave it in schedule order): heap sort, one lane a cell
@@ -674,7 +614,7 @@ T4D_EXPORT int t4d_closest_build(const double *vertices, int64_t n_vert, const i
     T4D_HIP_CHECK(hipMemsetAsync(start, 0, sizeof(int32_t) * (size_t)(g.n_cells + 1), stream));
     hipLaunchKernelGGL(k_closest_records, dim3(blocks(g.n_prims, kBlock)), dim3(kBlock), 0, stream, vertices, faces, gd, rec);
     hipLaunchKernelGGL(k_closest_bin, dim3(blocks(g.n_prims, kBlock)), dim3(kBlock), 0, stream, gd, rec, start, entries, entry_capacity, 0);
-    exclusive_scan(start, work, bsum, g.n_cells + 1, L.nscan, stream);
+    t4d_scan_i32(start, start, work, bsum, g.n_cells + 1, stream);
     int32_t total = 0;
     T4D_HIP_CHECK(hipMemcpyAsync(&total, start + g.n_cells, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     T4D_HIP_CHECK(hipStreamSynchronize(stream));
@@ -750,7 +690,7 @@ T4D_EXPORT int t4d_closest_query(void *index, size_t index_bytes, const double *
     if (sorted) {
         T4D_HIP_CHECK(hipMemsetAsync(work, 0, sizeof(int32_t) * (size_t)(g.n_cells + 1), stream));
         hipLaunchKernelGGL(k_closest_query_cells, dim3(blocks(n_queries, kBlock)), dim3(kBlock), 0, stream, gd, points, n_queries, qcell, work);
-        exclusive_scan(work, nullptr, bsum, g.n_cells + 1, L.nscan, stream);
+        t4d_scan_i32(work, work, nullptr, bsum, g.n_cells + 1, stream);
         hipLaunchKernelGGL(k_closest_query_order, dim3(blocks(n_queries, kBlock)), dim3(kBlock), 0, stream, qcell, n_queries, work, order);
     }
     T4D_HIP_CHECK(hipMemsetAsync(fall, 0, sizeof(int32_t), stream));
@@ -803,7 +743,7 @@ T4D_EXPORT int t4d_closest_raycast(void *index, size_t index_bytes, const double
     if (sorted) {                                                   // the rays grouped by the cell of their origin
         T4D_HIP_CHECK(hipMemsetAsync(work, 0, sizeof(int32_t) * (size_t)(g.n_cells + 1), stream));
         hipLaunchKernelGGL(k_closest_query_cells, dim3(blocks(n_rays, kBlock)), dim3(kBlock), 0, stream, gd, origins, n_rays, qcell, work);
-        exclusive_scan(work, nullptr, bsum, g.n_cells + 1, L.nscan, stream);
+        t4d_scan_i32(work, work, nullptr, bsum, g.n_cells + 1, stream);
         hipLaunchKernelGGL(k_closest_query_order, dim3(blocks(n_rays, kBlock)), dim3(kBlock), 0, stream, qcell, n_rays, work, order);
     }
     hipLaunchKernelGGL(k_closest_raycast, dim3(blocks(n_rays, kBlock)), dim3(kBlock), 0, stream, gd, rec, start, entries, origins, dirs, n_rays,

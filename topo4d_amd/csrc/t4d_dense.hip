@@ -219,10 +219,8 @@ struct Grid {
 
 struct KnnLayout {
     size_t bbox, keys, cnt, start, cursor, slot, spts, sidx, bsum, fall, total;
-    int64_t table, nblocks_scan;
+    int64_t table;
 };
-
-constexpr int kScanBlock = 1024;
 
 KnnLayout knn_layout(int64_t n)
 {
@@ -230,7 +228,6 @@ KnnLayout knn_layout(int64_t n)
     int64_t t = 1;
     while (t < 2 * n) t <<= 1;                                      // at most n occupied cells: load factor <= 1/2
     L.table = t;
-    L.nblocks_scan = (t + kScanBlock - 1) / kScanBlock;
     size_t o = 0;
     L.bbox = o;   o += align_up(sizeof(double) * 6 * 1024);         // per-block min / max partials, then the grid
     L.keys = o;   o += align_up(sizeof(uint64_t) * t);
@@ -240,7 +237,7 @@ KnnLayout knn_layout(int64_t n)
     L.slot = o;   o += align_up(sizeof(int32_t) * n);
     L.spts = o;   o += align_up(sizeof(double) * 3 * n);
     L.sidx = o;   o += align_up(sizeof(int32_t) * n);
-    L.bsum = o;   o += align_up(sizeof(int32_t) * (L.nblocks_scan + 1));
+    L.bsum = o;   o += align_up(sizeof(int32_t) * t4d_scan_i32_sum_words(t));
     L.fall = o;   o += align_up(sizeof(int32_t) * (n + 1));         // [0]: count, then the open queries
     L.total = o + 256;                                              // + the Grid record
     return L;
@@ -334,55 +331,6 @@ __global__ __launch_bounds__(kBlock) void k_insert(const double *p, int64_t n, c
     }
     atomicAdd(&cnt[h], 1);
     slot[i] = (int32_t)h;
-}
-
-// exclusive scan of cnt over the table: per-block scans, a scan of the block sums, then the block offsets
-__global__ __launch_bounds__(kScanBlock) void k_scan_blocks(const int32_t *cnt, int32_t *start, int32_t *bsum, int64_t t)
-{
-    __shared__ int32_t s[kScanBlock];
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    const int32_t v = i < t ? cnt[i] : 0;
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 1; w < kScanBlock; w <<= 1) {
-        const int32_t add = (int)threadIdx.x >= w ? s[threadIdx.x - w] : 0;
-        __syncthreads();
-        s[threadIdx.x] += add;
-        __syncthreads();
-    }
-    if (i < t) start[i] = s[threadIdx.x] - v;
-    if (threadIdx.x == kScanBlock - 1) bsum[blockIdx.x] = s[threadIdx.x];
-}
-
-__global__ __launch_bounds__(kScanBlock) void k_scan_sums(int32_t *bsum, int64_t nb)
-{
-    __shared__ int32_t s[kScanBlock];
-    int32_t carry = 0;
-    for (int64_t base = 0; base < nb; base += kScanBlock) {
-        const int64_t i = base + threadIdx.x;
-        const int32_t v = i < nb ? bsum[i] : 0;
-        s[threadIdx.x] = v;
-        __syncthreads();
-        for (int w = 1; w < kScanBlock; w <<= 1) {
-            const int32_t add = (int)threadIdx.x >= w ? s[threadIdx.x - w] : 0;
-            __syncthreads();
-            s[threadIdx.x] += add;
-            __syncthreads();
-        }
-        if (i < nb) bsum[i] = carry + s[threadIdx.x] - v;
-        const int32_t tot = s[kScanBlock - 1];
-        __syncthreads();
-        carry += tot;
-    }
-}
-
-__global__ __launch_bounds__(kScanBlock) void k_scan_add(int32_t *start, int32_t *cursor, const int32_t *bsum, int64_t t)
-{
-    const int64_t i = (int64_t)blockIdx.x * kScanBlock + threadIdx.x;
-    if (i < t) {
-        start[i] += bsum[blockIdx.x];
-        cursor[i] = start[i];
-    }
 }
 
 // points grouped by cell (the order inside a cell depends on the schedule; the query result does not)
@@ -592,9 +540,7 @@ T4D_EXPORT int t4d_knn_mean_sq_dist(const double *points, int64_t n, int32_t k, 
     hipLaunchKernelGGL(k_grid, dim3(1), dim3(1), 0, stream, part, nb, n, grid);
     hipLaunchKernelGGL(k_fill, dim3(blocks(L.table, kBlock)), dim3(kBlock), 0, stream, keys, cnt, L.table);
     hipLaunchKernelGGL(k_insert, dim3(blocks(n, kBlock)), dim3(kBlock), 0, stream, points, n, grid, keys, cnt, slot, mask);
-    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)L.nblocks_scan), dim3(kScanBlock), 0, stream, cnt, start, bsum, L.table);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanBlock), 0, stream, bsum, L.nblocks_scan);
-    hipLaunchKernelGGL(k_scan_add, dim3((unsigned)L.nblocks_scan), dim3(kScanBlock), 0, stream, start, cursor, bsum, L.table);
+    t4d_scan_i32(cnt, start, cursor, bsum, L.table, stream);
     hipLaunchKernelGGL(k_scatter, dim3(blocks(n, kBlock)), dim3(kBlock), 0, stream, points, n, slot, cursor, spts, sidx);
     hipError_t e = hipMemsetAsync(fall, 0, sizeof(int32_t), stream);
     if (e != hipSuccess) return t4d_fail(T4D_ERR_HIP, "t4d_knn_mean_sq_dist memset: %s", hipGetErrorString(e));

@@ -44,4 +44,17 @@ static inline int t4d_launch_status(const char *entry)
 int t4d_closest_index_records(const char *entry, const void *index, size_t index_bytes, void *hip_stream, const double **records,
                               int64_t *n_prims, int *is_tri);
 
+// t4d_scan.hip: exclusive scan of `words` int32 from `in` to `out` (in == out allowed), also written to `copy` unless that is
+// NULL.  With a zero in the last word of `in`, the last word of `out` holds the total.  `bsum` is scratch of
+// t4d_scan_i32_sum_words(words) int32.
+constexpr int kScanI32Block = 1024;
+static inline int64_t t4d_scan_i32_sum_words(int64_t words) { return (words + kScanI32Block - 1) / kScanI32Block + 1; }
+void t4d_scan_i32(const int32_t *in, int32_t *out, int32_t *copy, int32_t *bsum, int64_t words, hipStream_t stream);
+
+// t4d_scan.hip: off[b] = count[0] + ... + count[b - 1] for nb >= 1 bins, saturated at 0xffffffff, and *total = the sum of all
+// counts in 64 bits.  `chunk_sum` is scratch of t4d_scan_bins_chunks(nb) uint32.
+constexpr int kScanBinsChunk = 1024;
+static inline int t4d_scan_bins_chunks(int nb) { return (nb + kScanBinsChunk - 1) / kScanBinsChunk; }
+void t4d_scan_bins(const uint32_t *count, int nb, uint32_t *off, uint32_t *chunk_sum, unsigned long long *total, hipStream_t stream);
+
 static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }

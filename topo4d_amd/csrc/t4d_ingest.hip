@@ -20,6 +20,7 @@
 // range: _clip_warp_output), k_warp (order-1 warp in float64 through an LDS-staged source tile, clip, round to float32).
 #include <hip/hip_runtime.h>
 
+#include "t4d_block.h"
 #include "t4d_host.h"
 #include "t4d_jpeg.h"
 
@@ -49,8 +50,6 @@ struct Layout {
     size_t plans, huff, tiles, clen, nrst, compact, rst, S, E0, E1, counts, prefix, changed, coef, planes, total;
     int64_t n_tiles, n_lanes, n_segs, n_blocks, n_px, data_bytes, plane_bytes;
 };
-
-__host__ __device__ inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // the plans (may be NULL) and the totals; false: an image the decoder does not take
 __host__ __device__ inline bool make_plans(const T4DJpegImage *im, int n, int chunk_bits, ImgPlan *plans, Layout *L)
@@ -163,26 +162,9 @@ __device__ inline int keep_byte(const uint8_t *d, int64_t nb, int64_t j, int *rs
 
 constexpr uint64_t kRstOne = 1ull << 40;
 
-__device__ inline uint64_t block_exclusive_scan(uint64_t v, uint64_t *total)
-{
-    __shared__ uint64_t s[kBlock];
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int off = 1; off < kBlock; off <<= 1) {
-        const uint64_t x = t >= off ? s[t - off] : 0;
-        __syncthreads();
-        s[t] += x;
-        __syncthreads();
-    }
-    const uint64_t incl = s[t];
-    *total = s[kBlock - 1];
-    __syncthreads();
-    return incl - v;
-}
-
 __global__ void k_stuff_count(const ImgPlan *P, int n, const uint8_t *data, uint64_t *tiles)
 {
+    __shared__ uint64_t tmp[kBlock];
     const int64_t tile = blockIdx.x;
     const int i = find_plan(P, n, tile, [](const ImgPlan &p) { return p.tile_base; });
     const ImgPlan &p = P[i];
@@ -195,19 +177,20 @@ __global__ void k_stuff_count(const ImgPlan *P, int n, const uint8_t *data, uint
         v += rst ? kRstOne : 0;
     }
     uint64_t total;
-    block_exclusive_scan(v, &total);
+    block_exclusive_scan<kBlock>(v, tmp, &total);
     if (threadIdx.x == 0) tiles[tile] = total;
 }
 
 __global__ void k_stuff_scan(const ImgPlan *P, uint64_t *tiles, int64_t *clen, int64_t *nrst, int32_t *status)
 {
+    __shared__ uint64_t tmp[kBlock];
     const ImgPlan &p = P[blockIdx.x];
     uint64_t carry = 0;
     for (int64_t b = 0; b < p.n_tiles; b += kBlock) {
         const int64_t t = b + threadIdx.x;
         const uint64_t v = t < p.n_tiles ? tiles[p.tile_base + t] : 0;
         uint64_t total;
-        const uint64_t ex = block_exclusive_scan(v, &total);
+        const uint64_t ex = block_exclusive_scan<kBlock>(v, tmp, &total);
         if (t < p.n_tiles) tiles[p.tile_base + t] = carry + ex;
         carry += total;
     }
@@ -221,6 +204,7 @@ __global__ void k_stuff_scan(const ImgPlan *P, uint64_t *tiles, int64_t *clen, i
 __global__ void k_stuff_write(const ImgPlan *P, int n, const uint8_t *data, const uint64_t *tiles, uint8_t *compact,
                               int64_t *rst_pos, int32_t *status)
 {
+    __shared__ uint64_t tmp[kBlock];
     const int64_t tile = blockIdx.x;
     const int i = find_plan(P, n, tile, [](const ImgPlan &p) { return p.tile_base; });
     const ImgPlan &p = P[i];
@@ -234,7 +218,7 @@ __global__ void k_stuff_write(const ImgPlan *P, int n, const uint8_t *data, cons
         v += rst ? kRstOne : 0;
     }
     uint64_t total;
-    uint64_t at = tiles[tile] + block_exclusive_scan(v, &total);
+    uint64_t at = tiles[tile] + block_exclusive_scan<kBlock>(v, tmp, &total);
     for (int64_t j = j0; j < j0 + 16 && j < p.data_bytes; j++) {
         int rst;
         const int k = keep_byte(d, p.data_bytes, j, &rst);
@@ -327,20 +311,19 @@ __global__ void k_jpeg_sync_fallback(const ImgPlan *P, int n, const T4DJpegImage
 // exclusive prefix of the lanes' counts: the global index of a lane's first DC symbol and its DC predictors at entry
 __global__ void k_jpeg_lane_scan(const ImgPlan *P, const LaneCounts *counts, LaneCounts *prefix)
 {
+    __shared__ uint32_t tmp[kBlock];
     const ImgPlan &p = P[blockIdx.x];
     if (p.restart > 0) return;
-    int64_t carry[4] = {0, 0, 0, 0};
+    uint32_t carry[4] = {0, 0, 0, 0};                               // 32-bit two's-complement sums
     for (int64_t b = 0; b < p.n_lanes; b += kBlock) {
         const int64_t t = b + threadIdx.x;
         LaneCounts c = t < p.n_lanes ? counts[p.lane_base + t] : LaneCounts{0, {0, 0, 0}};
         const int32_t v[4] = {c.blocks, c.dc[0], c.dc[1], c.dc[2]};
         int32_t ex[4];
         for (int q = 0; q < 4; q++) {
-            uint64_t total;
-            // 32-bit two's-complement sums carried in the low word of the 64-bit scan
-            ex[q] = (int32_t)(uint32_t)block_exclusive_scan((uint64_t)(uint32_t)v[q], &total);
-            ex[q] = (int32_t)((uint32_t)ex[q] + (uint32_t)carry[q]);
-            carry[q] = (int64_t)(uint32_t)((uint32_t)carry[q] + (uint32_t)total);
+            uint32_t total;
+            ex[q] = (int32_t)(carry[q] + block_exclusive_scan<kBlock>((uint32_t)v[q], tmp, &total));
+            carry[q] += total;
         }
         if (t < p.n_lanes) prefix[p.lane_base + t] = LaneCounts{ex[0], {ex[1], ex[2], ex[3]}};
     }
@@ -450,22 +433,6 @@ __host__ __device__ inline int64_t warp_tiles(const T4DWarpView &v)
 __host__ __device__ inline int64_t range_blocks(const T4DWarpView &v)
 {
     return div_up((int64_t)v.rows * v.cols * v.channels, kRangeBytes);
-}
-
-template <typename F>
-__device__ inline int find_view(const T4DWarpView *V, int n, int64_t b, int64_t *local, F count)
-{
-    int64_t base = 0;
-    for (int i = 0; i < n; i++) {
-        const int64_t c = count(V[i]);
-        if (b < base + c) {
-            *local = b - base;
-            return i;
-        }
-        base += c;
-    }
-    *local = 0;
-    return -1;
 }
 
 __device__ inline unsigned long long order_key(double x)

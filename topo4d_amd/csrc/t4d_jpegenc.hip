@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "../../include/topo4d_raster.h"
+#include "t4d_block.h"
 #include "t4d_host.h"
 #include "t4d_jpeg_fdct.h"
 
@@ -285,39 +286,6 @@ __device__ __forceinline__ void walk_block(const int16_t *c, int pred, const uin
     if (run) put(ac[0] & 0xFFFFu, (int)(ac[0] >> 16));
 }
 
-__device__ __forceinline__ int block_sum(int v, int *tmp)
-{
-    const int t = threadIdx.x;
-    tmp[t] = v;
-    __syncthreads();
-    for (int st = kBlock / 2; st > 0; st >>= 1) {
-        if (t < st) tmp[t] += tmp[t + st];
-        __syncthreads();
-    }
-    const int all = tmp[0];
-    __syncthreads();
-    return all;
-}
-
-// exclusive prefix of one value per thread (Hillis-Steele in LDS); *total: the sum
-template <typename T>
-__device__ __forceinline__ T block_exclusive(T v, T *tmp, T *total)
-{
-    const int t = threadIdx.x;
-    tmp[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const T o = t >= d ? tmp[t - d] : (T)0;
-        __syncthreads();
-        tmp[t] += o;
-        __syncthreads();
-    }
-    const T excl = tmp[t] - v;
-    if (total) *total = tmp[kBlock - 1];
-    __syncthreads();
-    return excl;
-}
-
 template <int SS>
 __global__ __launch_bounds__(kBlock) void k_enc_size(const EncImage *plan, const int64_t *chunk0, int n, const int16_t *coef,
                                                      uint16_t *bits, int32_t *chunk_sum)
@@ -340,7 +308,7 @@ __global__ __launch_bounds__(kBlock) void k_enc_size(const EncImage *plan, const
         walk_block(c, pred, S.dc[tab], S.ac[tab], [&](uint32_t, int len) { nbits += len; });
     }
     bits[(int64_t)blockIdx.x * kBlock + threadIdx.x] = (uint16_t)nbits;
-    const int all = block_sum(nbits, tmp);
+    const int all = block_sum<kBlock>(nbits, tmp);
     if (threadIdx.x == 0) chunk_sum[blockIdx.x] = all;
 }
 
@@ -360,7 +328,7 @@ __global__ __launch_bounds__(kBlock) void k_enc_scan(const int64_t *first, const
     int64_t sum = 0;
     for (int64_t k = k0; k < k1; ++k) sum += sums[c0 + k];
     int64_t all = 0;
-    int64_t o = block_exclusive<int64_t>(sum, tmp, &all);
+    int64_t o = block_exclusive_scan<kBlock>(sum, tmp, &all);
     for (int64_t k = k0; k < k1; ++k) {
         off[c0 + k] = o;
         o += sums[c0 + k];
@@ -388,7 +356,7 @@ __global__ __launch_bounds__(kBlock) void k_enc_emit(const EncImage *plan, const
     const EncImage &im = plan[i];
     const int64_t b = ((int64_t)blockIdx.x - chunk0[i]) * kBlock + threadIdx.x;
     const int mine = bits[(int64_t)blockIdx.x * kBlock + threadIdx.x];
-    const int64_t at = chunk_off[blockIdx.x] + block_exclusive<int>(mine, tmp, nullptr);
+    const int64_t at = chunk_off[blockIdx.x] + block_exclusive_scan<kBlock, int>(mine, tmp, nullptr);
     if (b >= im.g.blocks) return;
     const int64_t m = b / BPM;
     const int k = (int)(b - m * BPM);
@@ -450,7 +418,7 @@ __global__ __launch_bounds__(kBlock) void k_enc_count(const EncImage *plan, cons
     int ff = 0;
 #pragma unroll
     for (int e = 0; e < kStuffPer; ++e) ff += (e < cnt && by[e] == 0xFF) ? 1 : 0;
-    const int all = block_sum(ff, tmp);
+    const int all = block_sum<kBlock>(ff, tmp);
     if (threadIdx.x == 0) ff_cnt[blockIdx.x] = all;
 }
 
@@ -494,7 +462,7 @@ __global__ __launch_bounds__(kBlock) void k_enc_scatter(const EncImage *plan, co
     int ff = 0;
 #pragma unroll
     for (int e = 0; e < kStuffPer; ++e) ff += (e < cnt && by[e] == 0xFF) ? 1 : 0;
-    const int before = block_exclusive<int>(ff, tmp, nullptr);
+    const int before = block_exclusive_scan<kBlock, int>(ff, tmp, nullptr);
     uint8_t *p = file + kJpegEncHeaderBytes + j0 + ff_off[blockIdx.x] + before;
 #pragma unroll
     for (int e = 0; e < kStuffPer; ++e) {

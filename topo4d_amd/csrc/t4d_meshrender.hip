@@ -13,7 +13,7 @@
 //                clamped; bilinear, or nearest with round-half-even; a uint8 texel reads as x / 255.0
 // Everything is float64 with FP contraction off; outputs are rounded to float32 once.  The launch set follows the UV bake of
 // t4d_texture.hip:
-//   k_mr_setup<count> / k_mr_chunk_sums / k_mr_scan / k_mr_setup<fill>   per-(view, triangle) record, then (triangle, 16x16 tile)
+//   k_mr_setup<count> / t4d_scan_bins / k_mr_setup<fill>   per-(view, triangle) record, then (triangle, 16x16 tile)
 //                pairs binned with a count / scan / fill; on a pair-capacity overflow the host learns the size and retries
 //   k_mr_tile    one workgroup per (view, tile): a triangle visits the pixels of its box inside the tile (16 lanes per record),
 //                a covered pixel enters an LDS 64-bit minimum with its key; then every pixel re-evaluates its winner with the very
@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include "../../include/topo4d_raster.h"
+#include "t4d_block.h"
 #include "t4d_host.h"
 
 namespace {
@@ -34,7 +35,6 @@ constexpr int kTile = 16;                    // 16x16 pixels per bin and per wor
 constexpr int kBlock = 256;
 constexpr int kStage = 64;                   // records staged in LDS per round (96 B each)
 constexpr int kGroup = 16;                   // lanes per record in the coverage loop
-constexpr int kScanChunk = 1024;
 constexpr double kNear = 0.01;               // setup_camera's near plane
 constexpr unsigned long long kNoKey = ~0ull;
 
@@ -55,12 +55,11 @@ struct MRP {
     const int32_t *tri, *uvtri;
     const uint8_t *texb;
     int nvert, ntri, nuv, th, tw, V, H, W, mapping;
-    int tx, ty, tpv, nb, n_chunks;           // tiles in x, in y, per view; bins; scan chunks
+    int tx, ty, tpv, nb;                     // tiles in x, in y, per view; bins
     uint32_t cap;
     float bg0, bg1, bg2;
     MRec *recs;
-    uint32_t *bin_count, *bin_cursor, *bin_off, *chunk_sum, *list;
-    unsigned long long *total;
+    uint32_t *bin_count, *bin_cursor, *bin_off, *list;
     float *color, *depth;
     int32_t *index;
 };
@@ -173,59 +172,6 @@ __global__ __launch_bounds__(kBlock) void k_mr_setup(const MRP P)
                 atomicAdd(&P.bin_count[b], 1u);
             }
         }
-}
-
-__global__ __launch_bounds__(kScanChunk) void k_mr_chunk_sums(const MRP P)
-{
-    __shared__ uint32_t s_w[kScanChunk / 64];
-    const int c = blockIdx.x, tid = threadIdx.x, b = c * kScanChunk + tid;
-    uint32_t x = b < P.nb ? P.bin_count[b] : 0u;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += (uint32_t)__shfl_xor((int)x, d, 64);
-    if ((tid & 63) == 0) s_w[tid >> 6] = x;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t tot = 0;
-#pragma unroll
-        for (int w = 0; w < kScanChunk / 64; w++) tot += s_w[w];
-        P.chunk_sum[c] = tot;
-    }
-}
-
-__global__ __launch_bounds__(kScanChunk) void k_mr_scan(const MRP P)
-{
-    __shared__ uint32_t s_w[16];
-    __shared__ unsigned long long s_carry;
-    const int chunk = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    if (wave == 0) {                                                // pairs in the chunks before this one
-        unsigned long long part = 0;
-        for (int i = lane; i < chunk; i += 64) part += P.chunk_sum[i];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1)
-            part += ((unsigned long long)(uint32_t)__shfl_xor((int)(part >> 32), d, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)part, d, 64);
-        if (lane == 0) s_carry = part;
-    }
-    const int b = chunk * kScanChunk + tid;
-    const uint32_t c = b < P.nb ? P.bin_count[b] : 0u;
-    uint32_t incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const uint32_t x = s_w[k];
-        if (k < wave) woff += x;
-        tot += x;
-    }
-    const unsigned long long carry = s_carry;
-    const unsigned long long off = carry + woff + incl - c;
-    if (b < P.nb) P.bin_off[b] = off > 0xffffffffull ? 0xffffffffu : (uint32_t)off;
-    if (tid == 0 && chunk == P.n_chunks - 1) *P.total = carry + tot;
 }
 
 __device__ __forceinline__ double texel(const MRP &P, const int iy, const int ix, const int c)
@@ -343,7 +289,7 @@ MRLayout mr_layout(int V, int ntri, int h, int w, int64_t cap)
     L.bin_cursor = o; o = align_up(o + nb * 4);
     L.zero_end = o;
     L.bin_off = o;    o = align_up(o + nb * 4);
-    L.chunk_sum = o;  o = align_up(o + ((nb + kScanChunk - 1) / kScanChunk) * 4);
+    L.chunk_sum = o;  o = align_up(o + ((nb + kScanBinsChunk - 1) / kScanBinsChunk) * 4);
     L.recs = o;       o = align_up(o + (size_t)V * ntri * sizeof(MRec));
     L.list = o;       o = align_up(o + (size_t)cap * 4);
     L.bytes = o;
@@ -370,13 +316,6 @@ struct IMP {
     double *part, *out;
     float win[kWin];
 };
-
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
 
 __global__ __launch_bounds__(kBlock) void k_im_tile(const IMP P)
 {
@@ -518,14 +457,11 @@ T4D_EXPORT int t4d_mesh_render(const float *vertices, int32_t n_vert, const int3
     P.tri = triangles; P.uvtri = uv_triangles;
     P.nvert = n_vert; P.ntri = n_tri; P.nuv = n_uv; P.th = tex_h; P.tw = tex_w; P.V = n_views; P.H = h; P.W = w; P.mapping = mapping;
     P.tx = (w + kTile - 1) / kTile; P.ty = (h + kTile - 1) / kTile; P.tpv = P.tx * P.ty; P.nb = n_views * P.tpv;
-    P.n_chunks = (P.nb + kScanChunk - 1) / kScanChunk;
     P.cap = (uint32_t)pair_capacity;
     P.bg0 = background[0]; P.bg1 = background[1]; P.bg2 = background[2];
-    P.total = (unsigned long long *)(sc + L.total_);
     P.bin_count = (uint32_t *)(sc + L.bin_count);
     P.bin_cursor = (uint32_t *)(sc + L.bin_cursor);
     P.bin_off = (uint32_t *)(sc + L.bin_off);
-    P.chunk_sum = (uint32_t *)(sc + L.chunk_sum);
     P.recs = (MRec *)(sc + L.recs);
     P.list = (uint32_t *)(sc + L.list);
     P.color = color; P.depth = depth; P.index = tri_index;
@@ -534,10 +470,10 @@ T4D_EXPORT int t4d_mesh_render(const float *vertices, int32_t n_vert, const int3
     if (n_tri > 0) {
         const int gt = (int)(((size_t)n_views * n_tri + kBlock - 1) / kBlock);
         hipLaunchKernelGGL(k_mr_setup<false>, dim3(gt), dim3(kBlock), 0, stream, P);
-        if (P.n_chunks > 1) hipLaunchKernelGGL(k_mr_chunk_sums, dim3(P.n_chunks), dim3(kScanChunk), 0, stream, P);
-        hipLaunchKernelGGL(k_mr_scan, dim3(P.n_chunks), dim3(kScanChunk), 0, stream, P);
+        unsigned long long *d_total = (unsigned long long *)(sc + L.total_);
+        t4d_scan_bins(P.bin_count, P.nb, P.bin_off, (uint32_t *)(sc + L.chunk_sum), d_total, stream);
         unsigned long long total = 0;
-        T4D_HIP_CHECK(hipMemcpyAsync(&total, P.total, 8, hipMemcpyDeviceToHost, stream));
+        T4D_HIP_CHECK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, stream));
         T4D_HIP_CHECK(hipStreamSynchronize(stream));          // once per frame: the pair count decides the fill
         if (pairs_needed) *pairs_needed = (int64_t)total;
         if (total > (unsigned long long)pair_capacity)

@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "../../include/topo4d_raster.h"
+#include "t4d_block.h"
 #include "t4d_host.h"
 #include "t4d_repr.h"
 
@@ -36,25 +37,7 @@ struct GlobalTransform {
     double t[3];
 };
 
-// ---- one-workgroup exclusive scans ---------------------------------------------------------------------------------------
-template <typename T>
-__device__ T block_exclusive_scan(T x, T *sh, T *total)
-{
-    const int t = threadIdx.x;
-    sh[t] = x;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const T v = t >= d ? sh[t - d] : (T)0;
-        __syncthreads();
-        sh[t] += v;
-        __syncthreads();
-    }
-    const T incl = sh[t];
-    *total = sh[kBlock - 1];
-    __syncthreads();
-    return incl - x;
-}
-
+// ---- one-workgroup exclusive scan ----------------------------------------------------------------------------------------
 // in[0..n) -> out[0..n] exclusive (out[n] = the sum); in == out allowed
 template <typename T>
 __global__ void __launch_bounds__(kBlock) k_obj_scan(const T *in, int64_t n, T *out, int64_t *total_out)
@@ -65,7 +48,7 @@ __global__ void __launch_bounds__(kBlock) k_obj_scan(const T *in, int64_t n, T *
         const int64_t i = base + threadIdx.x;
         const T x = i < n ? in[i] : (T)0;
         T tot;
-        const T ex = block_exclusive_scan(x, sh, &tot);
+        const T ex = block_exclusive_scan<kBlock>(x, sh, &tot);
         if (i < n) out[i] = carry + ex;
         carry += tot;
     }
@@ -301,7 +284,7 @@ __global__ void __launch_bounds__(kBlock) k_obj_float_rows(const double *values,
         line_len[r] = (int32_t)len;
     }
     int64_t tot;
-    block_exclusive_scan(len, sh, &tot);
+    block_exclusive_scan<kBlock>(len, sh, &tot);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
 
@@ -312,7 +295,7 @@ __global__ void __launch_bounds__(kBlock) k_obj_float_emit(int64_t rows, const u
     __shared__ int64_t sh[kBlock];
     const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     int64_t tot;
-    const int64_t ex = block_exclusive_scan(r < rows ? (int64_t)line_len[r] : (int64_t)0, sh, &tot);
+    const int64_t ex = block_exclusive_scan<kBlock>(r < rows ? (int64_t)line_len[r] : (int64_t)0, sh, &tot);
     if (r >= rows) return;
     uint8_t *p = out + block_offs[blockIdx.x] + ex;
     *p++ = 'v';
@@ -339,7 +322,7 @@ __global__ void __launch_bounds__(kBlock) k_obj_face_rows(const int64_t *face_of
         line_len[f] = (int32_t)len;
     }
     int64_t tot;
-    block_exclusive_scan(len, sh, &tot);
+    block_exclusive_scan<kBlock>(len, sh, &tot);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
 
@@ -350,7 +333,7 @@ __global__ void __launch_bounds__(kBlock) k_obj_face_emit(const int64_t *face_of
     __shared__ int64_t sh[kBlock];
     const int64_t f = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     int64_t tot;
-    const int64_t ex = block_exclusive_scan(f < n_faces ? (int64_t)line_len[f] : (int64_t)0, sh, &tot);
+    const int64_t ex = block_exclusive_scan<kBlock>(f < n_faces ? (int64_t)line_len[f] : (int64_t)0, sh, &tot);
     if (f >= n_faces) return;
     const int64_t at = block_offs[blockIdx.x] + ex;
     if (at + line_len[f] > out_capacity) return;                      // only with an inconsistent face_off (checked on the host)

@@ -27,6 +27,7 @@
 #include <math.h>
 
 #include "../../include/topo4d_raster.h"
+#include "t4d_block.h"
 #include "t4d_host.h"
 #include "t4d_png_huff.h"
 #include "t4d_quant.h"
@@ -214,29 +215,6 @@ __global__ __launch_bounds__(kBlock) void k_png_filter(const void *img, Shape s,
         const uint32_t pred = best == 0 ? 0u : best == 1 ? a : best == 2 ? b : best == 3 ? ((a + b) >> 1) : paeth(a, b, cc);
         out[1 + x] = (uint8_t)(v - pred);
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// block helpers (256 threads)
-// ---------------------------------------------------------------------------------------------------------------------------
-// exclusive scan of one value per thread; OP is + / max / min.  `tmp` holds kBlock entries.
-template <typename T, typename Op>
-__device__ T block_exclusive(T v, T identity, T *tmp, Op op, T *total)
-{
-    const int t = threadIdx.x;
-    tmp[t] = v;
-    __syncthreads();
-    for (int d = 1; d < kBlock; d <<= 1) {
-        const T o = t >= d ? tmp[t - d] : identity;
-        __syncthreads();
-        tmp[t] = op(tmp[t], o);
-        __syncthreads();
-    }
-    const T all = tmp[kBlock - 1];
-    const T excl = t > 0 ? tmp[t - 1] : identity;
-    __syncthreads();
-    if (total) *total = all;
-    return excl;
 }
 
 // reflected CRC-32 arithmetic: a * b mod P, bit 31 holds x^0
@@ -437,14 +415,14 @@ __global__ __launch_bounds__(kBlock) void k_png_encode(const uint8_t *filt, Shap
     int lmax = -1, lmin = n;
     for (int j = sl.c0; j < sl.c1; ++j)
         if (is_bnd(S.in, j)) { lmax = j; if (lmin == n) lmin = j; }
-    sl.prev_bnd = block_exclusive<int>(lmax, -1, S.scan_i32, [](int a, int b) { return max(a, b); }, nullptr);
+    sl.prev_bnd = block_exclusive_scan<kBlock, int>(lmax, -1, S.scan_i32, [](int a, int b) { return max(a, b); }, nullptr);
     {
         // suffix min: the exclusive prefix min over the reversed thread order
         S.scan_i32[t] = lmin;
         __syncthreads();
         const int rv = S.scan_i32[kBlock - 1 - t];
         __syncthreads();
-        const int e = block_exclusive<int>(rv, n, S.scan_i32, [](int a, int b) { return min(a, b); }, nullptr);
+        const int e = block_exclusive_scan<kBlock, int>(rv, n, S.scan_i32, [](int a, int b) { return min(a, b); }, nullptr);
         S.scan_i32[kBlock - 1 - t] = e;
         __syncthreads();
         sl.next_bnd = S.scan_i32[t];
@@ -492,8 +470,7 @@ __global__ __launch_bounds__(kBlock) void k_png_encode(const uint8_t *filt, Shap
     walk_tokens(S.in, sl, [&](uint32_t b) { my_bits += S.lit_len[b]; },
                 [&](int l) { const int li = len_index(l); my_bits += S.lit_len[257 + li] + c_len_extra[li] + 1; });
     unsigned long long data_bits = 0;
-    const unsigned long long my_off = block_exclusive<unsigned long long>(
-        my_bits, 0ull, S.scan_u64, [](unsigned long long a, unsigned long long b) { return a + b; }, &data_bits);
+    const unsigned long long my_off = block_exclusive_scan<kBlock>(my_bits, S.scan_u64, &data_bits);
     const uint64_t end_bits = S.head_bits + data_bits + S.lit_len[256];
     const uint64_t sync_at = last ? 0 : (end_bits + 3 + 7) / 8;       // byte of the empty stored block's LEN
     const uint64_t huff_bytes = last ? (end_bits + 7) / 8 : sync_at + 4;
@@ -563,8 +540,8 @@ __global__ __launch_bounds__(kBlock) void k_png_encode(const uint8_t *filt, Shap
         __syncthreads();
     }
     unsigned long long sa = 0, sb = 0;
-    block_exclusive<unsigned long long>(a, 0ull, S.scan_u64, [](unsigned long long x, unsigned long long y) { return x + y; }, &sa);
-    block_exclusive<unsigned long long>(b, 0ull, S.scan_u64, [](unsigned long long x, unsigned long long y) { return x + y; }, &sb);
+    block_exclusive_scan<kBlock>(a, S.scan_u64, &sa);
+    block_exclusive_scan<kBlock>(b, S.scan_u64, &sb);
     if (t == 0) {
         SegInfo si;
         si.bytes = out_bytes;
@@ -609,10 +586,9 @@ __global__ __launch_bounds__(kBlock) void k_png_finalize(Shape s, const SegInfo 
         b += si.adler_b + after * si.adler_a % kAdlerMod;
     }
     unsigned long long total = 0, ta = 0, tb = 0;
-    unsigned long long o = block_exclusive<unsigned long long>(sum, 0ull, tmp, [](unsigned long long x, unsigned long long y) { return x + y; },
-                                                               &total);
-    block_exclusive<unsigned long long>(a % kAdlerMod, 0ull, tmp, [](unsigned long long x, unsigned long long y) { return x + y; }, &ta);
-    block_exclusive<unsigned long long>(b % kAdlerMod, 0ull, tmp, [](unsigned long long x, unsigned long long y) { return x + y; }, &tb);
+    unsigned long long o = block_exclusive_scan<kBlock>(sum, tmp, &total);
+    block_exclusive_scan<kBlock>(a % kAdlerMod, tmp, &ta);
+    block_exclusive_scan<kBlock>(b % kAdlerMod, tmp, &tb);
     o += kHeadBytes;
     for (int64_t k = k0; k < k1; ++k) {
         offs[k] = (int64_t)o;

@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "../../include/topo4d_raster.h"
+#include "t4d_block.h"
 #include "t4d_host.h"
 #include "t4d_inflate.h"
 
@@ -113,23 +114,6 @@ __global__ void k_pngdec_layout(const T4DPngImage *images, int n, ImgPlan *plans
     }
 }
 
-// exclusive prefix over the wave's lanes of one value each, and the total
-__device__ int64_t wave_exclusive(int64_t v, int64_t *tmp, int64_t *total)
-{
-    const int lane = threadIdx.x;
-    __syncthreads();
-    tmp[lane] = v;
-    __syncthreads();
-    int64_t pre = 0, all = 0;
-    for (int j = 0; j < kWave; j++) {
-        const int64_t x = tmp[j];
-        if (j < lane) pre += x;
-        all += x;
-    }
-    *total = all;
-    return pre;
-}
-
 __global__ __launch_bounds__(kWave) void k_pngdec_plan(const T4DPngImage *images, const int64_t *chunks, ImgPlan *plans, int32_t *cls)
 {
     __shared__ int64_t tmp[kWave];
@@ -141,7 +125,7 @@ __global__ __launch_bounds__(kWave) void k_pngdec_plan(const T4DPngImage *images
     int64_t mine = 0;
     for (int c = c0; c < c1; c++) mine += max(chunks[2 * (int64_t)(im.first_chunk + c) + 1], (int64_t)0);
     int64_t total = 0;
-    int64_t soff = wave_exclusive(mine, tmp, &total);
+    int64_t soff = block_exclusive_scan<kWave>(mine, tmp, &total);
     int mixed = 0, last = -1;
     for (int c = c0; c < c1; c++) {
         const int k = im.first_chunk + c;
@@ -205,7 +189,7 @@ __global__ __launch_bounds__(kWave) void k_pngdec_scan(const T4DPngImage *images
             else mine += s;
         }
         int64_t total = 0;
-        int64_t o = wave_exclusive(mine, tmp, &total);
+        int64_t o = block_exclusive_scan<kWave>(mine, tmp, &total);
         s_bad[lane] = bad;
         __syncthreads();
         for (int j = 0; j < kWave; j++) bad |= s_bad[j];

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "../../include/topo4d_raster.h"
+#include "t4d_block.h"
 #include "t4d_host.h"
 
 namespace {
@@ -136,8 +137,7 @@ __device__ __forceinline__ void block_partials(float v[kNbrTerms], float *out)
     __shared__ float w[kNbrTerms][kBlock / 64];
 #pragma unroll
     for (int t = 0; t < kNbrTerms; t++) {
-        float s = v[t];
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        const float s = wave_sum(v[t]);
         if ((threadIdx.x & 63) == 0) w[t][threadIdx.x >> 6] = s;
     }
     __syncthreads();
@@ -379,7 +379,7 @@ __global__ __launch_bounds__(kBlock) void k_priors_vertices(const T4DPriors pr, 
         for (int t = 0; t < slots; t++) {
             float s = 0.f;
             for (int b = threadIdx.x; b < nb; b += kBlock) s += p.partial[kNbrTerms * (size_t)(sg.block0 + b) + t];
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            s = wave_sum(s);
             if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = s;
             __syncthreads();
             if (threadIdx.x == 0) acc[sg.term + t] = (w[0] + w[1]) + (w[2] + w[3]);

@@ -75,6 +75,7 @@
 #include <stdint.h>
 
 #include "../../include/topo4d_raster.h"
+#include "t4d_block.h"
 #include "t4d_host.h"
 
 namespace {
@@ -279,12 +280,6 @@ struct PSP {
     double stat_cos_min, stat_lo, stat_hi;
     unsigned long long *pair_count, *pair_sum;
 };
-
-__device__ __forceinline__ long long wave_sum(long long a)
-{
-    for (int m = 1; m < 64; m <<= 1) a += __shfl_xor(a, m, 64);
-    return a;
-}
 
 // whether view v takes part at the lane's texel, and its q
 __device__ __forceinline__ bool stat_eval(const PSP &P, int v, const Texel &t, long long q[3])

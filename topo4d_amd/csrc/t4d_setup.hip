@@ -20,6 +20,7 @@
 #include <math.h>
 
 #include "../../include/topo4d_raster.h"
+#include "t4d_block.h"
 #include "t4d_host.h"
 
 #pragma clang fp contract(off)
@@ -216,31 +217,25 @@ __global__ void __launch_bounds__(kBlock) k_edge_compact(const int32_t *__restri
                                                          const int32_t *__restrict__ info, int64_t *__restrict__ out,
                                                          int64_t *__restrict__ n_out)
 {
-    __shared__ int32_t sk[kBlock], st[kBlock];
+    __shared__ int2 tmp[kBlock];                                       // x: kept edges, y: edges with two faces
     const int t = threadIdx.x;
     int64_t keep_base = 0, two_base = 0;
     for (int64_t base = 0; base < n_edges; base += kBlock) {
         const int64_t e = base + t;
         const int cnt = e < n_edges ? info[3 * e] : 3;
         const int keep = cnt <= 2, two = cnt == 2;
-        sk[t] = keep, st[t] = two;
-        __syncthreads();
-        for (int d = 1; d < kBlock; d <<= 1) {
-            const int vk = t >= d ? sk[t - d] : 0, vt = t >= d ? st[t - d] : 0;
-            __syncthreads();
-            sk[t] += vk, st[t] += vt;
-            __syncthreads();
-        }
+        int2 all;
+        const int2 before = block_exclusive_scan<kBlock>(make_int2(keep, two), make_int2(0, 0), tmp,
+                                                         [](int2 a, int2 b) { return make_int2(a.x + b.x, a.y + b.y); }, &all);
         if (two) {
-            const int64_t idx = keep_base + sk[t] - 1, j = two_base + st[t] - 1;
+            const int64_t idx = keep_base + before.x, j = two_base + before.y;     // keep holds wherever two does
             out[j] = edges[2 * idx];
             out[n_edges + j] = edges[2 * idx + 1];
             out[2 * n_edges + j] = info[3 * e + 1];
             out[3 * n_edges + j] = info[3 * e + 2];
         }
-        keep_base += sk[kBlock - 1];
-        two_base += st[kBlock - 1];
-        __syncthreads();
+        keep_base += all.x;
+        two_base += all.y;
     }
     if (t == 0) *n_out = two_base;
 }

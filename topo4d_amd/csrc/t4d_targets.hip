@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include "../../include/topo4d_raster.h"
+#include "t4d_block.h"
 #include "t4d_host.h"
 
 namespace {
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void k_soft_color(const float *x, const flo
         }
     }
     // fixed-order reduction: lanes of a wave by xor butterflies, the four waves through LDS
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     __shared__ float w[kBlock / 64];
     if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(kBlock) void k_soft_color(const float *x, const flo
 __global__ __launch_bounds__(kScBlocks) void k_soft_color_final(const float *partial, const int n_partial, const float rows, float *loss)
 {
     float s = threadIdx.x < n_partial ? partial[threadIdx.x] : 0.f;
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    s = wave_sum(s);
     __shared__ float w[kScBlocks / 64];
     if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = s;
     __syncthreads();

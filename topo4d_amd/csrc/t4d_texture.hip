@@ -8,7 +8,7 @@
 // The reference walks the triangles serially and z-tests with a strict `>`, so a texel ends up with the triangle
 // of maximum interpolated depth and, among equals, the LOWEST index (for Topo4D every depth is 0: first triangle
 // wins).  That final state is order-independent, which is what makes a parallel formulation exact:
-//   k_tex_bin<count> / k_tex_scan / k_tex_bin<fill>   bin triangles by the 32x32-texel tiles their clipped pixel bbox touches
+//   k_tex_bin<count> / t4d_scan_bins / k_tex_bin<fill>   bin triangles by the 32x32-texel tiles their clipped pixel bbox touches
 //                                           (LDS histogram per workgroup, one global atomic per touched tile; the scan runs in
 //                                           1024-bin chunks on as many workgroups)
 //   k_tex_render                            one workgroup per tile: like the reference, a triangle visits only the texels of
@@ -40,7 +40,6 @@ struct Tri {                                // 80 bytes = five 16-byte words: th
     int i0, i1;                             // (pads the record to five 16-byte words)
 };
 static_assert(sizeof(Tri) == 80, "Tri must stay five float4 words");
-constexpr int kScanChunk = 1024;
 #ifndef T4D_TEX_GROUP
 #define T4D_TEX_GROUP 16               // lanes per triangle record in the texel loop (same box: 64 lanes 0.679 ms, 32: 0.638, 16: 0.622, 8: 0.640)
 #endif
@@ -51,11 +50,9 @@ struct TexP {
     const float *colors;
     int nver, ntri, h, w, c, row_begin, row_end;
     int bx, by, by0;              // bins in x, bins in y inside the row band, first bin row of the band
-    int n_chunks;
     uint32_t cap;
-    uint32_t *bin_count, *bin_cursor, *bin_off, *chunk_sum;
+    uint32_t *bin_count, *bin_cursor, *bin_off;
     uint4 *list;                  // per (tile, triangle) pair: the triangle's index and its three vertex indices (one fetch level less per tile)
-    unsigned long long *total;
     float *image, *depth;
     const float *bg;              // FRESH launches: background image [h,w,c] or nullptr = zeros
 };
@@ -145,60 +142,6 @@ __global__ __launch_bounds__(kBlock) void k_tex_bin(const TexP P)
                 }
             }
     }
-}
-
-__global__ __launch_bounds__(kScanChunk) void k_tex_chunk_sums(const TexP P)
-{
-    __shared__ uint32_t s_w[kScanChunk / 64];
-    const int c = blockIdx.x, tid = threadIdx.x, b = c * kScanChunk + tid;
-    uint32_t x = b < P.bx * P.by ? P.bin_count[b] : 0u;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += (uint32_t)__shfl_xor((int)x, d, 64);
-    if ((tid & 63) == 0) s_w[tid >> 6] = x;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t tot = 0;
-#pragma unroll
-        for (int w = 0; w < kScanChunk / 64; w++) tot += s_w[w];
-        P.chunk_sum[c] = tot;
-    }
-}
-
-__global__ __launch_bounds__(kScanChunk) void k_tex_scan(const TexP P)
-{
-    __shared__ uint32_t s_w[16];
-    __shared__ unsigned long long s_carry;
-    const int chunk = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int nb = P.bx * P.by;
-    if (wave == 0) {                                                // pairs in the chunks before this one
-        unsigned long long part = 0;
-        for (int i = lane; i < chunk; i += 64) part += P.chunk_sum[i];
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1)
-            part += ((unsigned long long)(uint32_t)__shfl_xor((int)(part >> 32), d, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)part, d, 64);
-        if (lane == 0) s_carry = part;
-    }
-    const int b = chunk * kScanChunk + tid;
-    const uint32_t c = b < nb ? P.bin_count[b] : 0u;
-    uint32_t incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const uint32_t x = s_w[k];
-        if (k < wave) woff += x;
-        tot += x;
-    }
-    const unsigned long long carry = s_carry;
-    const unsigned long long off = carry + woff + incl - c;
-    if (b < nb) P.bin_off[b] = off > 0xffffffffull ? 0xffffffffu : (uint32_t)off;
-    if (tid == 0 && chunk == P.n_chunks - 1) *P.total = carry + tot;
 }
 
 // One workgroup per 32x32-texel tile.  The first version let every texel test every triangle of its tile (3.4 G tests for
@@ -515,7 +458,7 @@ TexLayout tex_layout(int h, int w, int64_t cap)
     L.bin_cursor = o; o = align_up(o + nb * 4);
     L.zero_end = o;
     L.bin_off = o;    o = align_up(o + nb * 4);
-    L.chunk_sum = o;  o = align_up(o + ((nb + kScanChunk - 1) / kScanChunk) * 4);
+    L.chunk_sum = o;  o = align_up(o + ((nb + kScanBinsChunk - 1) / kScanBinsChunk) * 4);
     L.list = o;       o = align_up(o + (size_t)cap * sizeof(uint4));
     L.bytes = o;
     return L;
@@ -552,12 +495,9 @@ int texture_bake_impl(const bool fresh, const float *bg, const float *vertices, 
     P.by0 = row_begin / kTile;
     P.by = (row_end - 1) / kTile - P.by0 + 1;
     P.cap = (uint32_t)pair_capacity;
-    P.total = (unsigned long long *)(sc + L.total_);
     P.bin_count = (uint32_t *)(sc + L.bin_count);
     P.bin_cursor = (uint32_t *)(sc + L.bin_cursor);
     P.bin_off = (uint32_t *)(sc + L.bin_off);
-    P.chunk_sum = (uint32_t *)(sc + L.chunk_sum);
-    P.n_chunks = (P.bx * P.by + kScanChunk - 1) / kScanChunk;
     P.list = (uint4 *)(sc + L.list);
     P.image = image; P.depth = depth_buffer; P.bg = bg;
     if (pairs_needed) *pairs_needed = 0;
@@ -566,9 +506,9 @@ int texture_bake_impl(const bool fresh, const float *bg, const float *vertices, 
     if (ntri > 0) {
         const int gt = (ntri + kBlock - 1) / kBlock;
         hipLaunchKernelGGL(k_tex_bin<false>, dim3(gt), dim3(kBlock), 0, stream, P);
-        if (P.n_chunks > 1) hipLaunchKernelGGL(k_tex_chunk_sums, dim3(P.n_chunks), dim3(kScanChunk), 0, stream, P);
-        hipLaunchKernelGGL(k_tex_scan, dim3(P.n_chunks), dim3(kScanChunk), 0, stream, P);
-        T4D_HIP_CHECK(hipMemcpyAsync(&total, P.total, 8, hipMemcpyDeviceToHost, stream));
+        unsigned long long *d_total = (unsigned long long *)(sc + L.total_);
+        t4d_scan_bins(P.bin_count, P.bx * P.by, P.bin_off, (uint32_t *)(sc + L.chunk_sum), d_total, stream);
+        T4D_HIP_CHECK(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, stream));
         T4D_HIP_CHECK(hipStreamSynchronize(stream));          // once per bake (a per-frame export step, not the training loop)
         if (pairs_needed) *pairs_needed = (int64_t)total;
         if (total > (unsigned long long)pair_capacity)

@@ -8,6 +8,7 @@
 //                 memory, as is every tap of a tile whose footprint does not fit.
 #include <hip/hip_runtime.h>
 
+#include "t4d_block.h"
 #include "t4d_host.h"
 #include "t4d_lens.h"
 
@@ -17,27 +18,10 @@ constexpr int kBlock = 256;
 constexpr int kLds = 49152;                   // staged source bytes per tile
 constexpr int kMargin = 2;                    // samples around the perimeter's bounding box
 
-__host__ __device__ inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 __host__ __device__ inline int64_t view_tiles(const T4DLensView &v)
 {
     const int t = t4d_lens::tile_side(v.supersample);
     return div_up(v.out_rows, t) * div_up(v.out_cols, t);
-}
-
-__device__ inline int find_view(const T4DLensView *V, int n, int64_t b, int64_t *local)
-{
-    int64_t base = 0;
-    for (int i = 0; i < n; i++) {
-        const int64_t c = view_tiles(V[i]);
-        if (b < base + c) {
-            *local = b - base;
-            return i;
-        }
-        base += c;
-    }
-    *local = 0;
-    return -1;
 }
 
 __global__ void __launch_bounds__(kBlock) k_undistort(const T4DLensView *V, int n)
@@ -45,7 +29,7 @@ __global__ void __launch_bounds__(kBlock) k_undistort(const T4DLensView *V, int 
     __shared__ uint8_t lds[kLds];
     __shared__ double red[kBlock / 64][4];
     int64_t lt;
-    const int vi = find_view(V, n, blockIdx.x, &lt);
+    const int vi = find_view(V, n, blockIdx.x, &lt, [](const T4DLensView &w) { return view_tiles(w); });
     if (vi < 0) return;
     const T4DLensView v = V[vi];                  // by value: uniform registers, not re-read from memory after every store to dst
     const int s = v.supersample, T = t4d_lens::tile_side(s);
