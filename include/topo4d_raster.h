@@ -1013,6 +1013,37 @@ int t4d_project_texture_bands_skip(const float *pos, const float *nrm, const uin
                                    const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
                                    double depth_tol, float *low_color, float *weight, uint8_t *count, float *high,
                                    float *best_weight, const uint32_t *skip, int32_t skip_base, void *hip_stream);
+/* Registration (projtex.view_flows; project / project_bands / project_frame take its flows): calibration, the tracked mesh and the
+ * lens model are never exact to the pixel, so the views of one frame disagree by a pixel or two.  Each view carries a small 2D
+ * flow against the consensus of all views and its photograph is sampled through it (Eisemann et al., "Floating Textures").
+ * t4d_project_texture_flow / t4d_project_texture_bands_flow: t4d_project_texture_skip / t4d_project_texture_bands_skip with
+ * flows [n_views,h,w,2] int16 (device, aligned to 4 bytes; NULL: none, and every output bit is theirs: they forward here), the
+ * pair (f_y, f_x) of a pixel in 1/256 of a photograph pixel, in t4d_drift_dense's component order.  Per covered texel with a
+ * non-zero normal and view:
+ *   F.1. the view goes through every step of t4d_project_texture at the unshifted pixel (px, py), exactly as it stands: the near
+ *        plane, the four taps inside the image, the depth test on the four depth taps, cos >= cos_min, the weight with its edge
+ *        fade, and the skip bit.  Geometry decides visibility and weight; the flow only moves the colour sample.
+ *   F.2. for an accepted view the flow is read at the nearest pixel iy = (int)floor(py + 0.5), ix = (int)floor(px + 0.5), each
+ *        clamped to the image (one 32-bit load)
+ *   F.3. px' = px + f_x / 256.0, py' = py + f_y / 256.0, float64 operations
+ *   F.4. if one of the four bilinear taps at floor(px'), floor(py') lies outside the image the view is rejected as if F.1 had not
+ *        accepted it: it does not count, cannot be the best view and enters no blend
+ *   F.5. otherwise its sample is the bilinear mix of the photograph's taps at (px', py'), by the same expression; in the bands
+ *        entry the same holds for low.  Gains, blending, the ties of the best view and count are unchanged.
+ * tests/projtex_flow_ref.py reproduces every output bit.  Known limits of the flows projtex.view_flows makes: a block straddling a
+ * self-occlusion edge matches two surfaces; smooth skin keeps few blocks and falls back to zero flow; a misregistration beyond the
+ * search radius is dropped, not corrected.  Neither call synchronises the stream. */
+int t4d_project_texture_flow(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                             const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos, const float *depth,
+                             const double *gains, int32_t power, double cos_min, double fade_px, double depth_tol, int32_t mode,
+                             float *color, float *weight, uint8_t *count, const uint32_t *skip, int32_t skip_base, void *hip_stream,
+                             const int16_t *flows);
+int t4d_project_texture_bands_flow(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                   const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos, const float *low,
+                                   const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
+                                   double depth_tol, float *low_color, float *weight, uint8_t *count, float *high,
+                                   float *best_weight, const uint32_t *skip, int32_t skip_base, void *hip_stream,
+                                   const int16_t *flows);
 
 /* Exact closest point on a triangle soup, or on a bare point cloud, for many query points (csrc/t4d_closest.hip): what
  * topo4d_amd/scanscore.py scores a frame's face.obj against its multi-view-stereo scan with.  It stands in for

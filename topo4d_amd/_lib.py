@@ -251,6 +251,10 @@ SIGNATURES = {
                                  + [_VP] * 4 + [_I32, _VP]),
     "t4d_project_texture_bands_skip": (_INT, [_VP] * 3 + [_I32] * 2 + [_VP] + [_I32] * 3 + [_VP] * 4 + [_I32] + [C.c_double] * 3
                                        + [_VP] * 6 + [_I32, _VP]),
+    "t4d_project_texture_flow": (_INT, [_VP] * 3 + [_I32] * 2 + [_VP] + [_I32] * 3 + [_VP] * 3 + [_I32] + [C.c_double] * 3 + [_I32]
+                                 + [_VP] * 4 + [_I32, _VP, _VP]),
+    "t4d_project_texture_bands_flow": (_INT, [_VP] * 3 + [_I32] * 2 + [_VP] + [_I32] * 3 + [_VP] * 4 + [_I32] + [C.c_double] * 3
+                                       + [_VP] * 6 + [_I32, _VP, _VP]),
     "t4d_closest_index_bytes": (_SZ, [_I64, _I64, _VP, C.c_double, _I64]),
     "t4d_closest_build": (_INT, [_VP, _I64, _VP, _I64, _VP, C.c_double, _VP, _SZ, _I64, C.POINTER(_I64), _VP]),
     "t4d_closest_query_scratch_bytes": (_SZ, [_I64]),

@@ -46,6 +46,20 @@
 // and at the end low_color = float32(sl / sw), weight = float32(sw), high = float32(hb), best_weight = float32(bw), count as
 // above; every other texel gets zeros.  The caller adds the bands: color = low_color + high.
 //
+// Registration (t4d_project_texture_flow / t4d_project_texture_bands_flow; the rule is restated in tests/projtex_flow_ref.py):
+// calibration, the tracked mesh and the lens model are never exact to the pixel, so each view carries a small 2D flow against the
+// consensus of all views, flows [V,H,W,2] int16 = (f_y, f_x) in 1/256 px (projtex.view_flows), and the photograph is sampled
+// through it (Eisemann et al., "Floating Textures").  Geometry decides visibility and weight; the flow only moves the colour
+// sample.  Per texel and view:
+//   F.1. steps 1..5 and the skip bit at the unshifted pixel (px, py), exactly as they stand
+//   F.2. for an accepted view: ix = (int)floor(px + 0.5), iy = (int)floor(py + 0.5), each clamped to the image; (f_y, f_x) =
+//        flows[v][iy][ix], one 32-bit load
+//   F.3. px' = px + f_x / 256.0, py' = py + f_y / 256.0
+//   F.4. x0' = floor(px'), y0' = floor(py'); the view is rejected, as one that failed step 5, unless 0 <= x0', x0' + 1 <= W - 1,
+//        0 <= y0', y0' + 1 <= H - 1: it does not count, cannot be the best view and enters no blend
+//   F.5. steps 6 (and 6b) with fx = px' - x0', fy = py' - y0' over the taps at (y0', x0'); step 7 as it stands
+// The flow is a template flag of the two kernels (kFlow), so that the instances without it are what they were.
+//
 // Photo-consistency (t4d_projtex_consistency; the rule is restated in tests/projtex_consist_ref.py): a specular highlight, a
 // leak of the occlusion test (hair, lashes, a nose rim the mesh does not model) and transient content in one camera are no gain per
 // camera and no registration error; what they share is that one view disagrees with a consensus of the others (Waechter et al.,
@@ -107,6 +121,7 @@ struct PTP {
     uint8_t *count;
     const uint32_t *skip;                    // [th,tw] the consistency mask or NULL; view v is bit skip_base + v
     int skip_base;
+    const int16_t *flows;                    // [V,H,W,2] (f_y, f_x) in 1/256 px, or NULL
 };
 
 // The texel (tx, ty), and through texel_load the lane's texel of the 16x16 tile (tile_x, tile_y): whether it lies inside the texture, and there `at`; whether it is live (inside,
@@ -144,6 +159,7 @@ struct View {                                 // one view of size H x W: its rec
 
 struct Hit {                                  // an accepted view at a texel: weight, cosine, the first of its four taps and the bilinear fractions
     double w, cs, fx, fy;
+    double px, py;                           // the pixel of step 1, for view_flow
     size_t tap;
 };
 
@@ -193,6 +209,27 @@ __device__ __forceinline__ bool view_accept(const View &v, const Rule &r, const 
     h.cs = cs;
     h.fx = px - fx0;
     h.fy = py - fy0;
+    h.px = px;
+    h.py = py;
+    return true;
+}
+
+// Steps F.2..F.4 of the registration rule for an accepted view: the flow ([H,W,2] int16: (f_y, f_x) in 1/256 px) read at the
+// pixel nearest to (px, py) moves the taps and the fractions of `h`; false when a moved tap leaves the image.
+__device__ __forceinline__ bool view_flow(const int16_t *flow, const View &v, Hit &h)
+{
+#pragma clang fp contract(off)
+    const int W = v.W, H = v.H;
+    int ix = (int)floor(h.px + 0.5), iy = (int)floor(h.py + 0.5);
+    ix = ix < 0 ? 0 : (ix > W - 1 ? W - 1 : ix);
+    iy = iy < 0 ? 0 : (iy > H - 1 ? H - 1 : iy);
+    const uint32_t f = reinterpret_cast<const uint32_t *>(flow)[(size_t)iy * (size_t)W + (size_t)ix];     // f_y low, f_x high
+    const double px = h.px + (double)(int16_t)(f >> 16) / 256.0, py = h.py + (double)(int16_t)(f & 0xffffu) / 256.0;
+    const double fx0 = floor(px), fy0 = floor(py);
+    if (!(fx0 >= 0.0 && fx0 + 1.0 <= (double)(W - 1) && fy0 >= 0.0 && fy0 + 1.0 <= (double)(H - 1))) return false;
+    h.tap = (size_t)(int)fy0 * (size_t)W + (size_t)(int)fx0;
+    h.fx = px - fx0;
+    h.fy = py - fy0;
     return true;
 }
 
@@ -212,8 +249,8 @@ __device__ __forceinline__ void view_sample(const float *img, const View &v, con
     }
 }
 
-// (an instance per flag, so that the kernel without gains and without a mask is the one it was before they existed)
-template <bool kGains, bool kSkip>
+// (an instance per flag, so that the kernel without gains, without a mask and without flows is the one it was before they existed)
+template <bool kGains, bool kSkip, bool kFlow>
 __global__ __launch_bounds__(kTile * kTile) void k_projtex(const PTP P)
 {
 #pragma clang fp contract(off)
@@ -231,6 +268,7 @@ __global__ __launch_bounds__(kTile * kTile) void k_projtex(const PTP P)
             const View view = {P.T.views + (size_t)v * T4D_VIEW_FLOATS, P.depth + (size_t)v * plane, P.H, P.W};
             Hit h;
             if (!view_accept(view, P.T.rule, t, h)) continue;
+            if (kFlow && !view_flow(P.flows + (size_t)v * 2 * plane, view, h)) continue;         // F.4: as one that failed step 5
             ++cnt;
             if (best && !(h.w > sw)) continue;                              // a view that cannot win is counted but not gathered (ties stay with the lower view)
             double s[3];
@@ -535,9 +573,10 @@ struct PBP {
     uint8_t *count;
     const uint32_t *skip;                    // as PTP's
     int skip_base;
+    const int16_t *flows;                    // as PTP's
 };
 
-template <bool kGains, bool kSkip>
+template <bool kGains, bool kSkip, bool kFlow>
 __global__ __launch_bounds__(kTile * kTile) void k_projtex_bands(const PBP P)
 {
 #pragma clang fp contract(off)
@@ -555,6 +594,7 @@ __global__ __launch_bounds__(kTile * kTile) void k_projtex_bands(const PBP P)
             const double *gain = kGains ? P.T.gains + 3 * v : nullptr;
             Hit h;
             if (!view_accept(view, P.T.rule, t, h)) continue;
+            if (kFlow && !view_flow(P.flows + (size_t)v * 2 * plane, view, h)) continue;
             ++cnt;
             double s[3], l[3];
             view_sample(P.photos + (size_t)v * 3 * plane, view, h, gain, s);
@@ -621,11 +661,23 @@ static int skip_check(const char *name, const uint32_t *skip, int32_t skip_base,
     return T4D_OK;
 }
 
-T4D_EXPORT int t4d_project_texture_skip(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+// the flows of a blend: int16 pairs read as one 32-bit word
+static int flows_check(const char *name, const int16_t *flows)
+{
+    if (flows && (uintptr_t)flows % sizeof(uint32_t) != 0) return t4d_fail(T4D_ERR_ARG, "%s: flows must be aligned to 4 bytes", name);
+    return T4D_OK;
+}
+
+// the instance of a texel kernel for what a launch is given: K<gains, skip, flows>
+#define T4D_PROJTEX_INSTANCE(K, gains, skip, flows)                                                                              \
+    ((flows) ? ((skip) ? ((gains) ? K<true, true, true> : K<false, true, true>) : ((gains) ? K<true, false, true> : K<false, false, true>))   \
+             : ((skip) ? ((gains) ? K<true, true, false> : K<false, true, false>) : ((gains) ? K<true, false, false> : K<false, false, false>)))
+
+T4D_EXPORT int t4d_project_texture_flow(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
                                         const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
                                         const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
                                         double depth_tol, int32_t mode, float *color, float *weight, uint8_t *count,
-                                        const uint32_t *skip, int32_t skip_base, void *hip_stream)
+                                        const uint32_t *skip, int32_t skip_base, void *hip_stream, const int16_t *flows)
 {
     const char *name = "t4d_project_texture";
     if (const int rc = views_check(name, pos && nrm && coverage && views && photos && depth && color && weight && count, n_views, kMaxViews, h, w))
@@ -634,11 +686,22 @@ T4D_EXPORT int t4d_project_texture_skip(const float *pos, const float *nrm, cons
         return t4d_fail(T4D_ERR_ARG, "%s: mode must be T4D_PROJTEX_WEIGHTED or T4D_PROJTEX_BEST, got %d", name, mode);
     if (const int rc = projtex_check(name, tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
     if (const int rc = skip_check(name, skip, skip_base, n_views)) return rc;
+    if (const int rc = flows_check(name, flows)) return rc;
     const PTP P = {tex_block(pos, nrm, coverage, tex_h, tex_w, views, n_views, gains, power, cos_min, fade_px, depth_tol),
-                   photos, depth, h, w, mode, color, weight, count, skip, skip_base};
-    const auto kernel = skip ? (gains ? k_projtex<true, true> : k_projtex<false, true>) : (gains ? k_projtex<true, false> : k_projtex<false, false>);
+                   photos, depth, h, w, mode, color, weight, count, skip, skip_base, flows};
+    const auto kernel = T4D_PROJTEX_INSTANCE(k_projtex, gains, skip, flows);
     hipLaunchKernelGGL(kernel, tile_grid(tex_h, tex_w), dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
     return t4d_launch_status(name);
+}
+
+T4D_EXPORT int t4d_project_texture_skip(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                        const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
+                                        const float *depth, const double *gains, int32_t power, double cos_min, double fade_px,
+                                        double depth_tol, int32_t mode, float *color, float *weight, uint8_t *count,
+                                        const uint32_t *skip, int32_t skip_base, void *hip_stream)
+{
+    return t4d_project_texture_flow(pos, nrm, coverage, tex_h, tex_w, views, n_views, h, w, photos, depth, gains, power, cos_min,
+                                    fade_px, depth_tol, mode, color, weight, count, skip, skip_base, hip_stream, nullptr);
 }
 
 T4D_EXPORT int t4d_project_texture_gains(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
@@ -714,11 +777,12 @@ T4D_EXPORT int t4d_projtex_low_band(const float *photos, const float *depth, int
     return t4d_launch_status(name);
 }
 
-T4D_EXPORT int t4d_project_texture_bands_skip(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+T4D_EXPORT int t4d_project_texture_bands_flow(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
                                               const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
                                               const float *low, const float *depth, const double *gains, int32_t power, double cos_min,
                                               double fade_px, double depth_tol, float *low_color, float *weight, uint8_t *count,
-                                              float *high, float *best_weight, const uint32_t *skip, int32_t skip_base, void *hip_stream)
+                                              float *high, float *best_weight, const uint32_t *skip, int32_t skip_base, void *hip_stream,
+                                              const int16_t *flows)
 {
     const char *name = "t4d_project_texture_bands";
     if (const int rc = views_check(name, pos && nrm && coverage && views && photos && low && depth && low_color && weight && count && high && best_weight,
@@ -726,12 +790,23 @@ T4D_EXPORT int t4d_project_texture_bands_skip(const float *pos, const float *nrm
         return rc;
     if (const int rc = projtex_check(name, tex_h, tex_w, power, cos_min, fade_px, depth_tol)) return rc;
     if (const int rc = skip_check(name, skip, skip_base, n_views)) return rc;
+    if (const int rc = flows_check(name, flows)) return rc;
     const PBP P = {tex_block(pos, nrm, coverage, tex_h, tex_w, views, n_views, gains, power, cos_min, fade_px, depth_tol),
-                   photos, low, depth, h, w, low_color, weight, high, best_weight, count, skip, skip_base};
-    const auto kernel = skip ? (gains ? k_projtex_bands<true, true> : k_projtex_bands<false, true>)
-                             : (gains ? k_projtex_bands<true, false> : k_projtex_bands<false, false>);
+                   photos, low, depth, h, w, low_color, weight, high, best_weight, count, skip, skip_base, flows};
+    const auto kernel = T4D_PROJTEX_INSTANCE(k_projtex_bands, gains, skip, flows);
     hipLaunchKernelGGL(kernel, tile_grid(tex_h, tex_w), dim3(kTile * kTile), 0, (hipStream_t)hip_stream, P);
     return t4d_launch_status(name);
+}
+
+T4D_EXPORT int t4d_project_texture_bands_skip(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,
+                                              const float *views, int32_t n_views, int32_t h, int32_t w, const float *photos,
+                                              const float *low, const float *depth, const double *gains, int32_t power, double cos_min,
+                                              double fade_px, double depth_tol, float *low_color, float *weight, uint8_t *count,
+                                              float *high, float *best_weight, const uint32_t *skip, int32_t skip_base, void *hip_stream)
+{
+    return t4d_project_texture_bands_flow(pos, nrm, coverage, tex_h, tex_w, views, n_views, h, w, photos, low, depth, gains, power,
+                                          cos_min, fade_px, depth_tol, low_color, weight, count, high, best_weight, skip, skip_base,
+                                          hip_stream, nullptr);
 }
 
 T4D_EXPORT int t4d_project_texture_bands(const float *pos, const float *nrm, const uint8_t *coverage, int32_t tex_h, int32_t tex_w,

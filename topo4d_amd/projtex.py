@@ -3,6 +3,7 @@ The capture photographs projected into a frame's UV texture on the GPU, over csr
 states the per-texel rule; tests/projtex_ref.py restates it in numpy bit for bit):
 
     project(pos, nrm, coverage, cams, photos, depth, ...)   -> (color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8)
+    view_flows(renders, photos, depth, ...)                 -> (flows int16 [V,H,W,2], support uint8 [V,H,W], report): each view against the consensus
     low_band(photos, depth, radius)                         -> low [V,3,H,W] float32: each photograph's box mean over its mesh pixels
     project_bands(pos, nrm, coverage, cams, photos, low, depth, ...) -> (low_color, weight, count, high, best_weight): mode "twoband"
     surface_maps(face_obj, vertices, res, device)           -> (pos [h,w,3], nrm [h,w,3], coverage [h,w]) of a face.obj's UV layout
@@ -51,10 +52,30 @@ coverage keeps its highlights; a defect most voters share survives; the threshol
 a relative one would be.  --reject (train: --tex_reject) switches it on; --save_rejected also writes face_proj_rejected.png, the
 number of rejected views per texel.
 
+None of the stages above registers the views of one frame against each other: the gains equalise exposure, the consistency check
+drops outliers, two bands keep only the best view's detail.  The standard cure in photogrammetry texturing is a small 2D flow per
+view against the consensus, through which the photograph is sampled (Eisemann et al., "Floating Textures"); it lets "weighted" and
+the low band of "twoband" blend many views without blurring them.  project_frame(register=...) projects the frame once in mode
+"weighted" (with the gains and the mask), fills that texture's holes per island, renders it into every camera
+(meshrender.MeshRenderer.render) and calls view_flows, which matches every photograph against its render with the pieces of drift
+(match: the census block matcher; flow: sub-pixel offsets; dense_flow: a per-pixel field in 1/256 px) and returns the fields as
+int16.  project and project_bands take them as flows=: a view is accepted and weighed at its unshifted pixel exactly as without
+flows (geometry decides visibility and weight), the flow read at the nearest pixel moves only the colour sample, and a view whose
+moved taps leave the image is left out (include/topo4d_raster.h, F.1..F.5; tests/projtex_flow_ref.py restates it bit for bit).
+The stages run in the order equalise, reject, register, blend, fill.  --register (train: --tex_register) switches it on, with
+--reg_block, --reg_stride, --reg_radius, --reg_ratio, --reg_reach and --reg_rounds; every frame then also gets
+face_proj_register.json (the options and view_flows' report) and with --save_flows face_proj_flows.npz (flows, support, camera
+names).  Known limits: a block straddling a self-occlusion edge (nose over cheek) matches two surfaces; the census needs texture,
+so smooth skin at low resolution keeps few blocks and falls back to zero flow there; a misregistration beyond the radius is
+dropped, not corrected; consistency and pair_stats still sample unregistered, so rejection and gain statistics are taken on
+unregistered samples; the defaults (block 32, stride 16, radius 4, ratio 0.8, reach 1, one round) are conventional, not tuned on a
+capture.
+
 `python -m topo4d_amd.projtex -e EXP -s SEQ [-id ... -did ... -od ... -dr N] [--frames 1-10] [--views A,B] [--set low|dense]
 [--undistort] [--tex_res R] [--mode weighted|best|twoband [--band_radius R]] [--power P --cos_min C --fade_px F --depth_tol T] [--tex_pad R]
 [--tex_sizes 2048,1024] [--save_weight] [--tex_fill] [--equalize [--equalize_frames 1-10] | --gains FILE] [--stat_cos_min C --stat_lo L
---stat_hi H --eq_prior P --eq_min_overlap N] [--reject [--reject_tol T --vote_cos_min C --min_votes N] [--save_rejected]]` works on an output tree that already exists (the reference's too): it writes
+--stat_hi H --eq_prior P --eq_min_overlap N] [--reject [--reject_tol T --vote_cos_min C --min_votes N] [--save_rejected]]
+[--register [--reg_block B --reg_stride S --reg_radius R --reg_ratio Q --reg_reach K --reg_rounds N] [--save_flows]]` works on an output tree that already exists (the reference's too): it writes
 %06d/face_proj.png (and face_proj_<size>.png) beside every frame's face.obj, with --save_weight also face_proj_weight.png (the
 8-bit count of contributing views).  By default it projects the full-size photographs of the cameras training uses.
 --equalize gathers the pair statistics over --equalize_frames (default: the first frame projected), solves once, writes
@@ -95,6 +116,10 @@ GAINS_NAME = "proj_gains.json"
 MAX_REJECT_TOL = 4.0                                           # consistency: samples are clamped to [0, 4] before they are rounded
 CONSIST_DEFAULTS = dict(reject_tol=0.1, vote_cos_min=0.5, min_votes=3)
 REJECTED_NAME = "face_proj_rejected.png"
+MAX_REG_ROUNDS = 3
+REG_DEFAULTS = dict(block=32, stride=None, radius=4, ratio=0.8, reach=1)      # view_flows'; stride None: block // 2
+REGISTER_DEFAULTS = dict(**REG_DEFAULTS, rounds=1)                            # project_frame's `register`
+REGISTER_NAME, FLOWS_NAME = "face_proj_register.json", "face_proj_flows.npz"
 
 
 def _filled(defaults: dict, **given) -> dict:
@@ -147,6 +172,43 @@ def check_consist_options(reject_tol=None, vote_cos_min=None, min_votes=None) ->
     if isinstance(n, bool) or not isinstance(n, (int, float, np.integer, np.floating)) or not np.isfinite(n) or int(n) != n \
             or not 2 <= int(n) <= MAX_STAT_VIEWS:
         raise ValueError(f"min_votes must be an integer in [2, {MAX_STAT_VIEWS}], got {n!r}")
+    return o
+
+
+def _whole(x, what: str, lo: int, hi: int) -> int:
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) or int(x) != x \
+            or not lo <= int(x) <= hi:
+        raise ValueError(f"{what} must be an integer in [{lo}, {hi}], got {x!r}")
+    return int(x)
+
+
+def check_reg_options(block=None, stride=None, radius=None, ratio=None, reach=None) -> dict:
+    """ValueError for a parameter view_flows would refuse (callable without a device); the five options, None: REG_DEFAULTS'
+    (stride: block // 2).  block, stride and radius are drift.match's, ratio is drift.flow's, reach is drift.dense_flow's."""
+    from . import drift
+    o = _filled(REG_DEFAULTS, block=block, stride=None, radius=radius, ratio=ratio, reach=reach)
+    o["block"] = _whole(o["block"], "block", drift.MIN_BLOCK, drift.MAX_BLOCK)
+    o["radius"] = _whole(o["radius"], "radius", 0, drift.MAX_RADIUS)
+    o["reach"] = _whole(o["reach"], "reach", 1, drift.MAX_REACH)
+    o["stride"] = None if stride is None else _whole(stride, "stride", 1, o["block"])
+    o["block"], o["stride"], o["radius"], _ = drift.check_options(o["block"], o["stride"], o["radius"])
+    if isinstance(o["ratio"], bool) or not isinstance(o["ratio"], (int, float, np.integer, np.floating)) or not 0.0 < float(o["ratio"]) <= 1.0:
+        raise ValueError(f"ratio must be in (0, 1], got {o['ratio']!r}")
+    o["ratio"] = float(o["ratio"])
+    drift.check_reach(o["reach"], o["stride"], 0)
+    return o
+
+
+def check_register_options(register) -> dict:
+    """None, or the checked options of project_frame's `register`: a dict of view_flows' options and rounds (1..3), {} for
+    REGISTER_DEFAULTS; ValueError for anything else (callable without a device)."""
+    if register is None:
+        return None
+    if not isinstance(register, dict) or set(register) - set(REGISTER_DEFAULTS):
+        raise ValueError(f"register must be a dict of {', '.join(REGISTER_DEFAULTS)}, got {register!r}")
+    rounds = register.get("rounds")
+    o = check_reg_options(**{k: v for k, v in register.items() if k != "rounds"})
+    o["rounds"] = _whole(REGISTER_DEFAULTS["rounds"] if rounds is None else rounds, "rounds", 1, MAX_REG_ROUNDS)
     return o
 
 
@@ -221,6 +283,11 @@ def _skip(skip, skip_base, h: int, w: int, V: int) -> list:
     return [("skip", skip)]
 
 
+def _flows(flows, V: int, H: int, W: int) -> list:
+    """[] for no flows, or [("flows", flows)] for _placed: view_flows' int16 [V,H,W,2] tensor; ValueError for anything else"""
+    return [] if flows is None else [("flows", _map(flows, "flows", (V, H, W, 2), torch.int16))]
+
+
 def _placed(dev, pos, nrm, coverage, others, g) -> tuple:
     """The last step before a launch, after every argument error: the named tensors `others` live where pos does (ValueError), and
     that is a HIP device (RuntimeError).  (pos, nrm, coverage as uint8, others' tensors), all contiguous, and the gains uploaded."""
@@ -235,7 +302,7 @@ def _placed(dev, pos, nrm, coverage, others, g) -> tuple:
 
 def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, photos: torch.Tensor, depth: torch.Tensor, *,
             power=None, cos_min=None, fade_px=None, depth_tol=None, mode=None, gains=None, skip=None,
-            skip_base=0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+            skip_base=0, flows=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8).  pos / nrm [h,w,3] float32: each texel's point in the
     training world frame and its normal (any length; a zero normal switches the texel off); coverage [h,w] uint8 or bool;
     cams: a sequence of GaussianRasterizationSettings of one size, or (packed view records, H, W), as MeshRenderer.render takes
@@ -244,21 +311,25 @@ def project(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, 
     gains[v] in the kernel, in float64; no scaled copy of the photographs is made.  skip (None: no mask): consistency's int32
     [h,w] mask on the same device; view v of this call is left out at a texel, exactly as a view the rule does not accept there,
     when bit skip_base + v of skip is set (skip_base an integer, skip_base + V <= 32): it enters no blend, cannot be the best
-    view and does not count."""
+    view and does not count.  flows (None: none): view_flows' int16 [V,H,W,2] tensor on the same device, (f_y, f_x) in 1/256 px:
+    a view is accepted and weighed at its pixel (px, py) as without flows, and its photograph is then sampled at (px + f_x / 256,
+    py + f_y / 256), the flow read at the pixel nearest to (px, py); a view whose moved taps leave the image is left out as a
+    masked one is.  An all-zero flows gives the bits of None."""
     o = check_options(power, cos_min, fade_px, depth_tol, mode)
     if o["mode"] not in _MODES:
         raise ValueError(f"mode {o['mode']!r} has five outputs and takes the low bands: it is project_bands'")
     h, w, dev = _texel_maps(pos, nrm, coverage)
     views, V, H, W = _view_group(dev, cams, depth, photos=photos)
     g = _gains(gains, V)
-    mask = _skip(skip, skip_base, h, w, V)
-    pos, nrm, cov, (photos, depth, *mask), g = _placed(dev, pos, nrm, coverage, [("photos", photos), ("depth", depth), *mask], g)
+    mask, flow = _skip(skip, skip_base, h, w, V), _flows(flows, V, H, W)
+    pos, nrm, cov, (photos, depth, *held), g = _placed(dev, pos, nrm, coverage, [("photos", photos), ("depth", depth), *mask, *flow], g)
     color = torch.empty(h, w, 3, dtype=torch.float32, device=dev)
     weight = torch.empty(h, w, dtype=torch.float32, device=dev)
     count = torch.empty(h, w, dtype=torch.uint8, device=dev)
-    _lib.call("t4d_project_texture_skip", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(depth), ptr(g),
-              *_rule(o), _MODES[o["mode"]], ptr(color), ptr(weight), ptr(count), ptr(mask[0]) if mask else None, int(skip_base),
-              _lib.stream(dev))
+    name, more = ("t4d_project_texture_flow", (ptr(held[-1]),)) if flow else ("t4d_project_texture_skip", ())
+    _lib.call(name, ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(depth), ptr(g),
+              *_rule(o), _MODES[o["mode"]], ptr(color), ptr(weight), ptr(count), ptr(held[0]) if mask else None, int(skip_base),
+              _lib.stream(dev), *more)
     return color, weight, count
 
 
@@ -289,27 +360,89 @@ def low_band(photos: torch.Tensor, depth: torch.Tensor, radius: int = 8) -> torc
 
 def project_bands(pos: torch.Tensor, nrm: torch.Tensor, coverage: torch.Tensor, cams, photos: torch.Tensor, low: torch.Tensor,
                   depth: torch.Tensor, *, power=None, cos_min=None, fade_px=None, depth_tol=None, gains=None, skip=None,
-                  skip_base=0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                  skip_base=0, flows=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """(low_color [h,w,3] float32, weight [h,w] float32, count [h,w] uint8, high [h,w,3] float32, best_weight [h,w] float32): the
     two bands of mode "twoband".  The arguments of project and low [V,3,H,W] float32, low_band's.  Every view that project would
     accept at a texel gives its sample s and, by the same bilinear mix over the same taps of low, its low band l (both times
     gains[v] when given).  low_color, weight, count: the blend of the l as mode "weighted" blends the s.  high = s - l and
     best_weight = the weight of the view mode "best" would keep.  The texture is low_color + high; zeros where no view counts.
-    skip, skip_base: as project takes them; a masked view enters neither band."""
+    skip, skip_base: as project takes them; a masked view enters neither band.  flows: as project takes them; s and l are both
+    sampled at the moved position, and a view whose moved taps leave the image enters neither band."""
     o = check_options(power, cos_min, fade_px, depth_tol)
     h, w, dev = _texel_maps(pos, nrm, coverage)
     views, V, H, W = _view_group(dev, cams, depth, photos=photos, low=low)
     g = _gains(gains, V)
-    mask = _skip(skip, skip_base, h, w, V)
-    pos, nrm, cov, (photos, low, depth, *mask), g = _placed(dev, pos, nrm, coverage,
-                                                              [("photos", photos), ("low", low), ("depth", depth), *mask], g)
+    mask, flow = _skip(skip, skip_base, h, w, V), _flows(flows, V, H, W)
+    pos, nrm, cov, (photos, low, depth, *held), g = _placed(dev, pos, nrm, coverage,
+                                                              [("photos", photos), ("low", low), ("depth", depth), *mask, *flow], g)
     low_color, high = (torch.empty(h, w, 3, dtype=torch.float32, device=dev) for _ in range(2))
     weight, best_weight = (torch.empty(h, w, dtype=torch.float32, device=dev) for _ in range(2))
     count = torch.empty(h, w, dtype=torch.uint8, device=dev)
-    _lib.call("t4d_project_texture_bands_skip", ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(low), ptr(depth),
-              ptr(g), *_rule(o), ptr(low_color), ptr(weight), ptr(count), ptr(high), ptr(best_weight), ptr(mask[0]) if mask else None,
-              int(skip_base), _lib.stream(dev))
+    name, more = ("t4d_project_texture_bands_flow", (ptr(held[-1]),)) if flow else ("t4d_project_texture_bands_skip", ())
+    _lib.call(name, ptr(pos), ptr(nrm), ptr(cov), h, w, ptr(views), V, H, W, ptr(photos), ptr(low), ptr(depth),
+              ptr(g), *_rule(o), ptr(low_color), ptr(weight), ptr(count), ptr(high), ptr(best_weight), ptr(held[0]) if mask else None,
+              int(skip_base), _lib.stream(dev), *more)
     return low_color, weight, count, high, best_weight
+
+
+def flow_report(d, kept) -> dict:
+    """One view's entry of view_flows' report, on the host in float64: "blocks" and "kept", and over the kept blocks of drift.flow's
+    d [nby,nbx,2] the mean (the exactly rounded sum over their number), the lower median, p90 (the value of rank ceil(0.9 n)) and the
+    max of |d| = sqrt(dy dy + dx dx), in pixels; a view without a kept block has the first two only."""
+    import math
+    d, kept = np.asarray(d, np.float64).reshape(-1, 2), np.asarray(kept).reshape(-1) != 0
+    n = int(kept.sum())
+    out = {"blocks": int(kept.size), "kept": n}
+    if n:
+        srt = np.sort(np.sqrt(d[kept, 0] * d[kept, 0] + d[kept, 1] * d[kept, 1]))
+        out.update(mean=math.fsum(srt.tolist()) / n, median=float(srt[(n - 1) // 2]), p90=float(srt[min(n - 1, -(-9 * n // 10) - 1)]),
+                   max=float(srt[-1]))
+    return out
+
+
+def view_flows(renders: torch.Tensor, photos: torch.Tensor, depth: torch.Tensor, *, block=32, stride=None, radius=4, ratio=0.8,
+               reach=1) -> Tuple[torch.Tensor, torch.Tensor, list]:
+    """(flows int16 [V,H,W,2], support uint8 [V,H,W], report): every view registered against the consensus.  renders [V,3,H,W] float32:
+    the consensus texture in every camera (meshrender.MeshRenderer.render); photos [V,3,H,W] float32; depth [V,1,H,W] float32, the
+    render's; on one HIP device.  Per view: image A is texfinish.quantize of the render and B of the photograph; a pixel is valid in
+    both when depth > 0 and A's pixel is not zero in all three channels, and its label is then 1; drift.match(A, valid, B, valid,
+    labels, block, stride, radius), drift.flow(table, radius, ratio) and drift.dense_flow(d, kept, labels, block, stride, 0, reach)
+    give the field, which is cast to int16 (|f| <= (radius + 0.5) 256).  A at x shows what B shows at x + f / 256: what project's
+    flows are.  support: 1 where a kept block reaches the pixel; the flow is 0 elsewhere.  report: flow_report per view.  The options
+    (REG_DEFAULTS; stride None: block // 2) are conventional choices, not tuned on a capture.  The views go one after
+    the other: the peak memory is one view's intermediates and the int16 stack.  Known limits: a block straddling a self-occlusion
+    edge (nose over cheek) matches two surfaces; the census needs texture, so smooth skin at low resolution keeps few blocks and
+    falls back to zero flow there; a misregistration beyond `radius` is dropped, not corrected."""
+    from . import drift, texfinish
+    o = check_reg_options(block, stride, radius, ratio, reach)
+    if not isinstance(renders, torch.Tensor) or renders.dim() != 4 or renders.shape[1] != 3 or min(renders.shape) < 1:
+        raise ValueError(f"renders must be a float32 [V,3,H,W] tensor, got {list(getattr(renders, 'shape', ()))}")
+    V, _, H, W = (int(x) for x in renders.shape)
+    if V > MAX_VIEWS:
+        raise ValueError(f"at most {MAX_VIEWS} views per call, got {V}")
+    _map(renders, "renders", (V, 3, H, W), torch.float32)
+    _map(photos, "photos", (V, 3, H, W), torch.float32)
+    _map(depth, "depth", (V, 1, H, W), torch.float32)
+    for name, t in (("photos", photos), ("depth", depth)):
+        if t.device != renders.device:
+            raise ValueError(f"{name} must live on renders' device {renders.device}, got {t.device}")
+    if not renders.is_cuda:                                    # argument errors first, with or without a device
+        raise RuntimeError("topo4d_amd has no CPU path: the renders, the photographs and the depth must live on a HIP device")
+    dev = renders.device
+    flows = torch.empty(V, H, W, 2, dtype=torch.int16, device=dev)
+    support = torch.empty(V, H, W, dtype=torch.uint8, device=dev)
+    report = []
+    with torch.cuda.device(dev):
+        for v in range(V):
+            a = texfinish.quantize(renders[v].permute(1, 2, 0).contiguous())
+            b = texfinish.quantize(photos[v].permute(1, 2, 0).contiguous())
+            valid = ((depth[v, 0] > 0) & (a != 0).any(dim=2)).to(torch.uint8)      # the labels too: 1 on valid pixels
+            table = drift.match(a, valid, b, valid, valid, o["block"], o["stride"], o["radius"])
+            d, kept = drift.flow(table, o["radius"], o["ratio"])
+            f, s = drift.dense_flow(d, kept, valid, o["block"], o["stride"], 0, o["reach"], check=False)
+            flows[v], support[v] = f.to(torch.int16), s
+            report.append(flow_report(d.cpu().numpy(), kept.cpu().numpy()))
+    return flows, support, report
 
 
 def _mixed_views(dev, groups: list, name: str, what: str) -> tuple:
@@ -625,7 +758,7 @@ def frame_consistency(face_obj, vertices: torch.Tensor, dataset, res, *, gains=N
 
 
 def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power=None, cos_min=None, fade_px=None, depth_tol=None, mode=None,
-                  gains=None, device=None, band_radius: int = 8, reject=None):
+                  gains=None, device=None, band_radius: int = 8, reject=None, register=None):
     """(texture [h,w,3] uint8, weight [h,w] float32, count [h,w] uint8) of one frame: `dataset` holds ingest.get_dataset's entries
     ("cam", "im"), vertices [N,3] the mesh in the training world frame.  _frame_inputs gives the texel maps and the depth maps,
     project gathers, texfinish.quantize rounds as the PNG encoder does.  Views of one size go in one launch; a rig with several
@@ -637,14 +770,24 @@ def project_frame(face_obj, vertices: torch.Tensor, dataset, res, *, power=None,
     for CONSIST_DEFAULTS), at most 32 views: consistency runs first over all sizes at once, with the gains, and every size's
     projection takes its part of the mask, in every mode.  The order is equalise, reject, blend, fill.  With "twoband" the low bands
     are still made from every photograph; the mask decides which views enter the two blends and which may be the best view.
-    count is then the number of views that contributed."""
+    count is then the number of views that contributed.  register (None: no registration): a dict of view_flows' options (block,
+    stride, radius, ratio, reach) and rounds (1..3, default 1), {} for REGISTER_DEFAULTS: the views of the frame are registered
+    against their consensus before they are blended (Eisemann et al., "Floating Textures").  The frame is projected once in mode
+    "weighted", with the gains and the mask; that texture's holes are filled island by island (texfinish.fill_islands over
+    island_labels: a black hole would be an edge to match against); MeshRenderer.render puts it into every camera (mapping
+    "bilinear"); view_flows registers every size's photographs against these renders; and the requested mode is projected with the
+    flows.  With rounds > 1 the registered "weighted" projection is the next round's consensus.  The order is equalise, reject,
+    register, blend, fill.  Known limits: view_flows'; consistency and pair_stats still sample unregistered, so the mask and the
+    gains come from unregistered samples; the defaults are conventional, not tuned on a capture."""
     return _project_frame(face_obj, vertices, dataset, res, dict(power=power, cos_min=cos_min, fade_px=fade_px, depth_tol=depth_tol, mode=mode),
-                          gains, device, band_radius, reject)[:3]
+                          gains, device, band_radius, reject, register)[:3]
 
 
-def _project_frame(face_obj, vertices, dataset, res, options: dict, gains, device, band_radius, reject) -> tuple:
-    """project_frame, and as a fourth result the mask of consistency (group order; None without `reject`)"""
-    from . import texfinish
+def _project_frame(face_obj, vertices, dataset, res, options: dict, gains, device, band_radius, reject, register=None) -> tuple:
+    """project_frame, as a fourth result the mask of consistency (group order; None without `reject`) and as a fifth what the
+    registration found (None without `register`): dict(order: the entries of `dataset` in group order, flows and support: view_flows'
+    per size group, report: view_flows' entries in the order of `dataset`)"""
+    from . import meshrender, texfinish
     o = check_options(**options)
     mode, rule = o["mode"], {k: v for k, v in o.items() if k != "mode"}
     check_band_options(band_radius)
@@ -652,31 +795,55 @@ def _project_frame(face_obj, vertices, dataset, res, options: dict, gains, devic
         raise ValueError("project_frame: no views")
     gains = _gains(gains, len(dataset))
     reject = _reject_options(reject, len(dataset))
+    register = check_register_options(register)
     pos, nrm, cov, groups = _frame_inputs(face_obj, vertices, dataset, res, device)
-    skip, base = None, 0
-    if reject is not None:                                     # every size at once: a texel's voters come from all of them
+    skip = None
+    if reject is not None or register is not None:
         groups = list(groups)
         order = [k for ks, *_ in groups for k in ks]
+    if reject is not None:                                     # every size at once: a texel's voters come from all of them
         skip, _ = consistency(pos, nrm, cov, [g[1:] for g in groups], gains=None if gains is None else gains[order], **reject, **rule)
-    total = detail = count = None
-    for ks, cams, photos, depth in groups:
-        g = None if gains is None else gains[ks]
-        mask = {} if skip is None else dict(skip=skip, skip_base=base)      # the group's views are bits base .. base + len(ks) - 1
-        base += len(ks)
-        if mode == "twoband":
-            color, weight, n, high, best = project_bands(pos, nrm, cov, cams, photos, low_band(photos, depth, band_radius), depth, gains=g,
-                                                         **mask, **rule)
-            detail = (high, best) if detail is None else _keep_larger(detail, (high, best))
-        else:
-            color, weight, n = project(pos, nrm, cov, cams, photos, depth, mode=mode, gains=g, **mask, **rule)
-        if total is None:
-            total, count = (color, weight), n
-        else:
-            total, count = (_keep_larger if mode == "best" else _blend)(total, (color, weight)), count + n
-    color, weight = total
-    if detail is not None:                                     # the sum of two bands can leave [0, 1], and quantize wraps as numpy's cast does
-        color = (color + detail[0]).clamp_(0.0, 1.0)
-    return texfinish.quantize(color), weight, count, skip
+
+    def blend(mode, flows):
+        """(texture uint8, weight, count) of the groups in `mode`, group i sampled through flows[i] (flows None: none)"""
+        total = detail = count = None
+        base = 0
+        for i, (ks, cams, photos, depth) in enumerate(groups):
+            g = None if gains is None else gains[ks]
+            mask = {} if skip is None else dict(skip=skip, skip_base=base)      # the group's views are bits base .. base + len(ks) - 1
+            base += len(ks)
+            moved = {} if flows is None else dict(flows=flows[i])
+            if mode == "twoband":
+                color, weight, n, high, best = project_bands(pos, nrm, cov, cams, photos, low_band(photos, depth, band_radius), depth, gains=g,
+                                                             **mask, **moved, **rule)
+                detail = (high, best) if detail is None else _keep_larger(detail, (high, best))
+            else:
+                color, weight, n = project(pos, nrm, cov, cams, photos, depth, mode=mode, gains=g, **mask, **moved, **rule)
+            if total is None:
+                total, count = (color, weight), n
+            else:
+                total, count = (_keep_larger if mode == "best" else _blend)(total, (color, weight)), count + n
+        color, weight = total
+        if detail is not None:                                 # the sum of two bands can leave [0, 1], and quantize wraps as numpy's cast does
+            color = (color + detail[0]).clamp_(0.0, 1.0)
+        return texfinish.quantize(color), weight, count
+
+    if register is None:
+        return (*blend(mode, None), skip, None)
+    vf = {k: v for k, v in register.items() if k != "rounds"}
+    h, w = int(pos.shape[0]), int(pos.shape[1])
+    labels = island_labels(face_obj, h, w, device=pos.device)
+    faces, uv_faces = meshrender.triangulate(face_obj.faces_ori, face_obj.uv_faces_ori)
+    flows = None
+    for _ in range(register["rounds"]):
+        tex, _, n = blend("weighted", flows)                   # the consensus: at first unregistered, then the registered one
+        tex, _ = texfinish.fill_islands(tex, (n > 0).to(torch.uint8), labels)
+        renderer = meshrender.MeshRenderer(faces, uv_faces, face_obj.uvs, tex, device=pos.device)
+        found = [view_flows(renderer.render(vertices, cams, mapping="bilinear")[0], photos, depth, **vf) for _, cams, photos, depth in groups]
+        flows = [f for f, _, _ in found]
+    by_view = dict(zip(order, (r for _, _, rep in found for r in rep)))
+    found = dict(order=order, flows=flows, support=[s for _, s, _ in found], report=[by_view[k] for k in range(len(dataset))])
+    return (*blend(mode, flows), skip, found)
 
 
 def frame_stats(face_obj, vertices: torch.Tensor, dataset, res, *, out=None, device=None, **options):
@@ -748,7 +915,7 @@ def _names(dataset) -> list:
 
 
 def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: int = 0, sizes=(), save_weight: bool = False,
-                device=None, gains=None, fill: bool = False, save_rejected: bool = False) -> list:
+                device=None, gains=None, fill: bool = False, save_rejected: bool = False, register=None, save_flows: bool = False) -> list:
     """One frame's face_proj.png (and face_proj_<size>.png, face_proj_weight.png) in `frame_dir`, from the face.obj read there:
     what the command line and train --tex_project both call.  Returns the files written.  The gutter of `pad` texels is filled
     from the texels some view contributed to (count > 0), through texfinish.finish.  gains: None, or
@@ -757,7 +924,10 @@ def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: 
     for the gutter and the smaller levels; face_proj_weight.png is unchanged, so its zeros inside an island mark what was filled.
     Consistency options among `options` (reject_tol, vote_cos_min, min_votes: what _check_args merges under --reject) switch the
     photo-consistency check on (project_frame's reject); save_rejected then also writes face_proj_rejected.png, the 8-bit number
-    of rejected views per texel."""
+    of rejected views per texel.  register (None: no registration): project_frame's; the frame then also gets
+    face_proj_register.json, {"options", "cameras", "report": view_flows' entry per camera}, and with save_flows face_proj_flows.npz:
+    per image size "cameras_<H>x<W>", "flows_<H>x<W>" int16 [v,H,W,2] and "support_<H>x<W>" uint8 [v,H,W].  Without register every
+    file is what it was."""
     from . import texfinish
     from .evaluate import training_vertices
     from .png import write_png
@@ -765,6 +935,9 @@ def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: 
     options = {k: v for k, v in options.items() if k not in CONSIST_DEFAULTS}
     if save_rejected and reject is None:
         raise ValueError("save_rejected needs the consistency options: nothing is rejected without them")
+    register = check_register_options(register)
+    if save_flows and register is None:
+        raise ValueError("save_flows needs register: there are no flows without it")
     dev = torch.device(device if device is not None else "cuda")
     verts = torch.from_numpy(training_vertices(face_obj.vertices, trans_g)).to(dev)
     if gains is not None:
@@ -773,7 +946,7 @@ def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: 
             raise ValueError(f"no gains for camera(s) {', '.join(missing)}")
         gains = np.asarray([gains[n] for n in _names(dataset)], dtype=np.float64)
     band_radius = options.pop("band_radius", BAND_DEFAULTS["band_radius"])
-    tex, _, count, skip = _project_frame(face_obj, verts, dataset, res, options, gains, dev, band_radius, reject)
+    tex, _, count, skip, found = _project_frame(face_obj, verts, dataset, res, options, gains, dev, band_radius, reject, register)
     seen = (count > 0).to(torch.uint8)
     if fill:
         tex, filled = texfinish.fill_islands(tex, seen, island_labels(face_obj, tex.shape[0], tex.shape[1], device=dev))
@@ -788,6 +961,23 @@ def write_frame(frame_dir, face_obj, trans_g, dataset, res, options: dict, pad: 
         path = os.path.join(frame_dir, REJECTED_NAME)
         write_png(path, rejected_count(skip))
         written.append(path)
+    if register is not None:
+        names = _names(dataset)
+        path = os.path.join(frame_dir, REGISTER_NAME)
+        with open(path, "w") as f:
+            json.dump({"options": register, "cameras": [str(n) for n in names], "report": found["report"]}, f, indent=1)
+            f.write("\n")
+        written.append(path)
+        if save_flows:
+            arrays, at = {}, 0
+            for flows, support in zip(found["flows"], found["support"]):
+                v, size = int(flows.shape[0]), f"{int(flows.shape[1])}x{int(flows.shape[2])}"
+                arrays["cameras_" + size] = np.asarray([str(names[k]) for k in found["order"][at:at + v]])
+                arrays["flows_" + size], arrays["support_" + size] = flows.cpu().numpy(), support.cpu().numpy()
+                at += v
+            path = os.path.join(frame_dir, FLOWS_NAME)
+            np.savez_compressed(path, **arrays)
+            written.append(path)
     return written
 
 
@@ -865,6 +1055,32 @@ def consist_options_of(args) -> dict:
     return _flags_of(args, CONSIST_DEFAULTS)
 
 
+def add_register_options(p: argparse.ArgumentParser, suppress: bool = False) -> None:
+    """The parameters of the registration (--register here, --tex_register on train's parser), beside add_options' on both."""
+    helps = dict(
+        block="Registration: side of the matched blocks in pixels of the photograph, even, 8..64 (default 32).",
+        stride="Registration: distance between blocks, 1..block (default block / 2).",
+        radius="Registration: the largest misregistration searched for, in pixels, 0..16 (default 4); a larger one is dropped, not corrected.",
+        ratio="Registration: keep a block whose best cost is at most this times the second best, in (0, 1] (default 0.8).",
+        reach="Registration: a kept block's flow reaches this many strides, 1..4 (default 1).",
+        rounds=f"Registration: rounds, each against the consensus the one before registered, 1..{MAX_REG_ROUNDS} (default 1).")
+    metavar = dict(block="B", stride="S", radius="R", ratio="Q", reach="K", rounds="N")
+    for k, v in REGISTER_DEFAULTS.items():
+        p.add_argument(f"--reg_{k}", type=float if k == "ratio" else int, default=argparse.SUPPRESS if suppress else v, metavar=metavar[k],
+                       help=helps[k])
+
+
+def register_options_of(args):
+    """None without --register (train: --tex_register), else project_frame's `register` of a parse, checked: SystemExit for what
+    it would refuse"""
+    if not (getattr(args, "register", False) or getattr(args, "tex_register", False)):     # (this module's flag, train's flag)
+        return None
+    try:
+        return check_register_options(_flags_of(args, REGISTER_DEFAULTS, "reg_"))
+    except ValueError as e:
+        raise SystemExit(f"registration options: {e}") from None
+
+
 def check_frame_views(dataset, options: dict) -> None:
     """SystemExit when `options` (of _check_args) ask for the consistency check and the frame holds more views than its mask"""
     if any(k in options for k in CONSIST_DEFAULTS) and len(dataset) > MAX_STAT_VIEWS:
@@ -940,6 +1156,13 @@ def build_parser() -> argparse.ArgumentParser:
     add_consist_options(p)
     p.add_argument("--save_rejected", action="store_true",
                    help="With --reject: also write %%06d/face_proj_rejected.png, the number of rejected views per texel.")
+    p.add_argument("--register", action="store_true",
+                   help="Register every view to the blend of all views before it is projected: a small 2D flow per view, found by "
+                        "block matching against the weighted texture rendered into the camera (after --reject, before the blend); "
+                        "also writes %%06d/face_proj_register.json.")
+    add_register_options(p)
+    p.add_argument("--save_flows", action="store_true",
+                   help="With --register: also write %%06d/face_proj_flows.npz, every view's flow (1/256 px) and its support.")
     return p
 
 
@@ -969,6 +1192,9 @@ def project_tree(args, device=None) -> list:
     save_rejected = getattr(args, "save_rejected", False)
     if save_rejected and not getattr(args, "reject", False):
         raise SystemExit("--save_rejected writes what the consistency check rejects: it needs --reject")
+    register, save_flows = register_options_of(args), getattr(args, "save_flows", False)
+    if save_flows and register is None:
+        raise SystemExit("--save_flows writes what the registration finds: it needs --register")
     equalize, gains_file = getattr(args, "equalize", False), getattr(args, "gains", None)
     if equalize and gains_file:
         raise SystemExit("--equalize estimates the gains and --gains reads them: give one of the two")
@@ -1011,7 +1237,8 @@ def project_tree(args, device=None) -> list:
                     check_frame_views(dataset, opts)
                     written += write_frame(_run.frame_dir(run_dir, t), obj, trans_g, dataset, args.tex_res, opts,
                                            pad=args.tex_pad, sizes=args.tex_sizes, save_weight=args.save_weight, device=dev, gains=gains,
-                                           fill=getattr(args, "tex_fill", False), save_rejected=save_rejected)
+                                           fill=getattr(args, "tex_fill", False), save_rejected=save_rejected, register=register,
+                                           save_flows=save_flows)
         finally:
             pf.close()
     return written

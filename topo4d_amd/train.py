@@ -26,7 +26,9 @@ face_proj.png beside every face.obj, the frame's full-size photographs projected
 estimates one gain per camera and channel on the first frame written, stores proj_gains.json in the run directory and projects
 every frame with it; --tex_fill fills the texels of every UV island that no view sees by push-pull from the island's projected
 texels, texfinish.fill_islands; --tex_reject leaves a view out of a texel where it disagrees with the median of the views that
-face it, projtex.consistency, with --reject_tol, --vote_cos_min and --min_votes).  Without them nothing changes.
+face it, projtex.consistency, with --reject_tol, --vote_cos_min and --min_votes; --tex_register registers every view to the
+blend of all views before it is projected, projtex.view_flows, with --reg_block, --reg_stride, --reg_radius, --reg_ratio, --reg_reach
+and --reg_rounds).  Without them nothing changes.
 
 The region "freezes" of train.py:676-700 are FusedAdamPins pins, written by the step kernel itself; the pin set changes at
 most twice per frame (the dynamic-eye pins end at iteration int(0.7 n) of frame 0) and the learning rates once (the colour
@@ -328,6 +330,9 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
         raise SystemExit("--tex_fill fills the holes of the projected texture: it needs --tex_project")
     if getattr(args, "tex_reject", False) and not tex_project:
         raise SystemExit("--tex_reject rejects inconsistent views of the projected texture: it needs --tex_project")
+    if getattr(args, "tex_register", False) and not tex_project:
+        raise SystemExit("--tex_register registers the views of the projected texture: it needs --tex_project")
+    proj_register = projtex.register_options_of(args) if tex_project else None
     dev = _lib.hip_device(device, "the coarse setup")
     clock = _Clock(timings, dev)
     with torch.cuda.device(dev), clock("setup"):
@@ -461,7 +466,7 @@ def train(args, facial_regions: Optional[dict] = None, device=None, seed: int = 
                                 proj_gains = est.finish(os.path.join(out_dir, projtex.GAINS_NAME))
                             projtex.check_frame_views(dense, proj_opts)
                             projtex.write_frame(frame_dir, face_obj, trans_g, dense, args.tex_res, proj_opts, pad=tex_pad,
-                                                sizes=tex_sizes, device=dev, gains=proj_gains, fill=tex_fill)
+                                                sizes=tex_sizes, device=dev, gains=proj_gains, fill=tex_fill, register=proj_register)
                 state["frames"] = t + 1
                 if on_frame is not None:
                     on_frame(t, state)
@@ -529,11 +534,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--tex_reject', action='store_true', default=argparse.SUPPRESS,
                    help="With --tex_project: leave a view out of a texel where it disagrees with the median of the views that face "
                         "it (topo4d_amd.projtex --reject; --reject_tol, --vote_cos_min and --min_votes as it takes them).")
-    from .projtex import add_band_options, add_consist_options, add_eq_options, add_options
+    p.add_argument('--tex_register', action='store_true', default=argparse.SUPPRESS,
+                   help="With --tex_project: register every view to the blend of all views before it is projected "
+                        "(topo4d_amd.projtex --register; --reg_block, --reg_stride, --reg_radius, --reg_ratio, --reg_reach and "
+                        "--reg_rounds as it takes them).")
+    from .projtex import add_band_options, add_consist_options, add_eq_options, add_options, add_register_options
     add_options(p, suppress=True)
     add_band_options(p, suppress=True)
     add_eq_options(p, suppress=True)
     add_consist_options(p, suppress=True)
+    add_register_options(p, suppress=True)
     return p
 
 
