@@ -854,7 +854,8 @@ int t4d_views_to_u8(const float *src, int32_t channels, int32_t height, int32_t 
  * t4d_setup_flatten_edges: the FlattenLoss / SoftFlattenLoss constructors (loss_util.py:114-170, 262-318) over faces [F,3] int32
  * and their t4d_obj_vertex_faces CSR, for the candidate edges [n_edges,2] in the host's set order.  out [4, n_edges] int64
  * holds v0s, v1s, v2s, v3s in its first *n_out (device) columns.  status [2] (device): edge ends outside [0, n_vert), faces with
- * no third corner.  Scratch: t4d_setup_edges_scratch_bytes.
+ * no third corner met by an edge of at most two faces (the reference drops an edge of more before it looks at their corners).
+ * Scratch: t4d_setup_edges_scratch_bytes.
  * t4d_setup_neighbor_mask: FlattenLoss_v2's mask (loss_util.py:232-241): mask [n_vert,K,3] int64 = (k < neighbor_num[v]). */
 #define T4D_SETUP_MAX_MASKS 32
 size_t t4d_setup_colors_scratch_bytes(int64_t n_corners);

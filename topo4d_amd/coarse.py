@@ -365,7 +365,8 @@ def flatten_edges(faces, n_vert: Optional[int] = None, device=None):
     """(v0s, v1s, v2s, v3s) of FlattenLoss(faces) / SoftFlattenLoss(faces) (loss_util.py:114-170, 262-318), int64 CPU tensors
     like the modules' buffers.  Edges of more than two faces are dropped, v2 / v3 are the third corners of the lowest and the
     next face id, and only the two-face edges are kept, in candidate order.  As in the reference, v0s / v1s are read at the
-    edge's rank among the edges NOT dropped, which is the edge itself unless an earlier edge had more than two faces."""
+    edge's rank among the edges NOT dropped, which is the edge itself unless an earlier edge had more than two faces.
+    ValueError where the reference's `v[0]` fails: a face with no corner besides the ends, on an edge that is not dropped."""
     dev = _lib.hip_device(device, _WHAT)
     f = np.asarray(faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else faces)
     if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] == 0 or not np.issubdtype(f.dtype, np.integer):

@@ -31,12 +31,20 @@ constexpr int kBlock = 256;
 
 unsigned grid_of(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
+// One rounded operation each, compiled under the pragma above.  The headers' __dmul_rn / __dadd_rn / __fmul_rn / __fadd_rn are
+// defined before it: their operations keep the contract flag and, once inlined, a product and the sum it feeds become one fma
+// (a sum of squares was one v_mul_f64 and two v_fmac_f64), which the float32 casts hid on the golden scene.
+__device__ __forceinline__ double dmul(double a, double b) { return a * b; }
+__device__ __forceinline__ double dadd(double a, double b) { return a + b; }
+__device__ __forceinline__ float fmul(float a, float b) { return a * b; }
+__device__ __forceinline__ float fadd(float a, float b) { return a + b; }
+
 // Python's float `x % 1.0` (Objects/floatobject.c float_rem): fmod, shifted into [0, 1) when the signs differ, +0 for 0
 __device__ double py_mod1(double x)
 {
     double m = fmod(x, 1.0);
     if (m != 0.0) {
-        if (m < 0.0) m = __dadd_rn(m, 1.0);
+        if (m < 0.0) m = dadd(m, 1.0);
     } else {
         m = 0.0;
     }
@@ -51,8 +59,8 @@ __global__ void __launch_bounds__(kBlock) k_corner_colors(const uint8_t *__restr
     const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (c >= n_corners) return;
     const double u = py_mod1(uv[2 * c]), v = py_mod1(uv[2 * c + 1]);
-    const double x = __dmul_rn(u, (double)width);
-    const double y = __dmul_rn(__dadd_rn(1.0, -v), (double)height);
+    const double x = dmul(u, (double)width);
+    const double y = dmul(dadd(1.0, -v), (double)height);
     // int(x), int(y); getpixel raises for a column >= width or a row >= height (and int() for NaN): counted, nothing read
     if (!(x >= 0.0 && x < (double)width && y >= 0.0 && y < (double)height)) {
         for (int k = 0; k < 3; ++k) rgb[3 * c + k] = 0;
@@ -66,12 +74,12 @@ __global__ void __launch_bounds__(kBlock) k_corner_colors(const uint8_t *__restr
     const uint8_t *q21 = image + ((int64_t)y1 * width + x2) * channels;
     const uint8_t *q12 = image + ((int64_t)y2 * width + x1) * channels;
     const uint8_t *q22 = image + ((int64_t)y2 * width + x2) * channels;
-    const double ax = __dadd_rn((double)x2, -x), bx = __dadd_rn(x, -(double)x1);
-    const double ay = __dadd_rn((double)y2, -y), by = __dadd_rn(y, -(double)y1);
+    const double ax = dadd((double)x2, -x), bx = dadd(x, -(double)x1);
+    const double ay = dadd((double)y2, -y), by = dadd(y, -(double)y1);
     for (int k = 0; k < 3; ++k) {
-        const double r1 = __dadd_rn(__dmul_rn(ax, (double)q11[k]), __dmul_rn(bx, (double)q21[k]));
-        const double r2 = __dadd_rn(__dmul_rn(ax, (double)q12[k]), __dmul_rn(bx, (double)q22[k]));
-        const double p = __dadd_rn(__dmul_rn(ay, r1), __dmul_rn(by, r2));
+        const double r1 = dadd(dmul(ax, (double)q11[k]), dmul(bx, (double)q21[k]));
+        const double r2 = dadd(dmul(ax, (double)q12[k]), dmul(bx, (double)q22[k]));
+        const double p = dadd(dmul(ay, r1), dmul(by, r2));
         rgb[3 * c + k] = (int32_t)p;                                     // int(): truncation toward zero
     }
 }
@@ -106,19 +114,19 @@ __global__ void __launch_bounds__(kBlock) k_quaternions(const double *__restrict
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const float d0 = (float)normals[3 * i], d1 = (float)normals[3 * i + 1], d2 = (float)normals[3 * i + 2];
-    const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d0, d0), __fmul_rn(d1, d1)), __fmul_rn(d2, d2)));
+    const float nrm = sqrtf(fadd(fadd(fmul(d0, d0), fmul(d1, d1)), fmul(d2, d2)));
     const float u0 = __fdiv_rn(d0, nrm), u1 = __fdiv_rn(d1, nrm), u2 = __fdiv_rn(d2, nrm);
     // cross((1,0,0), u) = (0*u2 - 0*u1, 0*u0 - 1*u2, 1*u1 - 0*u0); angle = acos(1*u0 + 0*u1 + 0*u2)
-    const float ax = __fadd_rn(__fmul_rn(0.f, u2), -__fmul_rn(0.f, u1));
-    const float ay = __fadd_rn(__fmul_rn(0.f, u0), -u2);
-    const float az = __fadd_rn(u1, -__fmul_rn(0.f, u0));
-    const float ang = acosf(__fadd_rn(__fadd_rn(u0, __fmul_rn(0.f, u1)), __fmul_rn(0.f, u2)));
-    const float h = __fmul_rn(ang, 0.5f);                               // angle / 2 (exact)
+    const float ax = fadd(fmul(0.f, u2), -fmul(0.f, u1));
+    const float ay = fadd(fmul(0.f, u0), -u2);
+    const float az = fadd(u1, -fmul(0.f, u0));
+    const float ang = acosf(fadd(fadd(u0, fmul(0.f, u1)), fmul(0.f, u2)));
+    const float h = fmul(ang, 0.5f);                               // angle / 2 (exact)
     const float s = sinf(h);
     quat[4 * i] = cosf(h);
-    quat[4 * i + 1] = __fmul_rn(ax, s);
-    quat[4 * i + 2] = __fmul_rn(ay, s);
-    quat[4 * i + 3] = __fmul_rn(az, s);
+    quat[4 * i + 1] = fmul(ax, s);
+    quat[4 * i + 2] = fmul(ay, s);
+    quat[4 * i + 3] = fmul(az, s);
 }
 
 // ---- c. one-ring distances and weights --------------------------------------------------------------------------------
@@ -136,16 +144,16 @@ __global__ void __launch_bounds__(kBlock) k_one_ring(const float *__restrict__ m
         return;
     }
     double d[3], sq = 0.0, wh = 0.0;
-    for (int k = 0; k < 3; ++k) d[k] = __dadd_rn((double)means3D[3 * v + k], -(double)means3D[3 * j + k]);
-    sq = __dadd_rn(__dadd_rn(__dmul_rn(d[0], d[0]), __dmul_rn(d[1], d[1])), __dmul_rn(d[2], d[2]));
+    for (int k = 0; k < 3; ++k) d[k] = dadd((double)means3D[3 * v + k], -(double)means3D[3 * j + k]);
+    sq = dadd(dadd(dmul(d[0], d[0]), dmul(d[1], d[1])), dmul(d[2], d[2]));
     if (eye_del[j] && !eye_del[v]) {                                  // ((a - b) * 1000) ** 2, summed
         double e[3];
-        for (int k = 0; k < 3; ++k) e[k] = __dmul_rn(d[k], 1000.0);
-        wh = __dadd_rn(__dadd_rn(__dmul_rn(e[0], e[0]), __dmul_rn(e[1], e[1])), __dmul_rn(e[2], e[2]));
+        for (int k = 0; k < 3; ++k) e[k] = dmul(d[k], 1000.0);
+        wh = dadd(dadd(dmul(e[0], e[0]), dmul(e[1], e[1])), dmul(e[2], e[2]));
     } else {
         wh = sq;
     }
-    double w = exp(__dmul_rn(-2000.0, wh));
+    double w = exp(dmul(-2000.0, wh));
     if (w == 1.0) w = 0.0;
     weight[t] = (float)w;
     dist[t] = (float)__dsqrt_rn(sq);
@@ -172,13 +180,14 @@ __global__ void __launch_bounds__(kBlock) k_region_apply(const float *__restrict
     const uint32_t b = bits[t / K];
     float w = in[t];
     for (int m = 0; m < n_masks; ++m)
-        if (b >> m & 1u) w = __fmul_rn(w, factors[m]);
+        if (b >> m & 1u) w = fmul(w, factors[m]);
     out[t] = w;
 }
 
 // ---- e. flatten-edge topology -----------------------------------------------------------------------------------------
 // per edge: count of distinct faces holding both ends (face ids ascending: the CSR lists corners 3*face+k ascending), the
-// opposite corner of the first two.  status[0]: an endpoint out of range; status[1]: a face with no corner besides the ends
+// opposite corner of the first two.  status[0]: an endpoint out of range; status[1]: a face with no corner besides the ends, on
+// an edge of at most two faces
 __global__ void __launch_bounds__(kBlock) k_edge_faces(const int32_t *__restrict__ faces, int32_t n_vert, const int32_t *__restrict__ offsets,
                                                        const int32_t *__restrict__ entries, const int32_t *__restrict__ edges,
                                                        int64_t n_edges, int32_t *__restrict__ info, int32_t *__restrict__ status)
@@ -186,7 +195,7 @@ __global__ void __launch_bounds__(kBlock) k_edge_faces(const int32_t *__restrict
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (e >= n_edges) return;
     const int a = edges[2 * e], b = edges[2 * e + 1];
-    int count = 0, opp[2] = {-1, -1}, last = -1;
+    int count = 0, opp[2] = {-1, -1}, last = -1, no_third = 0;
     if (a < 0 || a >= n_vert || b < 0 || b >= n_vert) {
         atomicAdd(&status[0], 1);
     } else {
@@ -199,11 +208,13 @@ __global__ void __launch_bounds__(kBlock) k_edge_faces(const int32_t *__restrict
             if (count < 2) {
                 // np.copy(face)[v != v0][v != v1][0]: the first corner that is neither end
                 const int o = (c0 != a && c0 != b) ? c0 : (c1 != a && c1 != b) ? c1 : (c2 != a && c2 != b) ? c2 : -1;
-                if (o < 0) atomicAdd(&status[1], 1);
+                if (o < 0) ++no_third;
                 opp[count] = o;
             }
             ++count;
         }
+        // the reference skips an edge of more than two faces before it looks at their corners: only a kept edge can fail
+        if (count <= 2 && no_third) atomicAdd(&status[1], no_third);
     }
     info[3 * e] = count;
     info[3 * e + 1] = opp[0];
