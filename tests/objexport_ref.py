@@ -11,6 +11,9 @@ tools/gen_golden_mesh.py, tools/bench_objexport.py).  Plain numpy / torch on the
                          it are multiplied by their norm, not divided by it)
   seam_color_index       helpers.duplicate_texture_vertex_color_2 (helpers.py:923-934) as an index array
   save_mesh_vertices     the vertex arithmetic of helpers.save_mesh (helpers.py:963-979), torch / numpy on the CPU
+  vertex_corner_csr      the vertex -> corner CSR and the two status counts of t4d_obj_vertex_faces
+  normal_condition       the trimesh rule in long double, and each vertex's condition number (tests/obj_cases.py)
+  frame_vertices_rule    k_obj_frame_vertices operation by operation: float32 cast chain, float64 push and transform
 """
 import io
 
@@ -94,6 +97,108 @@ def trimesh_vertex_normals(vertices, faces):
     summed = np.zeros((len(vertices), 3), dtype=np.float64)
     np.add.at(summed, rows[first], weight[:, None] * normals[cols[first]])
     return unitize(summed)
+
+
+def vertex_corner_csr(faces, n_vert):
+    """The vertex -> corner CSR as t4d_obj_vertex_faces defines it: (offsets int32 [n_vert + 1], entries int32, corners out of
+    range, empty rows).  Corner 3 * face + k belongs to the vertex it names; a row lists its corners ascending; a corner naming
+    a vertex outside [0, n_vert) is counted and left out."""
+    named = np.asarray(faces, dtype=np.int64).reshape(-1)
+    ok = (named >= 0) & (named < n_vert)
+    counts = np.bincount(named[ok], minlength=n_vert)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    corners = np.nonzero(ok)[0]
+    entries = corners[np.argsort(named[ok], kind="stable")].astype(np.int32)
+    return offsets, entries, int((~ok).sum()), int((counts == 0).sum())
+
+
+def normal_condition(vertices, faces):
+    """(kappa [P], normals [P,3]) in np.longdouble (a 64-bit mantissa on x86): the trimesh rule of trimesh_vertex_normals
+    evaluated in long double, and per vertex
+
+        kappa_v = (sum_f |w_f| / || sum_f w_f n_f ||) / (the smallest sine of any angle of any face in the sum),
+
+    the factor by which one rounding of a face's angle (acos loses 1 / sin of it) or of its normal (the cross product of two
+    edges loses 1 / sin of their angle) grows in the unit sum.  w_f: the face's angles at the vertex, 0 for a face degenerate by
+    tol.merge; n_f: its unit normal, 0 at or below tol.zero.  Such faces add exactly nothing in any precision, so the minimum
+    runs over the others (which only lowers kappa); a vertex whose sum is exactly 0 has kappa = inf and a zero normal."""
+    L = np.longdouble
+    V = np.asarray(vertices, dtype=np.float64).astype(L)
+    faces = np.asarray(faces, dtype=np.int64)
+    tri = V[faces]
+    ab, ac, bc = tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], tri[:, 2] - tri[:, 1]
+
+    def norm(x):
+        return np.sqrt((x * x).sum(1))
+
+    def unit(x):
+        n = norm(x)
+        return x * np.where(n > TOL_ZERO, L(1) / np.where(n > 0, n, L(1)), n)[:, None]
+
+    cross = np.stack([ab[:, 1] * ac[:, 2] - ab[:, 2] * ac[:, 1], ab[:, 2] * ac[:, 0] - ab[:, 0] * ac[:, 2],
+                      ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]], axis=1)
+    has_normal = norm(cross) > TOL_ZERO
+    normals = np.where(has_normal[:, None], unit(cross), L(0))
+    u, v, w = unit(ab), unit(ac), unit(bc)
+    angles = np.zeros((len(faces), 3), dtype=L)
+    angles[:, 0] = np.arccos(np.clip((u * v).sum(1), -1, 1))
+    angles[:, 1] = np.arccos(np.clip((-u * w).sum(1), -1, 1))
+    angles[:, 2] = L(np.pi) - angles[:, 0] - angles[:, 1]
+    degenerate = (angles < TOL_MERGE).any(axis=1)
+    sines = np.sin(angles).min(axis=1)
+    angles[degenerate] = 0
+    in_sum = has_normal & ~degenerate
+    rows = faces.ravel()
+    weight = np.zeros(len(V), dtype=L)
+    np.add.at(weight, rows, np.abs(angles).ravel())
+    summed = np.zeros((len(V), 3), dtype=L)
+    np.add.at(summed, rows, (angles[:, :, None] * normals[:, None, :]).reshape(-1, 3))
+    least = np.full(len(V), np.inf, dtype=L)
+    np.minimum.at(least, rows, np.repeat(np.where(in_sum, sines, L(np.inf)), 3))
+    length = norm(summed)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        kappa = np.where(length > 0, weight / length / least, L(np.inf))
+    return kappa, unit(summed)
+
+
+def frame_vertices_rule(means3D, log_scales, rotations, normals, transform):
+    """k_obj_frame_vertices (csrc/t4d_obj.hip) operation by operation: (vertices float64 [P,3], cast float32 [P] or None).
+    normals None is frame 1.  Every float32 step is one numpy float32 operation per element in the kernel's order (numpy does
+    not contract), the push v + double(cast) * n and ((v0 r0 + v1 r1) + v2 r2) + t are float64; a NaN cast stays NaN.
+    transform: [3,4] float64 (rows of Rg, then tg).  Only exp is a library function."""
+    f = np.float32
+    one, two = f(1.0), f(2.0)
+    v = np.asarray(means3D, dtype=f).astype(np.float64)
+    t = np.asarray(transform, dtype=np.float64).reshape(3, 4)
+    cast = None
+    if normals is not None:
+        nd = np.asarray(normals, dtype=np.float64)
+        q = np.asarray(rotations, dtype=f)
+        ls = np.asarray(log_scales, dtype=f)
+        with np.errstate(all="ignore"):
+            r, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+            qn = np.sqrt(((r * r + x * x) + y * y) + z * z)
+            r, x, y, z = r / qn, x / qn, y / qn, z / qn
+            R = [one - two * (y * y + z * z), two * (x * y - r * z), two * (x * z + r * y),
+                 two * (x * y + r * z), one - two * (x * x + z * z), two * (y * z - r * x),
+                 two * (x * z - r * y), two * (y * z + r * x), one - two * (x * x + y * y)]
+            c00, c01, c02 = R[4] * R[8] - R[5] * R[7], R[5] * R[6] - R[3] * R[8], R[3] * R[7] - R[4] * R[6]
+            det = (R[0] * c00 + R[1] * c01) + R[2] * c02
+            Ri = [c00 / det, (R[2] * R[7] - R[1] * R[8]) / det, (R[1] * R[5] - R[2] * R[4]) / det,
+                  c01 / det, (R[0] * R[8] - R[2] * R[6]) / det, (R[2] * R[3] - R[0] * R[5]) / det,
+                  c02 / det, (R[1] * R[6] - R[0] * R[7]) / det, (R[0] * R[4] - R[1] * R[3]) / det]
+            nf = nd.astype(f)
+            acc = np.zeros(len(v), dtype=f)
+            for a in range(3):
+                nr = (Ri[3 * a] * nf[:, 0] + Ri[3 * a + 1] * nf[:, 1]) + Ri[3 * a + 2] * nf[:, 2]
+                s = np.exp(ls[:, a])
+                acc = acc + (nr * nr) / (s * s)
+            cast = np.sqrt(one / acc)
+            cast = np.where(np.isnan(cast), cast, np.minimum(np.maximum(cast, f(0.0)), f(0.001))).astype(f)
+            v = v + cast.astype(np.float64)[:, None] * nd
+    with np.errstate(all="ignore"):
+        out = np.stack([((v[:, 0] * t[a, 0] + v[:, 1] * t[a, 1]) + v[:, 2] * t[a, 2]) + t[a, 3] for a in range(3)], axis=1)
+    return out, cast
 
 
 def seam_color_index(uvs_ori, uvs_texture_ori):
