@@ -1170,6 +1170,110 @@ int t4d_profile_end(T4DKernelTime *out, int max_entries, int *n_entries);
 #define T4D_DEBUG_LAYOUT_FIELDS 16
 int t4d_debug_state_layout(const T4DProblem *prob, int has_sh, uint64_t *offsets, int n);
 
+/* Non-rigid fit of a template mesh to a scan (csrc/t4d_nricp.hip): the device half of topo4d_amd/startup.py, after Amberg,
+ * Romdhani and Vetter, "Optimal Step Nonrigid ICP" (CVPR 2007).  The host route this stands in for is
+ * trimesh.registration.nricp_amberg; the reference project has no counterpart (its README asks for a fitted face_v5.obj).
+ * Everything is float64 without contraction, dot3(u,v) = (u0 v0 + u1 v1) + u2 v2, no atomics, and every output is a function of
+ * the inputs alone; tests/startup_ref.py states every rule in numpy, bit for bit.  Device buffers unless stated; the stream
+ * comes last.  n is the number of template vertices, 1 <= n < 2^30 (n == 0 is T4D_OK and touches nothing).
+ *
+ * Unknowns.  One 4x3 matrix X_i per vertex; the moved vertex is p_i = X_i^T vt_i with vt_i = (v_i, 1) and v_i the pre-aligned
+ * template vertex in the normalised frame (the host's business).  A "field" holds one double per entry of every X_i as
+ * [3][4][n]: field[(4 c + r) n + i] is row r of coordinate column c of vertex i.  X, the right-hand side B, the residual R,
+ * the preconditioned residual Z, the direction P and K P are fields.  v is float64 [n,3].  The mesh's edges come as the CSR of
+ * every vertex's neighbours in ascending index: nbr_off int32 [n + 1], nbr int32 [nbr_off[n]], every entry in [0, n) (the
+ * caller checks); deg_i = nbr_off[i + 1] - nbr_off[i].
+ *
+ * The system of one outer step, per coordinate column c, with a2 = alpha^2, a2g = a2 gamma^2 (host doubles, finite, > 0),
+ * g_r = a2 for the rows r = 0, 1, 2 and a2g for r = 3, and s_i the vertex's data weight (float64 [n], >= 0):
+ *   (K P)_i[c][r] = g_r * L + d_r,   L = the sum over j in N(i), ascending, added to 0 in that order, of (P_i[c][r] - P_j[c][r]),
+ *                   t = ((v0 P_i[c][0] + v1 P_i[c][1]) + v2 P_i[c][2]) + P_i[c][3],  d = s_i * t,  d_r = v_r * d (r < 3), d_3 = d.
+ * t4d_nricp_assemble: s_i = w_i + bl_i with bl_i = beta2 * lw_i (lw NULL: bl_i = 0; beta2 host, finite, >= 0; w the data
+ * weights t4d_nricp_classify wrote, lw float64 [n] the landmark indicator or weight), the right-hand side
+ *   B_i[c][r] = vt_r * (w_i * c_i[c] + bl_i * lt_i[c])   (c: float64 [n,3] targets, lt: float64 [n,3] landmark targets; vt_3 = 1)
+ * and the Cholesky factor of the preconditioner's block M_i = diag(deg_i g_r) + s_i vt_i vt_i^T: A[r][q] = (s_i * vt_r) * vt_q
+ * for q <= r, A[r][r] = A[r][r] + deg_i * g_r, then for j = 0..3: L[j][j] = sqrt(A[j][j] - sum_{k<j} L[j][k] L[j][k]) and for
+ * i > j: L[i][j] = (A[i][j] - sum_{k<j} L[i][k] L[j][k]) / L[j][j], every sum taken by subtracting the products from the first
+ * term in ascending k.  A vertex without an edge (deg_i == 0) takes the identity: without data its block is zero, and with data
+ * it has rank one.  chol: float64 [10][n], entry r (r + 1) / 2 + q of L[r][q].  Outputs s, B, chol.
+ * t4d_nricp_precond: Z = M^-1 R per vertex and column: y_r = (R_r - sum_{k<r} L[r][k] y_k) / L[r][r] for r = 0..3, then
+ * z_r = (y_r - sum_{k>r} L[k][r] z_k) / L[r][r] for r = 3..0, sums as above in ascending k.  Quotients, no reciprocal.
+ * t4d_nricp_apply: Q = K P and dots[c] = P[c] . Q[c] (device, 3 doubles) by the reduction below over the per-vertex terms
+ * ((P0 Q0 + P1 Q1) + P2 Q2) + P3 Q3 of column c.
+ *
+ * Reduction order, fixed, for every sum over the vertices (the scheme of t4d_align_accumulate): G = min(ceil(n / 256),
+ * T4D_NRICP_MAX_GROUPS) workgroups of 256 lanes; lane l of all 256 G adds the vertices l, l + 256 G, ... to zeros in that order;
+ * a wave of 64 folds v[t] = v[t] + v[t + w] for w = 32 .. 1; a workgroup's four waves give (w0 + w1) + (w2 + w3); the G
+ * workgroup sums are added to zeros in index order.  The largest move is a maximum, exact in any order.
+ *
+ * Conjugate gradients, the three columns in lock-step, each with its own scalars.  state: T4D_NRICP_STATE_DOUBLES doubles, two
+ * records of 16 (record k & 1 is current after k iterations) and ||B[c]||^2 at T4D_NRICP_STATE_BB.  A record holds, per column,
+ * rz = R . Z at T4D_NRICP_RZ, rr = R . R at T4D_NRICP_RR, the last pq = P . K P at T4D_NRICP_PQ, the last step alpha at
+ * T4D_NRICP_ALPHA and beta at T4D_NRICP_BETA, and the iteration count at T4D_NRICP_ITER.
+ * t4d_nricp_cg_start: R = B - K X, Z = M^-1 R, P = Z, and record 0 with rz, rr (pq, alpha, beta, count 0) and bb.
+ * t4d_nricp_cg_run: `iters` iterations (0..T4D_NRICP_MAX_RUN) after the `done` (>= 0) already made, three launches each:
+ *   1. Q = K P with the workgroup sums of P . Q.
+ *   2. pq = those sums in index order; alpha_c = 0 if bit c of stop_mask is set or pq_c == 0, else rz_c / pq_c;
+ *      X = X + alpha P, R = R - alpha Q, Z = M^-1 R, with the workgroup sums of R . Z and R . R.
+ *   3. rz', rr' = those sums in index order; beta_c = 0 if alpha_c == 0, else rz'_c / rz_c; P = Z + beta P; the next record.
+ * A column with alpha = 0 is frozen: X and R keep their bits, no quotient with a zero denominator is taken, nothing is NaN.  A
+ * zero right-hand side from X = 0 is such a column (rz == 0 gives alpha == 0).  The host reads `state` when it wants to and
+ * sets stop_mask; plain launches only.
+ * t4d_nricp_positions: pos_i[c] = ((v0 X_i[c][0] + v1 X_i[c][1]) + v2 X_i[c][2]) + X_i[c][3] (float64 [n,3]) and
+ * *move2 (device) = the largest dot3(e, e), e = pos_i - prev_i, over the vertices (prev: float64 [n,3]; NULL: move2 = 0; prev
+ * may be pos).
+ *
+ * t4d_nricp_classify: points are the current p_i and d2, prim_index, closest what t4d_closest_query gave for them on `index`
+ * (of the scan, triangles or bare points).  With (a, b, c) the chosen triangle, nv = (b - a) x (c - a), nn = dot3(nv, nv),
+ * e = p - closest, en = dot3(e, nv), the class is the first that applies:
+ *   0 unmatched    prim_index < 0 (or beyond the index's primitives)
+ *   1 gated        gate2 >= 0 and d2 > gate2 (d2 == gate2 is kept)
+ *   2 degenerate   triangles only: nn == 0
+ *   3 off_normal   triangles only: d2 > 0 and en * en < (cos2 * d2) * nn (a closest point on the scan's open rim)
+ *   4 flipped      triangles only, normals not NULL: dot3(m, nh) < normal_cos with m the vertex normal (float64 [n,3]) and
+ *                  nh = nv / sqrt(nn) (three quotients); equality is kept
+ *   5 weightless   weights not NULL and weights[i] == 0
+ *   6 kept
+ * Outputs: cls int32 [n]; w float64 [n] = weights[i] (1 without weights) if kept, else 0; target float64 [n,3] = closest if
+ * kept, else 0; record (T4D_NRICP_RECORD_DOUBLES doubles): the class counts at 0..6 and the sum of d2 over the kept at
+ * T4D_NRICP_SUM_D2, by the reduction above.
+ *
+ * scratch: t4d_nricp_scratch_bytes(n) bytes for every call that takes one (0 and a message for n < 0 or >= 2^30).
+ * Refused before anything touches a device: NULL buffers, a count out of range, scratch too small (T4D_ERR_STATE_SIZE), a
+ * scalar that is not finite, a2 or a2g <= 0, beta2 < 0, cos2 or normal_cos outside [0, 1] / [-1, 1], iters or done out of range,
+ * stop_mask outside 0..7. */
+#define T4D_NRICP_MAX_GROUPS 1024
+#define T4D_NRICP_RECORD_DOUBLES 8
+#define T4D_NRICP_SUM_D2 7
+#define T4D_NRICP_STATE_DOUBLES 40
+#define T4D_NRICP_RZ 0
+#define T4D_NRICP_RR 3
+#define T4D_NRICP_PQ 6
+#define T4D_NRICP_ALPHA 9
+#define T4D_NRICP_BETA 12
+#define T4D_NRICP_ITER 15
+#define T4D_NRICP_STATE_BB 32
+#define T4D_NRICP_MAX_RUN 4096
+size_t t4d_nricp_scratch_bytes(int64_t n);
+int t4d_nricp_classify(const void *index, size_t index_bytes, const double *points, int64_t n, const double *d2,
+                       const int32_t *prim_index, const double *closest, const double *normals, const double *weights,
+                       double gate2, double cos2, double normal_cos, int32_t *cls, double *w, double *target, double *record,
+                       void *scratch, size_t scratch_bytes, void *hip_stream);
+int t4d_nricp_assemble(const double *v, int64_t n, const int32_t *nbr_off, const double *w, const double *c, const double *lw,
+                       const double *lt, double a2, double a2g, double beta2, double *s, double *b, double *chol,
+                       void *hip_stream);
+int t4d_nricp_precond(const double *chol, int64_t n, const double *r, double *z, void *hip_stream);
+int t4d_nricp_apply(const double *v, int64_t n, const int32_t *nbr_off, const int32_t *nbr, const double *s, double a2, double a2g,
+                    const double *p, double *q, double *dots, void *scratch, size_t scratch_bytes, void *hip_stream);
+int t4d_nricp_cg_start(const double *v, int64_t n, const int32_t *nbr_off, const int32_t *nbr, const double *s, double a2,
+                       double a2g, const double *chol, const double *b, const double *x, double *r, double *z, double *p,
+                       double *q, double *state, void *scratch, size_t scratch_bytes, void *hip_stream);
+int t4d_nricp_cg_run(const double *v, int64_t n, const int32_t *nbr_off, const int32_t *nbr, const double *s, double a2,
+                     double a2g, const double *chol, double *x, double *r, double *z, double *p, double *q, double *state,
+                     int32_t done, int32_t iters, int32_t stop_mask, void *scratch, size_t scratch_bytes, void *hip_stream);
+int t4d_nricp_positions(const double *v, int64_t n, const double *x, const double *prev, double *pos, double *move2,
+                        void *scratch, size_t scratch_bytes, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -267,6 +267,14 @@ SIGNATURES = {
     "t4d_profile_begin": (_INT, []),
     "t4d_profile_end": (_INT, [C.POINTER(T4DKernelTime), _INT, C.POINTER(_INT)]),
     "t4d_debug_state_layout": (_INT, [_PROB, _INT, C.POINTER(C.c_uint64), _INT]),
+    "t4d_nricp_scratch_bytes": (_SZ, [_I64]),
+    "t4d_nricp_classify": (_INT, [_VP, _SZ, _VP, _I64] + [_VP] * 5 + [C.c_double] * 3 + [_VP] * 5 + [_SZ, _VP]),
+    "t4d_nricp_assemble": (_INT, [_VP, _I64] + [_VP] * 5 + [C.c_double] * 3 + [_VP] * 4),
+    "t4d_nricp_precond": (_INT, [_VP, _I64, _VP, _VP, _VP]),
+    "t4d_nricp_apply": (_INT, [_VP, _I64, _VP, _VP, _VP, C.c_double, C.c_double] + [_VP] * 4 + [_SZ, _VP]),
+    "t4d_nricp_cg_start": (_INT, [_VP, _I64, _VP, _VP, _VP, C.c_double, C.c_double] + [_VP] * 9 + [_SZ, _VP]),
+    "t4d_nricp_cg_run": (_INT, [_VP, _I64, _VP, _VP, _VP, C.c_double, C.c_double] + [_VP] * 7 + [_I32] * 3 + [_VP, _SZ, _VP]),
+    "t4d_nricp_positions": (_INT, [_VP, _I64] + [_VP] * 5 + [_SZ, _VP]),
 }
 EXPORTS = tuple(SIGNATURES)
 
